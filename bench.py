@@ -14,11 +14,17 @@
     The tableau is generated on the device and resident in HBM before the timed region;
     nothing crosses PCIe inside it.  With N > 1 every rank owns one GPU and solves its own LP
     replica (seed = rank): the path shards by independent sub-problems, no data-path collective.
+    --steps K times exactly K steps: past STEPS_PER_LP steps the timed region goes on with a fresh
+    LP replica (seed rank + N, rank + 2N, ...) prepared like the first, outside the clock.
 --workload revised (BASELINE configs[2]): revised-simplex iterations/s at the same size and the
     fp64-MFMA B^-1*A product (roofline bound "mfma").
 --workload sens (row f4): ChangeRHS edits re-solved by the dual simplex on the optimal tableau.
 --workload bb (BASELINE configs[3]): level-synchronous Branch & Bound, sub-trees sharded over the
     ranks, ONE RCCL all-reduce(MAX) of the incumbent per level; value = sub-problem pivots/s.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path left for its caller
+(tableau, basis, pivot log, solution, result fields) as DIR/<name>.npy in float64, 64 MB at most;
+the inputs are seeded, so two builds run with the same arguments can be compared array by array.
 """
 from __future__ import annotations
 
@@ -33,10 +39,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E: 8.0 TB/s spec
 OVERLAP_BYTES = 80 << 20    # kOverlapBytes of csrc/lpr_engine.hip: above it the two-stream path runs
 MFMA_F64_PEAK_TFLOPS = 78.6  # MI355X datasheet fp64 matrix (= fp64 vector) peak; the local guide
 #                              has no fp64 MFMA row, tools/mfma_f64_peak.hip probes it on the device
+# Timed primal steps one LP replica takes at most: the headline LP (seed 0) reaches its optimum
+# after 121 866 pivots (README.md), 7 616 steps of 16; more steps go on to further replicas
+STEPS_PER_LP = 4096
+DUMP_BYTES_MAX = 64 << 20   # --dump-outputs: all arrays together
+TABLEAU_SAMPLE = 1 << 20    # entries of a fixed seeded sample of a tableau too large to dump whole
 
 
 def _cpu_model() -> str:
@@ -156,6 +167,27 @@ class Dist:
             self.dist.destroy_process_group()
 
 
+def _tableau_arrays(T: np.ndarray) -> dict:
+    """A tableau whole when it is small; else its objective row, its RHS column and the entries at
+    a fixed seeded sample of flat positions (the positions depend on the shape alone)."""
+    if T.nbytes <= DUMP_BYTES_MAX // 2:
+        return {"tableau": T}
+    idx = np.unique(np.random.default_rng(0).integers(0, T.size, TABLEAU_SAMPLE))
+    return {"tableau_row0": T[0], "tableau_rhs": T[:, -1],
+            "tableau_sample_index": idx, "tableau_sample": T.reshape(-1)[idx]}
+
+
+def _dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: every array as DIRECTORY/<name>.npy in float64 (integers are exact there)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES_MAX} byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------ primal
 def _sha(a) -> str:
     import hashlib
@@ -172,38 +204,60 @@ def run_primal(args, D: Dist):
     R, C = m + 1, n + m + 1
     bytes_per_pivot = 2 * 8 * R * C  # every tableau element read once + written once
     eng = pkg.Engine(D.device_index)
-    tab = pkg.Tableau.synthetic(eng, m, n, D.rank)  # one LP replica per rank (seed = rank)
     timed = not args.no_kernel_timing
-    # one pivot to learn how many pivots a step of the path chosen for this tableau applies
-    probe = tab.solve(max_pivots=1, variant=args.variant, block=args.block)
-    B = max(1, probe.block)
-    if B == 1 and args.block == 0 and args.variant == 0 and R * C * 8 <= (1 << 20):
-        # the single-launch path of small (cache-resident) tableaux has no per-kernel event
-        # timing (asking for it would switch to another path): whole-job figures only
-        timed = False
-    if W > 0:
-        # warm-up in the timed region's own mode (the engine creates its HIP events on first use:
-        # ~10 us each, which is not pivot time); the statistics below are differences
-        res = tab.solve(max_pivots=W * B, time_kernels=(args.time_stride if timed else 0),
+    B = None
+
+    def replica(i: int):
+        """LP replica i of this rank (seed rank + world * i; replica 0 is seed = rank), taken
+        through the probe pivot and the warm-up, so that its next pivot starts a timed step."""
+        nonlocal B, timed
+        tab = pkg.Tableau.synthetic(eng, m, n, D.rank + D.world * i)
+        # one pivot to learn how many pivots a step of the path chosen for this tableau applies
+        probe = tab.solve(max_pivots=1, variant=args.variant, block=args.block)
+        if B is None:
+            B = max(1, probe.block)
+            if B == 1 and args.block == 0 and args.variant == 0 and R * C * 8 <= (1 << 20):
+                # the single-launch path of small (cache-resident) tableaux has no per-kernel
+                # event timing (asking for it would switch to another path): whole-job figures only
+                timed = False
+        if W > 0:
+            # warm-up in the timed region's own mode (every tableau creates its HIP events and
+            # graphs on first use, which is not pivot time); the statistics below are differences
+            res = tab.solve(max_pivots=W * B, time_kernels=(args.time_stride if timed else 0),
+                            variant=args.variant, block=args.block)
+            if res.pivots != W * B:
+                raise SystemExit(f"warm-up ended after {res.pivots} pivots (status {res.status})")
+        return tab
+
+    # The K timed steps run on one replica while they fit in its LP, else in slices of
+    # STEPS_PER_LP steps on fresh replicas; only the solve calls themselves are timed.
+    dt, launches, kern_total, nsteps, step_total = 0.0, 0, 0.0, 0, 0.0
+    done, replicas, tab = 0, 0, None
+    while done < K:
+        if tab is not None:
+            tab.destroy()
+        tab = replica(replicas)
+        replicas += 1
+        k = min(K - done, STEPS_PER_LP)
+        k0, s0 = tab.kernel_stats(), tab.step_stats()
+        D.barrier(eng)
+        t0 = time.perf_counter()
+        res = tab.solve(max_pivots=k * B, time_kernels=(args.time_stride if timed else 0),
                         variant=args.variant, block=args.block)
-        if res.pivots != W * B:
-            raise SystemExit(f"warm-up ended after {res.pivots} pivots (status {res.status})")
-    k0, s0 = tab.kernel_stats(), tab.step_stats()
-    D.barrier(eng)
-    t0 = time.perf_counter()
-    res = tab.solve(max_pivots=K * B, time_kernels=(args.time_stride if timed else 0),
-                    variant=args.variant, block=args.block)
-    D.barrier(eng)
-    dt = time.perf_counter() - t0
-    if res.pivots != K * B or res.block != B:
-        raise SystemExit(f"timed region ended after {res.pivots} of {K * B} pivots "
-                         f"(status {res.status}); pick another seed / fewer steps")
-    k1, s1 = tab.kernel_stats(), tab.step_stats()
+        D.barrier(eng)
+        dt += time.perf_counter() - t0
+        if res.pivots != k * B or res.block != B:
+            raise SystemExit(f"timed region ended after {res.pivots} of {k * B} pivots on LP "
+                             f"replica {replicas - 1} (status {res.status})")
+        k1, s1 = tab.kernel_stats(), tab.step_stats()
+        launches += k1[0] - k0[0]
+        kern_total += k1[1] - k0[1]
+        nsteps += s1[0] - s0[0]
+        step_total += s1[1] - s0[1]
+        done += k
     dt_max = D.max(dt)
-    launches = k1[0] - k0[0]
-    kern_ms = (k1[1] - k0[1]) / launches if launches else None
-    nsteps = s1[0] - s0[0]
-    step_ms = (s1[1] - s0[1]) / nsteps if nsteps else None
+    kern_ms = kern_total / launches if launches else None
+    step_ms = step_total / nsteps if nsteps else None
 
     out = None
     if D.rank == 0:
@@ -317,12 +371,20 @@ def run_primal(args, D: Dist):
                                    f"one sweep of the tableau = {B} pivots",
                        "m": m, "n": n, "rows": R, "cols": C, "seed": "rank",
                        "parallelism": f"replica{D.world}", "update_variant": args.variant,
-                       "pivots_per_sweep": B, "timed_region": "one lpr_primal_solve call, "
-                       f"max_pivots = steps x {B} (pipeline fill and drain included)",
+                       "pivots_per_sweep": B, "lp_replicas": replicas,
+                       "timed_region": f"one lpr_primal_solve call per LP replica, max_pivots = "
+                       f"its steps x {B} (at most {STEPS_PER_LP} steps per replica; pipeline "
+                       f"fill and drain included)",
                        "launch": ("eager+events" if timed else
                                   ("hipGraph" if B == 1 else "eager"))},
             "roofline": roof, "cpu_baseline": cpu,
         }
+        if args.dump_outputs:
+            x, z = tab.extract_solution(n)
+            _dump_outputs(args.dump_outputs, {
+                "result": [res.status, res.block, res.pivots, res.total_pivots, res.z, z],
+                "x": x, "basis": tab.basis(), "pivot_log": tab.pivot_log(),
+                **_tableau_arrays(tab.read())})
     tab.destroy()
     eng.close()
     return out
@@ -404,6 +466,11 @@ def run_revised(args, D: Dist):
                          "traffic_source": pmc.get("source")},
             "cpu_baseline": cpu,
         }
+        if args.dump_outputs:
+            x, z = st.solution()
+            _dump_outputs(args.dump_outputs, {
+                "result": [res.status, res.iterations, res.total_iterations, res.z, z],
+                "x": x, "basis": st.basis(), "xb": st.xb(), "log": st.log()})
     st.destroy()
     eng.close()
     return out
@@ -549,6 +616,11 @@ def run_bb(args, D: Dist):
                                  % (Rm * Cm * 8 / 1e6, 1 << (levels - 1))},
             "cpu_baseline": cpu,
         }
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, {
+                "result": [res["status"], res["found"], res["z"], res["processed"], res["pivots"],
+                           res["levels"]],
+                "x": res["x"] if res["found"] else []})
     if comm is not None:
         comm.destroy()
     tree.destroy()
@@ -595,10 +667,12 @@ def run_sens(args, D: Dist):
     D.barrier(eng)
     t0 = time.perf_counter()
     piv = rolled = 0
+    edits = []
     for k in range(K):
         oc, p = edit(W + k)
         piv += p
         rolled += 1 if oc == 8 else 0
+        edits.append((oc, p))
     D.barrier(eng)
     dt = time.perf_counter() - t0
     dt_max = D.max(dt)
@@ -663,6 +737,11 @@ def run_sens(args, D: Dist):
                           f"row's RHS; cpu: {_cpu_model()}",
                 "edits_per_s": round(len(cpu_out) / cdt, 3),
                 "outcomes_and_pivots_match_gpu": bool(same)}
+        if args.dump_outputs:
+            T, basic, sol = sens.read()
+            _dump_outputs(args.dump_outputs, {
+                "edits": edits, "z": [sens.shape()[4]], "basic": basic, "solution": sol,
+                **_tableau_arrays(T)})
     sens.destroy()
     eng.close()
     return out
@@ -720,11 +799,16 @@ def main() -> int:
     ap.add_argument("--bb-levels", type=int, default=9)
     ap.add_argument("--bb-check-levels", type=int, default=6,
                     help="levels of the same search repeated on the CPU oracle and compared")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last "
+                         "step as DIR/<name>.npy (float64, a seeded sample of a large tableau)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 64 if args.workload == "primal" else 512
     if args.warmup is None:
         args.warmup = 8 if args.workload == "primal" else 64
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.time_stride <= 0:
         args.time_stride = 1 if args.steps <= 32 else 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

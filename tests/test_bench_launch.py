@@ -45,3 +45,47 @@ def test_self_launch_two_ranks_rehearsal_on_one_gpu():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and "rehearsal" in out
     assert out["config"]["nodes_processed"] > 1 and out["value"] > 0
+
+
+def _bench_line(*argv):
+    p = subprocess.run([sys.executable, BENCH, *argv], env=_env(), capture_output=True, text=True,
+                       timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_steps_and_warmup_are_checked_before_any_work():
+    p = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_env(), capture_output=True,
+                       text=True, timeout=300)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_float_bounded_and_repeat_bit_for_bit(tmp_path):
+    """Two runs with the same arguments dump the same arrays, byte for byte, in float64."""
+    import numpy as np
+    args = ["--m", "512", "--n", "1024", "--steps", "8", "--warmup", "2", "--cpu-pivots", "0"]
+    dumps = []
+    for run in ("a", "b"):
+        out = _bench_line(*args, "--dump-outputs", str(tmp_path / run))
+        assert out["steps"] == 8 and out["ms_per_step"] > 0
+        dumps.append({f: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"result.npy", "x.npy", "basis.npy", "pivot_log.npy"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), f
+        assert a[f].tobytes() == b[f].tobytes(), f
+    # probe pivot + warm-up + timed steps, all in the pivot log of the one LP replica
+    assert a["pivot_log.npy"].shape[0] == a["result.npy"][3]
+
+
+@pytest.mark.gpu
+def test_steps_beyond_one_lp_replica_are_all_timed():
+    """More steps than one headline LP holds before its optimum: the timed region goes on with a
+    second replica, and the result line still reports exactly the steps asked for."""
+    out = _bench_line("--steps", "5000", "--warmup", "2", "--cpu-pivots", "0")
+    assert out["steps"] == 5000 and out["config"]["lp_replicas"] == 2
+    assert out["ms_per_step"] > 0 and out["value"] > 0

@@ -16,7 +16,9 @@ def test_oracle_tests_pass_under_asan_ubsan():
     subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "asan"], check=True,
                    capture_output=True)
     env = dict(os.environ)
-    env.update({"LD_PRELOAD": asan, "LPR_ORACLE_SANITIZE": "1",
+    # the sanitizer runtime first, as ASan requires; a preload the environment already has stays
+    preload = " ".join(x for x in (asan, env.get("LD_PRELOAD", "")) if x)
+    env.update({"LD_PRELOAD": preload, "LPR_ORACLE_SANITIZE": "1",
                 # CPython "leaks" by design; everything else stops the run with a report
                 "ASAN_OPTIONS": "detect_leaks=0:abort_on_error=1:halt_on_error=1",
                 "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
