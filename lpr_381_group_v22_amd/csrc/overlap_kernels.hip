@@ -35,7 +35,8 @@
 // the sweep apart (1: no multiply-subtract chains, 2: no pivot-row loads, 4: half the chains,
 // 8: plain instead of non-temporal loads / stores, 16: static grid with every XCD on a contiguous
 // range of tiles, 32: tiles taken column-major, 64 / 128: write-through stores of system / agent
-// scope, 256: no half tiles at the tail of the queue).  The library is built with neither.
+// scope, 256: no half tiles at the tail of the queue, 512: every sweep in the same tile order).
+// The library is built with neither.
 #ifndef LPR_OV_DIAG
 #define LPR_OV_DIAG 0
 #endif
@@ -56,6 +57,14 @@ constexpr size_t kOvFlagWords = (size_t)(kOvDoneCopies + 1) * kOvDoneStride;
 #define LPR_OV_TILE_ROWS 32  // (tools/sweep_bench.hip overrides it)
 #endif
 constexpr int kOvTileRows = LPR_OV_TILE_ROWS;  // rows per sweep workgroup (TR in flight at a time)
+// The out-of-place sweep reads what the previous one wrote, in the opposite tile order: the first
+// kOvIcMB MB it reads are the last the previous one wrote.  Those are stored and loaded with the
+// default cache policy (everything else non-temporal) so that they can be served by the Infinity
+// Cache: a line stays there while the bytes moved between its two uses (~4 x kOvIcMB) fit.
+#ifndef LPR_OV_IC_MB
+#define LPR_OV_IC_MB 64
+#endif
+constexpr int kOvIcMB = LPR_OV_IC_MB;
 // ov_heads_rich: the unit of a hand-off is the WAVE, not the workgroup -- every wave publishes its
 // own partial once its own stores have drained and collects all G x kOvWPG of them itself: no LDS
 // combine, no workgroup barrier in a head (false: one partial per workgroup, four barriers per head)
@@ -72,7 +81,8 @@ struct OvCtl {
     int32_t kdone;     // pivots of the block the reader's tiles must apply
     int32_t slot;      // staging slot holding that block (the heads stage into slot ^ 1)
     int32_t cur;       // buffer holding the tableau before that block
-    int32_t sweep;     // parity of the sweep direction
+    int32_t sweep;     // parity of the sweep direction (flips with every sweep that applies pivots,
+                       // and is carried from one solve call to the next)
     int32_t r[kOvMax]; // pivot rows of that block
     int32_t error;     // a grid barrier timed out
     int32_t head_xcc;  // XCD the loop heads of the previous launch shared (-1: none / spread)
@@ -1355,7 +1365,7 @@ __device__ void ov_heads_rich(const OvBuffers B, int ld, int R, int C, int Rp, i
             const int ks = (status == kRunning) ? ci->kdone : 0;
             co->applied = ci->applied + ks;
             co->cur = (ks > 0) ? (ci->cur ^ 1) : ci->cur;
-            co->sweep = ci->sweep ^ 1;
+            co->sweep = ci->sweep ^ (ks > 0 ? 1 : 0);
         }
         if (solo) {
             B.tileq[1] = 0u;  // the in-place sweep that follows always runs on control block 1
@@ -1451,21 +1461,22 @@ __device__ __forceinline__ void ov_chunk(ov_v2d (&x)[TR], const ov_v2d (&p)[kOvM
     }
 }
 
-template <int TR, bool INPLACE>
+// PLAIN: default cache policy (in place, or the ends of the queue), else non-temporal
+template <int TR, bool PLAIN>
 __device__ __forceinline__ void ov_rows_load(ov_v2d (&x)[TR], const ov_v2d* src, int ld2) {
 #pragma unroll
     for (int k = 0; k < TR; ++k)
-        x[k] = (INPLACE || (LPR_OV_DIAG & 8)) ? src[(size_t)k * ld2]
-                                              : ov_ld_stream(&src[(size_t)k * ld2]);
+        x[k] = (PLAIN || (LPR_OV_DIAG & 8)) ? src[(size_t)k * ld2]
+                                            : ov_ld_stream(&src[(size_t)k * ld2]);
 }
 
-template <int TR, bool INPLACE>
+template <int TR, bool PLAIN>
 __device__ __forceinline__ void ov_rows_store(const ov_v2d (&x)[TR], ov_v2d* dst, int ld2,
                                               unsigned skip) {
 #pragma unroll
     for (int k = 0; k < TR; ++k) {
         if ((skip >> k) & 1u) continue;  // a pivot row of the block: recomputed afterwards
-        if (INPLACE || (LPR_OV_DIAG & 8)) dst[(size_t)k * ld2] = x[k];
+        if (PLAIN || (LPR_OV_DIAG & 8)) dst[(size_t)k * ld2] = x[k];
         else if (LPR_OV_DIAG & 64)
             asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(&dst[(size_t)k * ld2]),
                          "v"(x[k])
@@ -1493,7 +1504,9 @@ __device__ __forceinline__ void ov_rows_store(const ov_v2d (&x)[TR], ov_v2d* dst
 // tile.  `static_tile` >= 0: one given tile (the one-launch form k_ov_step has no queue).
 // TROWS rows are processed; the row tiles are counted in units of `unit` rows (>= TROWS) and this
 // call takes the TROWS rows at offset `off` inside its unit (the half tiles of the sweep's tail)
-template <int TR, bool DB, bool INPLACE, int TROWS = kOvTileRows>
+// POL (out of place only): bit 0 loads, bit 1 stores of the tile's rows with the default cache
+// policy instead of non-temporal (the ends of the queue, see ov_tiles)
+template <int TR, bool DB, bool INPLACE, int TROWS = kOvTileRows, int POL = 0>
 __device__ __forceinline__ void ov_one_tile(const OvBuffers& B, const OvCtl* ci,
                                             const double* __restrict__ fc,
                                             const ov_v2d* __restrict__ prow2, int tb, int ld,
@@ -1514,7 +1527,7 @@ __device__ __forceinline__ void ov_one_tile(const OvBuffers& B, const OvCtl* ci,
         if (ct >= nct) return;
     }
     if (rt >= nrt) return;
-    if (ci->sweep & 1) {
+    if ((ci->sweep & 1) && !(LPR_OV_DIAG & 512)) {
         ct = nct - 1 - ct;
         rt = nrt - 1 - rt;
     }
@@ -1546,17 +1559,18 @@ __device__ __forceinline__ void ov_one_tile(const OvBuffers& B, const OvCtl* ci,
         const v2d* src = Tin2 + (size_t)ibase * ld2 + c2;
         v2d* dst = Tout2 + (size_t)ibase * ld2 + c2;
         const size_t step = (size_t)TR * ld2;
+        constexpr bool kPlainLd = INPLACE || (POL & 1), kPlainSt = INPLACE || (POL & 2);
         if (DB) {
             v2d xa[TR], xb[TR];
-            ov_rows_load<TR, INPLACE>(xa, src, ld2);
+            ov_rows_load<TR, kPlainLd>(xa, src, ld2);
 #pragma unroll 1
             for (int j = 0; j < TROWS; j += 2 * TR) {
-                ov_rows_load<TR, INPLACE>(xb, src + step, ld2);
+                ov_rows_load<TR, kPlainLd>(xb, src + step, ld2);
                 ov_chunk<TR>(xa, p, fc + ibase + j, Rp);
-                ov_rows_store<TR, INPLACE>(xa, dst, ld2, (unsigned)(prmask >> j));
-                if (j + 2 * TR < TROWS) ov_rows_load<TR, INPLACE>(xa, src + 2 * step, ld2);
+                ov_rows_store<TR, kPlainSt>(xa, dst, ld2, (unsigned)(prmask >> j));
+                if (j + 2 * TR < TROWS) ov_rows_load<TR, kPlainLd>(xa, src + 2 * step, ld2);
                 ov_chunk<TR>(xb, p, fc + ibase + j + TR, Rp);
-                ov_rows_store<TR, INPLACE>(xb, dst + step, ld2, (unsigned)(prmask >> (j + TR)));
+                ov_rows_store<TR, kPlainSt>(xb, dst + step, ld2, (unsigned)(prmask >> (j + TR)));
                 src += 2 * step;
                 dst += 2 * step;
             }
@@ -1564,9 +1578,9 @@ __device__ __forceinline__ void ov_one_tile(const OvBuffers& B, const OvCtl* ci,
 #pragma unroll 1
             for (int j = 0; j < TROWS; j += TR) {
                 v2d x[TR];
-                ov_rows_load<TR, INPLACE>(x, src, ld2);
+                ov_rows_load<TR, kPlainLd>(x, src, ld2);
                 ov_chunk<TR>(x, p, fc + ibase + j, Rp);
-                ov_rows_store<TR, INPLACE>(x, dst, ld2, (unsigned)(prmask >> j));
+                ov_rows_store<TR, kPlainSt>(x, dst, ld2, (unsigned)(prmask >> j));
                 src += step;
                 dst += step;
             }
@@ -1643,7 +1657,8 @@ __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __res
                                          const double* __restrict__ prow, int ld, int R, int Rp,
                                          int G, int lp, int static_tile, int avoid,
                                          bool write_ctl = true, int sweeps_done = -1,
-                                         int wait_heads = -1, int hint_xcc = -1) {
+                                         int wait_heads = -1, int hint_xcc = -1,
+                                         int ic_tiles = 0) {
     static_assert(TROWS % TR == 0 && (!DB || TROWS % (2 * TR) == 0) && TROWS <= 64,
                   "tile rows: a multiple of the chunks in flight, and one bit each in prmask");
     __shared__ int s_tile;
@@ -1714,7 +1729,7 @@ __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __res
         if (write_ctl) {  // (the heads write these when they run ahead of the event, see there)
             co->applied = ci->applied + K;
             co->cur = (K > 0 && !INPLACE) ? (cur ^ 1) : cur;
-            co->sweep = ci->sweep ^ 1;
+            co->sweep = ci->sweep ^ (K > 0 ? 1 : 0);
         }
         B.tileq[lp ^ 1] = 0u;  // nobody touches the other queue during this launch
         if (INPLACE) {  // no heads in this launch: their fields are carried over here
@@ -1774,12 +1789,32 @@ __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __res
         const int tile = s_tile;
         __syncthreads();
         if (tile >= qtiles) return;
+        // position in the queue, in full tiles: its first / last ic_tiles keep the default cache
+        // policy for their loads / stores (the previous sweep went the other way round, so the
+        // first tiles read here are the last ones it wrote)
+        const int at = tile < tsplit ? tile : tsplit + ((tile - tsplit) >> 1);
+        const int pol = (at < ic_tiles ? 1 : 0) | (at >= ntiles - ic_tiles ? 2 : 0);
         if (tile < tsplit) {
-            ov_one_tile<TR, DB, INPLACE, TROWS>(B, ci, fc, prow2, tile, ld, R, Rp, K, cur);
+#define LPR_OV_FULL(P) ov_one_tile<TR, DB, INPLACE, TROWS, P>(B, ci, fc, prow2, tile, ld, R, Rp, K, cur)
+            switch (pol) {
+                case 1: LPR_OV_FULL(1); break;
+                case 2: LPR_OV_FULL(2); break;
+                case 3: LPR_OV_FULL(3); break;
+                default: LPR_OV_FULL(0); break;
+            }
+#undef LPR_OV_FULL
         } else {  // the tail of the queue: half tiles
             const int u = tile - tsplit;
-            ov_one_tile<TR, false, INPLACE, TROWS / 2>(B, ci, fc, prow2, tsplit + (u >> 1), ld, R, Rp,
-                                                       K, cur, TROWS, (u & 1) * (TROWS / 2));
+#define LPR_OV_HALF(P)                                                                             \
+    ov_one_tile<TR, false, INPLACE, TROWS / 2, P>(B, ci, fc, prow2, tsplit + (u >> 1), ld, R, Rp, \
+                                                  K, cur, TROWS, (u & 1) * (TROWS / 2))
+            switch (pol) {
+                case 1: LPR_OV_HALF(1); break;
+                case 2: LPR_OV_HALF(2); break;
+                case 3: LPR_OV_HALF(3); break;
+                default: LPR_OV_HALF(0); break;
+            }
+#undef LPR_OV_HALF
         }
     }
 }
@@ -1816,9 +1851,9 @@ __global__ __launch_bounds__(kOvNT) void k_ov2_sweep(const OvBuffers B,
                                                      const double* __restrict__ prow_ro, int ld,
                                                      int R, int Rp, int lp, int avoid,
                                                      int write_ctl, int sweeps_done,
-                                                     int wait_heads, int hint_xcc) {
+                                                     int wait_heads, int hint_xcc, int ic_tiles) {
     ov_tiles<TR, DB, false>(B, fcol_ro, prow_ro, ld, R, Rp, 0, lp, -1, avoid, write_ctl != 0,
-                            sweeps_done, wait_heads, hint_xcc);
+                            sweeps_done, wait_heads, hint_xcc, ic_tiles);
 }
 
 // The same two halves as separate launches: all K loop heads of a block in ONE persistent launch
@@ -1860,6 +1895,7 @@ struct lpr_overlap_ctx {
     hipEvent_t last_sweep = nullptr;  // the event that marks the latest sweep of the call as done
     unsigned* h_flags = nullptr;    // pinned copy of b.sflag[0..3]
     int head_xcc_hint = -1;         // the XCD the loop heads shared at the last poll (-1: unknown)
+    int sweep_dir = 0;              // direction of the next sweep (OvCtl::sweep) at the last poll
     bool batch_first = true;        // the next step is the first after the streams were joined
 };
 
@@ -2001,6 +2037,9 @@ int ov_begin(lpr_tableau* t, int64_t iter, int64_t max_iter) {
     h[0].max_iter = max_iter;
     h[0].log_cap = t->log_cap;
     h[0].head_xcc = -1;
+    // the first sweep of this call goes the other way round from the last one of the call before
+    // (it reads what that one wrote last first); the first launch of a call sweeps nothing
+    h[0].sweep = c->sweep_dir;
     h[1] = h[0];
     LPR_HIP(hipMemcpyAsync(c->b.ctl, h, 2 * sizeof(OvCtl), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_ov_prologue, dim3(1), dim3(1024), 0, s, t->T, t->ld, t->rows, t->cols,
@@ -2158,10 +2197,15 @@ int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t
     const int avoid = (flags & (2 | 4 | 8)) ? 0 : ((flags & 16) ? 1 : 2);
     // a sampled step: its stop event is the timing event (start = the kernel's own start)
     hipEvent_t sweep_done = ev_stop ? ev_stop : c->ev_s[cur];
+    // tiles at each end of the queue that keep the default cache policy (kOvIcMB); flags 128:
+    // none, every tile non-temporal (the form before)
+    const int ic_tiles =
+        (flags & 128) ? 0 : (int)(((size_t)kOvIcMB << 20) / ((size_t)kOvTileRows * kOvNT * 16));
 #define LPR_OV2_SWEEP(TR, DB)                                                                     \
     hipExtLaunchKernelGGL((k_ov2_sweep<TR, DB>), grid, blk, 0, S, ev_start, sweep_done, 0, c->b,   \
                           c->b.fcol, c->b.prow, t->ld, t->rows, c->Rp, lp, avoid, by_event ? 1 : 0, \
-                          by_event ? -1 : c->steps, sweep_dev ? c->steps : -1, c->head_xcc_hint)
+                          by_event ? -1 : c->steps, sweep_dev ? c->steps : -1, c->head_xcc_hint,    \
+                          ic_tiles)
     switch (ov_tile_code(tr)) {
         case 0x04: LPR_OV2_SWEEP(4, false); break;
         case 0x10: LPR_OV2_SWEEP(16, false); break;
@@ -2198,6 +2242,7 @@ int ov_poll(lpr_tableau* t, int parity, OvPoll* out) {
     LPR_HIP(hipStreamSynchronize(s));
     const OvCtl& h = c->h_ctl[parity];
     c->head_xcc_hint = h.head_xcc;
+    c->sweep_dir = h.sweep & 1;
     out->status = h.status;
     out->pending = h.pending;
     out->kdone = h.kdone;

@@ -4,6 +4,8 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DLPR_OV_KERNELS_ONLY \
 //         -DLPR_OV_DIAG=<bits> -I lpr_381_group_v22_amd/csrc -I include tools/sweep_bench.hip -o ...
 // usage: sweep_bench [reps] [wgs_per_cu] [leave_xcc (-1: none)] [tile code 4|8|16|0x24|0x28]
+//                    [R] [C] [mode] [ic_mb: MB at each end of the queue with default-policy
+//                    loads / stores, 0: all non-temporal]
 // prints one JSON line: average / min launch time by HIP events, GB/s of 2*8*R*ld.
 #include "overlap_kernels.hip"
 
@@ -65,6 +67,8 @@ int main(int argc, char** argv) {
     const int R = argc > 5 ? std::atoi(argv[5]) : 4097;
     const int C = argc > 6 ? std::atoi(argv[6]) : 12289;
     const int mode = argc > 7 ? std::atoi(argv[7]) : 0;  // 1: linear copy kernel, 2: hipMemcpyDtoD
+    const int ic_mb = argc > 8 ? std::atoi(argv[8]) : 0;
+    const int ic_tiles = (int)(((size_t)ic_mb << 20) / ((size_t)kOvTileRows * kOvNT * 16));
     const int ld = (C + 15) / 16 * 16, Rp = (R + 15) / 16 * 16;
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, 0));
@@ -126,7 +130,7 @@ int main(int argc, char** argv) {
         }
 #define SW(TR, DB)                                                                               \
     hipLaunchKernelGGL((k_ov2_sweep<TR, DB>), grid, blk, 0, S, b, b.fcol, b.prow, ld, R, Rp, lp, \
-                       avoid, 1, -1)
+                       avoid, 1, -1, -1, -1, ic_tiles)
         switch (tile) {
             case 0x04: SW(4, false); break;
             case 0x10: SW(16, false); break;
@@ -154,9 +158,9 @@ int main(int argc, char** argv) {
     }
     const double bytes = 2.0 * 8.0 * R * (double)ld;
     std::printf("{\"mode\": %d, \"diag\": %d, \"tile\": \"0x%x\", \"wgs_per_cu\": %d, \"grid\": %d, \"leave_xcc\": %d, "
-                "\"R\": %d, \"C\": %d, \"avg_us\": %.2f, \"min_us\": %.2f, \"avg_gbps\": %.1f, "
+                "\"R\": %d, \"C\": %d, \"ic_mb\": %d, \"avg_us\": %.2f, \"min_us\": %.2f, \"avg_gbps\": %.1f, "
                 "\"min_gbps\": %.1f}\n",
-                mode, (int)LPR_OV_DIAG, tile, wgs_per_cu, (int)grid.x, leave, R, C, 1e3 * sum / reps,
+                mode, (int)LPR_OV_DIAG, tile, wgs_per_cu, (int)grid.x, leave, R, C, ic_mb, 1e3 * sum / reps,
                 1e3 * mn, bytes / (sum / reps) * 1e-6, bytes / mn * 1e-6);
     return 0;
 }
