@@ -10,6 +10,11 @@ namespace lpr {
 // 144 KB of the CU's 160 KB = 36 864 columns.  lpr_bb_create rejects wider trees.
 constexpr size_t kBBEliminateLdsMax = (size_t)144 << 10;
 
+// Rows behind the score row that hold the -0.0 flags of a node (one byte per tableau row, bb_negz):
+// sized from rows_cap alone, so a tall tableau or one whose score row is full (nvars = cols - 1)
+// still has a byte for every row.
+inline int bb_negz_rows(int rows_cap, int ld) { return (rows_cap + 8 * ld - 1) / (8 * ld); }
+
 // States of one child LP while DoDualSimplex (:289-468) runs on it.
 enum : int32_t {
     kBBDual = 0,        // dual phase (:305-343)
@@ -52,8 +57,9 @@ struct lpr_bb {
     int rows0 = 0, cols0 = 0;   // root tableau shape
     int nvars = 0;
     int max_depth = 0;
-    int rows_cap = 0, ld = 0;   // every node buffer is (rows_cap + 2) x ld doubles: the tableau, then
-                                // the two rows k_bb_finish leaves behind it
+    int rows_cap = 0, ld = 0;   // every node buffer is (rows_cap + 2 + bb_negz_rows) x ld doubles: the
+                                // tableau, the two rows k_bb_finish leaves behind it, then one -0.0
+                                // flag byte per row (bb_negz)
     size_t buf_elems = 0;
     // node pool
     struct Node {

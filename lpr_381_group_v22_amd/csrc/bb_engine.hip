@@ -489,7 +489,8 @@ static int bb_create_common(lpr_engine* e, int rows, int cols, int nvars, int ma
     b->max_depth = max_depth;
     b->rows_cap = rows + max_depth;
     b->ld = align_up(cols + max_depth, kLdAlign);
-    b->buf_elems = (size_t)(b->rows_cap + 2) * b->ld;
+    // the tableau, k_bb_finish's scan and score rows, the -0.0 flag rows (bb_negz)
+    b->buf_elems = (size_t)(b->rows_cap + 2 + bb_negz_rows(b->rows_cap, b->ld)) * b->ld;
     e->live_bb.push_back(b);
     *out = b;
     return LPR_OK_OPTIMAL;

@@ -4,7 +4,7 @@
 // All kernels are batched: blockIdx.z (or .y / .x where noted) is the child sub-problem ("slot") of
 // the current batch, so the two children of a DFS node -- or the whole frontier of a level -- are
 // evaluated by the same launches.  Every node tableau lives in a rows_cap x ld buffer in HBM, ld a
-// multiple of 16 doubles.
+// multiple of 16 doubles, followed by k_bb_finish's scan and score rows and the -0.0 flags (bb_negz).
 //
 //   k_bb_child_init    AddConstraint, first half (:701-747): round, insert the slack column,
 //                      append the branching row, round again
@@ -130,18 +130,18 @@ __device__ __forceinline__ int block_min_int(int v, int* lds) {
 // :747).
 constexpr int kBBRowsPerThread = 8;  // rows a thread of the element-wise passes walks
 
-// Per node, one byte per row behind its scores (row rows_cap + 1 of its buffer: 1 + nvars doubles
-// are used, and 8 (ld - 1 - nvars) >= rows_cap bytes are left): 1 = k_bb_finish stored a -0.0 in
-// that row (Math.Round of a tiny negative value).  The children of the node start from its rows
-// with -0 made +0 (:307-313); a child that takes the buffer over in place only has to visit the
-// flagged rows for that.
-__device__ __forceinline__ uint8_t* bb_negz(double* T, int ld, int rows_cap, int nvars) {
-    return reinterpret_cast<uint8_t*>(T + (size_t)(rows_cap + 1) * ld + 1 + nvars);
+// Per node, one byte per row in rows of their own behind its scores (from row rows_cap + 2 of its
+// buffer on, bb_negz_rows(rows_cap, ld) of them: sized by the row count alone, whatever the shape):
+// 1 = k_bb_finish stored a -0.0 in that row (Math.Round of a tiny negative value).  The children
+// of the node start from its rows with -0 made +0 (:307-313); a child that takes the buffer over in
+// place only has to visit the flagged rows for that.
+__device__ __forceinline__ uint8_t* bb_negz(double* T, int ld, int rows_cap) {
+    return reinterpret_cast<uint8_t*>(T + (size_t)(rows_cap + 2) * ld);
 }
 
 __global__ __launch_bounds__(256) void k_bb_child_init(const BBSlot* __restrict__ slots, int ld,
                                                        uint8_t* __restrict__ touched_all,
-                                                       int rows_cap16, int rows_cap, int nvars) {
+                                                       int rows_cap16, int rows_cap) {
     const BBSlot& s = slots[blockIdx.z];
     if (s.inplace) return;  // (k_bb_child_inplace)
     const int Rc = s.rows, Cc = s.cols;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_bb_child_init(const BBSlot* __restrict_
     if (blockIdx.x == 0 && threadIdx.x < kBBRowsPerThread && i0 + (int)threadIdx.x < rows_cap16) {
         touched_all[(size_t)blockIdx.z * rows_cap16 + i0 + threadIdx.x] =
             (i0 + (int)threadIdx.x == Rc - 1) ? 1 : 0;
-        if (i0 + (int)threadIdx.x < rows_cap) bb_negz(s.cur, ld, rows_cap, nvars)[i0 + threadIdx.x] = 0;
+        if (i0 + (int)threadIdx.x < rows_cap) bb_negz(s.cur, ld, rows_cap)[i0 + threadIdx.x] = 0;
     }
     if (j >= ld) return;
     const double* __restrict__ P = s.parent;
@@ -187,14 +187,14 @@ __global__ __launch_bounds__(256) void k_bb_child_init(const BBSlot* __restrict_
 // AFTER k_bb_child_init of the batch (the sibling copies the parent's rows first).
 __global__ __launch_bounds__(256) void k_bb_child_inplace(const BBSlot* __restrict__ slots, int ld,
                                                           uint8_t* __restrict__ touched_all,
-                                                          int rows_cap16, int rows_cap, int nvars) {
+                                                          int rows_cap16, int rows_cap) {
     const BBSlot& s = slots[blockIdx.x];
     if (!s.inplace) return;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int Rc = s.rows, Cc = s.cols;
     const int R = Rc - 1, C = Cc - 1;  // parent shape
     double* __restrict__ T = s.cur;
-    uint8_t* __restrict__ negz = bb_negz(T, ld, rows_cap, nvars);
+    uint8_t* __restrict__ negz = bb_negz(T, ld, rows_cap);
     uint8_t* __restrict__ touched = touched_all + (size_t)blockIdx.x * rows_cap16;
     __shared__ int s_nz, s_rows[256];
     if (tid == 0) s_nz = 0;
@@ -773,7 +773,7 @@ __global__ __launch_bounds__(64) void k_bb_finish(BBSlot* __restrict__ slots, in
     const int R = s.rows, C = s.cols;
     if (k >= C) return;
     double* __restrict__ T = s.cur;
-    uint8_t* __restrict__ negz = bb_negz(T, ld, rows_cap, nvars);
+    uint8_t* __restrict__ negz = bb_negz(T, ld, rows_cap);
     double sum = 0.0;
     int key = R, frow = -1;
     bool big = false;
@@ -913,10 +913,10 @@ void bb_launch_add_constraint(lpr_bb* b, int nslots, int nparents, int rows_max,
     const dim3 egrid((b->ld + 255) / 256, (rows_max + kBBRowsPerThread - 1) / kBBRowsPerThread,
                      nslots);
     hipLaunchKernelGGL(k_bb_child_init, egrid, dim3(256), 0, st, b->d_slots, b->ld, b->touched,
-                       align_up(b->rows_cap, 16), b->rows_cap, b->nvars);
+                       align_up(b->rows_cap, 16), b->rows_cap);
     if (inplace)
         hipLaunchKernelGGL(k_bb_child_inplace, dim3(nslots), dim3(256), 0, st, b->d_slots, b->ld,
-                           b->touched, align_up(b->rows_cap, 16), b->rows_cap, b->nvars);
+                           b->touched, align_up(b->rows_cap, 16), b->rows_cap);
     if (!side)  // (otherwise every parent carries its scan in its own buffer: k_bb_finish)
         hipLaunchKernelGGL(k_bb_basic_scan, dim3((cols_max + 63) / 64, nparents), dim3(64), 0, st,
                            b->d_slots, b->ld, b->bflag, b->bkey);
