@@ -509,6 +509,65 @@ int lpr_sens_add_activity(lpr_sens* s, double c_new, const double* a_new, int32_
 int lpr_sens_add_constraint(lpr_sens* s, const double* tech, int32_t ntech, double rhs,
                             int32_t* outcome);
 
+/* ------------------------------------------------------------------------------------------
+ * Knapsack, menu option 5 (Program.cs:430-470).  The reference calls two classes it never
+ * defines (KnapsackBranchBoundSimplex; KnapsackBranchBoundSolver.cs is an empty class), so the
+ * rules are fixed in DESIGN.md section 11 and restated in tests/ref_py_knapsack.py. */
+
+/* KnapsackBranchBoundSolver.Solve(capacity, weights, values) (Program.cs:465): the 0/1 DP over an
+ * int64 row initialised to 0, *best = dp[capacity].  capacity < 0 or a weight < 0:
+ * LPR_BAD_ARGUMENT.  opts may be NULL; variant 0 = blocked LDS passes where the item weights fit
+ * the halo, 1 = one streaming pass per item (benchmarks and tests only, same result). */
+typedef struct lpr_knap_dp_opts {
+    int32_t variant;
+    int32_t reserved;
+} lpr_knap_dp_opts;
+int lpr_knap_dp(lpr_engine* e, int64_t capacity, const int32_t* weights, const int32_t* values,
+                int32_t n, const lpr_knap_dp_opts* opts, int64_t* best);
+
+typedef struct lpr_knap lpr_knap;
+/* new KnapsackBranchBoundSimplex(capacity, weights, values) (Program.cs:443-447): integral
+ * doubles, 1 <= w_i <= 2^31-1, 0 <= v_i <= 2^31-1, capacity >= 0, 1 <= n <= 8192; anything else
+ * is LPR_BAD_ARGUMENT naming the offending index.  Ranks the items by v/w (exact cross products,
+ * ties to the lower index) and uploads them in rank order. */
+int lpr_knap_bb_create(lpr_engine* e, int64_t capacity, const double* weights,
+                       const double* values, int32_t n, lpr_knap** out);
+int lpr_knap_bb_destroy(lpr_knap* k);
+
+typedef struct lpr_knap_bb_opts {
+    int64_t node_cap;  /* evaluated nodes; <= 0: 2^22.  A level is evaluated only if the total
+                          stays within it, else LPR_BB_NODE_CAP with the incumbent so far */
+    int32_t narrate;   /* node records kept for lpr_knap_bb_nodes_read: 0 none, > 0 the first
+                          `narrate` nodes, < 0 auto (4096 when n <= 64, else none) */
+    int32_t reserved;
+} lpr_knap_bb_opts;
+
+typedef struct lpr_knap_bb_result {
+    int32_t status;     /* LPR_OK_OPTIMAL or LPR_BB_NODE_CAP */
+    int32_t found;      /* an incumbent exists (always, once the root was evaluated) */
+    double z;           /* Z* (Solve(), Program.cs:449) */
+    int64_t evaluated;  /* nodes evaluated */
+    int64_t widest;     /* widest level evaluated */
+    int32_t levels;     /* levels evaluated */
+    int32_t reserved;
+} lpr_knap_bb_result;
+
+/* Solve() (Program.cs:449): the level-synchronous search on the device; opts may be NULL. */
+int lpr_knap_bb_solve(lpr_knap* k, const lpr_knap_bb_opts* opts, lpr_knap_bb_result* res);
+/* rank[p] = original index of the item at rank position p (n entries) */
+int lpr_knap_bb_rank_read(lpr_knap* k, int32_t* rank);
+/* GetSelectedItemsOriginal() (Program.cs:455): the incumbent's items, ascending original index;
+ * ids holds n entries, *count is set */
+int lpr_knap_bb_selected_read(lpr_knap* k, int32_t* ids, int32_t* count);
+int lpr_knap_bb_stats(lpr_knap* k, int32_t* levels, int64_t* evaluated, int64_t* widest);
+/* PrintIterations() (Program.cs:452): node records of the last solve in evaluation order (record
+ * 0 = root): parent record (-1 root), branch (0: x_k = 0, 1: x_k = 1), status (0 fractional,
+ * 1 fractional pruned, 2 integral, 3 infeasible), bound, k (ORIGINAL index of the critical item,
+ * -1 when integral or infeasible), V.  *count = records kept (<= cap). */
+int lpr_knap_bb_nodes_read(lpr_knap* k, int32_t* parent, int32_t* branch, int32_t* status,
+                           double* bound, int32_t* kitem, int64_t* value, int64_t cap,
+                           int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

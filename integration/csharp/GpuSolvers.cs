@@ -1,9 +1,10 @@
 // GpuSolvers.cs -- drop-in bodies for the three solver classes of LPR_381_Group_V22, calling the
 // MI355X engine through NativeMethods.  UNVERIFIED (never compiled: no C# toolchain in the build
 // image).  Public members, argument meaning and error behaviour are those of the reference classes
-// so that Program.cs (cases "1", "2", "3") compiles unchanged when these replace
-// Simplex/PrimalSimplexSolver.cs, Simplex/RevisedPrimalSimplexSolver.cs and
-// IntegerProgramming/BranchAndBoundAdapter.cs.
+// so that Program.cs (cases "1", "2", "3", "5") compiles unchanged when these replace
+// Simplex/PrimalSimplexSolver.cs, Simplex/RevisedPrimalSimplexSolver.cs,
+// IntegerProgramming/BranchAndBoundAdapter.cs and IntegerProgramming/KnapsackBranchBoundSolver.cs
+// (an empty class in the reference; KnapsackBranchBoundSimplex is defined nowhere there).
 using System;
 using System.Collections.Generic;
 using System.Linq;
@@ -258,6 +259,99 @@ namespace LPR_381_Group_V22.IntegerProgramming
                 return res.found != 0 ? (x.Take(nvars).ToList(), res.z) : (new List<double>(), double.NegativeInfinity);   // :23
             }
             finally { NativeMethods.lpr_bb_destroy(bb); }
+        }
+    }
+}
+
+namespace LPR_381_Group_V22.IntegerProgramming
+{
+    /// <summary>An item of GetSelectedItemsOriginal() (Program.cs:455-461): original 0-based index, value, weight.</summary>
+    public sealed class KnapsackItem
+    {
+        public int Id { get; }
+        public double Value { get; }
+        public double Weight { get; }
+        public KnapsackItem(int id, double value, double weight) { Id = id; Value = value; Weight = weight; }
+    }
+
+    /// <summary>
+    /// Menu option 5 (Program.cs:430-470): the level-synchronous knapsack branch-and-bound of DESIGN.md section 11 on the
+    /// device.  Inputs: integral weights 1..2^31-1, values 0..2^31-1, capacity >= 0, 1..8192 items.
+    /// </summary>
+    public class KnapsackBranchBoundSimplex : IDisposable
+    {
+        private IntPtr h;
+        private readonly double[] weights, values;
+        public long NodeCap = 0;      // 0: 2^22 evaluated nodes
+        public int Narrate = -1;      // node records for PrintIterations: -1 auto (4096 when n <= 64), 0 none
+        public int Status { get; private set; }
+        public long Evaluated { get; private set; }
+        public int Levels { get; private set; }
+
+        public KnapsackBranchBoundSimplex(int capacity, double[] weights, double[] values)
+        {
+            this.weights = (double[])weights.Clone();
+            this.values = (double[])values.Clone();
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_bb_create(Engine.Handle, capacity, this.weights, this.values,
+                this.weights.Length, out h), "lpr_knap_bb_create");
+        }
+
+        public double Solve()
+        {
+            var opts = new LprKnapBbOpts { node_cap = NodeCap, narrate = Narrate };
+            Status = NativeMethods.lpr_knap_bb_solve(h, ref opts, out var res);
+            NativeMethods.ThrowIfError(Status, "lpr_knap_bb_solve");
+            Evaluated = res.evaluated;
+            Levels = res.levels;
+            return res.z;
+        }
+
+        /// <summary>One line per node record, the same text as knapsack.py's narration_lines.</summary>
+        public void PrintIterations()
+        {
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_bb_nodes_read(h, null, null, null, null, null, null, 0, out long m), "lpr_knap_bb_nodes_read");
+            int n = (int)m, c = Math.Max(1, n);
+            var par = new int[c]; var br = new int[c]; var st = new int[c]; var kk = new int[c];
+            var bd = new double[c]; var V = new long[c];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_bb_nodes_read(h, par, br, st, bd, kk, V, m, out m), "lpr_knap_bb_nodes_read");
+            string[] statusText = { "fractional", "fractional, pruned", "integral", "infeasible" };
+            var label = new string[c];
+            var fixedText = new string[c];
+            for (int r = 0; r < n; r++)
+            {
+                if (par[r] < 0) { label[r] = "0"; fixedText[r] = ""; }
+                else
+                {
+                    label[r] = (par[r] == 0 ? "" : label[par[r]] + ".") + (br[r] + 1);
+                    string f = $"x{kk[par[r]] + 1}={br[r]}";
+                    fixedText[r] = fixedText[par[r]].Length > 0 ? fixedText[par[r]] + " " + f : f;
+                }
+                string tail = st[r] == 3 ? "bound = -; k = -; V = -"
+                    : $"bound = {bd[r]}; k = {(kk[r] >= 0 ? "x" + (kk[r] + 1) : "-")}; V = {V[r]}";
+                Console.WriteLine($"Node {label[r]}: fixed {(fixedText[r].Length > 0 ? fixedText[r] : "none")}; {statusText[st[r]]}; {tail}");
+            }
+            if (Evaluated > n)
+                Console.WriteLine($"({Evaluated - n} of {Evaluated} nodes in {Levels} levels not recorded)");
+        }
+
+        public List<KnapsackItem> GetSelectedItemsOriginal()
+        {
+            var ids = new int[Math.Max(1, weights.Length)];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_bb_selected_read(h, ids, out int count), "lpr_knap_bb_selected_read");
+            return ids.Take(count).Select(i => new KnapsackItem(i, values[i], weights[i])).ToList();
+        }
+
+        public void Dispose() { if (h != IntPtr.Zero) { NativeMethods.lpr_knap_bb_destroy(h); h = IntPtr.Zero; } }
+    }
+
+    /// <summary>The 0/1 DP cross-check of Program.cs:465 on the device (replaces the empty KnapsackBranchBoundSolver.cs).</summary>
+    public static class KnapsackBranchBoundSolver
+    {
+        public static double Solve(int capacity, int[] weights, int[] values)
+        {
+            var opts = new LprKnapDpOpts();
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_dp(Engine.Handle, capacity, weights, values, weights.Length, ref opts, out long best), "lpr_knap_dp");
+            return best;
         }
     }
 }

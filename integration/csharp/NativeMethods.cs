@@ -22,6 +22,18 @@ namespace LPR_381_Group_V22.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    internal struct LprKnapDpOpts { public int variant; public int reserved; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprKnapBbOpts { public long node_cap; public int narrate; public int reserved; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprKnapBbResult
+    {
+        public int status; public int found; public double z; public long evaluated; public long widest; public int levels; public int reserved;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     internal struct LprSolveResult
     {
         public int status; public int block; public long pivots; public long total_pivots; public double z;
@@ -174,6 +186,16 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_change_nonbasic_column(IntPtr sens, int row, int col, double newVal, out int outcome);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_add_activity(IntPtr sens, double cNew, double[] aNew, int na, out int outcome);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_add_constraint(IntPtr sens, double[] tech, int ntech, double rhs, out int outcome);
+
+        // ---- Knapsack, menu option 5 (Program.cs:430-470): KnapsackBranchBoundSolver.Solve, KnapsackBranchBoundSimplex ----
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_dp(IntPtr engine, long capacity, int[] weights, int[] values, int n, ref LprKnapDpOpts opts, out long best);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_create(IntPtr engine, long capacity, double[] weights, double[] values, int n, out IntPtr knap);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_destroy(IntPtr knap);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_solve(IntPtr knap, ref LprKnapBbOpts opts, out LprKnapBbResult res);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_rank_read(IntPtr knap, int[] rank);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_selected_read(IntPtr knap, int[] ids, out int count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_stats(IntPtr knap, out int levels, out long evaluated, out long widest);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_nodes_read(IntPtr knap, int[] parent, int[] branch, int[] status, double[] bound, int[] kitem, long[] value, long cap, out long count);
 
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 

@@ -9,6 +9,7 @@ from .branch_and_bound import (BranchAndBoundAdapter, BranchBoundTree, Comm,
                                solve_level_sync_native, solve_level_synchronous,
                                torch_collectives)
 from .input_file_parser import Constraint, InputFileParser
+from .knapsack import KnapsackBranchBoundSimplex, KnapsackBranchBoundSolver
 from .primal_simplex_solver import PrimalSimplexSolver
 from .revised_primal_simplex_solver import RevisedPrimalSimplexSolver, SolverException
 
@@ -16,6 +17,6 @@ __all__ = [
     "Engine", "Tableau", "default_engine", "Constraint", "InputFileParser",
     "PrimalSimplexSolver", "RevisedPrimalSimplexSolver", "RevisedState", "SolverException",
     "BranchAndBoundAdapter", "BranchBoundTree", "solve_level_synchronous", "torch_collectives",
-    "Comm", "solve_level_sync_native",
+    "Comm", "solve_level_sync_native", "KnapsackBranchBoundSimplex", "KnapsackBranchBoundSolver",
     "_native",
 ]

@@ -120,6 +120,33 @@ ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
 LPR_COMM_ID_BYTES = 128
 
 
+class KnapDpOpts(C.Structure):
+    _fields_ = [
+        ("variant", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class KnapBBOpts(C.Structure):
+    _fields_ = [
+        ("node_cap", C.c_int64),
+        ("narrate", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class KnapBBResult(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("found", C.c_int32),
+        ("z", C.c_double),
+        ("evaluated", C.c_int64),
+        ("widest", C.c_int64),
+        ("levels", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class BBResult(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -224,6 +251,14 @@ SIGNATURES = {
     "lpr_sens_change_nonbasic_column": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _I32]),
     "lpr_sens_add_activity": (C.c_int, [_P, C.c_double, _D, C.c_int32, _I32]),
     "lpr_sens_add_constraint": (C.c_int, [_P, _D, C.c_int32, C.c_double, _I32]),
+    "lpr_knap_dp": (C.c_int, [_P, C.c_int64, _I32, _I32, C.c_int32, C.POINTER(KnapDpOpts), _I64]),
+    "lpr_knap_bb_create": (C.c_int, [_P, C.c_int64, _D, _D, C.c_int32, _PP]),
+    "lpr_knap_bb_destroy": (C.c_int, [_P]),
+    "lpr_knap_bb_solve": (C.c_int, [_P, C.POINTER(KnapBBOpts), C.POINTER(KnapBBResult)]),
+    "lpr_knap_bb_rank_read": (C.c_int, [_P, _I32]),
+    "lpr_knap_bb_selected_read": (C.c_int, [_P, _I32, _I32]),
+    "lpr_knap_bb_stats": (C.c_int, [_P, _I32, _I64, _I64]),
+    "lpr_knap_bb_nodes_read": (C.c_int, [_P, _I32, _I32, _I32, _D, _I32, _I64, C.c_int64, _I64]),
 }
 
 

@@ -122,6 +122,7 @@ struct lpr_revised;
 struct lpr_bb;
 struct lpr_sens;
 struct lpr_comm;
+struct lpr_knap;
 
 struct lpr_engine {
     int device = 0;
@@ -135,6 +136,7 @@ struct lpr_engine {
     std::vector<lpr_bb*> live_bb;
     std::vector<lpr_sens*> live_sens;
     std::vector<lpr_comm*> live_comm;  // RCCL communicators whose collectives run on this stream
+    std::vector<lpr_knap*> live_knap;  // knapsack branch-and-bound handles (knapsack_engine.hip)
 };
 
 struct lpr_tableau {

@@ -84,6 +84,8 @@ void bb_orphan(lpr_bb* b);
 // sens_engine.hip
 void sens_orphan(lpr_sens* s);
 void comm_orphan(lpr_comm* c);
+// knapsack_engine.hip
+void knap_orphan(lpr_knap* k);
 }  // namespace lpr
 // cut_kernels.hip
 void lpr_cut_release(lpr_tableau* t);
@@ -787,6 +789,8 @@ int lpr_engine_close(lpr_engine* e) {
     e->live_sens.clear();
     for (lpr_comm* c : e->live_comm) comm_orphan(c);
     e->live_comm.clear();
+    for (lpr_knap* k : e->live_knap) knap_orphan(k);
+    e->live_knap.clear();
     if (e->stream) {
         hipStreamSynchronize(e->stream);
         hipStreamDestroy(e->stream);

@@ -4,9 +4,10 @@ CanonicalFormConverter.cs:15-98``) and ``OutputFileWrite`` (``IO/OutputFileWrite
 the same text model file drives the MI355X engine and produces the same ``output_results.txt``
 layout.  Everything numeric goes through the C ABI; this file is text plumbing.
 
+Option 5 (``Program.cs:430-470``) runs the knapsack branch-and-bound and DP of ``knapsack.py``
+under the rules of DESIGN.md section 11 (the reference calls both classes without defining them).
 Not mirrored (not on the pivot path): the sensitivity sub-menu
-(``Program.cs:158-294``), option 5 (does not compile in the reference, ``Program.cs:444,468``) and
-option 6 (golden-section demo).  PARITY UNPINNED for the exact text: the reference commits no
+(``Program.cs:158-294``) and option 6 (golden-section demo).  PARITY UNPINNED for the exact text: the reference commits no
 output file to compare with (``data/output_results.txt`` is empty).
 
     python -m lpr_381_group_v22_amd.program data/model.txt 1 [output_results.txt]
@@ -23,6 +24,7 @@ from typing import List, Optional, Sequence
 from . import table_iteration_formater as fmt
 from .branch_and_bound import BranchAndBoundAdapter
 from .input_file_parser import Constraint, InputFileParser
+from .knapsack import KnapsackBranchBoundSimplex, KnapsackBranchBoundSolver
 from .primal_simplex_solver import PrimalSimplexSolver
 from .revised_primal_simplex_solver import RevisedPrimalSimplexSolver
 
@@ -225,6 +227,37 @@ def run_option(parser: InputFileParser, choice: str, out_path: str = "data/outpu
         display_canonical_form(parser.ProblemType, parser.ObjectiveCoefficients,
                                parser.Constraints, parser.SignRestrictions)
         return {}
+    if choice == "5":  # Program.cs:430-470
+        print("Solving with Branch and Bound Knapsack Algorithm...")
+        capacity = 40
+        weights = [11, 8, 6, 14, 10, 10]
+        values = [2, 3, 3, 5, 2, 4]
+        print("Knapsack Problem")
+        print(f"Capacity: {capacity}")
+        print("Items (Value, Weight):")
+        for i in range(len(values)):
+            print(f"  Item {i + 1}: Value={values[i]}, Weight={weights[i]}")
+        print()
+        solver = KnapsackBranchBoundSimplex(capacity, [float(w) for w in weights],
+                                            [float(v) for v in values], engine=engine)
+        branchBoundResult = solver.Solve()
+        print("=== Branch and Bound Detailed Steps ===")
+        solver.PrintIterations()
+        chosen = solver.GetSelectedItemsOriginal()
+        print("\nChosen items (original numbering):")
+        totalW = 0
+        for it in chosen:
+            print(f"  x{it.Id + 1} = 1  (Value={dotnet_double_to_string(it.Value)}, "
+                  f"Weight={dotnet_double_to_string(it.Weight)})")
+            totalW += int(it.Weight)
+        print(f"Total Weight = {totalW}")
+        print(f"Branch & Bound Best Value Z* = {dotnet_double_to_string(branchBoundResult)}")
+        print("\n=== Comparison with Dynamic Programming ===")
+        dp = KnapsackBranchBoundSolver.Solve(capacity, weights, values, engine=engine)
+        print(f"Dynamic Programming Result: {dotnet_double_to_string(dp)}")
+        print(f"Results Match: {abs(dp - branchBoundResult) < 1e-6}")
+        solver.destroy()
+        return {"z": branchBoundResult, "dp": dp, "chosen": chosen, "solver": solver}
     print("Invalid choice. Please select a valid option (1-6).")
     return {}
 
