@@ -568,6 +568,66 @@ int lpr_knap_bb_nodes_read(lpr_knap* k, int32_t* parent, int32_t* branch, int32_
                            double* bound, int32_t* kitem, int64_t* value, int64_t cap,
                            int64_t* count);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched primal simplex.  One handle holds `count` independent LPs; one
+ * solve call runs PrimalSimplexSolver's loop for every LP on the device, with its rules per LP
+ * bit for bit: each LP ends with the bytes lpr_primal_solve (and the oracle) give for it alone.
+ * Shapes up to 1024 rows x 2048 columns (form H); a larger LP is LPR_BAD_ARGUMENT, to be solved
+ * alone with lpr_primal_solve.  The reference has no batch mode; every call cites the C# lines
+ * it repeats per LP. */
+typedef struct lpr_batch lpr_batch;
+
+/* new PrimalSimplexSolver(objective, constraints, isMaximization) per LP
+ * (Simplex/PrimalSimplexSolver.cs:27-87), built on the device with the bytes of
+ * lpr_tableau_from_lp.  count LPs; n[k], m[k] >= 0 with n[k] + m[k] >= 1; objective packed by
+ * n[k]; A packed as m[k] x n[k] row-major blocks; ncoef (NULL: full rows; else in [0, n[k]]),
+ * relation (LPR_REL_LE/GE/EQ) and rhs packed by m[k]; is_max per LP.  log_cap: pivot-log pairs
+ * kept per LP (0: 4 * (rows + cols), at most 4096). */
+int lpr_batch_from_lps(lpr_engine* e, int32_t count, const int32_t* n, const int32_t* m,
+                       const double* objective, const double* A, const int32_t* ncoef,
+                       const int8_t* relation, const double* rhs, const int8_t* is_max,
+                       int32_t log_cap, lpr_batch** out);
+/* Ready tableaux (lpr_tableau_create per LP, BranchAndBoundAdapter.cs:31-46) packed as
+ * rows[k] x cols[k] row-major blocks; basis packed by rows[k] - 1 (NULL: -1).  The decision
+ * variables of LP k are its first max(0, cols[k] - rows[k]) columns ([A | I | b]). */
+int lpr_batch_create(lpr_engine* e, int32_t count, const int32_t* rows, const int32_t* cols,
+                     const double* tableaux, const int32_t* basis, int32_t log_cap,
+                     lpr_batch** out);
+int lpr_batch_destroy(lpr_batch* b);
+
+typedef struct lpr_batch_opts {
+    int64_t max_pivots;  /* per LP, per call, as in lpr_primal_solve (<= 0: uncapped) */
+    int32_t chunk;       /* pivots per LP per launch (0: by form) */
+    int32_t variant;     /* 0 auto; 1 / 2 / 3 force form W / G / H on the LPs that fit it (tests
+                            and tuning only, same bits) */
+} lpr_batch_opts;
+
+typedef struct lpr_batch_result {
+    int32_t optimal, unbounded, limit;  /* LPs in each state after this call */
+    int32_t launches;                   /* solve kernels launched by this call */
+    int64_t pivots;                     /* pivots performed by this call, all LPs */
+} lpr_batch_result;
+
+/* PrimalSimplexSolver.Solve() (:102-150) for every LP not yet finished: FindEnteringVariable
+ * (:152-167) -> FindLeavingVariable (:169-191) -> Pivot (:193-211) -> basicVariables[r-1] = e
+ * (:142) until optimal / unbounded / max_pivots.  An LP at LPR_PIVOT_LIMIT resumes on the next
+ * call; finished LPs stay finished.  Returns LPR_OK_OPTIMAL unless the call itself failed. */
+int lpr_batch_solve(lpr_batch* b, const lpr_batch_opts* opts, lpr_batch_result* res);
+/* Status, pivots so far (C# `iteration`, :138) and T[0, cols-1] (FinalZ, :113: the host mirror
+ * keeps 0 on the unbounded exit) of every LP; count entries each, any may be NULL. */
+int lpr_batch_status_read(lpr_batch* b, int32_t* status, int64_t* pivots, double* z);
+/* ExtractSolution() (:213-252) of every LP, packed by n[k]; 0 for LPs that are not optimal. */
+int lpr_batch_solution_read(lpr_batch* b, double* x);
+/* basicVariables (:18-24) of every LP, packed by rows[k] - 1 (m[k]). */
+int lpr_batch_basis_read(lpr_batch* b, int32_t* basis);
+/* Pivot log of LP k, row 1-based as at :138: *count = min(pivots, log_cap, cap) pairs. */
+int lpr_batch_log_read(lpr_batch* b, int32_t k, int32_t* rows, int32_t* cols, int64_t cap,
+                       int64_t* count);
+/* GetFinalTableau() (:269-278) of LP k: rows[k] x cols[k] row-major. */
+int lpr_batch_tableau_read(lpr_batch* b, int32_t k, double* rowmajor);
+/* rows, cols and decision variables n of LP k; any may be NULL. */
+int lpr_batch_shape(lpr_batch* b, int32_t k, int32_t* rows, int32_t* cols, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,96 @@ namespace LPR_381_Group_V22.Simplex
         public void Dispose() { if (Tableau != IntPtr.Zero) { NativeMethods.lpr_tableau_destroy(Tableau); Tableau = IntPtr.Zero; } }
     }
 
+    /// <summary>
+    /// Many PrimalSimplexSolver models in one call (no reference counterpart: the reference solves one model per
+    /// object).  Each LP is built and solved on the device with the rules of PrimalSimplexSolver.cs, the same bits a
+    /// PrimalSimplexSolver gives for it alone; members are per-LP versions of that class's.
+    /// </summary>
+    public class PrimalSimplexBatch : IDisposable
+    {
+        private IntPtr batch;                           // lpr_batch*
+        private readonly int[] rows, cols, nvars;
+        public int Count { get; }
+        public List<int> Status { get; } = new List<int>();
+        public List<long> Iterations { get; } = new List<long>();
+        public List<double> FinalZ { get; } = new List<double>();
+        public List<List<double>> SolutionVector { get; } = new List<List<double>>();
+
+        public PrimalSimplexBatch(List<(List<double> objective, List<IOConstraint> constraints, bool isMaximization)> models, int logCap = 0)
+        {
+            Count = models.Count;
+            var n = new int[Count]; var m = new int[Count]; var isMax = new sbyte[Count];
+            var obj = new List<double>(); var A = new List<double>(); var ncoef = new List<int>();
+            var rel = new List<sbyte>(); var rhs = new List<double>();
+            rows = new int[Count]; cols = new int[Count]; nvars = new int[Count];
+            for (int k = 0; k < Count; k++)
+            {
+                var (objective, constraints, isMaximization) = models[k];
+                n[k] = objective.Count; m[k] = constraints.Count; isMax[k] = (sbyte)(isMaximization ? 1 : 0);
+                obj.AddRange(objective);
+                foreach (var c in constraints)
+                {
+                    int cnt = Math.Min(n[k], c.Coefficients.Count);        // PrimalSimplexSolver.cs:68-72
+                    for (int j = 0; j < n[k]; j++) A.Add(j < cnt ? c.Coefficients[j] : 0.0);
+                    ncoef.Add(cnt);
+                    rel.Add((sbyte)(c.Relation == ">=" ? 1 : c.Relation == "=" ? 2 : 0));
+                    rhs.Add(c.RHS);
+                }
+                rows[k] = m[k] + 1; cols[k] = n[k] + m[k] + 1; nvars[k] = n[k];
+            }
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_from_lps(Engine.Handle, Count, n, m, NonEmpty(obj), NonEmpty(A),
+                NonEmpty(ncoef), NonEmpty(rel), NonEmpty(rhs), isMax, logCap, out batch), "lpr_batch_from_lps");
+        }
+
+        private static T[] NonEmpty<T>(List<T> l) => l.Count > 0 ? l.ToArray() : new T[1];
+
+        /// <summary>Solve() of every unfinished LP; an LP stopped by maxPivots resumes on the next call.</summary>
+        public void Solve(long maxPivots = 0)
+        {
+            var opts = new LprBatchOpts { max_pivots = maxPivots };
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_solve(batch, ref opts, out _), "lpr_batch_solve");
+            var st = new int[Count]; var piv = new long[Count]; var z = new double[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_status_read(batch, st, piv, z), "lpr_batch_status_read");
+            var x = new double[Math.Max(1, nvars.Sum())];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_solution_read(batch, x), "lpr_batch_solution_read");
+            Status.Clear(); Iterations.Clear(); FinalZ.Clear(); SolutionVector.Clear();
+            for (int k = 0, at = 0; k < Count; at += nvars[k], k++)
+            {
+                Status.Add(st[k]); Iterations.Add(piv[k]);
+                bool optimal = st[k] == (int)LprStatus.Optimal;
+                FinalZ.Add(optimal ? z[k] : 0.0);                          // :113; stays 0 on the unbounded exit
+                SolutionVector.Add(optimal ? x.Skip(at).Take(nvars[k]).ToList() : null);
+            }
+        }
+
+        public List<int> BasicVariables(int k)
+        {
+            var b = new int[Math.Max(1, rows.Sum() - Count)];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_basis_read(batch, b), "lpr_batch_basis_read");
+            return b.Skip(rows.Take(k).Sum() - k).Take(rows[k] - 1).ToList();
+        }
+
+        public List<(int row, int col)> PivotLog(int k)
+        {
+            const int cap = 1 << 16;
+            var r = new int[cap]; var c = new int[cap];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_log_read(batch, k, r, c, cap, out long count), "lpr_batch_log_read");
+            var log = new List<(int, int)>();
+            for (long q = 0; q < count; q++) log.Add((r[q], c[q]));
+            return log;
+        }
+
+        public double[,] GetFinalTableau(int k)
+        {
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_shape(batch, k, out int r, out int c, out _), "lpr_batch_shape");
+            var t = new double[r, c];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_tableau_read(batch, k, t), "lpr_batch_tableau_read");
+            return t;
+        }
+
+        public void Dispose() { if (batch != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_batch_destroy(batch), "lpr_batch_destroy"); batch = IntPtr.Zero; } }
+    }
+
     public class RevisedPrimalSimplexSolver : IDisposable
     {
         private readonly int n, m;

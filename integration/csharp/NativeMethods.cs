@@ -34,6 +34,12 @@ namespace LPR_381_Group_V22.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    internal struct LprBatchOpts { public long max_pivots; public int chunk; public int variant; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprBatchResult { public int optimal, unbounded, limit, launches; public long pivots; }
+
+    [StructLayout(LayoutKind.Sequential)]
     internal struct LprSolveResult
     {
         public int status; public int block; public long pivots; public long total_pivots; public double z;
@@ -196,6 +202,18 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_selected_read(IntPtr knap, int[] ids, out int count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_stats(IntPtr knap, out int levels, out long evaluated, out long widest);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_bb_nodes_read(IntPtr knap, int[] parent, int[] branch, int[] status, double[] bound, int[] kitem, long[] value, long cap, out long count);
+
+        // ---- Batched primal simplex (DESIGN.md section 12): PrimalSimplexSolver per LP, many LPs per call ----
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_from_lps(IntPtr engine, int count, int[] n, int[] m, double[] objective, double[] A, int[] ncoef, sbyte[] relation, double[] rhs, sbyte[] is_max, int log_cap, out IntPtr batch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_create(IntPtr engine, int count, int[] rows, int[] cols, double[] tableaux, int[] basis, int log_cap, out IntPtr batch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_destroy(IntPtr batch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_solve(IntPtr batch, ref LprBatchOpts opts, out LprBatchResult res);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_status_read(IntPtr batch, int[] status, long[] pivots, double[] z);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_solution_read(IntPtr batch, double[] x);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_basis_read(IntPtr batch, int[] basis);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_log_read(IntPtr batch, int k, int[] rows, int[] cols, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_tableau_read(IntPtr batch, int k, [Out] double[,] rowmajor);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_shape(IntPtr batch, int k, out int rows, out int cols, out int n);
 
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 

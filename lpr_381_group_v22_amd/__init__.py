@@ -10,6 +10,7 @@ from .branch_and_bound import (BranchAndBoundAdapter, BranchBoundTree, Comm,
                                torch_collectives)
 from .input_file_parser import Constraint, InputFileParser
 from .knapsack import KnapsackBranchBoundSimplex, KnapsackBranchBoundSolver
+from .primal_batch import PrimalSimplexBatch, pack_models
 from .primal_simplex_solver import PrimalSimplexSolver
 from .revised_primal_simplex_solver import RevisedPrimalSimplexSolver, SolverException
 
@@ -18,5 +19,5 @@ __all__ = [
     "PrimalSimplexSolver", "RevisedPrimalSimplexSolver", "RevisedState", "SolverException",
     "BranchAndBoundAdapter", "BranchBoundTree", "solve_level_synchronous", "torch_collectives",
     "Comm", "solve_level_sync_native", "KnapsackBranchBoundSimplex", "KnapsackBranchBoundSolver",
-    "_native",
+    "PrimalSimplexBatch", "pack_models", "_native",
 ]

@@ -147,6 +147,24 @@ class KnapBBResult(C.Structure):
     ]
 
 
+class BatchOpts(C.Structure):
+    _fields_ = [
+        ("max_pivots", C.c_int64),
+        ("chunk", C.c_int32),
+        ("variant", C.c_int32),
+    ]
+
+
+class BatchResult(C.Structure):
+    _fields_ = [
+        ("optimal", C.c_int32),
+        ("unbounded", C.c_int32),
+        ("limit", C.c_int32),
+        ("launches", C.c_int32),
+        ("pivots", C.c_int64),
+    ]
+
+
 class BBResult(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -259,6 +277,17 @@ SIGNATURES = {
     "lpr_knap_bb_selected_read": (C.c_int, [_P, _I32, _I32]),
     "lpr_knap_bb_stats": (C.c_int, [_P, _I32, _I64, _I64]),
     "lpr_knap_bb_nodes_read": (C.c_int, [_P, _I32, _I32, _I32, _D, _I32, _I64, C.c_int64, _I64]),
+    "lpr_batch_from_lps": (C.c_int, [_P, C.c_int32, _I32, _I32, _D, _D, _I32, _I8, _D, _I8,
+                                     C.c_int32, _PP]),
+    "lpr_batch_create": (C.c_int, [_P, C.c_int32, _I32, _I32, _D, _I32, C.c_int32, _PP]),
+    "lpr_batch_destroy": (C.c_int, [_P]),
+    "lpr_batch_solve": (C.c_int, [_P, C.POINTER(BatchOpts), C.POINTER(BatchResult)]),
+    "lpr_batch_status_read": (C.c_int, [_P, _I32, _I64, _D]),
+    "lpr_batch_solution_read": (C.c_int, [_P, _D]),
+    "lpr_batch_basis_read": (C.c_int, [_P, _I32]),
+    "lpr_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, _I32, C.c_int64, _I64]),
+    "lpr_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
+    "lpr_batch_shape": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32]),
 }
 
 

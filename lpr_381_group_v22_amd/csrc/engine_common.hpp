@@ -123,6 +123,7 @@ struct lpr_bb;
 struct lpr_sens;
 struct lpr_comm;
 struct lpr_knap;
+struct lpr_batch;
 
 struct lpr_engine {
     int device = 0;
@@ -137,6 +138,7 @@ struct lpr_engine {
     std::vector<lpr_sens*> live_sens;
     std::vector<lpr_comm*> live_comm;  // RCCL communicators whose collectives run on this stream
     std::vector<lpr_knap*> live_knap;  // knapsack branch-and-bound handles (knapsack_engine.hip)
+    std::vector<lpr_batch*> live_batch;  // batched primal simplex handles (batch_engine.hip)
 };
 
 struct lpr_tableau {

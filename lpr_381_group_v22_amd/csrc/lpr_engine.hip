@@ -86,6 +86,8 @@ void sens_orphan(lpr_sens* s);
 void comm_orphan(lpr_comm* c);
 // knapsack_engine.hip
 void knap_orphan(lpr_knap* k);
+// batch_engine.hip
+void batch_orphan(lpr_batch* b);
 }  // namespace lpr
 // cut_kernels.hip
 void lpr_cut_release(lpr_tableau* t);
@@ -791,6 +793,8 @@ int lpr_engine_close(lpr_engine* e) {
     e->live_comm.clear();
     for (lpr_knap* k : e->live_knap) knap_orphan(k);
     e->live_knap.clear();
+    for (lpr_batch* b : e->live_batch) batch_orphan(b);
+    e->live_batch.clear();
     if (e->stream) {
         hipStreamSynchronize(e->stream);
         hipStreamDestroy(e->stream);

@@ -1,0 +1,269 @@
+"""Many independent ``PrimalSimplexSolver`` runs in one call (lpr_batch_*).
+
+Every LP of a batch is built and solved on the MI355X with the rules of
+Simplex/PrimalSimplexSolver.cs, the same bits ``PrimalSimplexSolver`` gives for that LP alone.
+The reference has no batch mode: the members below are per-LP lists / accessors named after the
+single-model mirror (primal_simplex_solver.py), and the batch keeps no iteration snapshots.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import numbers
+from typing import List, NamedTuple, Optional, Sequence
+
+import numpy as np
+
+from . import _native as N
+from .engine import Engine, default_engine
+
+
+class PackedModels(NamedTuple):
+    """The packed arrays of lpr_batch_from_lps."""
+    n: np.ndarray          # int32, per LP
+    m: np.ndarray          # int32, per LP
+    objective: np.ndarray  # float64, packed by n
+    A: np.ndarray          # float64, m x n row-major blocks
+    ncoef: np.ndarray      # int32, packed by m
+    relation: np.ndarray   # int8, packed by m
+    rhs: np.ndarray        # float64, packed by m
+    is_max: np.ndarray     # int8, per LP
+
+
+def _number(v, what: str) -> float:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (numbers.Real, np.floating,
+                                                                np.integer)):
+        raise ValueError(f"{what} is not a number: {v!r}")
+    return float(v)
+
+
+def _numbers(vals, what: str) -> np.ndarray:
+    a = np.asarray(list(vals))
+    if a.size and a.dtype.kind not in "fiu":  # bools, strings and objects are refused
+        raise ValueError(f"{what} holds entries that are not numbers")
+    return a.astype(np.float64).reshape(-1)
+
+
+def pack_models(models) -> PackedModels:
+    """``(objective, constraints, isMaximization)`` triples -> the packed ABI arrays.
+
+    The same flattening ``PrimalSimplexSolver`` does per model: a row keeps its first
+    ``min(n, len(Coefficients))`` coefficients (PrimalSimplexSolver.cs:68-72); ">=" and "=" map to
+    their relation codes, anything else is "<=" (:36-50).  Raises ValueError on malformed input."""
+    try:
+        models = list(models)
+    except TypeError:
+        raise ValueError("models must be a sequence of (objective, constraints, isMaximization)")
+    if not models:
+        raise ValueError("no models")
+    ns, ms, obj, A, nc, rel, rhs, mx = [], [], [], [], [], [], [], []
+    for k, model in enumerate(models):
+        try:
+            objective, constraints, is_max = model
+        except (TypeError, ValueError):
+            raise ValueError(f"model {k} is not an (objective, constraints, isMaximization) triple")
+        if isinstance(objective, (str, bytes)) or isinstance(constraints, (str, bytes)):
+            raise ValueError(f"model {k}: objective and constraints must be sequences")
+        try:
+            c = _numbers(objective, f"model {k} objective")
+            cons = list(constraints)
+        except TypeError:
+            raise ValueError(f"model {k}: objective and constraints must be sequences")
+        if not isinstance(is_max, (bool, np.bool_, numbers.Integral)):
+            raise ValueError(f"model {k}: isMaximization must be a bool")
+        n, m = len(c), len(cons)
+        if n + m == 0:
+            raise ValueError(f"model {k} has neither variables nor constraints")
+        block = np.zeros((m, n))
+        for i, con in enumerate(cons):
+            try:
+                coeffs, relation, b = con.Coefficients, con.Relation, con.RHS
+            except AttributeError:
+                raise ValueError(f"model {k} constraint {i} has no Coefficients / Relation / RHS")
+            if not isinstance(relation, str):
+                raise ValueError(f"model {k} constraint {i}: Relation must be a string")
+            try:
+                coeffs = list(coeffs)
+            except TypeError:
+                raise ValueError(f"model {k} constraint {i}: Coefficients must be a sequence")
+            cnt = min(n, len(coeffs))
+            block[i, :cnt] = _numbers(coeffs[:cnt], f"model {k} constraint {i} coefficients")
+            nc.append(cnt)
+            rel.append(N.LPR_REL_GE if relation == ">=" else
+                       (N.LPR_REL_EQ if relation == "=" else N.LPR_REL_LE))
+            rhs.append(_number(b, f"model {k} constraint {i} RHS"))
+        ns.append(n)
+        ms.append(m)
+        obj.append(c)
+        A.append(block.reshape(-1))
+        mx.append(1 if is_max else 0)
+    return PackedModels(
+        np.asarray(ns, dtype=np.int32), np.asarray(ms, dtype=np.int32),
+        np.concatenate(obj).astype(np.float64),
+        np.concatenate(A).astype(np.float64) if A else np.zeros(0),
+        np.asarray(nc, dtype=np.int32), np.asarray(rel, dtype=np.int8),
+        np.asarray(rhs, dtype=np.float64), np.asarray(mx, dtype=np.int8))
+
+
+def _ptr(a: np.ndarray, ctype):
+    return a.ctypes.data_as(C.POINTER(ctype)) if a.size else None
+
+
+class PrimalSimplexBatch:
+    """``count`` PrimalSimplexSolver models in one device handle.
+
+    ``Status[k]``, ``FinalZ[k]`` (0.0 unless optimal, as the C# leaves it on the unbounded exit),
+    ``SolutionVector[k]`` (None unless optimal) and ``Iterations[k]`` are set by ``Solve``;
+    ``BasicVariables(k)``, ``PivotLog(k)`` and ``GetFinalTableau(k)`` read LP k."""
+
+    def __init__(self, models, engine: Optional[Engine] = None, log_cap: int = 0):
+        p = pack_models(models)
+        self._init(engine)
+        h = C.c_void_p()
+        N.check(N.lib.lpr_batch_from_lps(
+            self._engine._h, len(p.n), _ptr(p.n, C.c_int32), _ptr(p.m, C.c_int32),
+            _ptr(p.objective, C.c_double), _ptr(p.A, C.c_double), _ptr(p.ncoef, C.c_int32),
+            _ptr(p.relation, C.c_int8), _ptr(p.rhs, C.c_double), _ptr(p.is_max, C.c_int8),
+            int(log_cap), C.byref(h)), "lpr_batch_from_lps")
+        self._attach(h, [(int(m) + 1, int(n) + int(m) + 1, int(n)) for n, m in zip(p.n, p.m)],
+                     log_cap)
+
+    @classmethod
+    def from_parsers(cls, parsers, engine: Optional[Engine] = None,
+                     log_cap: int = 0) -> "PrimalSimplexBatch":
+        """One LP per InputFileParser, maximising unless ProblemType is "min" (program.py)."""
+        models = [(p.ObjectiveCoefficients, p.Constraints,
+                   (p.ProblemType or "").lower() != "min") for p in parsers]
+        return cls(models, engine=engine, log_cap=log_cap)
+
+    @classmethod
+    def from_tableaux(cls, tableaux: Sequence[np.ndarray], bases=None,
+                      engine: Optional[Engine] = None, log_cap: int = 0) -> "PrimalSimplexBatch":
+        """Ready (rows x cols) tableaux, with their bases (rows - 1 entries each) or None."""
+        self = cls.__new__(cls)
+        self._init(engine)
+        T = [np.ascontiguousarray(t, dtype=np.float64) for t in tableaux]
+        if not T or any(t.ndim != 2 for t in T):
+            raise ValueError("tableaux must be a non-empty list of 2-D arrays")
+        rows = np.asarray([t.shape[0] for t in T], dtype=np.int32)
+        cols = np.asarray([t.shape[1] for t in T], dtype=np.int32)
+        flat = np.concatenate([t.reshape(-1) for t in T])
+        b = None
+        if bases is not None:
+            b = np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in bases] +
+                               [np.zeros(0, dtype=np.int32)])
+            if b.size != int(np.sum(rows - 1)):
+                raise ValueError("bases must hold rows - 1 entries per tableau")
+        h = C.c_void_p()
+        N.check(N.lib.lpr_batch_create(self._engine._h, len(T), _ptr(rows, C.c_int32),
+                                       _ptr(cols, C.c_int32), _ptr(flat, C.c_double),
+                                       None if b is None else _ptr(b, C.c_int32), int(log_cap),
+                                       C.byref(h)), "lpr_batch_create")
+        self._attach(h, [(int(r), int(c), max(0, int(c) - int(r))) for r, c in zip(rows, cols)],
+                     log_cap)
+        return self
+
+    def _init(self, engine: Optional[Engine]) -> None:
+        self._engine = engine or default_engine()
+        self._h = None
+
+    def _attach(self, h: C.c_void_p, shapes, log_cap: int) -> None:
+        """shapes: (rows, cols, n) per LP, as lpr_batch_shape reports them."""
+        self._h = h
+        self._shapes = shapes
+        # pairs kept per LP (include/lpr_engine.h: 0 means 4 * (rows + cols), at most 4096)
+        self._log_caps = [int(log_cap) if log_cap > 0 else min(4096, 4 * (r + c))
+                          for r, c, _ in shapes]
+        self._basis = None
+        self.Count = len(shapes)
+        self.Status: List[Optional[int]] = [None] * self.Count
+        self.FinalZ: List[float] = [0.0] * self.Count
+        self.SolutionVector: List[Optional[List[float]]] = [None] * self.Count
+        self.Iterations: List[int] = [0] * self.Count
+        self.LastResult: Optional[N.BatchResult] = None
+
+    def destroy(self) -> None:
+        if self._h:
+            N.lib.lpr_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    # -- Solve :102-150, per LP ------------------------------------------------------------
+    def Solve(self, max_pivots: int = 0, chunk: int = 0, variant: int = 0) -> N.BatchResult:
+        opts = N.BatchOpts(max_pivots=int(max_pivots), chunk=int(chunk), variant=int(variant))
+        res = N.BatchResult()
+        N.check(N.lib.lpr_batch_solve(self._h, C.byref(opts), C.byref(res)), "lpr_batch_solve")
+        self.LastResult = res
+        self._basis = None
+        st, piv, z = self.status_arrays()
+        x = self.solution_packed()
+        at = 0
+        for k, (_, _, n) in enumerate(self._shapes):
+            self.Status[k] = int(st[k])
+            self.Iterations[k] = int(piv[k])
+            if st[k] == N.LPR_OK_OPTIMAL:  # :110-126
+                self.FinalZ[k] = float(z[k])
+                self.SolutionVector[k] = [float(v) for v in x[at:at + n]]
+            else:  # :129-135 keeps FinalZ = 0 and SolutionVector null
+                self.FinalZ[k] = 0.0
+                self.SolutionVector[k] = None
+            at += n
+        return res
+
+    # -- bulk reads ------------------------------------------------------------------------
+    def status_arrays(self):
+        """(status int32[count], pivots int64[count], T[0, cols-1] float64[count])."""
+        st = np.zeros(self.Count, dtype=np.int32)
+        piv = np.zeros(self.Count, dtype=np.int64)
+        z = np.zeros(self.Count, dtype=np.float64)
+        N.check(N.lib.lpr_batch_status_read(self._h, _ptr(st, C.c_int32), _ptr(piv, C.c_int64),
+                                            _ptr(z, C.c_double)), "lpr_batch_status_read")
+        return st, piv, z
+
+    def solution_packed(self) -> np.ndarray:
+        x = np.zeros(max(sum(s[2] for s in self._shapes), 1), dtype=np.float64)
+        N.check(N.lib.lpr_batch_solution_read(self._h, _ptr(x, C.c_double)),
+                "lpr_batch_solution_read")
+        return x[:sum(s[2] for s in self._shapes)]
+
+    def basis_packed(self) -> np.ndarray:
+        total = sum(s[0] - 1 for s in self._shapes)
+        b = np.zeros(max(total, 1), dtype=np.int32)
+        N.check(N.lib.lpr_batch_basis_read(self._h, _ptr(b, C.c_int32)), "lpr_batch_basis_read")
+        return b[:total]
+
+    # -- per-LP reads :18-24, 269-278 --------------------------------------------------------
+    def Shape(self, k: int):
+        """(rows, cols, n) of LP k."""
+        return self._shapes[k]
+
+    def BasicVariables(self, k: int) -> List[int]:
+        if self._basis is None:  # one packed read per solve
+            self._basis = self.basis_packed()
+            self._basis_at = np.concatenate([[0], np.cumsum([s[0] - 1 for s in self._shapes])])
+        at = int(self._basis_at[k])
+        return [int(v) for v in self._basis[at:at + self._shapes[k][0] - 1]]
+
+    def PivotLog(self, k: int, cap: Optional[int] = None) -> np.ndarray:
+        """(row, column) of every pivot kept, row 1-based as in the console line of :138."""
+        if cap is None:
+            cap = self._log_caps[k]
+        rows = np.zeros(max(cap, 1), dtype=np.int32)
+        cols = np.zeros(max(cap, 1), dtype=np.int32)
+        cnt = C.c_int64()
+        N.check(N.lib.lpr_batch_log_read(self._h, int(k), _ptr(rows, C.c_int32),
+                                         _ptr(cols, C.c_int32), int(cap), C.byref(cnt)),
+                "lpr_batch_log_read")
+        n = cnt.value
+        return np.stack([rows[:n], cols[:n]], axis=1)
+
+    def GetFinalTableau(self, k: int) -> np.ndarray:
+        r, c, _ = self._shapes[k]
+        out = np.empty((r, c), dtype=np.float64)
+        N.check(N.lib.lpr_batch_tableau_read(self._h, int(k), _ptr(out, C.c_double)),
+                "lpr_batch_tableau_read")
+        return out
