@@ -122,8 +122,10 @@ typedef struct lpr_solve_opts {
     int32_t batch;         /* pivots queued between host polls of the device status word (0: auto) */
     int32_t variant;       /* kernel variant (0: auto); for tuning and tests only, same bits.  Low 16
                               bits: path + sweep tile (0x30tr two-stream overlap, 0x40tr heads then
-                              in-place sweep, 0x50tr one-launch overlap, 0x60tr one launch per head;
-                              tr = 0x04/0x08/0x10 rows per chunk, 0x24/0x28 two chunks in flight).
+                              in-place sweep; tr = 0x04/0x08/0x10 rows per chunk, 0x24/0x28 two
+                              chunks in flight).  0x50tr and 0x60tr named forms since retired and
+                              are accepted as aliases of 0x30tr and 0x40tr (so 0x60tr with block > 8
+                              now runs `block` pivots per sweep, where it used to cap them at 8).
                               Bits 16..23, K-pivot paths: 0x10000 diagnostic time stamps of the loop
                               heads, 0x20000 loop heads not confined to one XCD, 0x40000 confined
                               but hand-offs through the memory side, 0x80000 the sweep does not

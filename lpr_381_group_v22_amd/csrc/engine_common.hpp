@@ -173,20 +173,19 @@ struct lpr_tableau {
     int graph_batch = 0;
     int graph_variant = -1;
     // every kernel argument a capture bakes in: a graph is replayed only while all of them still
-    // hold (the fused / overlapped paths swap T and T2, the cut path grows rows, the log and the
-    // block scratch are re-allocated on demand)
+    // hold (the fused / overlapped paths swap T and T2, the cut path grows rows, the log is
+    // re-allocated on demand)
     struct GraphKey {
-        const void *T = nullptr, *T2 = nullptr, *log = nullptr, *basis = nullptr, *blk = nullptr;
+        const void *T = nullptr, *T2 = nullptr, *log = nullptr, *basis = nullptr;
         const void *next_col = nullptr, *colbuf = nullptr;
         int rows = 0, cols = 0, ld = 0;
         bool operator==(const GraphKey& o) const {
-            return T == o.T && T2 == o.T2 && log == o.log && basis == o.basis && blk == o.blk &&
+            return T == o.T && T2 == o.T2 && log == o.log && basis == o.basis &&
                    next_col == o.next_col && colbuf == o.colbuf && rows == o.rows &&
                    cols == o.cols && ld == o.ld;
         }
     } graph_key;
     void* ov = nullptr;               // lpr_overlap_ctx of the overlapped K-pivot path (overlap_kernels.hip)
-    void* blk = nullptr;              // lpr_block_ctx of the K-pivots-per-sweep path (block_kernels.hip)
     void* cut = nullptr;              // lpr_cut_ctx of the cutting-plane side path (cut_kernels.hip)
     void* small = nullptr;            // lpr_small_ctx of the cache-resident path (small_kernels.hip)
 };

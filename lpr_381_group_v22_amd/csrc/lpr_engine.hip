@@ -37,16 +37,6 @@ void launch_build(lpr_tableau* t, int n, int m, const double* d_obj, const doubl
                   const int32_t* d_ncoef, const int8_t* d_rel, const double* d_rhs, int is_max);
 void launch_synthetic(lpr_tableau* t, int m, int n, uint64_t seed);
 
-// block_kernels.hip
-int blk_max_pivots();
-void blk_release(lpr_tableau* t);
-int blk_ensure(lpr_tableau* t);
-int blk_upload_state(lpr_tableau* t, int64_t iter, int64_t max_iter);
-int blk_set_log_cap(lpr_tableau* t);
-int blk_poll(lpr_tableau* t, int32_t* status, int32_t* pending, int64_t* iter);
-void blk_launch_bootstrap(lpr_tableau* t);
-void blk_launch_heads(lpr_tableau* t, int K);
-void blk_launch_update(lpr_tableau* t, int tr);
 // overlap_kernels.hip
 int ov_max_pivots();
 void ov_release(lpr_tableau* t);
@@ -62,7 +52,6 @@ int small_poll(lpr_tableau* t, int32_t* status, int64_t* iter);
 int ov_ensure(lpr_tableau* t, bool second_buffer);
 int ov_begin(lpr_tableau* t, int64_t iter, int64_t max_iter);
 int ov_set_log(lpr_tableau* t, int parity);
-void ov_launch_step(lpr_tableau* t, int K, int tr, int lp);
 void ov_launch_heads(lpr_tableau* t, int K, int flags);
 int ov2_begin(lpr_tableau* t);
 int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t ev_start,
@@ -95,7 +84,7 @@ namespace lpr {
 
 enum : int { kSelEnter = 1, kSelLeave = 2, kSelCommit = 4, kSelFull = 7 };
 constexpr int kTimeStride = 4;  // opts.time_kernels samples one update launch in four (one-pivot
-                                // and 0x60tr paths; the overlapped paths time every sweep)
+                                // path; the K-pivot paths time every sweep)
 
 static int alloc_tableau(lpr_engine* e, int rows, int cols, lpr_tableau** out) {
     if (!e || !out || rows < 1 || cols < 2 || rows > 65535) {
@@ -111,7 +100,7 @@ static int alloc_tableau(lpr_engine* e, int rows, int cols, lpr_tableau** out) {
     t->ld = align_up(cols, kLdAlign);
     t->log_cap = 1 << 16;
     // Test hook: a small initial pivot-log capacity (LPR_TEST_LOG_CAP pairs, 16..65536) so that the
-    // growth path (ensure_log + the K-pivot paths' ov_set_log / blk_set_log_cap) is crossed after a
+    // growth path (ensure_log + the K-pivot paths' ov_set_log / small_set_log_cap) is crossed after a
     // few blocks, inside a solve short enough for the CPU oracle to check (tests/test_block_gpu.py).
     if (const char* lc = std::getenv("LPR_TEST_LOG_CAP")) {
         const long v = std::strtol(lc, nullptr, 10);
@@ -167,7 +156,6 @@ static lpr_tableau::GraphKey graph_key_now(const lpr_tableau* t) {
     k.T2 = t->T2;
     k.log = t->log;
     k.basis = t->basis;
-    k.blk = t->blk;
     k.next_col = t->next_col;
     k.colbuf = t->colbuf;
     k.rows = t->rows;
@@ -193,7 +181,6 @@ static void release_device(lpr_tableau* t) {
     if (t->eng->stream) hipStreamSynchronize(t->eng->stream);
     drop_graph(t);
     lpr_cut_release(t);
-    blk_release(t);
     ov_release(t);
     small_release(t);
     for (hipEvent_t ev : t->ev) hipEventDestroy(ev);
@@ -442,10 +429,11 @@ static int solve_small(lpr_tableau* t, const lpr_solve_opts& o, lpr_solve_result
 }
 
 // Tableaux above kFusedBytes: K pivots per sweep.  opts.block: 0 = auto (16), 1 = the
-// one-pivot-per-sweep path, 2..16 = that many (2..8 in block_kernels.hip's form, variant 0x60tr).
+// one-pivot-per-sweep path, 2..16 = that many.
 // opts.variant: 0 = by size (heads-then-sweep up to kOverlapBytes, two-stream overlap above),
-// 0x30tr / 0x40tr / 0x50tr / 0x60tr force a form with tr-row sweep tiles, any other non-zero value
-// (a k_update tile variant, 0x7fff) the one-pivot path.
+// 0x30tr / 0x40tr force a form with tr-row sweep tiles (0x50tr / 0x60tr, retired forms, are read
+// as 0x30tr / 0x40tr), any other non-zero value (a k_update tile variant, 0x7fff) the one-pivot
+// path.
 static constexpr int kDefaultBlock = 16;
 // (round 2, tools/size_sweep.sh: with 8-10 us loop heads the two-stream overlap wins from ~80 MB:
 // 67 MB 99.6 k vs 104.2 k pivots/s for heads-then-sweep, 101 MB 98.7 k vs 92.2 k, 227 MB 93.6 k vs
@@ -453,134 +441,36 @@ static constexpr int kDefaultBlock = 16;
 static constexpr size_t kOverlapBytes = (size_t)80 << 20;
 
 static int block_size(const lpr_tableau* t, const lpr_solve_opts& o) {
-    // a specific one-pivot update-kernel variant was asked for (0x60tr = this path, tile rows tr)
-    if (o.variant != 0 && (o.variant & 0xff00) != 0x6000 && (o.variant & 0xff00) != 0x5000 &&
-        (o.variant & 0xff00) != 0x4000 && (o.variant & 0xff00) != 0x3000)
+    // a specific one-pivot update-kernel variant was asked for
+    if (o.variant != 0 && (o.variant & 0xff00) != 0x4000 && (o.variant & 0xff00) != 0x3000)
         return 1;
     int k = o.block;
     if (k == 0) k = kDefaultBlock;
     if (k < 1) k = 1;
-    const int kmax = ((o.variant & 0xff00) == 0x6000) ? blk_max_pivots() : ov_max_pivots();
-    if (k > kmax) k = kmax;
+    if (k > ov_max_pivots()) k = ov_max_pivots();
     if (t->rows < 2) k = 1;
     return k;
 }
 
-static int solve_blocked(lpr_tableau* t, const lpr_solve_opts& o, int K, lpr_solve_result* res) {
-    lpr_engine* e = t->eng;
-    hipStream_t s = e->stream;
-    int rc = blk_ensure(t);
-    if (rc != LPR_OK_OPTIMAL) return rc;
-    const bool timed = o.time_kernels != 0;
-    const int tr = ((o.variant & 0xff00) == 0x6000) ? (o.variant & 0xff) : 8;  // sweep tile rows
-    int nblocks = o.batch > 0 ? (o.batch + K - 1) / K : (default_batch(t) + K - 1) / K;
-    if (nblocks < 1) nblocks = 1;
-    const int64_t start_iter = t->total_pivots;
-    const int64_t max_iter = o.max_pivots > 0 ? start_iter + o.max_pivots : 0;
-    rc = blk_upload_state(t, start_iter, max_iter);
-    if (rc != LPR_OK_OPTIMAL) return rc;
-    blk_launch_bootstrap(t);
-
-    int32_t status = kRunning, pending = kRunning;
-    int64_t iter = start_iter;
-    while (status == kRunning && pending == kRunning) {
-        int nb = nblocks;
-        if (max_iter > 0) {  // no more blocks than the limit can use (+1: the deciding head)
-            const int64_t left = max_iter - iter;
-            const int64_t need = left / K + 1;
-            if (need < nb) nb = (int)need;
-        }
-        const int64_t log_before = t->log_cap;
-        rc = ensure_log(t, iter + (int64_t)nb * K + 1);
-        if (rc != LPR_OK_OPTIMAL) return rc;
-        if (t->log_cap != log_before) {
-            rc = blk_set_log_cap(t);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        if (timed) {
-            while ((int)t->ev.size() < 2 * nb) {
-                hipEvent_t ev;
-                LPR_HIP(hipEventCreate(&ev));
-                t->ev.push_back(ev);
-            }
-            for (int k = 0; k < nb; ++k) {
-                blk_launch_heads(t, K);
-                const bool sample = (k % kTimeStride) == 0;
-                if (sample) LPR_HIP(hipEventRecord(t->ev[2 * k], s));
-                blk_launch_update(t, tr);
-                if (sample) LPR_HIP(hipEventRecord(t->ev[2 * k + 1], s));
-            }
-        } else {
-            const int gv = -100 - K * 64 - tr;  // graph key of this path
-            if (!graph_valid(t, nb, gv)) {
-                drop_graph(t);
-                hipGraph_t g = nullptr;
-                LPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                for (int k = 0; k < nb; ++k) {
-                    blk_launch_heads(t, K);
-                    blk_launch_update(t, tr);
-                }
-                LPR_HIP(hipStreamEndCapture(s, &g));
-                hipError_t ierr = hipGraphInstantiate(&t->graph, g, nullptr, nullptr, 0);
-                hipGraphDestroy(g);
-                if (ierr != hipSuccess) {
-                    t->graph = nullptr;
-                    set_error("hipGraphInstantiate failed: %s", hipGetErrorString(ierr));
-                    return LPR_DEVICE_ERROR;
-                }
-                graph_stamp(t, nb, gv);
-            }
-            LPR_HIP(hipGraphLaunch(t->graph, s));
-        }
-        LPR_HIP(hipGetLastError());
-        int64_t now = iter;
-        rc = blk_poll(t, &status, &pending, &now);
-        if (rc != LPR_OK_OPTIMAL) return rc;
-        const int64_t done = now - iter;
-        if (timed) {  // only sweeps that applied a full block count (K pivots each)
-            const int64_t full = done / K;
-            for (int64_t k = 0; k < full && k < nb; k += kTimeStride) {
-                float ms = 0.f;
-                LPR_HIP(hipEventElapsedTime(&ms, t->ev[2 * k], t->ev[2 * k + 1]));
-                t->timed_total_ms += ms;
-                t->timed_launches += 1;
-            }
-        }
-        iter = now;
-        if (status == kRunning && pending == kRunning && done == 0) {
-            set_error("blocked pivot loop made no progress (device status still running)");
-            return LPR_DEVICE_ERROR;
-        }
-    }
-    if (status == kRunning) status = pending;  // decided by the last block, not yet published
-    t->total_pivots = iter;
-    res->status = status;
-    res->block = K;
-    res->pivots = iter - start_iter;
-    res->total_pivots = iter;
-    double z = 0.0;
-    LPR_HIP(hipMemcpyAsync(&z, t->T + (t->cols - 1), sizeof(double), hipMemcpyDeviceToHost, s));
-    LPR_HIP(hipStreamSynchronize(s));
-    res->z = z;
-    return status;
-}
-
-// Large tableaux, default: K pivots per sweep with the next block's loop heads running beside the
-// current block's (out-of-place) sweep -- overlap_kernels.hip.
+// Tableaux above kFusedBytes that do not fit the cache-resident path: K pivots per sweep --
+// overlap_kernels.hip.  two_streams: the next block's loop heads run on a stream of their own
+// beside the current block's out-of-place sweep (0x30tr); otherwise the heads of a block, then its
+// sweep in place, both on the engine stream (0x40tr).
 //
-// A "step" is one launch pair: step j sweeps block j (K pivots) while its heads decide block j + 1.
-// A call that applies N blocks takes N + 1 steps (the first only decides, the last only sweeps);
-// the host learns the outcome from the control block the last step wrote: `status`, or -- when the
-// heads found the end (`pending`) and left nothing staged (`kdone == 0`) -- `pending` itself, so no
-// further launch is needed to publish it.
+// A "step" is one launch pair.  Two streams: step j sweeps block j (K pivots) while its heads decide
+// block j + 1, so a call that applies N blocks takes N + 1 steps (the first only decides, the last
+// only sweeps).  In place: step j decides block j and sweeps it.  The host learns the outcome from
+// the control block the last step wrote: `status`, or -- when the heads found the end (`pending`)
+// and left nothing staged (`kdone == 0`) -- `pending` itself, so no further launch is needed to
+// publish it.
 // opts.time_kernels: HIP events on the sweep's own stream bracket EVERY sweep launch (start =
 // both kernels of the previous step done); sweep time = stop - start, step time = start of the
 // next step - start of this one.  Only steps that swept a full block are counted.
-static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int tr, bool overlap,
+static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int tr,
                             bool two_streams, int hflags, lpr_solve_result* res) {
     lpr_engine* e = t->eng;
     hipStream_t s = e->stream;
-    int rc = ov_ensure(t, overlap);
+    int rc = ov_ensure(t, two_streams);
     if (rc != LPR_OK_OPTIMAL) return rc;
     const bool timed = o.time_kernels != 0;
     // opts.time_kernels = n > 1: events around every n-th step only (two event records per step
@@ -602,8 +492,10 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
     const int64_t max_iter = o.max_pivots > 0 ? start_iter + o.max_pivots : 0;
     rc = ov_begin(t, start_iter, max_iter);
     if (rc != LPR_OK_OPTIMAL) return rc;
-    if (two_streams && ov2_begin(t) != LPR_OK_OPTIMAL)
-        two_streams = false;  // no second stream: the one-launch form of the overlap does the same
+    if (two_streams) {
+        rc = ov2_begin(t);
+        if (rc != LPR_OK_OPTIMAL) return rc;
+    }
 
     OvPoll pl;
     pl.status = kRunning;
@@ -629,7 +521,7 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
         rc = ensure_log(t, applied + (int64_t)(nb + 1) * K + 1);
         if (rc != LPR_OK_OPTIMAL) return rc;
         if (t->log_cap != log_before || t->log != log_ptr) {
-            rc = ov_set_log(t, overlap ? (int)(step & 1) : 0);
+            rc = ov_set_log(t, two_streams ? (int)(step & 1) : 0);
             if (rc != LPR_OK_OPTIMAL) return rc;
         }
         // One or two launches per K pivots: plain launches keep the device busy (measured: a
@@ -650,10 +542,9 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
                 if (rc != LPR_OK_OPTIMAL) return rc;
                 continue;
             }
-            if (!overlap) ov_launch_heads(t, K, hflags);
+            ov_launch_heads(t, K, hflags);
             if (tk) LPR_HIP(hipEventRecord(t->ev[2 * k], s));
-            if (overlap) ov_launch_step(t, K, tr, lp);
-            else ov_launch_sweep(t, tr);
+            ov_launch_sweep(t, tr);
             if (tk) LPR_HIP(hipEventRecord(t->ev[2 * k + 1], s));
         }
         if (two_streams) {
@@ -662,7 +553,7 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
         }
         if (timed) LPR_HIP(hipEventRecord(t->ev[2 * nb], s));  // closes the last step's window
         LPR_HIP(hipGetLastError());
-        rc = ov_poll(t, overlap ? (int)(step & 1) : 0, &pl);
+        rc = ov_poll(t, two_streams ? (int)(step & 1) : 0, &pl);
         if (rc != LPR_OK_OPTIMAL) return rc;
         if (pl.error || pl.status == LPR_DEVICE_ERROR) {
             // the staging state is unusable (a head group never arrived): the handle is poisoned
@@ -676,10 +567,10 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
             status = pl.pending;  // the end was found and nothing is left to sweep
         if (timed) {
             // steps of this batch sweep full blocks in order: first (only in the very first batch
-            // of an overlapped call) the step that sweeps nothing, then full blocks, then at most
+            // of a two-stream call) the step that sweeps nothing, then full blocks, then at most
             // one partial block and idle steps
             const int64_t full_now = (pl.applied - start_iter) / K - swept_full;
-            const int first = (step == nb && overlap) ? 1 : 0;
+            const int first = (step == nb && two_streams) ? 1 : 0;
             for (int k = 0; k < nb && k < first + full_now; k += tstride) {
                 if (k < first) continue;  // (the sampled steps are the multiples of tstride)
                 float ms = 0.f;
@@ -964,6 +855,10 @@ int lpr_primal_solve(lpr_tableau* t, const lpr_solve_opts* opts, lpr_solve_resul
     if (opts) o = *opts;
     const int hflags = (o.variant >> 16) & 255;  // loop-head placement / diagnostics (K-pivot paths)
     o.variant &= 0xffff;                       // path + tile
+    // retired forms, kept as aliases: 0x50tr (the overlap in one launch) runs as the two-stream
+    // overlap, 0x60tr (one launch per loop head, K <= 8) as heads-then-sweep
+    if ((o.variant & 0xff00) == 0x5000) o.variant = 0x3000 | (o.variant & 0xff);
+    if ((o.variant & 0xff00) == 0x6000) o.variant = 0x4000 | (o.variant & 0xff);
     lpr_engine* e = t->eng;
     hipStream_t s = e->stream;
     LPR_HIP(hipSetDevice(e->device));
@@ -971,23 +866,20 @@ int lpr_primal_solve(lpr_tableau* t, const lpr_solve_opts* opts, lpr_solve_resul
     if (use_small(t, o)) return solve_small(t, o, res);
     if (use_fused(t, o)) return solve_fused(t, o, res);
     {
-        // variant 0x60tr: in-place blocked path; 0x50tr or none: the overlapped path
-        const int K = block_size(t, o);
-        if (K > 1 && (o.variant & 0xff00) == 0x6000) return solve_blocked(t, o, K, res);
-        // default / 0x50tr: sweep out of place with the next block's heads inside the same launch;
+        // 0x30tr: sweep out of place with the next block's heads beside it on a second stream;
         // 0x40tr: all heads of a block in one persistent launch, then the sweep in place (also the
-        // fallback when the second tableau buffer cannot be allocated)
+        // fallback when the second tableau buffer or the heads' stream cannot be had)
+        const int K = block_size(t, o);
         if (K > 1) {
             // measured (tools/size_sweep.sh): up to ~80 MB the heads-then-sweep form is faster
             // (9.1-9.6 us per pivot), above it hiding the sweep behind the next heads wins
             const size_t tbytes = (size_t)t->rows * t->ld * sizeof(double);
             // above kOverlapBytes the default is the two-stream form of the overlap (0x30tr)
             const bool big = (o.variant & 0xff00) == 0 && tbytes > kOverlapBytes;
-            const bool two_streams = (o.variant & 0xff00) == 0x3000 || big;
-            bool overlap = two_streams || (o.variant & 0xff00) == 0x5000;
+            bool two_streams = (o.variant & 0xff00) == 0x3000 || big;
             const int tr = (o.variant & 0xff00) ? (o.variant & 0xff) : 8;
-            if (overlap && ov_ensure(t, true) == LPR_OUT_OF_MEMORY) overlap = false;
-            return solve_overlapped(t, o, K, tr, overlap, two_streams && overlap, hflags, res);
+            if (two_streams && ov_ensure(t, true) != LPR_OK_OPTIMAL) two_streams = false;
+            return solve_overlapped(t, o, K, tr, two_streams, hflags, res);
         }
     }
     const int variant = (o.variant > 0 && o.variant < 0x7000) ? o.variant - 1 : default_variant(t);

@@ -3,12 +3,30 @@
 // while the sweep of the current K is running.
 // (reference: LPR_381_Group_V22/Simplex/PrimalSimplexSolver.cs:102-211)
 //
-// block_kernels.hip explains why K pivots can be decided from O(R + C) data each and then applied
-// to every element in one sweep with bit-identical results.  The pieces here:
-//   ov_heads / ov_heads_rich   the K loop heads of a block as ONE persistent group of G workgroups
-//                              with a spin barrier between the two phases of a head.
+// A pivot costs one read + one write of the whole tableau (2*8*R*C bytes) and the rank-1 update
+// kernel already moves them at the speed of the memory system.  The only way to go faster is to
+// move fewer bytes per pivot: this path decides K pivots FIRST, from O(R + C) data each, and then
+// applies all K to every element in ONE sweep -- the element goes through the same K
+// multiply-round-subtract-round steps it would go through in K separate sweeps, in registers, so
+// the stored bits are identical to the C#'s.
+//
+// What pivot q of a block needs of the tableau T^(q-1) (T^(0) = the tableau in memory):
+//   * its Z row, to pick the entering column (:152-167)       -> carried analytically:
+//         Z^(q) = Z^(q-1) - (f_q[0] * p_q)                       (the expression :208 stores)
+//   * column e_q and the RHS column, for the ratio test (:169-191) and as factors f_q (:206):
+//         column: gathered from T^(0) and taken through the q-1 earlier pivots;
+//         RHS:    b^(q) = b^(q-1) - (f_q * p_q[rhs]), b^(q)[r_q] = p_q[rhs]
+//   * row r_q, normalised (:198-199): read from T^(0), taken through the q-1 earlier pivots.
+// "Taken through pivot s": x -> x - (f_s[i] * p_s[j]), or p_s[j] itself on the pivot row r_s --
+// exactly what the sweep does to every element.  A head that meets the end of the solve (optimal,
+// unbounded, pivot limit) records it in `pending`; the pivots staged before it are still applied by
+// the sweep, and the host (or the next launch) publishes the status.
+//
+// The pieces here:
+//   ov_heads                   the K loop heads of a block as ONE persistent group of G workgroups
+//                              with a hand-off between the two phases of a head.
 //   ov_tiles                   the sweep: 32-row x 256-double2 tiles.
-// and three ways of putting them on the device (lpr_engine.hip picks by tableau size):
+// and two ways of putting them on the device (lpr_engine.hip picks by tableau size):
 //   k_ov_heads + k_ov_sweep    heads, then the sweep in place (0x40tr; 1 MB .. 80 MB).
 //   k_ov2_heads || k_ov2_sweep two kernels on two streams (0x30tr; above 80 MB): the sweep is out
 //                              of place (tableau buffer `cur` -> `cur ^ 1`), so while it runs the
@@ -16,8 +34,6 @@
 //                              of the next block work from that very buffer, taking every column /
 //                              row they fetch through the block being swept plus their own earlier
 //                              pivots.  A step lasts max(sweep, heads).
-//   k_ov_step                  the same overlap in one launch (0x50tr): workgroups [0, G) are the
-//                              heads -- dispatched first, so resident together -- the rest sweep.
 //
 // Control state that a launch both reads and updates exists twice (`OvCtl ctl[2]`): the launch
 // with parity p reads ctl[p] and its two lead workgroups write ctl[p ^ 1] -- so no workgroup can
@@ -65,7 +81,7 @@ constexpr int kOvTileRows = LPR_OV_TILE_ROWS;  // rows per sweep workgroup (TR i
 #define LPR_OV_IC_MB 64
 #endif
 constexpr int kOvIcMB = LPR_OV_IC_MB;
-// ov_heads_rich: the unit of a hand-off is the WAVE, not the workgroup -- every wave publishes its
+// ov_heads: the unit of a hand-off is the WAVE, not the workgroup -- every wave publishes its
 // own partial once its own stores have drained and collects all G x kOvWPG of them itself: no LDS
 // combine, no workgroup barrier in a head (false: one partial per workgroup, four barriers per head)
 #ifndef LPR_OV_WAVE_HANDOFF
@@ -101,7 +117,7 @@ struct OvBuffers {      // everything the step kernel touches, passed by value
     ZPart* zparts;      // [2][kOvGroups]
     double* rparts;     // [3][kOvGroups] ratio-test partials: ratio, pivot element, row (as double); + f0
     unsigned long long* gran;  // [3][kOvGroups][3] partials as {epoch, 32-bit value} granules:
-                               // Z-row partials bank 0 / 1, ratio partials (ov_heads_rich)
+                               // Z-row partials bank 0 / 1, ratio partials (ov_heads)
     unsigned long long* xgran;  // [kOvGroups] {launch epoch, XCC id} of every head workgroup
     unsigned long long* hx;     // {launch epoch, 0x100 | XCC id}: the XCD this launch's heads share
     unsigned* tileq;            // [2] next tile of the sweep (work queue), by launch parity
@@ -167,7 +183,7 @@ __global__ __launch_bounds__(1024) void k_ov_prologue(const double* __restrict__
         bank[tid].v = v;
         bank[tid].i = i;
     }
-    // the same partials as granules (ov_heads_rich), see gr_publish: one per workgroup, or one per
+    // the same partials as granules (ov_heads), see gr_publish: one per workgroup, or one per
     // wave of every workgroup
     const int nparts = kOvWaveHandoff ? G * kOvWPG : G;
     if (tid < nparts) {
@@ -190,18 +206,9 @@ __global__ __launch_bounds__(1024) void k_ov_prologue(const double* __restrict__
 __device__ __forceinline__ double xld(const double* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void xst(double* p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int xld(const int* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void xst(int* p, int v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // The same hand-off when every head workgroup of the launch sits on ONE XCD (checked per launch,
-// see ov_heads_rich): the XCD's L2 is the coherence point, so the producer stores with workgroup
+// see ov_heads): the XCD's L2 is the coherence point, so the producer stores with workgroup
 // scope (sc0: the line stays in that L2) and the consumer still loads with sc1 (past its own L1,
 // served by the L2) -- a hand-off costs an L2 round trip instead of a trip to the memory side.
 __device__ __forceinline__ void hst(double* p, double v, bool l2) {
@@ -300,366 +307,6 @@ __device__ __forceinline__ Cand ov_wave_min(Cand c) {
     r.v = vmin;
     r.i = (imin == INT_MAX) ? -1 : imin;
     return r;
-}
-
-// arg-min over the G partials, one per lane (G <= 64), every wave on its own
-__device__ __forceinline__ Cand ov_reduce_zparts(const ZPart* bank, int G) {
-    const int lane = threadIdx.x & (kWave - 1);
-    Cand c;
-    c.v = 0.0;
-    c.i = -1;
-    if (lane < G) {
-        c.v = xld(&bank[lane].v);
-        c.i = xld(&bank[lane].i);
-    }
-    return wave_cand_min(c);
-}
-
-// Barrier over the G head workgroups.  Returns false when it timed out.  No cache maintenance:
-// the workgroup barrier waits for every lane's (sc1) stores to complete, the arrival and the poll
-// are memory-side atomics, and what is read afterwards is read with sc1 loads (see xld).
-__device__ __forceinline__ bool ov_barrier(unsigned* bar, unsigned target) {
-    __shared__ int ok;
-    __builtin_amdgcn_s_waitcnt(0);  // this lane's stores have been acknowledged
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned spins = 0;
-        int good = 1;
-        while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > kOvSpinMax) {
-                good = 0;
-                break;
-            }
-        }
-        ok = good;
-    }
-    __syncthreads();
-    return ok != 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// The heads of the next block (workgroups [0, G)).
-template <int NT>
-__device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K, int G, int lp,
-                         bool solo) {
-    __shared__ double lds_v[16];
-    __shared__ int lds_i[16];
-    __shared__ double lds_p[2];
-    __shared__ int s_r[kOvMax];   // rows of the pivots staged by this launch
-    __shared__ int rA[kOvMax];    // rows of the pivots of the block being swept
-    __shared__ double s_fa[kOvMax], s_fn[kOvMax];  // f_t[r] of the earlier pivots
-    __shared__ double s_pa[kOvMax], s_pn[kOvMax];  // p_t[e], later p_t[rhs]
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int g = blockIdx.x;
-    const bool lead = (g == 0);
-    const OvCtl* ci = B.ctl + lp;
-    OvCtl* co = B.ctl + (lp ^ 1);
-    const int32_t status = ci->status;
-    const int32_t pend_in = ci->pending;
-    const int kb = solo ? 0 : ci->kdone;  // pivots of the block being swept right now
-    const int sa = ci->slot;        // ... staged in this slot
-    const int64_t staged0 = ci->staged;
-    const int64_t mx = ci->max_iter;
-    const int64_t log_cap = ci->log_cap;
-    const double* __restrict__ Tin = B.Tb[ci->cur];
-    const int ld2 = ld >> 1;
-    const int rhs = C - 1;
-    const size_t slotP = (size_t)kOvMax * ld, slotF = (size_t)kOvMax * Rp;
-    // not __restrict__: other head workgroups write these between the barriers
-    double* prowA = B.prow + (size_t)sa * slotP;
-    double* fcolA = B.fcol + (size_t)sa * slotF;
-    double* prowN = B.prow + (size_t)(sa ^ 1) * slotP;
-    double* fcolN = B.fcol + (size_t)(sa ^ 1) * slotF;
-    double* zrow = B.zrow;
-    unsigned* bar = B.bar + lp;
-    if (tid < kOvMax) rA[tid] = (tid < kb) ? ci->r[tid] : -1;
-    __syncthreads();
-
-    int32_t pend_out = pend_in;
-    int32_t status_out = status;
-    int count = 0;
-    int err = 0;
-    unsigned nbar = 0;
-
-    if (status == kRunning && pend_in != kRunning) {
-        status_out = pend_in;  // the block staged before is being swept by this very launch
-    } else if (status == kRunning) {
-        for (int q = 1; q <= K; ++q) {
-            const int64_t pidx = staged0 + q - 1;
-            const ZPart* bank_in = B.zparts + (pidx & 1) * kOvGroups;
-            ZPart* bank_out = B.zparts + ((pidx + 1) & 1) * kOvGroups;
-            const double* bprev = B.bvec + (size_t)(pidx & 1) * Rp;
-            double* bnew = B.bvec + (size_t)((pidx + 1) & 1) * Rp;
-            double* colq = fcolN + (size_t)(q - 1) * Rp;
-
-            // ---- entering column (:152-167) from the partials of the previous head ----
-            const int e = ov_reduce_zparts(bank_in, G).i;
-            if (e < 0) {
-                pend_out = LPR_OK_OPTIMAL;
-                break;
-            }
-            // ---- column e of the tableau after all earlier pivots, this workgroup's rows ----
-            if (tid < kb) s_pa[tid] = prowA[(size_t)tid * ld + e];
-            if (tid >= 32 && tid - 32 < q - 1) s_pn[tid - 32] = xld(&prowN[(size_t)(tid - 32) * ld + e]);
-            __syncthreads();
-            Cand rc;
-            rc.v = DBL_MAX;
-            rc.i = -1;
-            double a_of_best = 0.0;
-            for (int i = g * nt + tid; i < R; i += G * nt) {
-                double c = Tin[(size_t)i * ld + e];
-                for (int t0 = 0; t0 < kb; t0 += kOvMax) {  // through the block being swept
-                    double f[kOvMax];
-#pragma unroll
-                    for (int u = 0; u < kOvMax; ++u)
-                        f[u] = (t0 + u < kb) ? fcolA[(size_t)(t0 + u) * Rp + i] : 0.0;
-#pragma unroll
-                    for (int u = 0; u < kOvMax; ++u) {
-                        const int t = t0 + u;
-                        if (t < kb) {
-                            if (i == rA[t]) {
-                                c = s_pa[t];
-                            } else {
-                                const double prod = f[u] * s_pa[t];
-                                c = c - prod;
-                            }
-                        }
-                    }
-                }
-                for (int t0 = 0; t0 < q - 1; t0 += 8) {  // through this block's earlier pivots
-                    double f[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        f[u] = (t0 + u < q - 1) ? fcolN[(size_t)(t0 + u) * Rp + i] : 0.0;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int t = t0 + u;
-                        if (t < q - 1) {
-                            if (i == s_r[t]) {
-                                c = s_pn[t];
-                            } else {
-                                const double prod = f[u] * s_pn[t];
-                                c = c - prod;
-                            }
-                        }
-                    }
-                }
-                xst(&colq[i], c);
-                // FindLeavingVariable (:169-191) on this lane's rows: its RHS entries are its own
-                if (i == 0) xst(&B.rparts[3 * kOvGroups], c);  // T[0, e], the Z row's factor
-                if (i >= 1 && c > 1e-9) {
-                    const double ratio = ieee_div(bprev[i], c);
-                    if (ratio >= 0 && ratio < rc.v) {
-                        rc.v = ratio;
-                        rc.i = i;
-                        a_of_best = c;
-                    }
-                }
-            }
-            {   // this workgroup's (ratio, row) minimum and its pivot element -> the partials
-                const int my_best = rc.i;
-                rc = block_cand_min(rc, lds_v, lds_i);
-                if (rc.i >= 0 && my_best == rc.i) lds_p[0] = a_of_best;  // one lane owns that row
-                __syncthreads();
-                if (tid == 0) {
-                    xst(&B.rparts[g], rc.v);
-                    xst(&B.rparts[kOvGroups + g], rc.i >= 0 ? lds_p[0] : 0.0);
-                    xst(&B.rparts[2 * kOvGroups + g], (double)rc.i);
-                }
-            }
-            if (!ov_barrier(bar, (++nbar) * (unsigned)G)) {
-                err = 1;
-                break;
-            }
-
-            // ---- the leaving row: lexicographic minimum of the G partials (every wave on its own)
-            double p, f0;
-            int r;
-            {
-                const int lane = tid & (kWave - 1);
-                Cand c;
-                c.v = DBL_MAX;
-                c.i = -1;
-                double a = 0.0;
-                if (lane < G) {
-                    c.v = xld(&B.rparts[lane]);
-                    a = xld(&B.rparts[kOvGroups + lane]);
-                    c.i = (int)xld(&B.rparts[2 * kOvGroups + lane]);
-                }
-                f0 = xld(&B.rparts[3 * kOvGroups]);
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    Cand o;
-                    o.v = __shfl_xor(c.v, off, kWave);
-                    o.i = __shfl_xor(c.i, off, kWave);
-                    const double oa = __shfl_xor(a, off, kWave);
-                    const Cand m = cand_min(c, o);
-                    if (m.i != c.i || m.v != c.v) a = oa;  // the other side won
-                    c = m;
-                }
-                r = c.i;
-                p = a;
-            }
-            if (r < 0) {
-                pend_out = LPR_UNBOUNDED;
-                break;
-            }
-            if (mx > 0 && pidx >= mx) {
-                pend_out = LPR_PIVOT_LIMIT;
-                break;
-            }
-            if (tid == 0) s_r[q - 1] = r;
-
-            // ---- row r after all earlier pivots, normalised (:199); next Z row; partial ----
-            // f_t[r] of every earlier pivot, once per workgroup
-            if (tid < kb) s_fa[tid] = fcolA[(size_t)tid * Rp + r];
-            if (tid >= 32 && tid - 32 < q - 1) s_fn[tid - 32] = xld(&fcolN[(size_t)(tid - 32) * Rp + r]);
-            if (tid >= 64 && tid - 64 < kb) s_pa[tid - 64] = prowA[(size_t)(tid - 64) * ld + rhs];
-            if (tid >= 96 && tid - 96 < q - 1) s_pn[tid - 96] = xld(&prowN[(size_t)(tid - 96) * ld + rhs]);
-            double wr = (tid == 128) ? Tin[(size_t)r * ld + rhs] : 0.0;
-            __syncthreads();
-            const double2* Tin2 = reinterpret_cast<const double2*>(Tin);
-            const double2* prowA2 = reinterpret_cast<const double2*>(prowA);
-            double2* prowN2 = reinterpret_cast<double2*>(prowN);
-            double2* zrow2 = reinterpret_cast<double2*>(zrow);
-            Cand n;
-            n.v = 0.0;
-            n.i = -1;
-            for (int c2 = g * nt + tid; c2 < ld2; c2 += G * nt) {
-                double2 w = Tin2[(size_t)r * ld2 + c2];
-                double2 z = zrow2[c2];
-                for (int t0 = 0; t0 < kb; t0 += kOvMax) {
-                    double2 ps[kOvMax];
-#pragma unroll
-                    for (int u = 0; u < kOvMax; ++u)
-                        ps[u] = (t0 + u < kb) ? prowA2[(size_t)(t0 + u) * ld2 + c2]
-                                              : make_double2(0.0, 0.0);
-#pragma unroll
-                    for (int u = 0; u < kOvMax; ++u) {
-                        const int t = t0 + u;
-                        if (t < kb) {
-                            if (r == rA[t]) {
-                                w = ps[u];
-                            } else {
-                                const double f = s_fa[t];
-                                const double px = f * ps[u].x;
-                                const double py = f * ps[u].y;
-                                w.x = w.x - px;
-                                w.y = w.y - py;
-                            }
-                        }
-                    }
-                }
-                for (int t0 = 0; t0 < q - 1; t0 += 8) {
-                    double2 ps[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        ps[u] = (t0 + u < q - 1) ? prowN2[(size_t)(t0 + u) * ld2 + c2]
-                                                 : make_double2(0.0, 0.0);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int t = t0 + u;
-                        if (t < q - 1) {
-                            if (r == s_r[t]) {
-                                w = ps[u];
-                            } else {
-                                const double f = s_fn[t];
-                                const double px = f * ps[u].x;
-                                const double py = f * ps[u].y;
-                                w.x = w.x - px;
-                                w.y = w.y - py;
-                            }
-                        }
-                    }
-                }
-                const int j = 2 * c2;
-                double2 pq;
-                pq.x = (j < C) ? ieee_div(w.x, p) : 0.0;  // :199 true division
-                pq.y = (j + 1 < C) ? ieee_div(w.y, p) : 0.0;
-                xst(&prowN[(size_t)(q - 1) * ld + 2 * c2], pq.x);
-                xst(&prowN[(size_t)(q - 1) * ld + 2 * c2 + 1], pq.y);
-                const double mxp = f0 * pq.x;  // :208 product rounded, then the difference
-                const double myp = f0 * pq.y;
-                z.x = z.x - mxp;
-                z.y = z.y - myp;
-                zrow2[c2] = z;
-                if (j < C - 1 && z.x < n.v) {
-                    n.v = z.x;
-                    n.i = j;
-                }
-                if (j + 1 < C - 1 && z.y < n.v) {
-                    n.v = z.y;
-                    n.i = j + 1;
-                }
-            }
-            n = block_cand_min(n, lds_v, lds_i);
-
-            // ---- RHS column after this pivot ----
-            if (tid == 128) {
-                for (int t = 0; t < kb; ++t) {
-                    if (r == rA[t]) {
-                        wr = s_pa[t];
-                    } else {
-                        const double prod = s_fa[t] * s_pa[t];
-                        wr = wr - prod;
-                    }
-                }
-                for (int t = 0; t < q - 1; ++t) {
-                    if (r == s_r[t]) {
-                        wr = s_pn[t];
-                    } else {
-                        const double prod = s_fn[t] * s_pn[t];
-                        wr = wr - prod;
-                    }
-                }
-                lds_p[0] = ieee_div(wr, p);  // p was read by every lane before the arg-min barriers above
-            }
-            __syncthreads();
-            const double prhs = lds_p[0];
-            for (int i = g * nt + tid; i < R; i += G * nt) {
-                const double prod = colq[i] * prhs;  // own rows: written by this lane above
-                xst(&bnew[i], (i == r) ? prhs : bprev[i] - prod);
-            }
-            if (tid == 0) {
-                xst(&bank_out[g].v, n.v);
-                xst(&bank_out[g].i, n.i);
-                if (lead) {
-                    co->r[q - 1] = r;
-                    B.basis[r - 1] = e;  // :142
-                    if (pidx < log_cap) {
-                        B.log[2 * pidx] = r;
-                        B.log[2 * pidx + 1] = e;
-                    }
-                }
-            }
-            count = q;
-            if (!ov_barrier(bar, (++nbar) * (unsigned)G)) {
-                err = 1;
-                break;
-            }
-        }
-    }
-
-    if (lead && tid == 0) {  // the next launch's view (fields owned by the heads)
-        const bool staged_now = (status == kRunning && pend_in == kRunning);
-        co->status = err ? LPR_DEVICE_ERROR : status_out;
-        co->pending = pend_out;
-        co->kdone = staged_now ? count : 0;
-        co->slot = staged_now ? (sa ^ 1) : sa;
-        co->staged = staged0 + (staged_now ? count : 0);
-        co->max_iter = mx;
-        co->log_cap = log_cap;
-        co->error = err | ci->error;
-        co->head_xcc = -1;
-        B.bar[lp ^ 1] = 0u;  // nobody touches the other counter during this launch
-        if (solo) {  // no sweep in this launch: its fields are carried over here
-            co->applied = ci->applied;
-            co->cur = ci->cur;
-            co->sweep = ci->sweep;
-        }
-    }
 }
 
 // ---- partials as granules (the data is the flag) ------------------------------------------------
@@ -783,10 +430,9 @@ __device__ __forceinline__ void ov_publish_min(Cand c, double* lds_v, int* lds_i
 }
 
 // ------------------------------------------------------------------------------------------
-// The heads again, for the launches where they have a kernel (and so a register file) of their
-// own (k_ov_heads, k_ov2_heads).  Same protocol and arithmetic as ov_heads; what differs is where
-// the operands live.  A lane owns one row (gather / RHS) and one column pair (pivot row / Z row),
-// and everything that belongs to them stays in registers for the whole launch:
+// The K loop heads of a block, as one persistent launch of G working workgroups (k_ov_heads,
+// k_ov2_heads).  A lane owns one row (gather / RHS) and one column pair (pivot row / Z row), and
+// everything that belongs to them stays in registers for the whole launch:
 //   fA / pA   its slices of the block being swept (the same for every pivot of the launch)
 //   myf / myp its slices of this block's own pivots so far (it computed them itself)
 //   myz, myb  its Z-row pair and RHS entry after the pivots staged so far
@@ -813,9 +459,8 @@ __device__ __forceinline__ void ov_publish_min(Cand c, double* lds_v, int* lds_i
 // the control-block fields the sweep used to write (applied / cur / sweep parity): the sweep of the
 // same step only reads the control block.
 template <int NT, bool STAMP>
-__device__ void ov_heads_rich(const OvBuffers B, int ld, int R, int C, int Rp, int K, int G, int lp,
-                              bool solo, int spread, int no_l2, int wait_sweeps,
-                              int heads_done = -1) {
+__device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K, int G, int lp,
+                         bool solo, int spread, int no_l2, int wait_sweeps, int heads_done = -1) {
     if ((int)blockIdx.x % spread != 0) return;
     __shared__ double lds_v[16];
     __shared__ int lds_i[16];
@@ -1495,13 +1140,13 @@ __device__ __forceinline__ void ov_rows_store(const ov_v2d (&x)[TR], ov_v2d* dst
 // Work distribution: the launch is PERSISTENT (a few workgroups per CU); every workgroup takes the
 // next tile from a counter in memory until none is left.  Workgroups are dealt to the 8 XCDs round
 // robin, so with a static tile -> workgroup map the slowest XCD sets the time of the sweep -- and
-// one XCD is slow by design: the one that hosts the loop heads of the next block (ov_heads_rich),
+// one XCD is slow by design: the one that hosts the loop heads of the next block (ov_heads),
 // which run beside this sweep with a high priority and one wave per SIMD.  With the queue every XCD
 // takes what it can, and the heads' XCD takes nothing: its workgroups leave at once when the
 // previous launch's heads sat there (the hint `head_xcc` of the control block), or as soon as this
 // launch's heads have said where they are (B.hx) -- the heads then run as fast as with nothing
 // beside them.  Wrong or missing hints cost time, never correctness: any workgroup may take any
-// tile.  `static_tile` >= 0: one given tile (the one-launch form k_ov_step has no queue).
+// tile.  `static_tile` >= 0: one given tile (the in-place sweep runs alone and has no queue).
 // TROWS rows are processed; the row tiles are counted in units of `unit` rows (>= TROWS) and this
 // call takes the TROWS rows at offset `off` inside its unit (the half tiles of the sweep's tail)
 // POL (out of place only): bit 0 loads, bit 1 stores of the tile's rows with the default cache
@@ -1655,14 +1300,14 @@ __device__ __forceinline__ void ov_one_tile(const OvBuffers& B, const OvCtl* ci,
 template <int TR, bool DB, bool INPLACE, int TROWS = kOvTileRows>
 __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __restrict__ fcol,
                                          const double* __restrict__ prow, int ld, int R, int Rp,
-                                         int G, int lp, int static_tile, int avoid,
+                                         int lp, int static_tile, int avoid,
                                          bool write_ctl = true, int sweeps_done = -1,
                                          int wait_heads = -1, int hint_xcc = -1,
                                          int ic_tiles = 0) {
     static_assert(TROWS % TR == 0 && (!DB || TROWS % (2 * TR) == 0) && TROWS <= 64,
                   "tile rows: a multiple of the chunks in flight, and one bit each in prmask");
     __shared__ int s_tile;
-    const bool first_wg = ((int)blockIdx.x == G);
+    const bool first_wg = (blockIdx.x == 0);
     // this launch has started, so every earlier sweep of the stream is complete and its stores
     // are visible (kernel boundary): tell the heads that wait for exactly that
     if (first_wg && threadIdx.x == 0 && sweeps_done >= 0)
@@ -1819,31 +1464,14 @@ __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __res
     }
 }
 
-template <int TR, bool DB>
-__global__ __launch_bounds__(kOvNT) void k_ov_step(const OvBuffers B,
-                                                   const double* __restrict__ fcol_ro,
-                                                   const double* __restrict__ prow_ro, int ld,
-                                                   int R, int C, int Rp, int K, int G, int lp) {
-    // fcol_ro / prow_ro alias B.fcol / B.prow, which the heads of this launch write -- but only the
-    // OTHER staging slot (ci->slot ^ 1) than the one the tiles read, so the read-only view holds
-    if ((int)blockIdx.x < G)
-        ov_heads<kOvNT>(B, ld, R, C, Rp, K, G, lp, false);
-    else
-        ov_tiles<TR, DB, false>(B, fcol_ro, prow_ro, ld, R, Rp, G, lp, (int)blockIdx.x - G, 0);
-}
-
-// The two halves as separate kernels on two streams, running concurrently (variant 0x30tr): same
-// protocol as k_ov_step, but each kernel has its own register budget (in k_ov_step the heads'
-// registers cap the occupancy of the sweep's tiles and vice versa).
+// The overlap: the heads of the next block and the sweep of the current one as two kernels on two
+// streams, running concurrently (variant 0x30tr), each with its own register budget.
 template <int NT, bool STAMP>
 __global__ __launch_bounds__(NT) void k_ov2_heads(const OvBuffers B, int ld, int R, int C, int Rp,
                                                   int K, int G, int lp, int spread, int no_l2,
                                                   int wait_sweeps, int heads_done) {
-    ov_heads_rich<NT, STAMP>(B, ld, R, C, Rp, K, G, lp, false, spread, no_l2, wait_sweeps,
-                             heads_done);
+    ov_heads<NT, STAMP>(B, ld, R, C, Rp, K, G, lp, false, spread, no_l2, wait_sweeps, heads_done);
 }
-
-
 
 template <int TR, bool DB>
 __global__ __launch_bounds__(kOvNT) void k_ov2_sweep(const OvBuffers B,
@@ -1852,7 +1480,9 @@ __global__ __launch_bounds__(kOvNT) void k_ov2_sweep(const OvBuffers B,
                                                      int R, int Rp, int lp, int avoid,
                                                      int write_ctl, int sweeps_done,
                                                      int wait_heads, int hint_xcc, int ic_tiles) {
-    ov_tiles<TR, DB, false>(B, fcol_ro, prow_ro, ld, R, Rp, 0, lp, -1, avoid, write_ctl != 0,
+    // fcol_ro / prow_ro alias B.fcol / B.prow, which the heads beside this launch write -- but only
+    // the OTHER staging slot (ci->slot ^ 1) than the one the tiles read, so the read-only view holds
+    ov_tiles<TR, DB, false>(B, fcol_ro, prow_ro, ld, R, Rp, lp, -1, avoid, write_ctl != 0,
                             sweeps_done, wait_heads, hint_xcc, ic_tiles);
 }
 
@@ -1862,7 +1492,7 @@ __global__ __launch_bounds__(kOvNT) void k_ov2_sweep(const OvBuffers B,
 template <int NT, bool STAMP>
 __global__ __launch_bounds__(NT) void k_ov_heads(const OvBuffers B, int ld, int R, int C, int Rp,
                                                  int K, int G, int spread, int no_l2) {
-    ov_heads_rich<NT, STAMP>(B, ld, R, C, Rp, K, G, 0, true, spread, no_l2, -1);
+    ov_heads<NT, STAMP>(B, ld, R, C, Rp, K, G, 0, true, spread, no_l2, -1);
 }
 
 template <int TR, bool DB, int TROWS = kOvTileRows>
@@ -1873,7 +1503,7 @@ __global__ __launch_bounds__(kOvNT) void k_ov_sweep(const OvBuffers B,
     // nothing runs beside the in-place sweep: one workgroup per tile, dealt by the hardware (the
     // queue's counter costs a burst of ~1000 atomics on one word at the start of every sweep).
     // TROWS = 8: small tableaux, where 32-row tiles would leave most CUs without a tile
-    ov_tiles<TR, DB, true, TROWS>(B, fcol_ro, prow_ro, ld, R, Rp, 0, 1, (int)blockIdx.x, 0);
+    ov_tiles<TR, DB, true, TROWS>(B, fcol_ro, prow_ro, ld, R, Rp, 1, (int)blockIdx.x, 0);
 }
 
 }  // namespace lpr
@@ -1888,7 +1518,7 @@ struct lpr_overlap_ctx {
     lpr::OvCtl* h_ctl = nullptr;  // pinned, 2 entries
     double* h_z = nullptr;        // pinned, 2 entries
     double* T2 = nullptr;         // the second tableau buffer (owned here)
-    hipStream_t hstream = nullptr;  // the heads' stream of the two-stream variant
+    hipStream_t hstream = nullptr;  // the heads' stream of the two-stream variant (created with T2)
     hipEvent_t ev_h[2] = {nullptr, nullptr}, ev_s[2] = {nullptr, nullptr};
     int ev_idx = 0;
     int steps = 0;                  // launch pairs queued by the current solve call
@@ -1915,10 +1545,10 @@ void ov_release(lpr_tableau* t) {
     if (c->hstream) {
         hipStreamSynchronize(c->hstream);
         hipStreamDestroy(c->hstream);
-        for (int k = 0; k < 2; ++k) {
-            hipEventDestroy(c->ev_h[k]);
-            hipEventDestroy(c->ev_s[k]);
-        }
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (c->ev_h[k]) hipEventDestroy(c->ev_h[k]);
+        if (c->ev_s[k]) hipEventDestroy(c->ev_s[k]);
     }
     hipFree(c->T2);
     hipFree(c->b.prow);
@@ -1942,6 +1572,8 @@ void ov_release(lpr_tableau* t) {
     t->ov = nullptr;
 }
 
+// second_buffer: also the second tableau buffer and the heads' stream with its events, everything
+// the two-stream form needs beyond the in-place one.  Failing that, the caller falls back in place.
 int ov_ensure(lpr_tableau* t, bool second_buffer) {
     lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
     if (c && c->rows == t->rows && c->ld == t->ld && (c->T2 || !second_buffer))
@@ -1956,7 +1588,16 @@ int ov_ensure(lpr_tableau* t, bool second_buffer) {
     auto chk = [&](hipError_t x) { if (err == hipSuccess) err = x; };
     const size_t D = sizeof(double);
     const size_t tbytes = (size_t)t->rows * t->ld * D;
-    if (second_buffer) chk(hipMalloc(&c->T2, tbytes));
+    if (second_buffer) {
+        int lo = 0, hi = 0;
+        chk(hipMalloc(&c->T2, tbytes));
+        chk(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        chk(hipStreamCreateWithPriority(&c->hstream, hipStreamNonBlocking, hi));
+        for (int k = 0; k < 2; ++k) {
+            chk(hipEventCreateWithFlags(&c->ev_h[k], hipEventDisableTiming));
+            chk(hipEventCreateWithFlags(&c->ev_s[k], hipEventDisableTiming));
+        }
+    }
     chk(hipMalloc(&c->b.prow, (size_t)2 * kOvMax * c->ld * D));
     chk(hipMalloc(&c->b.fcol, (size_t)2 * kOvMax * c->Rp * D));
     chk(hipMalloc(&c->b.zrow, (size_t)c->ld * D));
@@ -2065,23 +1706,6 @@ int ov_set_log(lpr_tableau* t, int parity) {
     return LPR_OK_OPTIMAL;
 }
 
-void ov_launch_step(lpr_tableau* t, int K, int tr, int lp) {
-    lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
-    hipStream_t s = t->eng->stream;
-    const int G = ov_groups(t);
-    const int ld2 = t->ld / 2;
-    const int nct = (ld2 + kOvNT - 1) / kOvNT;
-    const int nrt = (t->rows + kOvTileRows - 1) / kOvTileRows;
-    const dim3 grid(G + nct * nrt), blk(kOvNT);
-#define LPR_OV_STEP(TR, DB)                                                                      \
-    hipLaunchKernelGGL((k_ov_step<TR, DB>), grid, blk, 0, s, c->b, c->b.fcol, c->b.prow, t->ld,   \
-                       t->rows, t->cols, c->Rp, K, G, lp)
-    if (tr >= 16) LPR_OV_STEP(16, false);
-    else if (tr >= 8) LPR_OV_STEP(8, false);
-    else LPR_OV_STEP(4, false);
-#undef LPR_OV_STEP
-}
-
 // flags (opts.variant >> 16): 1 = diagnostic time stamps, 2 = do not confine the heads to one XCD
 // (one workgroup per group, memory-side hand-offs: the round-1 form), 4 = confine them but keep
 // the memory-side hand-offs.
@@ -2131,15 +1755,6 @@ void ov_launch_sweep(lpr_tableau* t, int tr) {
 // Step k's kernels both start when both kernels of step k-1 are done.
 int ov2_begin(lpr_tableau* t) {
     lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
-    if (!c->hstream) {
-        int lo = 0, hi = 0;
-        LPR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        LPR_HIP(hipStreamCreateWithPriority(&c->hstream, hipStreamNonBlocking, hi));
-        for (int k = 0; k < 2; ++k) {
-            LPR_HIP(hipEventCreateWithFlags(&c->ev_h[k], hipEventDisableTiming));
-            LPR_HIP(hipEventCreateWithFlags(&c->ev_s[k], hipEventDisableTiming));
-        }
-    }
     // everything queued on the engine stream so far (prologue, control block) precedes step 0
     c->ev_idx = 0;
     c->steps = 0;

@@ -1,5 +1,5 @@
 // select_common.hpp -- device helpers shared by the pivot-selection kernels of the primal path
-// (primal_kernels.hip, block_kernels.hip).  Not part of the ABI.
+// (primal_kernels.hip, overlap_kernels.hip, small_kernels.hip).  Not part of the ABI.
 #pragma once
 
 #include "engine_common.hpp"

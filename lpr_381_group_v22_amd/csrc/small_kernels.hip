@@ -12,7 +12,7 @@
 // L2 / Infinity Cache (column e, row r), two (value, index) arg-min reductions, seven barriers.
 // Then one in-place sweep applies the block to every element (k_small_sweep), each element going
 // through the same K rounded multiply / rounded subtract steps, in the same order, as K separate
-// C# pivots would put it through -- the stored bits are identical (see block_kernels.hip for the
+// C# pivots would put it through -- the stored bits are identical (see overlap_kernels.hip for the
 // argument; nothing is re-associated, no FMA).
 //
 // What pivot q of a block needs of the not yet materialised tableau T^(q-1):

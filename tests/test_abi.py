@@ -103,10 +103,11 @@ def test_product_does_not_touch_the_oracle():
     assert "oracle" not in ldd
 
 
-def test_no_fma_in_pivot_kernels():
+def test_no_fma_in_update_and_sweep_kernels():
     """The C# rounds the product before the subtraction (PrimalSimplexSolver.cs:208); a contracted
     v_fma_f64 in the rank-1 update would change bits.  Check the gfx950 ISA of every k_update
-    instantiation (division expansions in k_select legitimately use FMAs)."""
+    instantiation and of the K-pivot sweeps (division expansions in k_select legitimately use
+    FMAs)."""
     csrc = os.path.join(PKG, "csrc")
     subprocess.run(["make", "-C", csrc, "isa"], check=True, capture_output=True)
     s = open(os.path.join(csrc, "_obj", "primal_kernels.s")).read()
@@ -117,8 +118,7 @@ def test_no_fma_in_pivot_kernels():
         assert "v_mul_f64" in body and "v_add_f64" in body, name
         assert "global_load_dwordx4" in body and "global_store_dwordx4" in body, name
     # the K-pivots-per-sweep kernels: the sweeps contain no division at all, so no FMA of any kind
-    for fname, pat in (("block_kernels.s", r"_ZN3lpr12k_blk_update\w+"),
-                       ("overlap_kernels.s", r"_ZN3lpr10k_ov_sweep\w+"),
+    for fname, pat in (("overlap_kernels.s", r"_ZN3lpr10k_ov_sweep\w+"),
                        ("overlap_kernels.s", r"_ZN3lpr11k_ov2_sweep\w+")):
         s = open(os.path.join(csrc, "_obj", fname)).read()
         bodies = re.findall(r"^(" + pat + r"):[^\n]*\n(.*?)\.Lfunc_end", s, flags=re.S | re.M)

@@ -1,11 +1,11 @@
 """GPU parity tests of the K-pivots-per-sweep paths (opts.block): deciding K pivots ahead from
 O(R + C) data and applying them in one sweep must give the same status, pivot log, basis and
 tableau BITS as the oracle's one-pivot-at-a-time loop, for every K, every stop reason and every
-way a pivot limit can cut a block.  Two implementations: csrc/overlap_kernels.hip (default on
-large tableaux: out-of-place sweep with the next block's loop heads inside the same launch,
-variant 0x50tr; the same as two concurrent kernels on two streams, variant 0x30tr; and variant 0x40tr: all loop heads of a block in one persistent
-launch, then the sweep in place) and csrc/block_kernels.hip (in place, one launch per loop head,
-variant 0x60tr)."""
+way a pivot limit can cut a block.  Both forms live in csrc/overlap_kernels.hip: variant 0x30tr
+(default above 80 MB), an out-of-place sweep with the next block's loop heads beside it as a
+concurrent kernel on a second stream; and variant 0x40tr, all loop heads of a block in one
+persistent launch, then the sweep in place.  Variants 0x50tr and 0x60tr named forms since retired;
+they are aliases of 0x30tr and 0x40tr, so OV and INPLACE below run those two paths again."""
 import hashlib
 
 import numpy as np
@@ -15,6 +15,7 @@ import lp_cases
 
 pytestmark = pytest.mark.gpu
 
+# OV (0x5008) and INPLACE (0x6008) are the retired forms' variant values, aliases of OV2 / SEQ
 SEQ, OV, INPLACE, OV2 = 0x4008, 0x5008, 0x6008, 0x3008
 # bits 16..18 of the variant (K-pivot paths): the loop heads are normally confined to one XCD and
 # hand off through its L2 when the launch finds them there; SPREAD = one workgroup per group

@@ -1,5 +1,5 @@
-# tuning sweep of the K-pivot paths: "base:K:tr" triples, base = 4 (fused heads, in-place sweep),
-# 5 (overlapped), 6 (one launch per head)   (run on the GPU box)
+# tuning sweep of the K-pivot paths: "base:K:tr" triples, base = 3 (two-stream overlap), 4 (fused
+# heads, in-place sweep); 5 and 6 are aliases of 3 and 4   (run on the GPU box)
 mkdir -p gpurun_out
 for spec in "$@"; do
   IFS=: read base blk tr <<< "$spec"

@@ -85,8 +85,6 @@ def main():
             r = run(eng, m, n, 0x4000 | tile | fl, label=f"seq {label} tile {tile:#x}")
             print(json.dumps(r), flush=True)
     if not quick:
-        r = run(eng, m, n, 0x5008, label="ov (one launch)")
-        print(json.dumps(r), flush=True)
         r = run(eng, m, n, 0, block=1, warm=32, steps=128, label="one pivot per sweep")
         print(json.dumps(r), flush=True)
     for label, v in (("ov2 default", 0x3008), ("ov2 live word only", 0x3008 | NOHINT),
