@@ -630,6 +630,78 @@ int lpr_batch_tableau_read(lpr_batch* b, int32_t k, double* rowmajor);
 /* rows, cols and decision variables n of LP k; any may be NULL. */
 int lpr_batch_shape(lpr_batch* b, int32_t k, int32_t* rows, int32_t* cols, int32_t* n);
 
+
+/* ------------------------------------------------------- batched branch and bound */
+
+/* Many independent integer programs per device call.  Every IP runs the
+ * whole BranchAndBound.ExecuteBranchAndBound (IntegerProgramming/BranchBoundSimplexSolver.cs:
+ * 1006-1233) on the device, with no host step per node, and gives the bits lpr_bb_run gives for
+ * that root alone.  One IP per wave (form W) or per workgroup (G: its working pair in LDS, H: in
+ * HBM), picked by the footprint of the child LP at full depth; the DFS stack stays in HBM.  The
+ * reference has no batch mode; every call cites the C# lines it repeats per IP. */
+typedef struct lpr_bb_batch lpr_bb_batch;
+
+/* BranchAndBoundAdapter.SolveFromPrimal's set-up (BranchAndBoundAdapter.cs:9-24) per IP: root k is
+ * the rows[k] x cols[k] row-major block of `tableaux` (packed), SetNumVars(nvars[k]) with nvars[k]
+ * in [0, cols[k] - 1].  node_cap: the hard stop of :1038-1042 for every IP (<= 0: 20, at most 64);
+ * each IP's shape at full depth, (rows + node_cap) x (cols + node_cap), must stay within 1024 x
+ * 2048.  trace_cap: pivot-trace quads kept per IP (<= 0: 256; the count is always exact). */
+int lpr_bb_batch_create(lpr_engine* e, int32_t count, const int32_t* rows, const int32_t* cols,
+                        const double* tableaux, const int32_t* nvars, int32_t node_cap,
+                        int32_t trace_cap, lpr_bb_batch** out);
+/* SolveFromPrimal (:9-24) for every LP of a solved lpr_batch, its FinalTableau copied device to
+ * device: nvars = n[k] for an optimal LP (SolutionVector.Count), max(1, cols - 1) for an unbounded
+ * one (InferNumVariables).  An LP without a FinalTableau (LPR_PIVOT_LIMIT, or never solved) makes
+ * the call fail with LPR_BAD_ARGUMENT naming it.  The new handle does not depend on `lps`. */
+int lpr_bb_batch_from_batch(lpr_batch* lps, int32_t node_cap, int32_t trace_cap,
+                            lpr_bb_batch** out);
+int lpr_bb_batch_destroy(lpr_bb_batch* b);
+
+typedef struct lpr_bb_batch_opts {
+    int32_t enable_pruning;   /* ShouldPrunebranch (:985-1004); Program.cs:389 passes false */
+    int32_t chunk;            /* pops per IP per launch (0: by form) */
+    int32_t variant;          /* 0 auto; 1 / 2 / 3 force form W / G / H on the IPs that fit it
+                                 (tests and tuning only, same bits) */
+    int32_t max_child_pivots; /* pivots one child LP may take before its IP ends with
+                                 LPR_PIVOT_LIMIT (0: 65 536) */
+} lpr_bb_batch_opts;
+
+typedef struct lpr_bb_batch_result {
+    int32_t done;        /* IPs whose stack emptied (LPR_OK_OPTIMAL) */
+    int32_t node_cap;    /* IPs stopped by the node cap (LPR_BB_NODE_CAP) */
+    int32_t pivot_limit; /* IPs ended by a child LP over max_child_pivots (LPR_PIVOT_LIMIT) */
+    int32_t launches;    /* search kernels launched by this call */
+    int64_t pops;        /* nodes popped (branchCount, :1045), all IPs */
+    int64_t pivots;      /* pivot-trace entries, all IPs */
+} lpr_bb_batch_result;
+
+/* ExecuteBranchAndBound (:1006-1233) for every IP, from its root: RoundAllTableaux (:1021), DFS
+ * stack, on each pop RoundAllTableaux (:1047), GetObjective (:892-897), ShouldPrunebranch,
+ * UpdateOptimalSolution (:935-983), CreateBranches (:859-890); lower child then upper, each
+ * AddConstraint (:694-803) + DoDualSimplex (:289-468); the solved ones rounded (:1124, :1187) and
+ * pushed upper first (:1210-1213).  A second call starts again from the roots.  Returns
+ * LPR_OK_OPTIMAL unless the call itself failed; each IP's status is in lpr_bb_batch_result_read. */
+int lpr_bb_batch_run(lpr_bb_batch* b, const lpr_bb_batch_opts* opts, lpr_bb_batch_result* res);
+/* lpr_bb_result's fields per IP, count entries each, any pointer may be NULL: status
+ * (LPR_OK_OPTIMAL / LPR_BB_NODE_CAP / LPR_PIVOT_LIMIT), found, processed, best_node, z
+ * (optimalValue, -inf if none), pivots, nodes_created. */
+int lpr_bb_batch_result_read(lpr_bb_batch* b, int32_t* status, int32_t* found, int64_t* processed,
+                             int32_t* best_node, double* z, int64_t* pivots,
+                             int64_t* nodes_created);
+/* The incumbent x of every IP (:1059-1066), packed by nvars[k]; 0 where none was found. */
+int lpr_bb_batch_solution_read(lpr_bb_batch* b, double* x);
+/* Node records of IP k, as lpr_bb_records_read (a child that hit max_child_pivots has status
+ * LPR_PIVOT_LIMIT). */
+int lpr_bb_batch_records_read(lpr_bb_batch* b, int32_t k, int32_t* parent, int32_t* kind,
+                              int32_t* depth, int32_t* var, double* bound, int32_t* status,
+                              double* z, int64_t cap, int64_t* count);
+/* Record ids of IP k in the order they were popped, as lpr_bb_pop_order_read. */
+int lpr_bb_batch_pop_order_read(lpr_bb_batch* b, int32_t k, int32_t* ids, int64_t cap,
+                                int64_t* count);
+/* Pivot trace of IP k, as lpr_bb_trace_read: *count = min(pivots, trace_cap, cap) quads. */
+int lpr_bb_batch_trace_read(lpr_bb_batch* b, int32_t k, int32_t* quads, int64_t cap,
+                            int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,7 @@ namespace LPR_381_Group_V22.Simplex
     public class PrimalSimplexBatch : IDisposable
     {
         private IntPtr batch;                           // lpr_batch*
+        internal IntPtr Handle => batch;
         private readonly int[] rows, cols, nvars;
         public int Count { get; }
         public List<int> Status { get; } = new List<int>();
@@ -174,6 +175,98 @@ namespace LPR_381_Group_V22.Simplex
         }
 
         public void Dispose() { if (batch != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_batch_destroy(batch), "lpr_batch_destroy"); batch = IntPtr.Zero; } }
+    }
+
+    /// <summary>BranchAndBoundAdapter.SolveFromPrimal + ExecuteBranchAndBound (BranchBoundSimplexSolver.cs:1006-1233)
+    /// for many IPs in one device call (DESIGN.md section 13); each IP gives the bits of BranchAndBound alone.</summary>
+    public class BranchAndBoundBatch : IDisposable
+    {
+        private IntPtr bb;                              // lpr_bb_batch*
+        private readonly int[] nvars;
+        private readonly int nodeCap;
+        public int Count { get; }
+        public List<int> Status { get; } = new List<int>();
+        public List<double> OptimalValue { get; } = new List<double>();
+        public List<List<double>> OptimalSolution { get; } = new List<List<double>>();
+
+        /// <summary>Root tableaux (FinalTableau of each primal solve) and SetNumVars per IP.</summary>
+        public BranchAndBoundBatch(List<double[,]> roots, List<int> numVars, int nodeCap = 0, int traceCap = 0)
+        {
+            Count = roots.Count;
+            var r = new int[Count]; var c = new int[Count]; var flat = new List<double>();
+            nvars = numVars.ToArray();
+            for (int k = 0; k < Count; k++)
+            {
+                r[k] = roots[k].GetLength(0); c[k] = roots[k].GetLength(1);
+                foreach (var v in roots[k]) flat.Add(v);                       // row-major
+            }
+            this.nodeCap = nodeCap > 0 ? nodeCap : 20;
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_create(Engine.Handle, Count, r, c, flat.ToArray(), nvars,
+                nodeCap, traceCap, out bb), "lpr_bb_batch_create");
+        }
+
+        /// <summary>SolveFromPrimal (BranchAndBoundAdapter.cs:9-24) for every LP of a solved PrimalSimplexBatch.</summary>
+        public BranchAndBoundBatch(PrimalSimplexBatch primal, int nodeCap = 0, int traceCap = 0)
+        {
+            Count = primal.Count;
+            nvars = new int[Count];
+            for (int k = 0; k < Count; k++)                                     // :20
+                nvars[k] = primal.SolutionVector[k] != null ? primal.SolutionVector[k].Count
+                                                            : Math.Max(1, primal.GetFinalTableau(k).GetLength(1) - 1);
+            this.nodeCap = nodeCap > 0 ? nodeCap : 20;
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_from_batch(primal.Handle, nodeCap, traceCap, out bb),
+                "lpr_bb_batch_from_batch");
+        }
+
+        /// <summary>ExecuteBranchAndBound for every IP; x is null where no integer solution was found (:1215-1232).</summary>
+        public void Run(bool enablePruning = false)
+        {
+            var opts = new LprBbBatchOpts { enable_pruning = enablePruning ? 1 : 0 };
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_run(bb, ref opts, out _), "lpr_bb_batch_run");
+            var st = new int[Count]; var found = new int[Count]; var z = new double[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_result_read(bb, st, found, null, null, z, null, null),
+                "lpr_bb_batch_result_read");
+            var x = new double[Math.Max(1, nvars.Sum())];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_solution_read(bb, x), "lpr_bb_batch_solution_read");
+            Status.Clear(); OptimalValue.Clear(); OptimalSolution.Clear();
+            for (int k = 0, at = 0; k < Count; at += nvars[k], k++)
+            {
+                Status.Add(st[k]); OptimalValue.Add(z[k]);
+                OptimalSolution.Add(found[k] != 0 ? x.Skip(at).Take(nvars[k]).ToList() : null);
+            }
+        }
+
+        public List<int> PopOrder(int k)
+        {
+            var ids = new int[nodeCap];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_pop_order_read(bb, k, ids, nodeCap, out long count),
+                "lpr_bb_batch_pop_order_read");
+            return ids.Take((int)count).ToList();
+        }
+
+        public List<(int parent, int kind, int depth, int var, double bound, int status, double z)> Records(int k)
+        {
+            int cap = 1 + 2 * nodeCap;
+            var p = new int[cap]; var kd = new int[cap]; var d = new int[cap]; var v = new int[cap];
+            var b = new double[cap]; var s = new int[cap]; var z = new double[cap];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_records_read(bb, k, p, kd, d, v, b, s, z, cap, out long count),
+                "lpr_bb_batch_records_read");
+            var recs = new List<(int, int, int, int, double, int, double)>();
+            for (long q = 0; q < count; q++) recs.Add((p[q], kd[q], d[q], v[q], b[q], s[q], z[q]));
+            return recs;
+        }
+
+        public List<(int node, int phase, int row, int col)> Trace(int k, int cap = 1 << 16)
+        {
+            var q4 = new int[4 * cap];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_trace_read(bb, k, q4, cap, out long count),
+                "lpr_bb_batch_trace_read");
+            var tr = new List<(int, int, int, int)>();
+            for (long q = 0; q < count; q++) tr.Add((q4[4 * q], q4[4 * q + 1], q4[4 * q + 2], q4[4 * q + 3]));
+            return tr;
+        }
+
+        public void Dispose() { if (bb != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_destroy(bb), "lpr_bb_batch_destroy"); bb = IntPtr.Zero; } }
     }
 
     public class RevisedPrimalSimplexSolver : IDisposable

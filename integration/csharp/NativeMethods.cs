@@ -40,6 +40,12 @@ namespace LPR_381_Group_V22.Native
     internal struct LprBatchResult { public int optimal, unbounded, limit, launches; public long pivots; }
 
     [StructLayout(LayoutKind.Sequential)]
+    internal struct LprBbBatchOpts { public int enable_pruning, chunk, variant, max_child_pivots; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprBbBatchResult { public int done, node_cap, pivot_limit, launches; public long pops, pivots; }
+
+    [StructLayout(LayoutKind.Sequential)]
     internal struct LprSolveResult
     {
         public int status; public int block; public long pivots; public long total_pivots; public double z;
@@ -214,6 +220,17 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_log_read(IntPtr batch, int k, int[] rows, int[] cols, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_tableau_read(IntPtr batch, int k, [Out] double[,] rowmajor);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_shape(IntPtr batch, int k, out int rows, out int cols, out int n);
+
+        // ---- Batched branch and bound (DESIGN.md section 13): ExecuteBranchAndBound per IP, many IPs per call ----
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_create(IntPtr engine, int count, int[] rows, int[] cols, double[] tableaux, int[] nvars, int node_cap, int trace_cap, out IntPtr bbBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_from_batch(IntPtr batch, int node_cap, int trace_cap, out IntPtr bbBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_destroy(IntPtr bbBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_run(IntPtr bbBatch, ref LprBbBatchOpts opts, out LprBbBatchResult res);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_result_read(IntPtr bbBatch, int[] status, int[] found, long[] processed, int[] best_node, double[] z, long[] pivots, long[] nodes_created);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_solution_read(IntPtr bbBatch, double[] x);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_records_read(IntPtr bbBatch, int k, int[] parent, int[] kind, int[] depth, int[] var, double[] bound, int[] status, double[] z, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_pop_order_read(IntPtr bbBatch, int k, int[] ids, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_trace_read(IntPtr bbBatch, int k, int[] quads, long cap, out long count);
 
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 

@@ -5,6 +5,7 @@ Importing this package loads ``_lib/liblpr_engine.so`` (hand-written HIP for gfx
 """
 from . import _native
 from .engine import Engine, RevisedState, Tableau, default_engine
+from .bb_batch import BranchAndBoundBatch, solve_integer_programs
 from .branch_and_bound import (BranchAndBoundAdapter, BranchBoundTree, Comm,
                                solve_level_sync_native, solve_level_synchronous,
                                torch_collectives)
@@ -19,5 +20,6 @@ __all__ = [
     "PrimalSimplexSolver", "RevisedPrimalSimplexSolver", "RevisedState", "SolverException",
     "BranchAndBoundAdapter", "BranchBoundTree", "solve_level_synchronous", "torch_collectives",
     "Comm", "solve_level_sync_native", "KnapsackBranchBoundSimplex", "KnapsackBranchBoundSolver",
-    "PrimalSimplexBatch", "pack_models", "_native",
+    "PrimalSimplexBatch", "pack_models", "BranchAndBoundBatch", "solve_integer_programs",
+    "_native",
 ]

@@ -165,6 +165,26 @@ class BatchResult(C.Structure):
     ]
 
 
+class BBBatchOpts(C.Structure):
+    _fields_ = [
+        ("enable_pruning", C.c_int32),
+        ("chunk", C.c_int32),
+        ("variant", C.c_int32),
+        ("max_child_pivots", C.c_int32),
+    ]
+
+
+class BBBatchResult(C.Structure):
+    _fields_ = [
+        ("done", C.c_int32),
+        ("node_cap", C.c_int32),
+        ("pivot_limit", C.c_int32),
+        ("launches", C.c_int32),
+        ("pops", C.c_int64),
+        ("pivots", C.c_int64),
+    ]
+
+
 class BBResult(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -288,6 +308,17 @@ SIGNATURES = {
     "lpr_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, _I32, C.c_int64, _I64]),
     "lpr_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
     "lpr_batch_shape": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32]),
+    "lpr_bb_batch_create": (C.c_int, [_P, C.c_int32, _I32, _I32, _D, _I32, C.c_int32, C.c_int32,
+                                      _PP]),
+    "lpr_bb_batch_from_batch": (C.c_int, [_P, C.c_int32, C.c_int32, _PP]),
+    "lpr_bb_batch_destroy": (C.c_int, [_P]),
+    "lpr_bb_batch_run": (C.c_int, [_P, C.POINTER(BBBatchOpts), C.POINTER(BBBatchResult)]),
+    "lpr_bb_batch_result_read": (C.c_int, [_P, _I32, _I32, _I64, _I32, _D, _I64, _I64]),
+    "lpr_bb_batch_solution_read": (C.c_int, [_P, _D]),
+    "lpr_bb_batch_records_read": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32, _I32, _D, _I32, _D,
+                                            C.c_int64, _I64]),
+    "lpr_bb_batch_pop_order_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
+    "lpr_bb_batch_trace_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
 }
 
 

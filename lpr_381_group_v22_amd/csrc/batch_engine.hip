@@ -168,6 +168,14 @@ void batch_orphan(lpr_batch* b) {  // lpr_engine_close
     batch_release_device(b);
     b->eng = nullptr;
 }
+// What lpr_bb_batch_from_batch reads of a batch: its engine (null once orphaned), the host mirror
+// of its descriptors and the tableau slab.
+lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab) {
+    if (!b) return nullptr;
+    *desc = &b->h_desc;
+    *slab = b->slab;
+    return b->eng;
+}
 }  // namespace lpr
 
 #define LPR_LIVE_B(b)                                                                       \

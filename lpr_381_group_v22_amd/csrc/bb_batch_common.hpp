@@ -1,0 +1,91 @@
+// bb_batch_common.hpp -- definitions shared by the batched Branch & Bound (bb_batch_engine.hip,
+// host) and its kernels (bb_batch_kernels.hip).  Not part of the ABI (include/lpr_engine.h is).
+#pragma once
+
+#include "engine_common.hpp"
+
+namespace lpr {
+
+// Forms of one IP in a batch, as those of the LP batch (section 12).  The
+// host picks one per IP by the footprint of its working pair at full depth: two tableaux of
+// (R + c) x (C + c) doubles and the staged factor column of R + c doubles, c the node cap.
+enum BBBatchForm : int { kBBFormW = 0, kBBFormG = 1, kBBFormH = 2, kBBNumForms = 3 };
+
+// Every workgroup keeps kBBBatchWgScratch bytes of static LDS for itself (the reduction slots).
+constexpr size_t kBBBatchWgScratch = (size_t)1 << 10;
+// W: one wave per IP, four IPs per 256-lane workgroup, each in a quarter of the 64 KiB a
+// workgroup gets without the dynamic-LDS attribute.
+constexpr size_t kBBBatchWgLdsW = (size_t)64 << 10;
+constexpr size_t kBBBatchMaxLdsW = (kBBBatchWgLdsW - kBBBatchWgScratch) / 4;
+// G: one workgroup per IP, the pair in dynamic LDS: 160 KiB less the workgroup's scratch.
+constexpr size_t kBBBatchMaxLdsG = ((size_t)160 << 10) - kBBBatchWgScratch;
+// H: one workgroup per IP, the pair in its slice of the global work slab, the factor column in
+// LDS.  Shapes at full depth up to the limit of the LP batch's form H.
+constexpr int kBBBatchMaxRowsH = 1024;
+constexpr int kBBBatchMaxColsH = 2048;
+// Node cap: <= 0 means the reference's 20 (:1038); more than kBBBatchMaxNodeCap is refused.
+constexpr int kBBBatchDefaultNodeCap = 20;
+constexpr int kBBBatchMaxNodeCap = 64;
+// Pops per IP per launch, by form: a launch stays within a few milliseconds.
+constexpr int kBBBatchChunk[kBBNumForms] = {32, 16, 4};
+// Pivots one child LP may take before its IP ends with LPR_PIVOT_LIMIT (0 in the options): the
+// `1 << 16` guard of bb_expand.
+constexpr int kBBBatchMaxChildPivots = 1 << 16;
+// Pivot-trace quads kept per IP when the caller passes trace_cap = 0.
+constexpr int kBBBatchTraceDefault = 1024;
+
+// Integers per node record (parent, kind, depth, var, status); two doubles (bound, z) go with them.
+constexpr int kBBRecInts = 5;
+
+// One IP of a batch, in device memory.  The host owns the offsets and the options; the kernels own
+// the search state between launches.
+struct BBBatchDesc {
+    int64_t stack_off;  // doubles: node_cap + 2 slots of slot_n(), slot node_cap + 1 = the root
+    int64_t work_off;   // doubles of the work slab (form H): two tableaux + the factor column
+    int64_t x_off;      // nvars doubles: incumbent x, and as many of node scratch (decision values)
+    int64_t rec_off;    // records: 1 + 2 node_cap of them
+    int64_t pop_off;    // pop order: node_cap ids
+    int64_t trace_off;  // trace_cap quads
+    int64_t int_off;    // 2 (cols + node_cap) ints: basic-column keys and their sorted list
+    int64_t stk_off;    // 2 (node_cap + 1) ints: the DFS stack's (record id, depth) per slot
+    int64_t pivots;     // pivot-trace entries (exact; the trace keeps the first trace_cap)
+    int64_t processed;  // branchCount (:1045)
+    double best_z;      // optimalValue (:1024)
+    int32_t rows, cols, nvars, node_cap, trace_cap;
+    int32_t status;     // kRunning or LPR_OK_OPTIMAL / LPR_BB_NODE_CAP / LPR_PIVOT_LIMIT
+    int32_t sp;         // nodes on the stack
+    int32_t iteration;  // :1036
+    int32_t nrec;       // node records
+    int32_t found;      // an incumbent exists
+    int32_t best_node;  // its record id, -1 if none
+    int32_t enable_pruning;
+    int32_t max_child_pivots;
+    int32_t pad;
+    __host__ __device__ int64_t slot_n() const {
+        return (int64_t)(rows + node_cap) * (cols + node_cap);
+    }
+};
+
+// Device buffers of a batch, passed by value to the kernels.
+struct BBBatchBufs {
+    BBBatchDesc* desc;
+    double* stack;   // per IP (node_cap + 2) * slot_n doubles
+    double* work;    // form H working pairs
+    double* x;       // incumbent x, packed by nvars
+    double* vals;    // decision values of the popped node, packed by nvars
+    int32_t* rec_i;  // kBBRecInts per record
+    double* rec_d;   // 2 per record
+    int32_t* pops;
+    int32_t* trace;  // 4 per quad
+    int32_t* ints;
+    int32_t* stk;
+};
+
+// Doubles of LDS (or of the work slab) one IP needs: the working pair at full depth and the factor
+// column.
+inline size_t bb_batch_footprint(int rows, int cols, int node_cap) {
+    const size_t r = (size_t)rows + node_cap, c = (size_t)cols + node_cap;
+    return 2 * r * c + r;
+}
+
+}  // namespace lpr

@@ -1,0 +1,558 @@
+// bb_batch_engine.hip -- host side of the batched Branch & Bound (include/lpr_engine.h,
+// lpr_bb_batch_*).  Every IP of a batch runs ExecuteBranchAndBound on the
+// device; the host only picks each IP's form, relaunches the bounded search kernels while IPs are
+// still running (one small counter read per launch round) and copies results out.
+#include "batch_common.hpp"
+#include "bb_batch_common.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+namespace lpr {
+int bb_batch_launch(int form, hipStream_t s, const BBBatchBufs& B, const int32_t* idx_in,
+                    int n_in, int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles,
+                    int max_rows);
+void bb_batch_launch_load(hipStream_t s, const BBBatchDesc* desc, int count, const double* src,
+                          const int64_t* src_off, double* stack);
+void bb_batch_launch_reset(hipStream_t s, const BBBatchBufs& B, int count);
+lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
+}  // namespace lpr
+
+using namespace lpr;
+
+struct lpr_bb_batch {
+    lpr_engine* eng = nullptr;
+    int32_t count = 0;
+    int32_t node_cap = 0;
+    std::vector<BBBatchDesc> h_desc;  // host mirror, current after every create / run
+    BBBatchBufs d{};                  // device buffers (d.work grows on demand)
+    int64_t work_n = 0;               // doubles allocated at d.work
+    int32_t* idx = nullptr;           // 2 x count: the running lists, in and out, per form
+    int32_t* counters = nullptr;      // kBBNumForms running counts (device)
+    int32_t* h_counters = nullptr;    // pinned
+    int64_t x_total = 0, rec_total = 0, trace_total = 0;
+    bool ran = false;
+};
+
+namespace {
+
+int bbb_oom(const char* what, int64_t n, size_t elem) {
+    set_error("lpr_bb_batch: cannot allocate %s (%lld elements, %.3f GB)", what, (long long)n,
+              (double)n * (double)elem / 1e9);
+    return LPR_OUT_OF_MEMORY;
+}
+
+void bbb_release_device(lpr_bb_batch* b) {
+    hipFree(b->d.desc);
+    hipFree(b->d.stack);
+    hipFree(b->d.work);
+    hipFree(b->d.x);
+    hipFree(b->d.vals);
+    hipFree(b->d.rec_i);
+    hipFree(b->d.rec_d);
+    hipFree(b->d.pops);
+    hipFree(b->d.trace);
+    hipFree(b->d.ints);
+    hipFree(b->d.stk);
+    hipFree(b->idx);
+    hipFree(b->counters);
+    if (b->h_counters) hipHostFree(b->h_counters);
+    b->d = BBBatchBufs{};
+    b->work_n = 0;
+    b->idx = nullptr;
+    b->counters = nullptr;
+    b->h_counters = nullptr;
+}
+
+// A root of rows x cols with nvars decision columns whose shape at full depth stays within form H.
+bool bbb_shape_ok(const char* where, int32_t k, int64_t rows, int64_t cols, int64_t nvars,
+                  int node_cap) {
+    if (rows < 1 || cols < 2 || nvars < 0 || nvars > cols - 1) {
+        set_error("%s: IP %d has a %lld x %lld root with nvars=%lld; it needs rows >= 1, "
+                  "cols >= 2 and 0 <= nvars <= cols - 1",
+                  where, k, (long long)rows, (long long)cols, (long long)nvars);
+        return false;
+    }
+    if (rows + node_cap > kBBBatchMaxRowsH || cols + node_cap > kBBBatchMaxColsH) {
+        set_error("%s: IP %d has a %lld x %lld root, %lld x %lld at the full depth of node cap %d: "
+                  "beyond the batch limit of %d x %d (form H); run it alone with lpr_bb_run",
+                  where, k, (long long)rows, (long long)cols, (long long)(rows + node_cap),
+                  (long long)(cols + node_cap), node_cap, kBBBatchMaxRowsH, kBBBatchMaxColsH);
+        return false;
+    }
+    return true;
+}
+
+bool bbb_caps_ok(const char* where, int32_t node_cap, int32_t* cap_out, int32_t trace_cap,
+                 int32_t* tcap_out) {
+    const int32_t c = node_cap <= 0 ? kBBBatchDefaultNodeCap : node_cap;
+    if (c > kBBBatchMaxNodeCap) {
+        set_error("%s: node_cap %d is above the batch maximum of %d", where, node_cap,
+                  kBBBatchMaxNodeCap);
+        return false;
+    }
+    *cap_out = c;
+    *tcap_out = trace_cap <= 0 ? kBBBatchTraceDefault : trace_cap;
+    return true;
+}
+
+// Offsets and device memory for `count` IPs of the given shapes.  On failure nothing is left.
+int bbb_alloc(lpr_engine* e, int32_t count, const std::vector<int32_t>& R,
+              const std::vector<int32_t>& Cc, const std::vector<int32_t>& nv, int32_t node_cap,
+              int32_t trace_cap, lpr_bb_batch** out) {
+    lpr_bb_batch* b = new (std::nothrow) lpr_bb_batch();
+    if (!b) return bbb_oom("handle", 1, sizeof(lpr_bb_batch));
+    b->eng = e;
+    b->count = count;
+    b->node_cap = node_cap;
+    try {
+        b->h_desc.resize((size_t)count);
+    } catch (...) {
+        delete b;
+        return bbb_oom("descriptors", count, sizeof(BBBatchDesc));
+    }
+    int64_t st = 0, x = 0, rec = 0, pop = 0, tr = 0, in = 0, stk = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        BBBatchDesc& d = b->h_desc[(size_t)k];
+        std::memset(&d, 0, sizeof d);
+        d.rows = R[(size_t)k];
+        d.cols = Cc[(size_t)k];
+        d.nvars = nv[(size_t)k];
+        d.node_cap = node_cap;
+        d.trace_cap = trace_cap;
+        d.stack_off = st;
+        d.x_off = x;
+        d.rec_off = rec;
+        d.pop_off = pop;
+        d.trace_off = tr;
+        d.int_off = in;
+        d.stk_off = stk;
+        d.status = LPR_OK_OPTIMAL;  // not run yet: no search state
+        d.best_node = -1;
+        d.best_z = -INFINITY;
+        st += (int64_t)(node_cap + 2) * d.slot_n();
+        x += d.nvars;
+        rec += 1 + 2 * node_cap;
+        pop += node_cap;
+        tr += trace_cap;
+        in += 2 * (int64_t)(d.cols + node_cap);
+        stk += 2 * (int64_t)(node_cap + 1);
+    }
+    b->x_total = x;
+    b->rec_total = rec;
+    b->trace_total = tr;
+    auto one = [](int64_t n) { return (size_t)std::max<int64_t>(n, 1); };
+    int rc = LPR_OK_OPTIMAL;
+    BBBatchBufs& D = b->d;
+    if (hipMalloc(&D.desc, (size_t)count * sizeof(BBBatchDesc)) != hipSuccess)
+        rc = bbb_oom("descriptors", count, sizeof(BBBatchDesc));
+    else if (hipMalloc(&D.stack, one(st) * sizeof(double)) != hipSuccess)
+        rc = bbb_oom("DFS stack slab: (node_cap + 2) (rows + node_cap) (cols + node_cap) doubles "
+                     "per IP",
+                     st, sizeof(double));
+    else if (hipMalloc(&D.x, one(x) * sizeof(double)) != hipSuccess ||
+             hipMalloc(&D.vals, one(x) * sizeof(double)) != hipSuccess)
+        rc = bbb_oom("incumbents", 2 * x, sizeof(double));
+    else if (hipMalloc(&D.rec_i, one(rec) * kBBRecInts * sizeof(int32_t)) != hipSuccess ||
+             hipMalloc(&D.rec_d, one(rec) * 2 * sizeof(double)) != hipSuccess)
+        rc = bbb_oom("node records", rec, kBBRecInts * sizeof(int32_t) + 2 * sizeof(double));
+    else if (hipMalloc(&D.pops, one(pop) * sizeof(int32_t)) != hipSuccess)
+        rc = bbb_oom("pop orders", pop, sizeof(int32_t));
+    else if (hipMalloc(&D.trace, one(tr) * 4 * sizeof(int32_t)) != hipSuccess)
+        rc = bbb_oom("pivot traces", tr, 4 * sizeof(int32_t));
+    else if (hipMalloc(&D.ints, one(in) * sizeof(int32_t)) != hipSuccess ||
+             hipMalloc(&D.stk, one(stk) * sizeof(int32_t)) != hipSuccess)
+        rc = bbb_oom("scratch", in + stk, sizeof(int32_t));
+    else if (hipMalloc(&b->idx, (size_t)count * 2 * sizeof(int32_t)) != hipSuccess)
+        rc = bbb_oom("running lists", count, 2 * sizeof(int32_t));
+    else if (hipMalloc(&b->counters, kBBNumForms * sizeof(int32_t)) != hipSuccess ||
+             hipHostMalloc(&b->h_counters, kBBNumForms * sizeof(int32_t)) != hipSuccess)
+        rc = bbb_oom("counters", kBBNumForms, sizeof(int32_t));
+    if (rc == LPR_OK_OPTIMAL &&
+        hipMemcpy(D.desc, b->h_desc.data(), (size_t)count * sizeof(BBBatchDesc),
+                  hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("lpr_bb_batch: descriptor upload failed");
+        rc = LPR_DEVICE_ERROR;
+    }
+    if (rc != LPR_OK_OPTIMAL) {
+        bbb_release_device(b);
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return LPR_OK_OPTIMAL;
+}
+
+// The roots into their stack slots: src on the device, src_off[k] the start of root k there.
+int bbb_load(lpr_bb_batch* b, const double* d_src, const std::vector<int64_t>& src_off) {
+    hipStream_t s = b->eng->stream;
+    int64_t* d_off = nullptr;
+    if (hipMalloc(&d_off, (size_t)b->count * sizeof(int64_t)) != hipSuccess)
+        return bbb_oom("root offsets", b->count, sizeof(int64_t));
+    hipError_t err = hipMemcpyAsync(d_off, src_off.data(), (size_t)b->count * sizeof(int64_t),
+                                    hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) {
+        bb_batch_launch_load(s, b->d.desc, b->count, d_src, d_off, b->d.stack);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    hipFree(d_off);
+    if (err != hipSuccess) {
+        set_error("lpr_bb_batch: loading the roots failed: %s", hipGetErrorString(err));
+        return LPR_DEVICE_ERROR;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// The form of one IP: the smallest that holds its working pair at full depth, or the forced one
+// (opts.variant 1/2/3) if the IP fits it.
+int bbb_form(const BBBatchDesc& d, int variant) {
+    const size_t bytes = bb_batch_footprint(d.rows, d.cols, d.node_cap) * sizeof(double);
+    const bool fitW = bytes <= kBBBatchMaxLdsW, fitG = bytes <= kBBBatchMaxLdsG;
+    if (variant == 1 && fitW) return kBBFormW;
+    if (variant == 2 && fitG) return kBBFormG;
+    if (variant == 3) return kBBFormH;
+    return fitW ? kBBFormW : (fitG ? kBBFormG : kBBFormH);
+}
+
+}  // namespace
+
+namespace lpr {
+void bb_batch_orphan(lpr_bb_batch* b) {  // lpr_engine_close
+    bbb_release_device(b);
+    b->eng = nullptr;
+}
+}  // namespace lpr
+
+#define LPR_LIVE_BBB(b)                                                                     \
+    do {                                                                                    \
+        if (!(b) || !(b)->eng) {                                                            \
+            set_error("B&B batch handle is null or orphaned: its engine has been closed");  \
+            return LPR_BAD_ARGUMENT;                                                        \
+        }                                                                                   \
+        LPR_HIP(hipSetDevice((b)->eng->device));                                            \
+    } while (0)
+
+extern "C" {
+
+// BranchAndBoundAdapter.SolveFromPrimal's set-up (:9-24) per IP, from host tableaux
+int lpr_bb_batch_create(lpr_engine* e, int32_t count, const int32_t* rows, const int32_t* cols,
+                        const double* tableaux, const int32_t* nvars, int32_t node_cap,
+                        int32_t trace_cap, lpr_bb_batch** out) {
+    static const char* W = "lpr_bb_batch_create";
+    if (!e || !out || count < 1 || !rows || !cols || !tableaux || !nvars) {
+        set_error("%s: bad arguments (count=%d, or a null engine / handle / rows / cols / "
+                  "tableaux / nvars)", W, count);
+        return LPR_BAD_ARGUMENT;
+    }
+    *out = nullptr;
+    int32_t cap = 0, tcap = 0;
+    if (!bbb_caps_ok(W, node_cap, &cap, trace_cap, &tcap)) return LPR_BAD_ARGUMENT;
+    std::vector<int32_t> R((size_t)count), Cc((size_t)count), nv((size_t)count);
+    std::vector<int64_t> off((size_t)count);
+    int64_t total = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        if (!bbb_shape_ok(W, k, rows[k], cols[k], nvars[k], cap)) return LPR_BAD_ARGUMENT;
+        R[(size_t)k] = rows[k];
+        Cc[(size_t)k] = cols[k];
+        nv[(size_t)k] = nvars[k];
+        off[(size_t)k] = total;
+        total += (int64_t)rows[k] * cols[k];
+    }
+    LPR_HIP(hipSetDevice(e->device));
+    lpr_bb_batch* b = nullptr;
+    int rc = bbb_alloc(e, count, R, Cc, nv, cap, tcap, &b);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    double* d_src = nullptr;
+    if (hipMalloc(&d_src, (size_t)total * sizeof(double)) != hipSuccess) {
+        rc = bbb_oom("root upload", total, sizeof(double));
+    } else if (hipMemcpy(d_src, tableaux, (size_t)total * sizeof(double),
+                         hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("%s: root upload failed", W);
+        rc = LPR_DEVICE_ERROR;
+    } else {
+        rc = bbb_load(b, d_src, off);
+    }
+    hipFree(d_src);
+    if (rc != LPR_OK_OPTIMAL) {
+        bbb_release_device(b);
+        delete b;
+        return rc;
+    }
+    e->live_bb_batch.push_back(b);
+    *out = b;
+    return LPR_OK_OPTIMAL;
+}
+
+// SolveFromPrimal (:9-24) per LP of a solved lpr_batch: FinalTableau (:11-14) device to device,
+// SetNumVars(SolutionVector?.Count ?? InferNumVariables(finalTable)) (:20)
+int lpr_bb_batch_from_batch(lpr_batch* lps, int32_t node_cap, int32_t trace_cap,
+                            lpr_bb_batch** out) {
+    static const char* W = "lpr_bb_batch_from_batch";
+    const std::vector<BatchDesc>* bd = nullptr;
+    const double* slab = nullptr;
+    lpr_engine* e = batch_view(lps, &bd, &slab);
+    if (!e || !out) {
+        set_error("%s: the LP batch is null or orphaned (its engine has been closed), or a null "
+                  "handle", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    *out = nullptr;
+    int32_t cap = 0, tcap = 0;
+    if (!bbb_caps_ok(W, node_cap, &cap, trace_cap, &tcap)) return LPR_BAD_ARGUMENT;
+    const int32_t count = (int32_t)bd->size();
+    std::vector<int32_t> R((size_t)count), Cc((size_t)count), nv((size_t)count);
+    std::vector<int64_t> off((size_t)count);
+    for (int32_t k = 0; k < count; ++k) {
+        const BatchDesc& d = (*bd)[(size_t)k];
+        if (d.status != LPR_OK_OPTIMAL && d.status != LPR_UNBOUNDED) {
+            set_error("%s: LP %d has no FinalTableau (status %d: %s); \"Primal simplex has not "
+                      "been solved yet.\" (BranchAndBoundAdapter.cs:11-14)",
+                      W, k, d.status,
+                      d.status == LPR_PIVOT_LIMIT ? "stopped at its pivot limit" : "not solved");
+            return LPR_BAD_ARGUMENT;
+        }
+        const int32_t n = d.status == LPR_OK_OPTIMAL ? d.n : std::max(1, d.cols - 1);
+        if (!bbb_shape_ok(W, k, d.rows, d.cols, n, cap)) return LPR_BAD_ARGUMENT;
+        R[(size_t)k] = d.rows;
+        Cc[(size_t)k] = d.cols;
+        nv[(size_t)k] = n;
+        off[(size_t)k] = d.t_off;
+    }
+    LPR_HIP(hipSetDevice(e->device));
+    lpr_bb_batch* b = nullptr;
+    int rc = bbb_alloc(e, count, R, Cc, nv, cap, tcap, &b);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    rc = bbb_load(b, slab, off);  // synchronous: the LP batch may go right after
+    if (rc != LPR_OK_OPTIMAL) {
+        bbb_release_device(b);
+        delete b;
+        return rc;
+    }
+    e->live_bb_batch.push_back(b);
+    *out = b;
+    return LPR_OK_OPTIMAL;
+}
+
+int lpr_bb_batch_destroy(lpr_bb_batch* b) {
+    if (!b) return LPR_BAD_ARGUMENT;
+    if (b->eng) {
+        hipSetDevice(b->eng->device);
+        hipStreamSynchronize(b->eng->stream);
+        bbb_release_device(b);
+        auto& lv = b->eng->live_bb_batch;
+        for (size_t q = 0; q < lv.size(); ++q)
+            if (lv[q] == b) {
+                lv.erase(lv.begin() + q);
+                break;
+            }
+    }
+    delete b;
+    return LPR_OK_OPTIMAL;
+}
+
+// ExecuteBranchAndBound (:1006-1233) for every IP, from its root
+int lpr_bb_batch_run(lpr_bb_batch* b, const lpr_bb_batch_opts* opts, lpr_bb_batch_result* res) {
+    static const char* W = "lpr_bb_batch_run";
+    LPR_LIVE_BBB(b);
+    if (!res) {
+        set_error("%s: null result", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    lpr_bb_batch_opts o;
+    std::memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    if (o.variant < 0 || o.variant > 3 || o.chunk < 0 || o.max_child_pivots < 0) {
+        set_error("%s: variant %d (0 auto, 1 W, 2 G, 3 H) / chunk %d (>= 0) / max_child_pivots "
+                  "%d (>= 0)", W, o.variant, o.chunk, o.max_child_pivots);
+        return LPR_BAD_ARGUMENT;
+    }
+    std::memset(res, 0, sizeof *res);
+    hipStream_t s = b->eng->stream;
+    const int32_t count = b->count;
+    std::vector<int32_t> lists[kBBNumForms];
+    int slot[kBBNumForms] = {0, 0, 0};
+    int max_rows = 0;
+    int64_t work = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        BBBatchDesc& d = b->h_desc[(size_t)k];
+        d.enable_pruning = o.enable_pruning ? 1 : 0;
+        d.max_child_pivots = o.max_child_pivots > 0 ? o.max_child_pivots : kBBBatchMaxChildPivots;
+        const int f = bbb_form(d, o.variant);
+        lists[f].push_back(k);
+        const int64_t fp = (int64_t)bb_batch_footprint(d.rows, d.cols, d.node_cap);
+        if (f == kBBFormH) {
+            d.work_off = work;
+            work += fp;
+            max_rows = std::max(max_rows, d.rows + d.node_cap);
+        } else {
+            d.work_off = 0;
+            slot[f] = std::max(slot[f], (int)((fp + 1) & ~1LL));
+        }
+    }
+    if (work > b->work_n) {
+        hipFree(b->d.work);
+        b->d.work = nullptr;
+        b->work_n = 0;
+        if (hipMalloc(&b->d.work, (size_t)work * sizeof(double)) != hipSuccess)
+            return bbb_oom("form H working pairs", work, sizeof(double));
+        b->work_n = work;
+    }
+    int32_t* in = b->idx;
+    int32_t* outl = b->idx + count;
+    int32_t off[kBBNumForms], live[kBBNumForms];
+    for (int f = 0, at = 0; f < kBBNumForms; ++f) {
+        off[f] = at;
+        live[f] = (int32_t)lists[f].size();
+        if (live[f] > 0)
+            LPR_HIP(hipMemcpyAsync(in + at, lists[f].data(), (size_t)live[f] * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, s));
+        at += live[f];
+    }
+    LPR_HIP(hipMemcpyAsync(b->d.desc, b->h_desc.data(), (size_t)count * sizeof(BBBatchDesc),
+                           hipMemcpyHostToDevice, s));
+    bb_batch_launch_reset(s, b->d, count);
+    LPR_HIP(hipGetLastError());
+    int launches = 0;
+    while (live[kBBFormW] + live[kBBFormG] + live[kBBFormH] > 0) {
+        LPR_HIP(hipMemsetAsync(b->counters, 0, kBBNumForms * sizeof(int32_t), s));
+        for (int f = 0; f < kBBNumForms; ++f) {
+            if (live[f] == 0) continue;
+            const int chunk = o.chunk > 0 ? o.chunk : kBBBatchChunk[f];
+            const int rc = bb_batch_launch(f, s, b->d, in + off[f], live[f], outl + off[f],
+                                           b->counters + f, chunk, slot[f], max_rows);
+            if (rc != LPR_OK_OPTIMAL) return rc;
+            ++launches;
+        }
+        LPR_HIP(hipMemcpyAsync(b->h_counters, b->counters, kBBNumForms * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+        LPR_HIP(hipStreamSynchronize(s));
+        for (int f = 0; f < kBBNumForms; ++f) live[f] = b->h_counters[f];
+        std::swap(in, outl);
+    }
+    LPR_HIP(hipMemcpyAsync(b->h_desc.data(), b->d.desc, (size_t)count * sizeof(BBBatchDesc),
+                           hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    b->ran = true;
+    for (const BBBatchDesc& d : b->h_desc) {
+        res->done += d.status == LPR_OK_OPTIMAL;
+        res->node_cap += d.status == LPR_BB_NODE_CAP;
+        res->pivot_limit += d.status == LPR_PIVOT_LIMIT;
+        res->pops += d.processed;
+        res->pivots += d.pivots;
+    }
+    res->launches = launches;
+    return LPR_OK_OPTIMAL;
+}
+
+// lpr_bb_result's fields (:1006-1233's outputs) per IP
+int lpr_bb_batch_result_read(lpr_bb_batch* b, int32_t* status, int32_t* found, int64_t* processed,
+                             int32_t* best_node, double* z, int64_t* pivots,
+                             int64_t* nodes_created) {
+    LPR_LIVE_BBB(b);
+    for (int32_t k = 0; k < b->count; ++k) {
+        const BBBatchDesc& d = b->h_desc[(size_t)k];
+        if (status) status[k] = d.status;
+        if (found) found[k] = d.found;
+        if (processed) processed[k] = d.processed;
+        if (best_node) best_node[k] = d.best_node;
+        if (z) z[k] = d.best_z;
+        if (pivots) pivots[k] = d.pivots;
+        if (nodes_created) nodes_created[k] = d.nrec;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// optimalSolution (:1059-1066) of every IP, packed by nvars
+int lpr_bb_batch_solution_read(lpr_bb_batch* b, double* x) {
+    LPR_LIVE_BBB(b);
+    if (!x) {
+        set_error("lpr_bb_batch_solution_read: null x");
+        return LPR_BAD_ARGUMENT;
+    }
+    if (b->x_total == 0) return LPR_OK_OPTIMAL;
+    if (!b->ran) {
+        std::fill(x, x + b->x_total, 0.0);
+        return LPR_OK_OPTIMAL;
+    }
+    LPR_HIP(hipMemcpyAsync(x, b->d.x, (size_t)b->x_total * sizeof(double), hipMemcpyDeviceToHost,
+                           b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+static int bbb_ip(lpr_bb_batch* b, const char* where, int32_t k, int64_t cap, int64_t* count) {
+    if (k < 0 || k >= b->count || cap < 0 || !count) {
+        set_error("%s: IP %d out of range (0..%d), cap %lld or null count", where, k,
+                  b->count - 1, (long long)cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// Node records of IP k, as lpr_bb_records_read
+int lpr_bb_batch_records_read(lpr_bb_batch* b, int32_t k, int32_t* parent, int32_t* kind,
+                              int32_t* depth, int32_t* var, double* bound, int32_t* status,
+                              double* z, int64_t cap, int64_t* count) {
+    LPR_LIVE_BBB(b);
+    int rc = bbb_ip(b, "lpr_bb_batch_records_read", k, cap, count);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    const BBBatchDesc& d = b->h_desc[(size_t)k];
+    const int64_t n = b->ran ? std::min<int64_t>(d.nrec, cap) : 0;
+    *count = n;
+    if (n == 0) return LPR_OK_OPTIMAL;
+    std::vector<int32_t> ri((size_t)n * kBBRecInts);
+    std::vector<double> rd((size_t)n * 2);
+    LPR_HIP(hipMemcpyAsync(ri.data(), b->d.rec_i + (int64_t)kBBRecInts * d.rec_off,
+                           ri.size() * sizeof(int32_t), hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipMemcpyAsync(rd.data(), b->d.rec_d + 2 * d.rec_off, rd.size() * sizeof(double),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t* e = ri.data() + kBBRecInts * q;
+        if (parent) parent[q] = e[0];
+        if (kind) kind[q] = e[1];
+        if (depth) depth[q] = e[2];
+        if (var) var[q] = e[3];
+        if (status) status[q] = e[4];
+        if (bound) bound[q] = rd[(size_t)(2 * q)];
+        if (z) z[q] = rd[(size_t)(2 * q + 1)];
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// Record ids of IP k in pop order, as lpr_bb_pop_order_read
+int lpr_bb_batch_pop_order_read(lpr_bb_batch* b, int32_t k, int32_t* ids, int64_t cap,
+                                int64_t* count) {
+    LPR_LIVE_BBB(b);
+    int rc = bbb_ip(b, "lpr_bb_batch_pop_order_read", k, cap, count);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    const BBBatchDesc& d = b->h_desc[(size_t)k];
+    const int64_t n = b->ran ? std::min<int64_t>(d.processed, cap) : 0;
+    *count = n;
+    if (n == 0 || !ids) return LPR_OK_OPTIMAL;
+    LPR_HIP(hipMemcpyAsync(ids, b->d.pops + d.pop_off, (size_t)n * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// Pivot trace of IP k, as lpr_bb_trace_read
+int lpr_bb_batch_trace_read(lpr_bb_batch* b, int32_t k, int32_t* quads, int64_t cap,
+                            int64_t* count) {
+    LPR_LIVE_BBB(b);
+    int rc = bbb_ip(b, "lpr_bb_batch_trace_read", k, cap, count);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    const BBBatchDesc& d = b->h_desc[(size_t)k];
+    const int64_t n = b->ran ? std::min<int64_t>(std::min<int64_t>(d.pivots, d.trace_cap), cap)
+                             : 0;
+    *count = n;
+    if (n == 0 || !quads) return LPR_OK_OPTIMAL;
+    LPR_HIP(hipMemcpyAsync(quads, b->d.trace + 4 * d.trace_off, (size_t)n * 4 * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+}  // extern "C"

@@ -124,6 +124,7 @@ struct lpr_sens;
 struct lpr_comm;
 struct lpr_knap;
 struct lpr_batch;
+struct lpr_bb_batch;
 
 struct lpr_engine {
     int device = 0;
@@ -139,6 +140,7 @@ struct lpr_engine {
     std::vector<lpr_comm*> live_comm;  // RCCL communicators whose collectives run on this stream
     std::vector<lpr_knap*> live_knap;  // knapsack branch-and-bound handles (knapsack_engine.hip)
     std::vector<lpr_batch*> live_batch;  // batched primal simplex handles (batch_engine.hip)
+    std::vector<lpr_bb_batch*> live_bb_batch;  // batched B&B handles (bb_batch_engine.hip)
 };
 
 struct lpr_tableau {

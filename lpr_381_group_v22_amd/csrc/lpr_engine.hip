@@ -77,6 +77,8 @@ void comm_orphan(lpr_comm* c);
 void knap_orphan(lpr_knap* k);
 // batch_engine.hip
 void batch_orphan(lpr_batch* b);
+// bb_batch_engine.hip
+void bb_batch_orphan(lpr_bb_batch* b);
 }  // namespace lpr
 // cut_kernels.hip
 void lpr_cut_release(lpr_tableau* t);
@@ -686,6 +688,8 @@ int lpr_engine_close(lpr_engine* e) {
     e->live_knap.clear();
     for (lpr_batch* b : e->live_batch) batch_orphan(b);
     e->live_batch.clear();
+    for (lpr_bb_batch* b : e->live_bb_batch) bb_batch_orphan(b);
+    e->live_bb_batch.clear();
     if (e->stream) {
         hipStreamSynchronize(e->stream);
         hipStreamDestroy(e->stream);

@@ -1,0 +1,297 @@
+"""Measures the batched Branch & Bound and prints one JSON line per workload:
+
+  W   65536 option-3 IPs: n ~ U{6..10} binaries, m ~ U{1..3} integer-weight knapsack rows
+      (c ~ U{1..19}, a ~ U{1..14}, b = floor(sum(a) * U(0.3, 0.6))), node_cap 20
+  G   4096 IPs of 24 binaries x 8 rows, the same style
+  H   256 IPs of 96 binaries x 32 rows, the same style
+
+Every model goes through option 3 up to the root: the n rows "x_i <= 1", PrimalSimplexSolver (one
+PrimalSimplexBatch, not timed), FinalTableau and SetNumVars as SolveFromPrimal sets them.
+Per workload: IPs/s, pops/s and pivots/s end to end (lpr_bb_batch_create from the host roots,
+lpr_bb_batch_run, the bulk reads of results and x, closed by an engine sync) and for
+lpr_bb_batch_run alone (best of --repeat); launches; the forms the IPs took; the same roots one at
+a time through BranchBoundTree.from_array + run in a Python loop (a time-bounded prefix); the CPU
+oracle on one core (a prefix).  256 IPs per workload are checked against the oracle's orc_bb_solve
+bit for bit (status, found, processed, best_node, z, x, every record, pop order, pivot count, the
+kept trace); any mismatch makes the exit status non-zero.  Inputs are seeded (numpy
+RandomState(seed + workload)).
+
+Run it under a time limit:  timeout -k 10 1200 python tools/bb_batch_bench.py [--out FILE]
+Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python
+tools/bb_batch_bench.py --no-check --repeat 1
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+
+CHECK = 256
+NODE_CAP = 20
+TRACE_CAP = 256
+W_MAX, G_MAX = (64 * 1024 - 1024) // 4, 160 * 1024 - 1024  # kBBBatchMaxLdsW / kBBBatchMaxLdsG
+
+
+def gen_models(name: str, seed: int):
+    """Option-3 models (objective, constraints with the unit rows, True) of one workload."""
+    from lpr_381_group_v22_amd import Constraint
+    rng = np.random.RandomState(seed)
+    count, fixed = {"W": (65536, None), "G": (4096, (24, 8)), "H": (256, (96, 32))}[name]
+    models = []
+    for _ in range(count):
+        n, m = fixed if fixed else (int(rng.randint(6, 11)), int(rng.randint(1, 4)))
+        c = rng.randint(1, 20, size=n).astype(float)
+        A = rng.randint(1, 15, size=(m, n)).astype(float)
+        b = np.floor(A.sum(axis=1) * rng.uniform(0.3, 0.6, size=m))
+        cons = [Constraint(A[i].tolist(), "<=", float(b[i])) for i in range(m)]
+        for i in range(n):  # program._append_unit_bound_rows
+            co = [0.0] * (n + 3)
+            co[i] = 1.0
+            co[n + 1] = 1.0
+            cons.append(Constraint(co, "<=", 1.0))
+        models.append((c.tolist(), cons, True))
+    return models
+
+
+def roots_of(pkg, N, eng, models):
+    """FinalTableau and SetNumVars (BranchAndBoundAdapter.cs:20) of every model."""
+    lp = pkg.PrimalSimplexBatch(models, engine=eng)
+    lp.Solve()
+    roots, nvars = [], []
+    for k in range(lp.Count):
+        T = lp.GetFinalTableau(k)
+        roots.append(T)
+        nvars.append(lp.Shape(k)[2] if lp.Status[k] == N.LPR_OK_OPTIMAL
+                     else max(1, T.shape[1] - 1))
+    lp.destroy()
+    return roots, nvars
+
+
+def form_of(T):
+    r, c = T.shape[0] + NODE_CAP, T.shape[1] + NODE_CAP
+    b = 8 * (2 * r * c + r)
+    return "W" if b <= W_MAX else ("G" if b <= G_MAX else "H")
+
+
+T0 = time.perf_counter()
+
+
+def progress(msg: str) -> None:
+    print(f"[{time.perf_counter() - T0:8.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+def ptr(a, t):
+    return a.ctypes.data_as(C.POINTER(t)) if a.size else None
+
+
+def run_batch(N, eng, packed):
+    """One end-to-end pass: (seconds end to end, seconds of the run, result, outputs)."""
+    rows, cols, flat, nv = packed
+    count = len(rows)
+    out = dict(status=np.zeros(count, dtype=np.int32), found=np.zeros(count, dtype=np.int32),
+               processed=np.zeros(count, dtype=np.int64),
+               best_node=np.zeros(count, dtype=np.int32), z=np.zeros(count),
+               pivots=np.zeros(count, dtype=np.int64),
+               nodes_created=np.zeros(count, dtype=np.int64),
+               x=np.zeros(max(int(nv.sum()), 1)))
+    h = C.c_void_p()
+    opts = N.BBBatchOpts(enable_pruning=0, chunk=0, variant=0, max_child_pivots=0)
+    res = N.BBBatchResult()
+    eng.sync()
+    t0 = time.perf_counter()
+    N.check(N.lib.lpr_bb_batch_create(eng._h, count, ptr(rows, C.c_int32), ptr(cols, C.c_int32),
+                                      ptr(flat, C.c_double), ptr(nv, C.c_int32), NODE_CAP,
+                                      TRACE_CAP, C.byref(h)), "lpr_bb_batch_create")
+    t1 = time.perf_counter()
+    N.check(N.lib.lpr_bb_batch_run(h, C.byref(opts), C.byref(res)), "lpr_bb_batch_run")
+    t2 = time.perf_counter()
+    N.check(N.lib.lpr_bb_batch_result_read(
+        h, ptr(out["status"], C.c_int32), ptr(out["found"], C.c_int32),
+        ptr(out["processed"], C.c_int64), ptr(out["best_node"], C.c_int32),
+        ptr(out["z"], C.c_double), ptr(out["pivots"], C.c_int64),
+        ptr(out["nodes_created"], C.c_int64)), "lpr_bb_batch_result_read")
+    N.check(N.lib.lpr_bb_batch_solution_read(h, ptr(out["x"], C.c_double)),
+            "lpr_bb_batch_solution_read")
+    eng.sync()
+    t3 = time.perf_counter()
+    out["h"] = h
+    return t3 - t0, t2 - t1, res, out
+
+
+def single_loop(pkg, eng, roots, nvars, budget_s: float, skip):
+    done = pops = pivots = 0
+    t0 = time.perf_counter()
+    while done < len(roots) and time.perf_counter() - t0 < budget_s:
+        if skip[done]:
+            done += 1
+            continue
+        tree = pkg.BranchBoundTree.from_array(eng, roots[done], nvars[done], max_depth=NODE_CAP)
+        r, _ = tree.run(enable_pruning=False, node_cap=NODE_CAP)
+        tree.destroy()
+        pops += int(r.processed)
+        pivots += int(r.pivots)
+        done += 1
+    dt = time.perf_counter() - t0
+    return dict(ips=done, seconds=dt, ips_per_s=done / dt, pops_per_s=pops / dt,
+                pivots_per_s=pivots / dt)
+
+
+def oracle_loop(orc, roots, nvars, budget_s: float, skip):
+    done = pops = pivots = 0
+    t0 = time.perf_counter()
+    while done < len(roots) and time.perf_counter() - t0 < budget_s:
+        if skip[done]:
+            done += 1
+            continue
+        r = orc.bb_solve(roots[done], nvars[done], node_cap=NODE_CAP, rec_cap=64,
+                         piv_cap=TRACE_CAP)
+        pops += r["processed"]
+        done += 1
+    dt = time.perf_counter() - t0
+    return dict(ips=done, seconds=dt, ips_per_s=done / dt, pops_per_s=pops / dt)
+
+
+def bit_check(N, orc, roots, nvars, out, skip) -> int:
+    """IPs among the first CHECK that differ from the oracle in any output."""
+    h = out["h"]
+    bad = 0
+    at = 0
+    for k in range(min(CHECK, len(roots))):
+        nv = nvars[k]
+        if skip[k]:
+            at += nv
+            continue
+        ref = orc.bb_solve(roots[k], nv, node_cap=NODE_CAP, piv_cap=1 << 16)
+        ok = (out["status"][k] == ref["status"] and bool(out["found"][k]) == ref["found"]
+              and out["processed"][k] == ref["processed"]
+              and out["best_node"][k] == ref["best_node"]
+              and np.float64(out["z"][k]).tobytes() == np.float64(ref["z"]).tobytes()
+              and out["pivots"][k] == len(ref["trace"])
+              and out["nodes_created"][k] == len(ref["records"]))
+        xk = out["x"][at:at + nv]
+        ok = ok and (xk.tobytes() == np.asarray(ref["x"], dtype=np.float64).tobytes()
+                     if ref["found"] else not np.any(xk))
+        cap = 1 + 2 * NODE_CAP
+        p, kd, d, v, s = (np.zeros(cap, dtype=np.int32) for _ in range(5))
+        b, z = np.zeros(cap), np.zeros(cap)
+        n = C.c_int64()
+        N.check(N.lib.lpr_bb_batch_records_read(h, k, ptr(p, C.c_int32), ptr(kd, C.c_int32),
+                                                ptr(d, C.c_int32), ptr(v, C.c_int32),
+                                                ptr(b, C.c_double), ptr(s, C.c_int32),
+                                                ptr(z, C.c_double), cap, C.byref(n)),
+                "lpr_bb_batch_records_read")
+        recs = [(int(p[i]), int(kd[i]), int(d[i]), int(v[i]), np.float64(b[i]).tobytes(),
+                 int(s[i]), np.float64(z[i]).tobytes()) for i in range(n.value)]
+        want = [(r["parent"], r["kind"], r["depth"], r["var"], np.float64(r["bound"]).tobytes(),
+                 r["status"], np.float64(r["z"]).tobytes()) for r in ref["records"]]
+        ok = ok and recs == want
+        ids = np.zeros(NODE_CAP, dtype=np.int32)
+        N.check(N.lib.lpr_bb_batch_pop_order_read(h, k, ptr(ids, C.c_int32), NODE_CAP,
+                                                  C.byref(n)), "lpr_bb_batch_pop_order_read")
+        ok = ok and ids[:n.value].tolist() == ref["pop_order"]
+        q = np.zeros(4 * TRACE_CAP, dtype=np.int32)
+        N.check(N.lib.lpr_bb_batch_trace_read(h, k, ptr(q, C.c_int32), TRACE_CAP, C.byref(n)),
+                "lpr_bb_batch_trace_read")
+        got = [tuple(t) for t in q[:4 * n.value].reshape(-1, 4).tolist()]
+        ok = ok and got == [tuple(t) for t in ref["trace"][:TRACE_CAP]]
+        bad += 0 if ok else 1
+        at += nv
+    return bad
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="W,G,H")
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=20261016)
+    ap.add_argument("--single-seconds", type=float, default=5.0)
+    ap.add_argument("--oracle-seconds", type=float, default=5.0)
+    ap.add_argument("--no-check", action="store_true", help="skip the bit check and the loops")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+
+    import lpr_381_group_v22_amd as pkg
+    from lpr_381_group_v22_amd import _native as N
+    from lpr_381_group_v22_amd.bb_batch import pack_roots
+    orc = None
+    if not args.no_check:
+        from oracle_lib import Oracle
+        orc = Oracle()
+    failures = 0
+    lines = []
+    with pkg.Engine(0) as eng:
+        for i, name in enumerate(args.workloads.split(",")):
+            progress(f"{name}: generating")
+            models = gen_models(name, args.seed + i)
+            progress(f"{name}: primal batch")
+            roots, nvars = roots_of(pkg, N, eng, models)
+            packed = pack_roots(roots, nvars, NODE_CAP)
+            count = len(roots)
+            forms = {f: 0 for f in "WGH"}
+            for T in roots:
+                forms[form_of(T)] += 1
+            runs = []
+            for _ in range(max(1, args.repeat)):
+                if runs:  # only the last handle is kept (for the bit check)
+                    N.lib.lpr_bb_batch_destroy(runs[-1][3].pop("h"))
+                runs.append(run_batch(N, eng, packed))
+                progress(f"{name}: run {len(runs)}: e2e {runs[-1][0]:.4f}s, run {runs[-1][1]:.4f}s")
+            best_e2e = min(r[0] for r in runs)
+            best_run = min(r[1] for r in runs)
+            res, out = runs[-1][2], runs[-1][3]
+            pops, pivots = int(res.pops), int(res.pivots)
+            rec = dict(workload=name, ips=count,
+                       rows=[int(packed.rows.min()), int(packed.rows.max())],
+                       cols=[int(packed.cols.min()), int(packed.cols.max())],
+                       node_cap=NODE_CAP, forms=forms, pops=pops, pivots=pivots,
+                       done=res.done, node_capped=res.node_cap, pivot_limit=res.pivot_limit,
+                       found=int(out["found"].sum()), launches=res.launches,
+                       e2e_seconds=best_e2e, e2e_ips_per_s=count / best_e2e,
+                       e2e_pops_per_s=pops / best_e2e, e2e_pivots_per_s=pivots / best_e2e,
+                       run_seconds=best_run, run_ips_per_s=count / best_run,
+                       run_pops_per_s=pops / best_run, run_pivots_per_s=pivots / best_run,
+                       e2e_seconds_all=[r[0] for r in runs],
+                       run_seconds_all=[r[1] for r in runs])
+            if not args.no_check:
+                # an IP whose child LP hit the pivot limit cycles: the oracle, like the C#, would
+                # never return from it, so the loops and the check pass over those IPs
+                skip = out["status"] == N.LPR_PIVOT_LIMIT
+                rec["pivot_limit_ips_skipped_by_loops"] = int(skip.sum())
+                bad = bit_check(N, orc, roots, nvars, out, skip)
+                progress(f"{name}: bit check, {bad} mismatches")
+                rec["bit_checked"] = min(CHECK, count) - int(skip[:CHECK].sum())
+                rec["bit_mismatches"] = bad
+                failures += bad
+                rec["single_handle"] = single_loop(pkg, eng, roots, nvars, args.single_seconds,
+                                                    skip)
+                progress(f"{name}: single-handle loop done")
+                rec["cpu_oracle_1core"] = oracle_loop(orc, roots, nvars, args.oracle_seconds,
+                                                      skip)
+                rec["speedup_e2e_vs_single"] = rec["e2e_ips_per_s"] / \
+                    rec["single_handle"]["ips_per_s"]
+                rec["speedup_e2e_vs_oracle"] = rec["e2e_ips_per_s"] / \
+                    rec["cpu_oracle_1core"]["ips_per_s"]
+            N.lib.lpr_bb_batch_destroy(runs[-1][3]["h"])
+            line = json.dumps(rec)
+            print(line, flush=True)
+            lines.append(line)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    if failures:
+        print(f"bit check: {failures} IP(s) differ from the oracle", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
