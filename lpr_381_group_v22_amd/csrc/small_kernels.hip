@@ -53,6 +53,7 @@ struct lpr_small_ctx {
     double* fcol = nullptr;   // [K][Rp]  factor columns (the column of T^(q-1) before pivot q)
     SmallState* st = nullptr;
     SmallState* h_st = nullptr;  // pinned
+    int rows = 0, ld = 0;        // the shape prow / fcol / the LDS footprint were sized for
     int Rp = 0;
     unsigned long long* dbg = nullptr;  // LPR_SMALL_STAMPS=1
 };
@@ -441,10 +442,17 @@ void small_release(lpr_tableau* t) {
     t->small = nullptr;
 }
 
+// Rebuilt whenever the tableau's shape changed since it was made (the cut path grows rows on the
+// same handle): Rp strides fcol and the heads' LDS, so a stale one overlaps factor columns and
+// runs past both allocations.
 int small_ensure(lpr_tableau* t) {
-    if (t->small) return LPR_OK_OPTIMAL;
+    const lpr_small_ctx* old = static_cast<const lpr_small_ctx*>(t->small);
+    if (old && old->rows == t->rows && old->ld == t->ld) return LPR_OK_OPTIMAL;
+    small_release(t);
     lpr_small_ctx* c = new (std::nothrow) lpr_small_ctx();
     if (!c) return LPR_OUT_OF_MEMORY;
+    c->rows = t->rows;
+    c->ld = t->ld;
     c->Rp = align_up(t->rows, 16);
     hipError_t err = hipMalloc(&c->prow, (size_t)kSmallK * t->ld * sizeof(double));
     if (err == hipSuccess) err = hipMalloc(&c->fcol, (size_t)kSmallK * c->Rp * sizeof(double));

@@ -87,3 +87,36 @@ def test_cutting_plane(oracle, max_cuts):
         assert join(obj, rows).tobytes() == T.tobytes(), name
         exits.add(rc)
     assert len(exits) >= 2, exits
+
+
+def test_stride_cases_are_decided_by_the_planted_candidates(oracle):
+    """The GPU shape tests (test_side_shapes_gpu.py) plant ties one or more 1024-lane strides apart;
+    here the oracle confirms that the planted candidate really makes the first selection, so that
+    those tests cannot silently turn into easy cases."""
+    cases = cut_cases.stride_cases()
+    assert len(cases) >= 30
+    for name, solver, T, field, planted in cases:
+        R, C = T.shape
+        assert R - 1 > 1024 or C - 1 > 1024, name
+        assert C % 16 != 0, name                 # padding columns exist
+        rc, k, T2, log = cut_cases.run_oracle(oracle, solver, T, hard_cap=200)
+        assert log, name
+        assert log[0][0] == {"dual": 0, "primal2": 1, "cut": 2}[solver], name
+        assert log[0][field] == planted, (name, log[0], planted)
+        assert len(log) <= 200, name
+    # the two candidates of every mode sit in different strides: the later one wins only out of band
+    winners = {name: planted for name, _, _, _, planted in cases}
+    assert winners["dual_rows_exact_gap1124"] == 37
+    assert winners["dual_rows_later_better_out_of_band_gap1124"] == 37 + 1124
+    assert winners["dual_rows_three_strides"] == 37
+
+
+def test_many_cuts_on_a_tall_tableau(oracle):
+    """More than 1024 constraint rows, stopped by max_cuts only: 12 cuts, so the device buffer
+    (capacity rows + 8 per growth) is re-allocated twice."""
+    T0 = cut_cases.many_cuts_tall()
+    assert T0.shape[0] - 1 > 1024
+    rc, cuts, T, log = oracle.cutting_plane(T0, max_cuts=12, hard_cap=300)
+    assert (rc, cuts) == (6, 12)
+    assert T.shape[0] == T0.shape[0] + 12
+    assert sum(1 for e in log if e[0] == 2) == 12

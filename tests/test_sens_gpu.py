@@ -11,34 +11,8 @@ import sens_cases
 
 pytestmark = pytest.mark.gpu
 
-
-def _same_state(dev, orc, tag):
-    T, basic, sol = dev.read()
-    st = orc.state()
-    assert (T.shape == st["T"].shape), tag
-    assert T.tobytes() == st["T"].tobytes(), tag
-    assert basic.tolist() == st["basic"], tag
-    assert sol.tobytes() == st["sol"].tobytes(), tag
-    assert dev.shape()[4] == st["z"] or (math.isnan(st["z"]) and math.isnan(dev.shape()[4])), tag
-    assert dev.log() == orc.log(), tag
-
-
-def _run_script(engine, oracle, name, base, ops):
-    from lpr_381_group_v22_amd.engine import SensState
-    T, x, z, basis = base
-    o = oracle.sens(T, x, z, basis)
-    d = SensState.create(engine, T, x, z)
-    _same_state(d, o, (name, "ctor"))
-    codes = []
-    for k, (op, args) in enumerate(ops):
-        op, args = sens_cases.materialize(op, args, o.state()["T"], k)
-        rc = getattr(o, op)(*args)
-        oc = getattr(d, op)(*args)
-        assert oc == rc, (name, k, op, oc, rc)
-        _same_state(d, o, (name, k, op))
-        codes.append(rc)
-    d.destroy()
-    return codes
+_same_state = sens_cases.same_state
+_run_script = sens_cases.run_script
 
 
 def test_edit_scripts_match_oracle(engine, oracle):

@@ -5,7 +5,10 @@
   * sensitivity re-solve (row f4): random edit scripts on one analyzer (indices in and out of range,
     basic and non-basic columns, edits that are rolled back or leave the state mid-way) -- outcome
     code and tableau / basis / solution / Z / pivot log after EVERY edit.
-    python tools/fuzz_side_gpu.py [seconds] [first seed]"""
+    python tools/fuzz_side_gpu.py [--large] [seconds] [first seed]
+--large: about one LP in three gets m or n drawn from 1000..1099, across the 1024 lanes of the
+single-workgroup folds (slower: the oracle solves those LPs first).  Without it the draws are
+the same as ever, so a seed keeps naming the same case."""
 import math
 import sys
 import time
@@ -23,6 +26,7 @@ from lpr_381_group_v22_amd.engine import SensState  # noqa: E402
 
 DUAL_STATUS = {0: 0, 1: 2, 3: 3, 5: 5}
 PRIM_STATUS = {0: 0, 1: 1, 3: 3, 5: 5}
+LARGE = False   # --large
 
 
 def fail(*what):
@@ -33,6 +37,12 @@ def fail(*what):
 def random_lp(rng, integer):
     m, n = int(rng.randint(2, 14)), int(rng.randint(2, 18))
     seed = int(rng.randint(0, 1 << 30))
+    if LARGE and rng.randint(0, 3) == 0:   # extra draws only with --large
+        big = int(rng.randint(1000, 1100))
+        if rng.randint(0, 2):
+            m = big
+        else:
+            n = big
     if integer:
         obj, cons, _ = lp_cases.tie_heavy(m, n, seed)
         cons = [type(c)(c.Coefficients, "<=", abs(c.RHS) + float(rng.randint(0, 3))) for c in cons]
@@ -163,8 +173,11 @@ def sens_case(oracle, eng, rng, seed):
 
 
 def main():
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-    seed = seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    global LARGE
+    args = [a for a in sys.argv[1:] if a != "--large"]
+    LARGE = len(args) != len(sys.argv) - 1
+    budget = float(args[0]) if len(args) > 0 else 120.0
+    seed = seed0 = int(args[1]) if len(args) > 1 else 1
     oracle = Oracle()
     eng = pkg.Engine(0)
     t_end = time.time() + budget
