@@ -6,9 +6,12 @@
 // constraintRows).  Same pivot shape as PrimalSimplexSolver with two differences: rows whose
 // factor is within 1e-9 of zero are left untouched (DualSimplex.cs:166, PrimalSimplexSolver2.cs:160)
 // and every selection is an EPS-band sequential fold ("better by more than EPS"), replayed exactly
-// by the next-take search also used by the revised solver.  Not pipelined: this path is dead code
-// in the reference's menu (Program.cs:417-428); parity is the bar here, not the roofline.
+// and in one pass by eps_fold (fold_common.hpp), as in the sensitivity re-solve.  Not pipelined:
+// this path is dead code in the reference's menu (Program.cs:417-428); parity is the bar here, not
+// the roofline.
 #include "engine_common.hpp"
+#include "fold_common.hpp"
+#include "select_common.hpp"
 
 #include <new>
 
@@ -17,6 +20,8 @@
 namespace lpr {
 
 constexpr double kCutEps = 1e-9;  // DualSimplex.cs:8, PrimalSimplexSolver2.cs, CuttingPlaneSolver.cs:10
+static_assert(kCutEps == kFoldEps, "eps_fold replays the cut path's EPS band");
+constexpr int kCutK = 16;  // eps_fold candidates cached per lane: 16 384 rows / columns in one pass
 
 struct CutState {
     int32_t status;      // kRunning or an lpr_status
@@ -32,20 +37,6 @@ struct CutState {
     int32_t scratch[8];  // cutting-plane step results
 };
 
-__device__ __forceinline__ int cut_block_min_int(int v, int* lds) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x / kWave;
-    const int nwaves = blockDim.x / kWave;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
-    __syncthreads();
-    if (lane == 0) lds[wave] = v;
-    __syncthreads();
-    int r = lds[0];
-    for (int w = 1; w < nwaves; ++w) r = min(r, lds[w]);
-    return r;
-}
-
 // |num / a| over the negative entries of row `prow` with a non-zero objective entry; NaN = skip
 __device__ __forceinline__ double dual_ratio(const double* __restrict__ T, int ld, int prow,
                                              int j) {
@@ -56,30 +47,15 @@ __device__ __forceinline__ double dual_ratio(const double* __restrict__ T, int l
     return fabs(ieee_div(num, a));
 }
 
-// Replays `for j ascending: if (ratio < best - EPS || (|ratio - best| <= EPS && (pc == -1 ||
-// j < pc))) take` (DualSimplex.cs:53-70, CuttingPlaneSolver.cs:116-132) on row `prow`.
-__device__ int fold_dual_column(const double* __restrict__ T, int ld, int C, int prow, int* lds) {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    int pc = -1;
-    double best = INFINITY;
-    for (;;) {
-        int first = INT_MAX;
-        for (int j = tid; j < C - 1; j += nt) {
-            if (j <= pc) continue;
-            const double ratio = dual_ratio(T, ld, prow, j);
-            if (ratio != ratio) continue;
-            if (ratio < best - kCutEps ||
-                (fabs(ratio - best) <= kCutEps && (pc == -1 || j < pc))) {
-                first = j;
-                break;
-            }
-        }
-        first = cut_block_min_int(first, lds);
-        if (first == INT_MAX) break;
-        pc = first;
-        best = dual_ratio(T, ld, prow, pc);
-    }
-    return pc;
+// Pivot column of the dual ratio test on row `prow` (DualSimplex.cs:53-70,
+// CuttingPlaneSolver.cs:116-132): `ratio < best - EPS || (|ratio - best| <= EPS && (pc == -1 ||
+// j < pc))` over j ascending.  The tie clause never fires: j ascends, so `j < pc` is false once a
+// column has been taken; before that best is +inf and |ratio - inf| is inf (NaN for ratio = inf),
+// never <= EPS.  What is left is eps_fold's "better by more than EPS".
+__device__ __forceinline__ int fold_dual_column(const double* __restrict__ T, int ld, int C,
+                                                int prow, int* lds, double* lds_v) {
+    return eps_fold<kCutK>(
+        0, C - 1, INFINITY, [&](int j) { return dual_ratio(T, ld, prow, j); }, lds, lds_v);
 }
 
 enum : int { kCutDual = 0, kCutPrimal2 = 1 };
@@ -90,7 +66,8 @@ __global__ __launch_bounds__(1024) void k_cut_select(double* __restrict__ T, int
                                                      double* __restrict__ colbuf,
                                                      int32_t* __restrict__ log, CutState* st,
                                                      int mode) {
-    __shared__ int lds[16];
+    __shared__ int lds[32];
+    __shared__ double lds_v[32];
     if (st->status != kRunning) return;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int rhs = C - 1;
@@ -117,82 +94,47 @@ __global__ __launch_bounds__(1024) void k_cut_select(double* __restrict__ T, int
         }
     }
 
+    // Each selection below is a sequential fold over ascending indices whose C# condition also
+    // has a tie clause on `index < current choice`.  An ascending scan only meets indices above
+    // its current choice, so those clauses are dead and eps_fold replays what is left.
     if (mode == kCutDual) {
         // pivot row: `rhs < mostNeg - EPS || (|rhs - mostNeg| <= EPS && pivotRow != -1 &&
-        // r < pivotRow)` over constraint rows r ascending (:29-37)
-        int prow = -1;  // constraint index
-        double mostNeg = 0.0;
-        for (;;) {
-            int first = INT_MAX;
-            for (int r = tid; r < R - 1; r += nt) {
-                if (r <= prow) continue;
-                const double v = T[(size_t)(r + 1) * ld + rhs];
-                if (v < mostNeg - kCutEps ||
-                    (fabs(v - mostNeg) <= kCutEps && prow != -1 && r < prow)) {
-                    first = r;
-                    break;
-                }
-            }
-            first = cut_block_min_int(first, lds);
-            if (first == INT_MAX) break;
-            prow = first;
-            mostNeg = T[(size_t)(prow + 1) * ld + rhs];
-        }
+        // r < pivotRow)` over constraint rows r ascending, mostNeg = 0 at the start (:29-37);
+        // r > pivotRow whenever pivotRow != -1
+        const int prow = eps_fold<kCutK>(
+            0, R - 1, 0.0, [&](int r) { return T[(size_t)(r + 1) * ld + rhs]; }, lds, lds_v);
         if (prow < 0) {
             if (tid == 0) st->status = LPR_OK_OPTIMAL;  // "Dual phase complete" :40-44
             return;
         }
         pr = prow + 1;
-        pc = fold_dual_column(T, ld, C, pr, lds);
+        pc = fold_dual_column(T, ld, C, pr, lds, lds_v);
         if (pc < 0) {
             if (tid == 0) st->status = LPR_INFEASIBLE_BASIS;  // return false :72-76
             return;
         }
     } else {
-        // entering column: `c < mostNeg - EPS || (...)` (:102-117)
-        double mostNeg = 0.0;
-        for (;;) {
-            int first = INT_MAX;
-            for (int j = tid; j < rhs; j += nt) {
-                if (j <= pc) continue;
-                const double c = T[j];
-                if (c < mostNeg - kCutEps ||
-                    (fabs(c - mostNeg) <= kCutEps && pc != -1 && j < pc)) {
-                    first = j;
-                    break;
-                }
-            }
-            first = cut_block_min_int(first, lds);
-            if (first == INT_MAX) break;
-            pc = first;
-            mostNeg = T[pc];
-        }
+        // entering column: `c < mostNeg - EPS || (|c - mostNeg| <= EPS && pc != -1 && j < pc)`,
+        // mostNeg = 0 at the start (:102-117); j > pc whenever pc != -1
+        pc = eps_fold<kCutK>(0, rhs, 0.0, [&](int j) { return T[j]; }, lds, lds_v);
         if (pc < 0) {
             if (tid == 0) st->status = LPR_OK_OPTIMAL;  // :54-60
             return;
         }
-        // leaving row (:120-141), with the C#'s operator precedence:
+        // leaving row over the rows with a > EPS (:120-141), with the C#'s operator precedence:
         // (ratio > EPS && ratio < best - EPS) || ((|ratio - best| <= EPS && bestRow == -1) ? true
         //                                                                           : i < bestRow)
-        double best = INFINITY;
-        for (;;) {
-            int first = INT_MAX;
-            for (int i = 1 + tid; i < R; i += nt) {
-                if (i <= pr) continue;
+        // The second operand is never true: with bestRow == -1 best is +inf, so the ternary's
+        // condition is false and `i < -1` is false; afterwards i > bestRow.
+        pr = eps_fold<kCutK>(
+            1, R, INFINITY,
+            [&](int i) -> double {
                 const double a = T[(size_t)i * ld + pc];
-                if (!(a > kCutEps)) continue;
+                if (!(a > kCutEps)) return NAN;
                 const double ratio = ieee_div(T[(size_t)i * ld + rhs], a);
-                const bool second = (fabs(ratio - best) <= kCutEps && pr == -1) ? true : (i < pr);
-                if ((ratio > kCutEps && ratio < best - kCutEps) || second) {
-                    first = i;
-                    break;
-                }
-            }
-            first = cut_block_min_int(first, lds);
-            if (first == INT_MAX) break;
-            pr = first;
-            best = ieee_div(T[(size_t)pr * ld + rhs], T[(size_t)pr * ld + pc]);
-        }
+                return (ratio > kCutEps) ? ratio : NAN;
+            },
+            lds, lds_v);
         if (pr < 0) {
             if (tid == 0) st->status = LPR_UNBOUNDED;  // return false :63-68
             return;
@@ -226,18 +168,17 @@ __global__ __launch_bounds__(1024) void k_cut_select(double* __restrict__ T, int
 }
 
 // Pivot with the row skip (DualSimplex.cs:150-178, PrimalSimplexSolver2.cs:145-164): row i is
-// rewritten only if |f_i| > EPS.
+// rewritten only if |f_i| > EPS.  No state is written here: the bookkeeping lives in k_cut_select.
 template <int TR>
 __global__ __launch_bounds__(256) void k_cut_update(double* __restrict__ T, int ld, int R,
                                                     const double* __restrict__ rowbuf,
                                                     const double* __restrict__ colbuf,
-                                                    CutState* st, int check_status, int finish) {
+                                                    CutState* st, int check_status) {
     if (check_status && st->status != kRunning) return;
     const int ld2 = ld >> 1;
     const int c2 = blockIdx.x * blockDim.x + threadIdx.x;
     const int i0 = blockIdx.y * TR;
     const int r = st->pr;
-    (void)finish;  // bookkeeping lives in k_cut_select (no state is written by this kernel)
     if (c2 >= ld2) return;
     const double2 pr2 = reinterpret_cast<const double2*>(rowbuf)[c2];
     double2* __restrict__ T2 = reinterpret_cast<double2*>(T);
@@ -275,65 +216,38 @@ __global__ __launch_bounds__(1024) void k_cut_add(double* __restrict__ T, int ld
                                                   double* __restrict__ rowbuf,
                                                   double* __restrict__ colbuf,
                                                   int32_t* __restrict__ log, CutState* st) {
-    __shared__ int lds[16];
-    __shared__ double lds_v[16];
+    __shared__ int lds[32];
+    __shared__ double lds_v[32];
     const int tid = threadIdx.x, nt = blockDim.x;
     const int rhs = C - 1;
     // lexicographic min of (|frac - 0.5|, index) over rows with frac > EPS
-    double bk = INFINITY;
-    int bi = INT_MAX;
+    Cand best;
+    best.v = INFINITY;
+    best.i = -1;
     for (int i = tid; i < R - 1; i += nt) {
         const double fr = cut_frac(T[(size_t)(i + 1) * ld + rhs]);
         if (fr > kCutEps) {
             const double key = fabs(fr - 0.5);
-            if (bi == INT_MAX || key < bk) {
-                bk = key;
-                bi = i;
+            if (best.i < 0 || key < best.v) {  // ascending i per thread: strict < keeps the first
+                best.v = key;
+                best.i = i;
             }
         }
     }
-    {  // block reduce (value, index) -- associative: smaller key, then smaller index
-        const int lane = tid & (kWave - 1), wave = tid / kWave, nw = nt / kWave;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ok = __shfl_xor(bk, off, kWave);
-            const int oi = __shfl_xor(bi, off, kWave);
-            if (oi != INT_MAX && (bi == INT_MAX || ok < bk || (ok == bk && oi < bi))) {
-                bk = ok;
-                bi = oi;
-            }
-        }
-        __syncthreads();
-        if (lane == 0) {
-            lds_v[wave] = bk;
-            lds[wave] = bi;
-        }
-        __syncthreads();
-        bk = lds_v[0];
-        bi = lds[0];
-        for (int w = 1; w < nw; ++w) {
-            const double ok = lds_v[w];
-            const int oi = lds[w];
-            if (oi != INT_MAX && (bi == INT_MAX || ok < bk || (ok == bk && oi < bi))) {
-                bk = ok;
-                bi = oi;
-            }
-        }
-        __syncthreads();
-    }
-    if (bi == INT_MAX) {
+    best = block_cand_min(best, lds_v, lds);
+    if (best.i < 0) {
         if (tid == 0) {
             st->scratch[0] = -1;
             st->scratch[1] = -1;
         }
         return;
     }
-    const int chosen = bi;
+    const int chosen = best.i;
     for (int j = tid; j < ld; j += nt)  // cut row (:99-110), padding stays 0
         T[(size_t)R * ld + j] = (j < C) ? -cut_frac(T[(size_t)(chosen + 1) * ld + j]) : 0.0;
-    __syncthreads();
+    __syncthreads();  // the fold reads the row this workgroup has just written
     __threadfence_block();
-    const int pc = fold_dual_column(T, ld, C, R, lds);  // :113-132 on the new row
+    const int pc = fold_dual_column(T, ld, C, R, lds, lds_v);  // :113-132 on the new row
     if (tid == 0) {
         st->scratch[0] = chosen;
         st->scratch[1] = pc;
@@ -391,7 +305,6 @@ struct lpr_cut_ctx {  // per-tableau scratch of this path, hung off the tableau 
     lpr::CutState* h_state = nullptr;
     int32_t* log = nullptr;
     int64_t log_cap = 0;
-    int row_cap = 0;  // rows the tableau buffer can hold
 };
 
 using namespace lpr;
@@ -403,7 +316,6 @@ int cut_ensure(lpr_tableau* t) {
     lpr_cut_ctx* c = new (std::nothrow) lpr_cut_ctx();
     if (!c) return LPR_OUT_OF_MEMORY;
     c->log_cap = 1 << 16;
-    c->row_cap = t->rows;
     hipError_t err = hipMalloc(&c->state, sizeof(CutState));
     if (err == hipSuccess) err = hipHostMalloc(&c->h_state, sizeof(CutState));
     if (err == hipSuccess) err = hipMalloc(&c->log, (size_t)c->log_cap * 3 * sizeof(int32_t));
@@ -421,60 +333,12 @@ int cut_ensure(lpr_tableau* t) {
     return LPR_OK_OPTIMAL;
 }
 
-// make room for `rows_needed` tableau rows (the cut appends one row per call)
-int cut_grow_rows(lpr_tableau* t, int rows_needed) {
-    lpr_cut_ctx* c = static_cast<lpr_cut_ctx*>(t->cut);
-    if (rows_needed <= c->row_cap) return LPR_OK_OPTIMAL;
-    hipStream_t s = t->eng->stream;
-    const int cap = rows_needed + 8;
-    double *nT = nullptr, *ncol = nullptr;
-    LPR_HIP(hipMalloc(&nT, (size_t)cap * t->ld * sizeof(double)));
-    LPR_HIP(hipMemsetAsync(nT, 0, (size_t)cap * t->ld * sizeof(double), s));
-    LPR_HIP(hipMemcpyAsync(nT, t->T, (size_t)t->rows * t->ld * sizeof(double),
-                           hipMemcpyDeviceToDevice, s));
-    LPR_HIP(hipMalloc(&ncol, (size_t)align_up(cap, 16) * sizeof(double)));
-    LPR_HIP(hipStreamSynchronize(s));
-    hipFree(t->T);
-    hipFree(t->colbuf);
-    hipFree(t->T2);  // the fused path's second buffer no longer matches the shape
-    t->T2 = nullptr;
-    t->T = nT;
-    t->colbuf = ncol;
-    // next_col / next_rhs / basis belong to the pipelined primal path; re-size them too so that a
-    // later lpr_primal_solve on the grown tableau stays valid
-    double *nc = nullptr, *nr = nullptr;
-    int32_t* nb = nullptr;
-    LPR_HIP(hipMalloc(&nc, (size_t)align_up(cap, 16) * sizeof(double)));
-    LPR_HIP(hipMalloc(&nr, (size_t)align_up(cap, 16) * sizeof(double)));
-    LPR_HIP(hipMalloc(&nb, (size_t)cap * sizeof(int32_t)));
-    LPR_HIP(hipMemsetAsync(nb, 0xff, (size_t)cap * sizeof(int32_t), s));
-    if (t->rows > 1)
-        LPR_HIP(hipMemcpyAsync(nb, t->basis, (size_t)(t->rows - 1) * sizeof(int32_t),
-                               hipMemcpyDeviceToDevice, s));
-    LPR_HIP(hipStreamSynchronize(s));
-    hipFree(t->next_col);
-    hipFree(t->next_rhs);
-    hipFree(t->basis);
-    t->next_col = nc;
-    t->next_rhs = nr;
-    t->basis = nb;
-    if (t->graph) {  // (a stale graph would also be rejected by its key: rows / T changed)
-        hipGraphExecDestroy(t->graph);
-        t->graph = nullptr;
-        t->graph_batch = 0;
-        t->graph_variant = -1;
-        t->graph_key = lpr_tableau::GraphKey();
-    }
-    c->row_cap = cap;
-    return LPR_OK_OPTIMAL;
-}
-
-void cut_launch_update(lpr_tableau* t, int check_status, int finish) {
+void cut_launch_update(lpr_tableau* t, int check_status) {
     lpr_cut_ctx* c = static_cast<lpr_cut_ctx*>(t->cut);
     constexpr int TR = 8;
     dim3 grid((t->ld / 2 + 255) / 256, (t->rows + TR - 1) / TR);
     hipLaunchKernelGGL((k_cut_update<TR>), grid, dim3(256), 0, t->eng->stream, t->T, t->ld, t->rows,
-                       t->rowbuf, t->colbuf, c->state, check_status, finish);
+                       t->rowbuf, t->colbuf, c->state, check_status);
 }
 
 // DualSimplexSolver.Solve / PrimalSimplexSolver2.Solve driver; returns the lpr_status
@@ -497,7 +361,7 @@ int cut_run_solver(lpr_tableau* t, int mode, int max_iters, int print_steps, int
         for (int k = 0; k < batch; ++k) {
             hipLaunchKernelGGL(k_cut_select, dim3(1), dim3(1024), 0, s, t->T, t->ld, t->rows,
                                t->cols, t->rowbuf, t->colbuf, c->log, c->state, mode);
-            cut_launch_update(t, 1, 1);
+            cut_launch_update(t, 1);
         }
         LPR_HIP(hipGetLastError());
         LPR_HIP(hipMemcpyAsync(hs, c->state, sizeof(CutState), hipMemcpyDeviceToHost, s));
@@ -506,6 +370,36 @@ int cut_run_solver(lpr_tableau* t, int mode, int max_iters, int print_steps, int
     }
     if (pivots) *pivots = hs->done;
     return hs->status;
+}
+
+// needDual / needPrimal / anyFractional of the tableau as it stands -> h_state->scratch[2..4]
+int cut_read_flags(lpr_tableau* t) {
+    lpr_cut_ctx* c = static_cast<lpr_cut_ctx*>(t->cut);
+    hipStream_t s = t->eng->stream;
+    hipLaunchKernelGGL(k_cut_flags, dim3(1), dim3(1024), 0, s, t->T, t->ld, t->rows, t->cols,
+                       c->state);
+    LPR_HIP(hipGetLastError());
+    LPR_HIP(hipMemcpyAsync(c->h_state, c->state, sizeof(CutState), hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    return LPR_OK_OPTIMAL;
+}
+
+// lpr_dual_solve / lpr_primal2_solve after their argument checks
+int cut_solve_entry(lpr_tableau* t, int mode, int max_iters, int print_steps, int64_t hard_cap,
+                    lpr_solve_result* res) {
+    LPR_HIP(hipSetDevice(t->eng->device));
+    int rc = cut_ensure(t);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    int64_t piv = 0;
+    const int st = cut_run_solver(t, mode, max_iters, print_steps, hard_cap, &piv);
+    if (st < 0) return st;
+    res->status = st;
+    res->block = 1;
+    res->pivots = piv;
+    res->total_pivots = piv;
+    res->z = 0.0;
+    LPR_HIP(hipMemcpy(&res->z, t->T + (t->cols - 1), sizeof(double), hipMemcpyDeviceToHost));
+    return st;
 }
 
 }  // namespace
@@ -537,19 +431,7 @@ int lpr_dual_solve(lpr_tableau* t, int max_iters, int print_steps, int64_t hard_
         set_error("lpr_dual_solve: no constraint rows");  // ArgumentException :17
         return LPR_BAD_ARGUMENT;
     }
-    LPR_HIP(hipSetDevice(t->eng->device));
-    int rc = cut_ensure(t);
-    if (rc != LPR_OK_OPTIMAL) return rc;
-    int64_t piv = 0;
-    const int st = cut_run_solver(t, kCutDual, max_iters, print_steps, hard_cap, &piv);
-    if (st < 0) return st;
-    res->status = st;
-    res->block = 1;
-    res->pivots = piv;
-    res->total_pivots = piv;
-    res->z = 0.0;
-    LPR_HIP(hipMemcpy(&res->z, t->T + (t->cols - 1), sizeof(double), hipMemcpyDeviceToHost));
-    return st;
+    return cut_solve_entry(t, kCutDual, max_iters, print_steps, hard_cap, res);
 }
 
 int lpr_primal2_solve(lpr_tableau* t, int max_iters, int print_steps, int64_t hard_cap,
@@ -559,19 +441,7 @@ int lpr_primal2_solve(lpr_tableau* t, int max_iters, int print_steps, int64_t ha
         set_error("lpr_primal2_solve: no constraint rows");  // ArgumentException :27
         return LPR_BAD_ARGUMENT;
     }
-    LPR_HIP(hipSetDevice(t->eng->device));
-    int rc = cut_ensure(t);
-    if (rc != LPR_OK_OPTIMAL) return rc;
-    int64_t piv = 0;
-    const int st = cut_run_solver(t, kCutPrimal2, max_iters, print_steps, hard_cap, &piv);
-    if (st < 0) return st;
-    res->status = st;
-    res->block = 1;
-    res->pivots = piv;
-    res->total_pivots = piv;
-    res->z = 0.0;
-    LPR_HIP(hipMemcpy(&res->z, t->T + (t->cols - 1), sizeof(double), hipMemcpyDeviceToHost));
-    return st;
+    return cut_solve_entry(t, kCutPrimal2, max_iters, print_steps, hard_cap, res);
 }
 
 int lpr_cutting_plane(lpr_tableau* t, int max_cuts, int64_t hard_cap, int32_t* exit_code,
@@ -592,14 +462,12 @@ int lpr_cutting_plane(lpr_tableau* t, int max_cuts, int64_t hard_cap, int32_t* e
     for (;;) {
         if (ncuts >= max_cuts) {
             // do not add a cut we are not allowed to; but "all integral" still wins (exit 1)
-            hipLaunchKernelGGL(k_cut_flags, dim3(1), dim3(1024), 0, s, t->T, t->ld, t->rows,
-                               t->cols, c->state);
-            LPR_HIP(hipMemcpyAsync(hs, c->state, sizeof(CutState), hipMemcpyDeviceToHost, s));
-            LPR_HIP(hipStreamSynchronize(s));
+            rc = cut_read_flags(t);
+            if (rc != LPR_OK_OPTIMAL) return rc;
             ex = hs->scratch[4] ? 6 : 1;
             break;
         }
-        rc = cut_grow_rows(t, t->rows + 1);
+        rc = tableau_reserve_rows(t, t->rows + 1);  // the cut appends one row
         if (rc != LPR_OK_OPTIMAL) return rc;
         // steps 1-6 (+ staging of the pivot on the cut)
         hs->status = LPR_OK_OPTIMAL;
@@ -615,22 +483,17 @@ int lpr_cutting_plane(lpr_tableau* t, int max_cuts, int64_t hard_cap, int32_t* e
         ncuts += 1;
         if (hs->scratch[1] == -1) { ex = 2; break; }  // no valid pivot column :134-138
         if (hs->scratch[1] == -2) { ex = 3; break; }  // pivot too small :146-150
-        cut_launch_update(t, 0, 0);                   // step 7
-        hipLaunchKernelGGL(k_cut_flags, dim3(1), dim3(1024), 0, s, t->T, t->ld, t->rows, t->cols,
-                           c->state);
-        LPR_HIP(hipGetLastError());
-        LPR_HIP(hipMemcpyAsync(hs, c->state, sizeof(CutState), hipMemcpyDeviceToHost, s));
-        LPR_HIP(hipStreamSynchronize(s));
+        cut_launch_update(t, 0);                      // step 7
+        rc = cut_read_flags(t);
+        if (rc != LPR_OK_OPTIMAL) return rc;
         bool needDual = hs->scratch[2] != 0, needPrimal = hs->scratch[3] != 0;
         if (needDual) {  // :186-194, printSteps: true
             const int st = cut_run_solver(t, kCutDual, 10000, 1, hard_cap, nullptr);
             if (st < 0) return st;
             if (st == LPR_PIVOT_TOO_SMALL) { ex = 7; break; }
             if (st != LPR_OK_OPTIMAL) { ex = 4; break; }
-            hipLaunchKernelGGL(k_cut_flags, dim3(1), dim3(1024), 0, s, t->T, t->ld, t->rows,
-                               t->cols, c->state);
-            LPR_HIP(hipMemcpyAsync(hs, c->state, sizeof(CutState), hipMemcpyDeviceToHost, s));
-            LPR_HIP(hipStreamSynchronize(s));
+            rc = cut_read_flags(t);
+            if (rc != LPR_OK_OPTIMAL) return rc;
             needPrimal = hs->scratch[3] != 0;
         }
         if (needPrimal) {  // :196-212; the result of Solve is ignored by the C#
@@ -638,10 +501,8 @@ int lpr_cutting_plane(lpr_tableau* t, int max_cuts, int64_t hard_cap, int32_t* e
             if (st < 0) return st;
             if (st == LPR_PIVOT_TOO_SMALL) { ex = 7; break; }
         }
-        hipLaunchKernelGGL(k_cut_flags, dim3(1), dim3(1024), 0, s, t->T, t->ld, t->rows, t->cols,
-                           c->state);
-        LPR_HIP(hipMemcpyAsync(hs, c->state, sizeof(CutState), hipMemcpyDeviceToHost, s));
-        LPR_HIP(hipStreamSynchronize(s));
+        rc = cut_read_flags(t);
+        if (rc != LPR_OK_OPTIMAL) return rc;
         if (!hs->scratch[3] && !hs->scratch[2]) {  // :215
             if (hs->scratch[4]) continue;           // another Gomory cut (:217-222)
             ex = 0;                                 // "Displayed the Optimal Tableau" :224

@@ -146,6 +146,7 @@ struct lpr_engine {
 struct lpr_tableau {
     lpr_engine* eng = nullptr;
     int rows = 0, cols = 0, ld = 0;  // ld = cols rounded up to kLdAlign
+    int row_cap = 0;                 // rows the row-sized buffers can hold (tableau_reserve_rows)
     double* T = nullptr;             // rows x ld, row-major, padding columns kept at 0
     double* T2 = nullptr;            // second buffer of the fused small-tableau path (lazy)
     double* rowbuf = nullptr;        // ld doubles: normalised pivot row
@@ -191,3 +192,8 @@ struct lpr_tableau {
     void* cut = nullptr;              // lpr_cut_ctx of the cutting-plane side path (cut_kernels.hip)
     void* small = nullptr;            // lpr_small_ctx of the cache-resident path (small_kernels.hip)
 };
+
+namespace lpr {
+// lpr_engine.hip: make room for `rows_needed` tableau rows on a live handle
+int tableau_reserve_rows(lpr_tableau* t, int rows_needed);
+}  // namespace lpr

@@ -1,5 +1,6 @@
 // fold_common.hpp -- the sequential "better by more than EPS" fold of the reference's selection
-// loops, replayed exactly on one workgroup (used by sens_engine.hip and revised_kernels.hip).
+// loops, replayed exactly on one workgroup (used by sens_engine.hip, cut_kernels.hip and
+// revised_kernels.hip).
 // Not part of the ABI.
 #pragma once
 

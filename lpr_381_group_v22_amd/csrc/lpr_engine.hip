@@ -98,6 +98,7 @@ static int alloc_tableau(lpr_engine* e, int rows, int cols, lpr_tableau** out) {
     if (!t) return LPR_OUT_OF_MEMORY;
     t->eng = e;
     t->rows = rows;
+    t->row_cap = rows;
     t->cols = cols;
     t->ld = align_up(cols, kLdAlign);
     t->log_cap = 1 << 16;
@@ -149,6 +150,64 @@ static void drop_graph(lpr_tableau* t) {
     t->graph_batch = 0;
     t->graph_variant = -1;
     t->graph_key = lpr_tableau::GraphKey();
+}
+
+// Make room for `rows_needed` tableau rows (the cutting plane appends one row per cut).  Re-sized
+// here: what alloc_tableau sizes by `rows` -- T (new rows zero), colbuf, next_col, next_rhs and
+// basis (new entries -1), with 8 rows of slack; T2 no longer matches the shape and is dropped, as
+// is the captured graph.  Not touched: the small and overlap contexts are keyed by (rows, ld) and
+// rebuild themselves in small_ensure / ov_ensure.  Everything new is allocated and filled before
+// anything old is freed: on failure the handle is left exactly as it was.
+int tableau_reserve_rows(lpr_tableau* t, int rows_needed) {
+    if (rows_needed <= t->row_cap) return LPR_OK_OPTIMAL;
+    hipStream_t s = t->eng->stream;
+    const int cap = rows_needed + 8;
+    const size_t tbytes = (size_t)cap * t->ld * sizeof(double);
+    const size_t cbytes = (size_t)align_up(cap, 16) * sizeof(double);
+    const size_t bbytes = (size_t)cap * sizeof(int32_t);
+    double *nT = nullptr, *ncol = nullptr, *nnc = nullptr, *nnr = nullptr;
+    int32_t* nb = nullptr;
+    hipError_t err = hipSuccess;
+    auto chk = [&](hipError_t x) { if (err == hipSuccess) err = x; };
+    chk(hipMalloc(&nT, tbytes));
+    chk(hipMalloc(&ncol, cbytes));
+    chk(hipMalloc(&nnc, cbytes));
+    chk(hipMalloc(&nnr, cbytes));
+    chk(hipMalloc(&nb, bbytes));
+    if (err == hipSuccess) err = hipMemsetAsync(nT, 0, tbytes, s);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(nT, t->T, (size_t)t->rows * t->ld * sizeof(double),
+                             hipMemcpyDeviceToDevice, s);
+    if (err == hipSuccess) err = hipMemsetAsync(nb, 0xff, bbytes, s);
+    if (err == hipSuccess && t->rows > 1)
+        err = hipMemcpyAsync(nb, t->basis, (size_t)(t->rows - 1) * sizeof(int32_t),
+                             hipMemcpyDeviceToDevice, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    if (err != hipSuccess) {
+        set_error("growing a %d x %d tableau to %d rows failed: %s", t->rows, t->cols, cap,
+                  hipGetErrorString(err));
+        hipFree(nT);
+        hipFree(ncol);
+        hipFree(nnc);
+        hipFree(nnr);
+        hipFree(nb);
+        return err == hipErrorOutOfMemory ? LPR_OUT_OF_MEMORY : LPR_DEVICE_ERROR;
+    }
+    hipFree(t->T);
+    hipFree(t->T2);
+    hipFree(t->colbuf);
+    hipFree(t->next_col);
+    hipFree(t->next_rhs);
+    hipFree(t->basis);
+    t->T = nT;
+    t->T2 = nullptr;
+    t->colbuf = ncol;
+    t->next_col = nnc;
+    t->next_rhs = nnr;
+    t->basis = nb;
+    t->row_cap = cap;
+    drop_graph(t);  // T, colbuf, next_col and basis are captured kernel arguments
+    return LPR_OK_OPTIMAL;
 }
 
 // what a capture made now would bake in

@@ -1,5 +1,6 @@
-// select_common.hpp -- device helpers shared by the pivot-selection kernels of the primal path
-// (primal_kernels.hip, overlap_kernels.hip, small_kernels.hip).  Not part of the ABI.
+// select_common.hpp -- device helpers shared by the pivot-selection kernels: the primal path
+// (primal_kernels.hip, overlap_kernels.hip, small_kernels.hip) and the strict arg-mins of the two
+// EPS-band side paths (block_cand_min in cut_kernels.hip and sens_engine.hip).  Not part of the ABI.
 #pragma once
 
 #include "engine_common.hpp"

@@ -7,9 +7,10 @@
 // with the same layout as the primal path (row 0 = Z row, rows padded to 16 doubles).  The edits
 // touch O(1) .. O(rows + cols) entries and are done with scalar copies / tiny kernels; what costs
 // is the re-solve after them: the dual / primal ratio folds ("better by more than EPS", replayed
-// exactly by the next-take search) and the rank-1 pivot with the C#'s |factor| < EPS row skip.
+// exactly by eps_fold) and the rank-1 pivot with the C#'s |factor| < EPS row skip.
 #include "engine_common.hpp"
 #include "fold_common.hpp"
+#include "select_common.hpp"
 
 #include <algorithm>
 #include <new>
@@ -61,20 +62,6 @@ struct SensState {
     int64_t done;        // pivots of this run
     int64_t log_n, log_cap;
 };
-
-__device__ __forceinline__ int sens_block_min_int(int v, int* lds) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x / kWave;
-    const int nwaves = blockDim.x / kWave;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
-    __syncthreads();
-    if (lane == 0) lds[wave] = v;
-    __syncthreads();
-    int r = lds[0];
-    for (int w = 1; w < nwaves; ++w) r = min(r, lds[w]);
-    return r;
-}
 
 // ---- RebuildBasicsFromTableau / GetBasicRow -------------------------------------------------
 // IsPivotColumn(i, j) && |T[i][j] - 1| < EPS  <=>  exactly one row (1..R-1) of column j has
@@ -227,15 +214,16 @@ __global__ __launch_bounds__(1024) void k_sens_select(double* __restrict__ T, in
         kind = 1;
         // IsOptimal (:86-96) and the entering column `rc < mostNeg`, first index (:131-141)
         int notopt = 0;
-        double bv = 0.0;
-        int bj = INT_MAX;
+        Cand best;  // `rc < mostNeg`, mostNeg = 0.0 at the start
+        best.v = 0.0;
+        best.i = -1;
         for (int j = tid; j < rhs; j += nt) {
             if (bcount[j] > 0) continue;
             const double rc = T[j];
             if (rc < -kSensEps) notopt = 1;
-            if (rc < bv) {  // ascending j per thread: strict < keeps the first index
-                bv = rc;
-                bj = j;
+            if (rc < best.v) {  // ascending j per thread: strict < keeps the first index
+                best.v = rc;
+                best.i = j;
             }
         }
         notopt = __syncthreads_or(notopt);
@@ -247,39 +235,12 @@ __global__ __launch_bounds__(1024) void k_sens_select(double* __restrict__ T, in
             if (tid == 0) st->status = LPR_SENS_ITER_LIMIT;
             return;
         }
-        {  // block arg-min, smaller value first, then smaller index
-            const int lane = tid & (kWave - 1), wave = tid / kWave, nw = nt / kWave;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const double ov = __shfl_xor(bv, off, kWave);
-                const int oj = __shfl_xor(bj, off, kWave);
-                if (oj != INT_MAX && (bj == INT_MAX || ov < bv || (ov == bv && oj < bj))) {
-                    bv = ov;
-                    bj = oj;
-                }
-            }
-            if (lane == 0) {
-                lds_v[wave] = bv;
-                lds[wave] = bj;
-            }
-            __syncthreads();
-            bv = lds_v[0];
-            bj = lds[0];
-            for (int w = 1; w < nw; ++w) {
-                const double ov = lds_v[w];
-                const int oj = lds[w];
-                if (oj != INT_MAX && (bj == INT_MAX || ov < bv || (ov == bv && oj < bj))) {
-                    bv = ov;
-                    bj = oj;
-                }
-            }
-            __syncthreads();
-        }
-        if (bj == INT_MAX) {  // `if (enter == -1) break` (:142) -- falls out to the epilogue
+        best = block_cand_min(best, lds_v, lds);  // smaller value first, then smaller index
+        if (best.i < 0) {  // `if (enter == -1) break` (:142) -- falls out to the epilogue
             if (tid == 0) st->status = LPR_SENS_OK;
             return;
         }
-        enter = bj;
+        enter = best.i;
         // one strided pass: the entering column becomes dense (it is also the factor column)
         for (int i = tid; i < R; i += nt) colbuf[i] = T[(size_t)i * ld + enter];
         __syncthreads();
