@@ -702,6 +702,88 @@ int lpr_bb_batch_pop_order_read(lpr_bb_batch* b, int32_t k, int32_t* ids, int64_
 int lpr_bb_batch_trace_read(lpr_bb_batch* b, int32_t k, int32_t* quads, int64_t cap,
                             int64_t* count);
 
+
+/* ------------------------------------------------------- sensitivity scenario batch */
+
+/* One solved model, many what-if scripts per device call.  A scenario is a
+ * private copy of a base analyzer's state -- the tableau, basicVars as stored, finalZ and
+ * solutionVector (SensitivityAnalysis/SensitivityAnalyzer.cs:14-18) -- plus a script: an ordered
+ * list of edits applied to that copy on the device, with no host step per edit or per pivot.
+ * Scenario k ends with the state and the reports a fresh lpr_sens handle holding the base state
+ * gives when the same edits are called on it one after another.  One 256-lane workgroup per
+ * scenario, its tableau in LDS (form G) or in its slice of a global slab (form H, up to 1024 x
+ * 2048).  The reference has no batch mode; every call cites the C# lines it repeats per scenario. */
+typedef struct lpr_sens_batch lpr_sens_batch;
+
+/* The edits that keep the tableau's shape.  AddNewActivity (:534-584) and AddNewConstraint
+ * (:609-659) change it: they stay with lpr_sens_add_* on a single handle. */
+enum lpr_sens_edit_op {
+    LPR_SENS_EDIT_RESOLVE_ALL = 0,     /* ResolveAll :203-208; no arguments                       */
+    LPR_SENS_EDIT_NONBASIC_CBAR = 1,   /* ChangeNonBasicReducedCost :300-321; a = index, v = new  */
+    LPR_SENS_EDIT_BASIC = 2,           /* ChangeBasic :362-393; a = col, v = delta                */
+    LPR_SENS_EDIT_RHS = 3,             /* ChangeRHS :427-470; a = k, v = new b                    */
+    LPR_SENS_EDIT_NONBASIC_COLUMN = 4  /* ChangeNonBasicColumn :502-531; a = row, b = col, v = new */
+};
+
+typedef struct lpr_sens_edit {
+    int32_t op, a, b, reserved;
+    double v;
+} lpr_sens_edit;
+
+/* count scenarios on the state `base` holds now (:22-39 is not run again: basicVars is taken as
+ * stored, stale entries included).  Script k is nedits[k] >= 0 entries of `edits`, packed; 0 edits
+ * is the base state.  An unknown op, or one that changes the shape, is LPR_BAD_ARGUMENT; an index
+ * out of range is not: that edit reports LPR_SENS_INVALID_INDEX and changes nothing.  The base
+ * must be within 1024 x 2048.  log_cap: pivot-log triples kept per scenario (0: 4 * (rows +
+ * cols), at most 4096; the count is always exact).  The base is only read, and may be destroyed
+ * once this call has returned. */
+int lpr_sens_batch_create(lpr_sens* base, int32_t count, const int32_t* nedits,
+                          const lpr_sens_edit* edits, int32_t log_cap, lpr_sens_batch** out);
+int lpr_sens_batch_destroy(lpr_sens_batch* b);
+
+typedef struct lpr_sens_batch_opts {
+    int64_t max_pivots;  /* per scenario, per call (<= 0: only the C#'s own 10 001 per loop) */
+    int32_t chunk;       /* pivots per scenario per launch (0: by form) */
+    int32_t variant;     /* 0 auto; 2 / 3 force form G / H where the base fits it (tests and tuning
+                            only, same bits); ignored while scenarios are stopped inside an edit */
+} lpr_sens_batch_opts;
+
+typedef struct lpr_sens_batch_result {
+    int32_t finished;  /* scenarios whose script has ended */
+    int32_t running;   /* scenarios stopped by max_pivots; the next call resumes them */
+    int32_t launches;  /* script kernels launched by this call */
+    int32_t form;      /* the form this call ran: 1 G, 2 H */
+    int64_t pivots;    /* pivots performed by this call, all scenarios */
+} lpr_sens_batch_result;
+
+/* Every script, edit after edit: the edit itself (:300-321, :362-393, :427-470 with its snapshot
+ * and rollback, :502-531), RebuildBasicsFromTableau (:706-723), DualSimplexIfNeeded (:168-201),
+ * ReOptimize (:121-166), Pivot (:98-119).  A script goes on after an edit that did not end OK.
+ * A scenario stopped by max_pivots -- inside an edit, inside the dual phase -- resumes on the
+ * next call; finished scenarios stay finished.  opts may be NULL.  Returns LPR_OK_OPTIMAL unless
+ * the call itself failed. */
+int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
+                       lpr_sens_batch_result* res);
+/* count, numRows, numCols, edits of all scripts together, the pivot-log capacity per scenario and
+ * the form of the last run (0 before the first); any may be NULL. */
+int lpr_sens_batch_info(lpr_sens_batch* b, int32_t* count, int32_t* rows, int32_t* cols,
+                        int64_t* total_edits, int32_t* log_cap, int32_t* form);
+/* Per edit, packed as the scripts are: the lpr_sens_outcome (-100 for an edit that has not ended)
+ * and its pivots (what lpr_sens_shape's last_pivots gives after that edit); either may be NULL. */
+int lpr_sens_batch_outcomes_read(lpr_sens_batch* b, int32_t* outcome, int64_t* pivots);
+/* CurrentZ :728 and solutionVector.Count per scenario, basicVars packed by rows - 1; any may be
+ * NULL. */
+int lpr_sens_batch_state_read(lpr_sens_batch* b, double* z, int32_t* nsol, int32_t* basic);
+/* CurrentSolutionVector :729 of scenario k: *count entries, the first min(*count, cap) copied. */
+int lpr_sens_batch_solution_read(lpr_sens_batch* b, int32_t k, double* x, int32_t cap,
+                                 int32_t* count);
+/* CurrentTableau :727 of scenario k: rows x cols row-major. */
+int lpr_sens_batch_tableau_read(lpr_sens_batch* b, int32_t k, double* rowmajor);
+/* (kind 0 dual / 1 primal, leaveRow, enterCol) of scenario k's pivots, as lpr_sens_log_read:
+ * *count = all of them, the first min(*count, log_cap, cap) copied. */
+int lpr_sens_batch_log_read(lpr_sens_batch* b, int32_t k, int32_t* triples, int64_t cap,
+                            int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

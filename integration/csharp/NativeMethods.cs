@@ -43,6 +43,15 @@ namespace LPR_381_Group_V22.Native
     internal struct LprBbBatchOpts { public int enable_pruning, chunk, variant, max_child_pivots; }
 
     [StructLayout(LayoutKind.Sequential)]
+    internal struct LprSensEdit { public int op, a, b, reserved; public double v; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprSensBatchOpts { public long max_pivots; public int chunk; public int variant; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprSensBatchResult { public int finished, running, launches, form; public long pivots; }
+
+    [StructLayout(LayoutKind.Sequential)]
     internal struct LprBbBatchResult { public int done, node_cap, pivot_limit, launches; public long pops, pivots; }
 
     [StructLayout(LayoutKind.Sequential)]
@@ -231,6 +240,17 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_records_read(IntPtr bbBatch, int k, int[] parent, int[] kind, int[] depth, int[] var, double[] bound, int[] status, double[] z, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_pop_order_read(IntPtr bbBatch, int k, int[] ids, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_trace_read(IntPtr bbBatch, int k, int[] quads, long cap, out long count);
+
+        // ---- Sensitivity scenario batch (DESIGN.md section 14): one solved model, many what-if scripts per call ----
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_create(IntPtr sens, int count, int[] nedits, LprSensEdit[] edits, int log_cap, out IntPtr sensBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_destroy(IntPtr sensBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_run(IntPtr sensBatch, ref LprSensBatchOpts opts, out LprSensBatchResult res);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_info(IntPtr sensBatch, out int count, out int rows, out int cols, out long total_edits, out int log_cap, out int form);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_outcomes_read(IntPtr sensBatch, int[] outcome, long[] pivots);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_state_read(IntPtr sensBatch, double[] z, int[] nsol, int[] basic);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_solution_read(IntPtr sensBatch, int k, double[] x, int cap, out int count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_tableau_read(IntPtr sensBatch, int k, [Out] double[,] rowmajor);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_log_read(IntPtr sensBatch, int k, int[] triples, long cap, out long count);
 
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 

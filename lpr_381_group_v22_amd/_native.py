@@ -43,6 +43,13 @@ LPR_SENS_ROLLED_BACK = 8
 LPR_SENS_INDEX_OUT_OF_RANGE = 9
 LPR_SENS_INVALID_INDEX = -1
 
+# lpr_sens_edit_op
+LPR_SENS_EDIT_RESOLVE_ALL = 0
+LPR_SENS_EDIT_NONBASIC_CBAR = 1
+LPR_SENS_EDIT_BASIC = 2
+LPR_SENS_EDIT_RHS = 3
+LPR_SENS_EDIT_NONBASIC_COLUMN = 4
+
 
 class SolveOpts(C.Structure):
     _fields_ = [
@@ -185,6 +192,34 @@ class BBBatchResult(C.Structure):
     ]
 
 
+class SensEdit(C.Structure):
+    _fields_ = [
+        ("op", C.c_int32),
+        ("a", C.c_int32),
+        ("b", C.c_int32),
+        ("reserved", C.c_int32),
+        ("v", C.c_double),
+    ]
+
+
+class SensBatchOpts(C.Structure):
+    _fields_ = [
+        ("max_pivots", C.c_int64),
+        ("chunk", C.c_int32),
+        ("variant", C.c_int32),
+    ]
+
+
+class SensBatchResult(C.Structure):
+    _fields_ = [
+        ("finished", C.c_int32),
+        ("running", C.c_int32),
+        ("launches", C.c_int32),
+        ("form", C.c_int32),
+        ("pivots", C.c_int64),
+    ]
+
+
 class BBResult(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -319,6 +354,15 @@ SIGNATURES = {
                                             C.c_int64, _I64]),
     "lpr_bb_batch_pop_order_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
     "lpr_bb_batch_trace_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
+    "lpr_sens_batch_create": (C.c_int, [_P, C.c_int32, _I32, C.POINTER(SensEdit), C.c_int32, _PP]),
+    "lpr_sens_batch_destroy": (C.c_int, [_P]),
+    "lpr_sens_batch_run": (C.c_int, [_P, C.POINTER(SensBatchOpts), C.POINTER(SensBatchResult)]),
+    "lpr_sens_batch_info": (C.c_int, [_P, _I32, _I32, _I32, _I64, _I32, _I32]),
+    "lpr_sens_batch_outcomes_read": (C.c_int, [_P, _I32, _I64]),
+    "lpr_sens_batch_state_read": (C.c_int, [_P, _D, _I32, _I32]),
+    "lpr_sens_batch_solution_read": (C.c_int, [_P, C.c_int32, _D, C.c_int32, _I32]),
+    "lpr_sens_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
+    "lpr_sens_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
 }
 
 

@@ -79,6 +79,8 @@ void knap_orphan(lpr_knap* k);
 void batch_orphan(lpr_batch* b);
 // bb_batch_engine.hip
 void bb_batch_orphan(lpr_bb_batch* b);
+// sens_batch_engine.hip
+void sens_batch_orphan(lpr_sens_batch* b);
 }  // namespace lpr
 // cut_kernels.hip
 void lpr_cut_release(lpr_tableau* t);
@@ -749,6 +751,8 @@ int lpr_engine_close(lpr_engine* e) {
     e->live_batch.clear();
     for (lpr_bb_batch* b : e->live_bb_batch) bb_batch_orphan(b);
     e->live_bb_batch.clear();
+    for (lpr_sens_batch* b : e->live_sens_batch) sens_batch_orphan(b);
+    e->live_sens_batch.clear();
     if (e->stream) {
         hipStreamSynchronize(e->stream);
         hipStreamDestroy(e->stream);

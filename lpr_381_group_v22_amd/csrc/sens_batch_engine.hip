@@ -1,0 +1,429 @@
+// sens_batch_engine.hip -- host side of the sensitivity scenario batch (include/lpr_engine.h,
+// lpr_sens_batch_*).  Every scenario runs its whole script on the device
+// with the rules of SensitivityAnalyzer; the host copies the base state in, relaunches the
+// bounded script kernel while scenarios are still running (one counter read per launch) and
+// copies results out.
+#include "sens_batch_common.hpp"
+
+#include <algorithm>
+#include <new>
+
+namespace lpr {
+int sens_batch_launch(int form, hipStream_t s, const SensBatchView& vw, const int32_t* idx_in,
+                      int n_in, int32_t* idx_out, int32_t* n_out, int chunk);
+int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, const double* baseT,
+                           int ld, const int32_t* base_basic, const int32_t* base_bcount,
+                           const double* base_sol, int nsol);
+// sens_engine.hip
+lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,
+                      const int32_t** basic, const int32_t** bcount,
+                      const std::vector<double>** sol, double* z);
+}  // namespace lpr
+
+using namespace lpr;
+
+struct lpr_sens_batch {
+    lpr_engine* eng = nullptr;
+    int32_t count = 0;
+    int64_t total_edits = 0;
+    int form = 0;  // the form of the last run (0: none yet)
+    SensBatchView vw{};
+    std::vector<SensScenario> h_desc;  // host mirror, current after create and every run
+    lpr_sens_edit* d_edits = nullptr;
+    int32_t* idx = nullptr;         // 2 x count: the running lists, in and out
+    int32_t* counter = nullptr;     // the running count (device)
+    int32_t* h_counter = nullptr;   // pinned
+};
+
+namespace {
+
+int sb_oom(const char* what, int64_t n) {
+    set_error("lpr_sens_batch: cannot allocate %s (%lld elements)", what, (long long)n);
+    return LPR_OUT_OF_MEMORY;
+}
+
+void sb_release_device(lpr_sens_batch* b) {
+    SensBatchView& v = b->vw;
+    hipFree(v.desc); hipFree(v.cur); hipFree(v.alt); hipFree(v.basic); hipFree(v.bcount);
+    hipFree(v.snap); hipFree(v.sol); hipFree(v.log); hipFree(v.outcome); hipFree(v.edit_piv);
+    hipFree(b->d_edits); hipFree(b->idx); hipFree(b->counter);
+    if (b->h_counter) hipHostFree(b->h_counter);
+    v.desc = nullptr;
+    v.cur = v.alt = v.sol = nullptr;
+    v.basic = v.bcount = v.snap = v.log = v.outcome = nullptr;
+    v.edit_piv = nullptr;
+    v.edits = nullptr;
+    b->d_edits = nullptr;
+    b->idx = b->counter = b->h_counter = nullptr;
+}
+
+int sb_fail(lpr_sens_batch* b, int rc) {
+    sb_release_device(b);
+    delete b;
+    return rc;
+}
+
+}  // namespace
+
+namespace lpr {
+void sens_batch_orphan(lpr_sens_batch* b) {  // lpr_engine_close
+    sb_release_device(b);
+    b->eng = nullptr;
+}
+}  // namespace lpr
+
+#define LPR_LIVE_SB(b)                                                                      \
+    do {                                                                                    \
+        if (!(b) || !(b)->eng) {                                                            \
+            set_error("scenario batch handle is null or orphaned: its engine has been "     \
+                      "closed");                                                            \
+            return LPR_BAD_ARGUMENT;                                                        \
+        }                                                                                   \
+        LPR_HIP(hipSetDevice((b)->eng->device));                                            \
+    } while (0)
+
+extern "C" {
+
+// count private copies of the state of `base` (SensitivityAnalyzer.cs:14-18), one script each
+int lpr_sens_batch_create(lpr_sens* base, int32_t count, const int32_t* nedits,
+                          const lpr_sens_edit* edits, int32_t log_cap, lpr_sens_batch** out) {
+    static const char* W = "lpr_sens_batch_create";
+    int R = 0, C = 0, ld = 0;
+    const double* baseT = nullptr;
+    const int32_t *base_basic = nullptr, *base_bcount = nullptr;
+    const std::vector<double>* base_sol = nullptr;
+    double z = 0.0;
+    lpr_engine* e = sens_view(base, &R, &C, &ld, &baseT, &base_basic, &base_bcount, &base_sol, &z);
+    if (!e) {
+        set_error("%s: the base handle is null or orphaned: its engine has been closed", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (!out || count < 1 || !nedits || log_cap < 0) {
+        set_error("%s: bad arguments (count=%d, log_cap=%d, or a null handle / nedits)", W, count,
+                  log_cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    *out = nullptr;
+    if (R > kBatchMaxRowsH || C > kBatchMaxColsH) {
+        set_error("%s: the base is a %d x %d tableau, beyond the batch limit of %d x %d (form H); "
+                  "edit it alone with lpr_sens_*", W, R, C, kBatchMaxRowsH, kBatchMaxColsH);
+        return LPR_BAD_ARGUMENT;
+    }
+    int64_t total = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        if (nedits[k] < 0) {
+            set_error("%s: scenario %d has nedits=%d; it must be >= 0", W, k, nedits[k]);
+            return LPR_BAD_ARGUMENT;
+        }
+        total += nedits[k];
+    }
+    if (total > 0 && !edits) {
+        set_error("%s: null edits for scripts that have entries", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    for (int64_t q = 0; q < total; ++q) {
+        const int op = edits[q].op;
+        if (op < LPR_SENS_EDIT_RESOLVE_ALL || op > LPR_SENS_EDIT_NONBASIC_COLUMN) {
+            set_error("%s: edit %lld has op %d; a batch takes the ops 0..4 that keep the tableau's "
+                      "shape -- AddNewActivity / AddNewConstraint go through lpr_sens_add_activity "
+                      "/ lpr_sens_add_constraint on a single handle", W, (long long)q, op);
+            return LPR_BAD_ARGUMENT;
+        }
+    }
+    LPR_HIP(hipSetDevice(e->device));
+    lpr_sens_batch* b = new (std::nothrow) lpr_sens_batch();
+    if (!b) return sb_oom("handle", 1);
+    b->eng = e;
+    b->count = count;
+    b->total_edits = total;
+    const int m = R - 1;
+    const int nsol = (int)base_sol->size();
+    SensBatchView& v = b->vw;
+    v.R = R;
+    v.C = C;
+    v.sol_cap = std::max(std::max(nsol, C - 1), 1);
+    v.log_cap = log_cap > 0 ? log_cap : std::min<int32_t>(kBatchLogDefaultMax, 4 * (R + C));
+    try {
+        b->h_desc.resize((size_t)count);
+    } catch (...) {
+        delete b;
+        return sb_oom("descriptors", count);
+    }
+    int64_t at = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        SensScenario& d = b->h_desc[(size_t)k];
+        std::memset(&d, 0, sizeof d);
+        d.z = z;
+        d.old_z = z;
+        d.edit_off = at;
+        d.nedits = nedits[k];
+        d.phase = kPhaseApply;
+        d.nsol = nsol;
+        d.status = kRunning;
+        at += nedits[k];
+    }
+    const int64_t n = count, RC = (int64_t)R * C;
+    const int64_t te = std::max<int64_t>(total, 1);
+    int rc = LPR_OK_OPTIMAL;
+    auto get = [&](auto** p, int64_t elems, const char* what) {
+        if (rc != LPR_OK_OPTIMAL) return;
+        if (hipMalloc(reinterpret_cast<void**>(p), (size_t)elems * sizeof(**p)) != hipSuccess) {
+            *p = nullptr;
+            (void)hipGetLastError();
+            rc = sb_oom(what, elems);
+        }
+    };
+    get(&v.desc, n, "descriptors");
+    get(&v.cur, n * RC, "tableau slab");
+    get(&v.alt, n * RC, "second tableau slab");
+    get(&v.basic, n * std::max(m, 1), "basicVars");
+    get(&v.bcount, n * C, "membership counts");
+    get(&v.snap, n * (m + C), "ChangeRHS snapshots");
+    get(&v.sol, n * v.sol_cap, "solution vectors");
+    get(&v.log, n * 3 * v.log_cap, "pivot logs");
+    get(&v.outcome, te, "outcomes");
+    get(&v.edit_piv, te, "pivot counts");
+    get(&b->d_edits, te, "edits");
+    get(&b->idx, 2 * n, "running lists");
+    get(&b->counter, 1, "counter");
+    if (rc == LPR_OK_OPTIMAL && hipHostMalloc(&b->h_counter, sizeof(int32_t)) != hipSuccess)
+        rc = sb_oom("pinned counter", 1);
+    if (rc != LPR_OK_OPTIMAL) return sb_fail(b, rc);
+    v.edits = b->d_edits;
+    hipStream_t s = e->stream;
+    double* d_sol = nullptr;  // the base's solutionVector is a host mirror
+    hipError_t err = hipSuccess;
+    if (nsol > 0) {
+        if (hipMalloc(&d_sol, (size_t)nsol * sizeof(double)) != hipSuccess)
+            return sb_fail(b, sb_oom("base solution", nsol));
+        err = hipMemcpyAsync(d_sol, base_sol->data(), (size_t)nsol * sizeof(double),
+                             hipMemcpyHostToDevice, s);
+    }
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(v.desc, b->h_desc.data(), (size_t)count * sizeof(SensScenario),
+                             hipMemcpyHostToDevice, s);
+    if (err == hipSuccess && total > 0)
+        err = hipMemcpyAsync(b->d_edits, edits, (size_t)total * sizeof(lpr_sens_edit),
+                             hipMemcpyHostToDevice, s);
+    std::vector<int32_t> not_run;  // every outcome starts as kSensEditNotRun
+    try {
+        not_run.assign((size_t)te, kSensEditNotRun);
+    } catch (...) {
+        hipFree(d_sol);
+        return sb_fail(b, sb_oom("outcomes (host)", te));
+    }
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(v.outcome, not_run.data(), (size_t)te * sizeof(int32_t),
+                             hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) err = hipMemsetAsync(v.edit_piv, 0, (size_t)te * sizeof(int64_t), s);
+    if (err == hipSuccess) err = hipMemsetAsync(v.sol, 0, (size_t)(n * v.sol_cap) * sizeof(double), s);
+    rc = LPR_OK_OPTIMAL;
+    if (err == hipSuccess)
+        rc = sens_batch_launch_init(s, v, count, baseT, ld, base_basic, base_bcount, d_sol, nsol);
+    if (err == hipSuccess && rc == LPR_OK_OPTIMAL)
+        err = hipStreamSynchronize(s);  // edits are borrowed, and the base may go after this call
+    hipFree(d_sol);
+    if (err != hipSuccess) {
+        set_error("%s: %s", W, hipGetErrorString(err));
+        rc = LPR_DEVICE_ERROR;
+    }
+    if (rc != LPR_OK_OPTIMAL) return sb_fail(b, rc);
+    e->live_sens_batch.push_back(b);
+    *out = b;
+    return LPR_OK_OPTIMAL;
+}
+
+int lpr_sens_batch_destroy(lpr_sens_batch* b) {
+    if (!b) return LPR_BAD_ARGUMENT;
+    if (b->eng) {
+        hipSetDevice(b->eng->device);
+        hipStreamSynchronize(b->eng->stream);
+        sb_release_device(b);
+        auto& lv = b->eng->live_sens_batch;
+        for (size_t q = 0; q < lv.size(); ++q)
+            if (lv[q] == b) {
+                lv.erase(lv.begin() + q);
+                break;
+            }
+    }
+    delete b;
+    return LPR_OK_OPTIMAL;
+}
+
+// Every script that has not ended, edit after edit (:203-208, :300-321, :362-393, :427-470,
+// :502-531)
+int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
+                       lpr_sens_batch_result* res) {
+    LPR_LIVE_SB(b);
+    if (!res) {
+        set_error("lpr_sens_batch_run: null result");
+        return LPR_BAD_ARGUMENT;
+    }
+    lpr_sens_batch_opts o;
+    std::memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    if ((o.variant != 0 && o.variant != 2 && o.variant != 3) || o.chunk < 0) {
+        set_error("lpr_sens_batch_run: variant %d (0 auto, 2 G, 3 H) / chunk %d (>= 0)", o.variant,
+                  o.chunk);
+        return LPR_BAD_ARGUMENT;
+    }
+    std::memset(res, 0, sizeof *res);
+    hipStream_t s = b->eng->stream;
+    const int32_t count = b->count;
+    const SensBatchView& v = b->vw;
+    std::vector<int32_t> list;
+    int64_t before = 0;
+    bool inside = false;  // a scenario is stopped inside an edit: its slices belong to one form
+    for (int32_t k = 0; k < count; ++k) {
+        SensScenario& d = b->h_desc[(size_t)k];
+        before += d.pivots;
+        if (d.status != kRunning && d.status != LPR_PIVOT_LIMIT) continue;  // finished stays so
+        inside = inside || d.phase != kPhaseApply;
+        d.status = kRunning;
+        d.pivot_stop = o.max_pivots > 0 ? d.pivots + o.max_pivots : 0;
+        list.push_back(k);
+    }
+    const bool fitG = sens_batch_fits_g(v.R, v.C);
+    int form = fitG ? kFormG : kFormH;
+    if (o.variant == 2 && fitG) form = kFormG;
+    if (o.variant == 3) form = kFormH;
+    if (inside && b->form != 0) form = b->form;
+    b->form = form;
+    res->form = form;
+    int32_t live = (int32_t)list.size();
+    int32_t* in = b->idx;
+    int32_t* outl = b->idx + count;
+    if (live > 0)
+        LPR_HIP(hipMemcpyAsync(in, list.data(), (size_t)live * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s));
+    LPR_HIP(hipMemcpyAsync(v.desc, b->h_desc.data(), (size_t)count * sizeof(SensScenario),
+                           hipMemcpyHostToDevice, s));
+    const int chunk = o.chunk > 0 ? o.chunk : kSensBatchChunk[form];
+    int launches = 0;
+    while (live > 0) {
+        LPR_HIP(hipMemsetAsync(b->counter, 0, sizeof(int32_t), s));
+        const int rc = sens_batch_launch(form, s, v, in, live, outl, b->counter, chunk);
+        if (rc != LPR_OK_OPTIMAL) return rc;
+        ++launches;
+        LPR_HIP(hipMemcpyAsync(b->h_counter, b->counter, sizeof(int32_t), hipMemcpyDeviceToHost,
+                               s));
+        LPR_HIP(hipStreamSynchronize(s));
+        live = *b->h_counter;
+        std::swap(in, outl);
+    }
+    LPR_HIP(hipMemcpyAsync(b->h_desc.data(), v.desc, (size_t)count * sizeof(SensScenario),
+                           hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    int64_t after = 0;
+    for (const SensScenario& d : b->h_desc) {
+        after += d.pivots;
+        res->finished += d.status == LPR_OK_OPTIMAL;
+        res->running += d.status == LPR_PIVOT_LIMIT;
+    }
+    res->launches = launches;
+    res->pivots = after - before;
+    return LPR_OK_OPTIMAL;
+}
+
+int lpr_sens_batch_info(lpr_sens_batch* b, int32_t* count, int32_t* rows, int32_t* cols,
+                        int64_t* total_edits, int32_t* log_cap, int32_t* form) {
+    if (!b) {
+        set_error("lpr_sens_batch_info: null handle");
+        return LPR_BAD_ARGUMENT;
+    }
+    if (count) *count = b->count;
+    if (rows) *rows = b->vw.R;
+    if (cols) *cols = b->vw.C;
+    if (total_edits) *total_edits = b->total_edits;
+    if (log_cap) *log_cap = b->vw.log_cap;
+    if (form) *form = b->form;
+    return LPR_OK_OPTIMAL;
+}
+
+// The outcome of every edit and its pivots, packed as the scripts are
+int lpr_sens_batch_outcomes_read(lpr_sens_batch* b, int32_t* outcome, int64_t* pivots) {
+    LPR_LIVE_SB(b);
+    if (b->total_edits == 0) return LPR_OK_OPTIMAL;
+    hipStream_t s = b->eng->stream;
+    if (outcome)
+        LPR_HIP(hipMemcpyAsync(outcome, b->vw.outcome, (size_t)b->total_edits * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+    if (pivots)
+        LPR_HIP(hipMemcpyAsync(pivots, b->vw.edit_piv, (size_t)b->total_edits * sizeof(int64_t),
+                               hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    return LPR_OK_OPTIMAL;
+}
+
+// CurrentZ :728, solutionVector.Count and basicVars of every scenario
+int lpr_sens_batch_state_read(lpr_sens_batch* b, double* z, int32_t* nsol, int32_t* basic) {
+    LPR_LIVE_SB(b);
+    for (int32_t k = 0; k < b->count; ++k) {
+        if (z) z[k] = b->h_desc[(size_t)k].z;
+        if (nsol) nsol[k] = b->h_desc[(size_t)k].nsol;
+    }
+    const int64_t nb = (int64_t)b->count * (b->vw.R - 1);
+    if (basic && nb > 0) {
+        LPR_HIP(hipMemcpyAsync(basic, b->vw.basic, (size_t)nb * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, b->eng->stream));
+        LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// CurrentSolutionVector :729 of scenario k
+int lpr_sens_batch_solution_read(lpr_sens_batch* b, int32_t k, double* x, int32_t cap,
+                                 int32_t* count) {
+    LPR_LIVE_SB(b);
+    if (k < 0 || k >= b->count || cap < 0 || !count) {
+        set_error("lpr_sens_batch_solution_read: scenario %d out of range (0..%d), cap %d or null "
+                  "count", k, b->count - 1, cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    const int32_t ns = b->h_desc[(size_t)k].nsol;
+    *count = ns;
+    const int32_t n = std::min(ns, cap);
+    if (n == 0 || !x) return LPR_OK_OPTIMAL;
+    LPR_HIP(hipMemcpyAsync(x, b->vw.sol + (size_t)k * b->vw.sol_cap, (size_t)n * sizeof(double),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// CurrentTableau :727 of scenario k
+int lpr_sens_batch_tableau_read(lpr_sens_batch* b, int32_t k, double* rowmajor) {
+    LPR_LIVE_SB(b);
+    if (k < 0 || k >= b->count || !rowmajor) {
+        set_error("lpr_sens_batch_tableau_read: scenario %d out of range (0..%d) or null output",
+                  k, b->count - 1);
+        return LPR_BAD_ARGUMENT;
+    }
+    const size_t RC = (size_t)b->vw.R * b->vw.C;
+    const double* src = (b->h_desc[(size_t)k].in_alt ? b->vw.alt : b->vw.cur) + (size_t)k * RC;
+    LPR_HIP(hipMemcpyAsync(rowmajor, src, RC * sizeof(double), hipMemcpyDeviceToHost,
+                           b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// The pivot log of scenario k, as lpr_sens_log_read
+int lpr_sens_batch_log_read(lpr_sens_batch* b, int32_t k, int32_t* triples, int64_t cap,
+                            int64_t* count) {
+    LPR_LIVE_SB(b);
+    if (k < 0 || k >= b->count || cap < 0 || !count) {
+        set_error("lpr_sens_batch_log_read: scenario %d out of range (0..%d), cap %lld or null "
+                  "count", k, b->count - 1, (long long)cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    const int64_t total = b->h_desc[(size_t)k].log_n;
+    *count = total;
+    const int64_t n = std::min(std::min<int64_t>(total, b->vw.log_cap), cap);
+    if (n == 0 || !triples) return LPR_OK_OPTIMAL;
+    LPR_HIP(hipMemcpyAsync(triples, b->vw.log + (size_t)k * 3 * b->vw.log_cap,
+                           (size_t)n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost,
+                           b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+}  // extern "C"

@@ -1,0 +1,561 @@
+// sens_batch_kernels.hip -- the sensitivity scenario batch: many what-if
+// scripts over one solved model per launch, each applied with the rules of SensitivityAnalyzer
+// (SensitivityAnalysis/SensitivityAnalyzer.cs), the same bits as lpr_sens_* calls on a fresh
+// handle and the oracle give for that script alone.
+//
+//   k_sens_batch<kLds>   one 256-lane workgroup per scenario runs its script as a resumable state
+//                        machine: the edits (:300-321 :362-393 :427-470 :502-531),
+//                        RebuildBasicsFromTableau (:706-723), DualSimplexIfNeeded (:168-201),
+//                        ReOptimize (:121-166), Pivot (:98-119); at most `chunk` pivots per
+//                        launch; the tableau in LDS (form G) or in the global slab (form H)
+//   k_sens_batch_init    the base state copied into every scenario
+#include "sens_batch_common.hpp"
+#include "select_common.hpp"
+
+#pragma clang fp contract(off)
+
+namespace lpr {
+
+// The C#'s "take idx when val(idx) < best - EPS" fold over ascending idx, replayed as it is
+// written: the whole workgroup has staged val(idx) for idx in [lo, hi) (NaN = not a candidate) in
+// LDS, and one wave walks the values 64 at a time; a ballot finds the first lane after the last
+// take with val < best - EPS, which is what the sequential loop takes next.  This is the replay
+// stage of eps_fold (fold_common.hpp) without its prefix-minimum compaction: eps_fold keeps 12 KiB
+// of static LDS per instantiation for the compacted candidates, and form G leaves a workgroup
+// 1 KiB besides its tableau.  Returns the last index taken (-1: none), to every lane.
+__device__ __forceinline__ int staged_eps_fold(const double* stage, int lo, int hi, double best,
+                                               int* slot) {
+    if (threadIdx.x < kWave) {
+        const int lane = threadIdx.x;
+        int cur = -1;
+        for (int b0 = lo; b0 < hi; b0 += kWave) {
+            const int idx = b0 + lane;
+            const double x = (idx < hi) ? stage[idx] : (double)NAN;
+            unsigned long long alive = ~0ull;
+            for (;;) {
+                const unsigned long long hit = __ballot(x < best - kFoldEps) & alive;
+                if (hit == 0ull) break;
+                const int fl = __builtin_amdgcn_readfirstlane(__builtin_ctzll(hit));
+                best = readlane_f64(x, fl);
+                cur = b0 + fl;
+                alive = (fl == kWave - 1) ? 0ull : (~0ull << (fl + 1));
+            }
+        }
+        if (lane == 0) *slot = cur;
+    }
+    __syncthreads();
+    const int r = *slot;
+    __syncthreads();  // the slot is free for the next fold
+    return r;
+}
+
+// GetBasicRow (:69-84) of one column, by the whole workgroup: exactly one row of 1.. holds
+// |v| > EPS, and that row is within EPS of 1.
+__device__ __forceinline__ int block_basic_row(const double* T, int R, int C, int col, int* slot) {
+    int c = 0, rs = 0;
+    for (int i = 1 + (int)threadIdx.x; i < R; i += 256)
+        if (fabs(T[(size_t)i * C + col]) > kSensBatchEps) {
+            c += 1;
+            rs += i;
+        }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        c += __shfl_xor(c, off, kWave);
+        rs += __shfl_xor(rs, off, kWave);
+    }
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if (lane == 0) {
+        slot[2 * wave] = c;
+        slot[2 * wave + 1] = rs;
+    }
+    __syncthreads();
+    int tc = 0, tr = 0;
+    for (int w = 0; w < 4; ++w) {
+        tc += slot[2 * w];
+        tr += slot[2 * w + 1];
+    }
+    __syncthreads();
+    int r = -1;
+    if (tc == 1 && fabs(T[(size_t)tr * C + col] - 1.0) < kSensBatchEps) r = tr;
+    return r;
+}
+
+// GetBasicRow of column j by one lane (the column scans of :706-723 and :160-165)
+__device__ __forceinline__ int lane_basic_row(const double* T, int R, int C, int j) {
+    int c = 0, rs = 0;
+    for (int i = 1; i < R; ++i)
+        if (fabs(T[(size_t)i * C + j]) > kSensBatchEps) {
+            c += 1;
+            rs += i;
+        }
+    if (c == 1 && fabs(T[(size_t)rs * C + j] - 1.0) < kSensBatchEps) return rs;
+    return -1;
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
+                                                    const int32_t* __restrict__ idx_in, int n_in,
+                                                    int32_t* __restrict__ idx_out,
+                                                    int32_t* __restrict__ n_out, int chunk) {
+    extern __shared__ double smem[];
+    __shared__ double red_v[8];
+    __shared__ int red_i[8];
+    __shared__ int slot[8];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= n_in) return;
+    const int k = idx_in[blockIdx.x];
+    SensScenario* const d = vw.desc + k;
+    const int R = vw.R, C = vw.C, m = R - 1, rhs = C - 1, RC = R * C;
+    double* const cur = vw.cur + (size_t)k * RC;
+    double* const alt = vw.alt + (size_t)k * RC;
+    int32_t* const g_basic = vw.basic + (size_t)k * m;
+    int32_t* const g_bcount = vw.bcount + (size_t)k * C;
+    int32_t* const g_snap = vw.snap + (size_t)k * (m + C);
+    double* const g_sol = vw.sol + (size_t)k * vw.sol_cap;
+    int32_t* const g_log = vw.log + (size_t)k * 3 * vw.log_cap;
+
+    // LDS: [tableau (G)] factor column (R), pivot row (C), membership counts (C), basicVars (R - 1);
+    // row-indexed data is staged in the factor column, column-indexed data in the pivot row
+    double* T;
+    double* fcol;
+    if constexpr (kLds) {
+        T = smem;
+        fcol = smem + RC;
+    } else {
+        T = cur;
+        fcol = smem;
+    }
+    double* const prow = fcol + R;
+    int32_t* const bcount = reinterpret_cast<int32_t*>(prow + C);
+    int32_t* const basic = bcount + C;
+
+    // the descriptor, uniform over the workgroup
+    double z = d->z, old_z = d->old_z;
+    const int64_t edit_off = d->edit_off, pivot_stop = d->pivot_stop;
+    int64_t pivots = d->pivots, edit_pivots = d->edit_pivots, log_n = d->log_n;
+    const int nedits = d->nedits;
+    int edit = d->edit, phase = d->phase, it_d = d->iter_dual, it_p = d->iter_primal;
+    int nsol = d->nsol;
+    bool dirty = false;  // G: the LDS tableau differs from the cur slice
+    if constexpr (kLds) {
+        const double* src = d->in_alt ? alt : cur;
+        dirty = d->in_alt != 0;
+        for (int x = tid; x < RC; x += 256) T[x] = src[x];
+    }
+    for (int j = tid; j < C; j += 256) bcount[j] = g_bcount[j];
+    for (int i = tid; i < m; i += 256) basic[i] = g_basic[i];
+    __syncthreads();
+
+    int32_t status = kRunning;
+    int done = 0, begun = 0;  // pivots and edits of this launch
+    while (status == kRunning) {
+        if (phase == kPhaseApply) {
+            if (edit >= nedits) {
+                status = LPR_OK_OPTIMAL;
+                break;
+            }
+            if (begun >= kSensBatchEditsPerLaunch) break;
+            ++begun;
+            const lpr_sens_edit e = vw.edits[edit_off + edit];
+            edit_pivots = 0;
+            it_d = 0;
+            it_p = 0;
+            bool valid = true;
+            if (e.op == LPR_SENS_EDIT_RESOLVE_ALL) {
+                phase = kPhaseRebuild;
+            } else if (e.op == LPR_SENS_EDIT_NONBASIC_CBAR) {  // :306-318
+                valid = e.a >= 0 && e.a < rhs && bcount[e.a] == 0;
+                if (valid) {
+                    if (tid == 0) T[e.a] = e.v;
+                    phase = kPhaseRebuild;
+                }
+            } else if (e.op == LPR_SENS_EDIT_BASIC) {  // :368-388
+                valid = e.a >= 0 && e.a < rhs && bcount[e.a] > 0;
+                int r = -1;
+                if (valid) r = block_basic_row(T, R, C, e.a, slot);
+                valid = valid && r >= 1;  // "Could not locate basic row." :379
+                if (valid) {
+                    for (int j = tid; j < C; j += 256) {  // j < C - 1, then the RHS entry
+                        const double prod = e.v * T[(size_t)r * C + j];
+                        T[j] = T[j] + prod;
+                    }
+                    __syncthreads();
+                    z = T[rhs];
+                    phase = kPhaseRebuild;
+                }
+            } else if (e.op == LPR_SENS_EDIT_RHS) {  // :430-451
+                valid = e.a >= 1 && e.a < R;
+                if (valid) {
+                    // snapshot (:437-439): tableau, finalZ, basicVars and the counts that shadow it
+                    if constexpr (kLds) {
+                        if (dirty)
+                            for (int x = tid; x < RC; x += 256) cur[x] = T[x];
+                        dirty = false;
+                    } else {
+                        for (int x = tid; x < RC; x += 256) alt[x] = T[x];
+                    }
+                    for (int i = tid; i < m; i += 256) g_snap[i] = basic[i];
+                    for (int j = tid; j < C; j += 256) g_snap[m + j] = bcount[j];
+                    old_z = z;
+                    const double delta = e.v - T[(size_t)e.a * C + rhs];  // :441-442
+                    const int sCol = (C - R) + (e.a - 1);
+                    __syncthreads();  // every lane has read the old b
+                    for (int i = tid; i < R; i += 256) {  // :445-450 (row 0: y_k * delta)
+                        const double prod = delta * T[(size_t)i * C + sCol];
+                        T[(size_t)i * C + rhs] = T[(size_t)i * C + rhs] + prod;
+                    }
+                    __syncthreads();
+                    z = T[rhs];
+                    phase = kPhaseDual;  // no rebuild (:455-456)
+                }
+            } else {  // LPR_SENS_EDIT_NONBASIC_COLUMN :505-526 (the create refused anything else)
+                valid = e.a >= 1 && e.a < R && e.b >= 0 && e.b < rhs && bcount[e.b] == 0;
+                if (valid) {
+                    const double oldVal = T[(size_t)e.a * C + e.b];
+                    const double yi = T[(C - R) + (e.a - 1)];
+                    const double cbar = T[e.b];
+                    __syncthreads();
+                    if (tid == 0) {
+                        const double delta = e.v - oldVal;
+                        const double prod = yi * delta;
+                        T[(size_t)e.a * C + e.b] = e.v;
+                        T[e.b] = cbar + prod;
+                    }
+                    phase = kPhaseRebuild;
+                }
+            }
+            __syncthreads();
+            if (!valid) {  // the C# prints "Invalid ..." and returns; nothing changed
+                if (tid == 0) {
+                    vw.outcome[edit_off + edit] = LPR_SENS_INVALID_INDEX;
+                    vw.edit_piv[edit_off + edit] = 0;
+                }
+                ++edit;
+                continue;
+            }
+            dirty = true;
+        }
+
+        if (phase == kPhaseRebuild) {  // RebuildBasicsFromTableau :706-723
+            for (int i = tid; i < m; i += 256) basic[i] = kSensNoBasic;
+            for (int j = tid; j < C; j += 256) bcount[j] = 0;
+            __syncthreads();
+            for (int j = tid; j < rhs; j += 256) {  // the first such column per row
+                const int r = lane_basic_row(T, R, C, j);
+                if (r >= 1) atomicMin(&basic[r - 1], j);
+            }
+            __syncthreads();
+            for (int i = tid; i < m; i += 256) {
+                const int b = basic[i];
+                if (b == kSensNoBasic)
+                    basic[i] = -1;
+                else
+                    atomicAdd(&bcount[b], 1);
+            }
+            __syncthreads();
+            phase = kPhaseDual;
+        }
+
+        int outcome = kSensEditNotRun;  // set when the re-solve of this edit ends
+        int leave = -1, enter = -1;
+        if (phase == kPhaseDual) {
+            // `bi < mostNeg - EPS`, mostNeg = 0.0 at the start, rows ascending (:174-178)
+            for (int i = tid; i < R; i += 256) fcol[i] = T[(size_t)i * C + rhs];
+            __syncthreads();
+            leave = staged_eps_fold(fcol, 1, R, 0.0, slot);
+            if (leave == -1) {
+                phase = kPhasePrimal;  // break (:180) -> ReOptimize
+            } else {
+                if (done >= chunk) break;
+                if (pivot_stop > 0 && pivots >= pivot_stop) {
+                    status = LPR_PIVOT_LIMIT;
+                    break;
+                }
+                if (it_d > kSensBatchMaxIter) {  // `if (iter++ > maxIter) throw` (:183)
+                    outcome = LPR_SENS_ITER_LIMIT;
+                } else {
+                    ++it_d;
+                    // `a < -EPS: ratio = cbar / (-a); ratio < best - EPS`, columns ascending
+                    const double* lrow = T + (size_t)leave * C;
+                    for (int j = tid; j < rhs; j += 256) {
+                        const double a = lrow[j];
+                        prow[j] = (a < -kSensBatchEps) ? ieee_div(T[j], -a) : (double)NAN;
+                    }
+                    __syncthreads();
+                    enter = staged_eps_fold(prow, 0, rhs, INFINITY, slot);
+                    if (enter == -1) outcome = LPR_SENS_INFEASIBLE;  // :197
+                }
+            }
+        }
+        if (phase == kPhasePrimal) {
+            // IsOptimal (:86-96) and the entering column `rc < mostNeg`, first index (:131-141)
+            int notopt = 0;
+            Cand best;
+            best.v = 0.0;
+            best.i = -1;
+            for (int j = tid; j < rhs; j += 256) {
+                if (bcount[j] > 0) continue;
+                const double rc = T[j];
+                if (rc < -kSensBatchEps) notopt = 1;
+                if (rc < best.v) {  // ascending j per lane: strict < keeps the first index
+                    best.v = rc;
+                    best.i = j;
+                }
+            }
+            notopt = __syncthreads_or(notopt);
+            if (!notopt) {
+                phase = kPhaseEpilogue;
+            } else {
+                if (done >= chunk) break;
+                if (pivot_stop > 0 && pivots >= pivot_stop) {
+                    status = LPR_PIVOT_LIMIT;
+                    break;
+                }
+                if (it_p > kSensBatchMaxIter) {  // `if (iter++ > maxIter) throw` (:126)
+                    outcome = LPR_SENS_ITER_LIMIT;
+                } else {
+                    ++it_p;
+                    best = dpp_block_cand_min(best, red_v, red_i);
+                    enter = best.i;
+                    if (enter < 0) {
+                        phase = kPhaseEpilogue;  // `if (enter == -1) break` (:142)
+                    } else {
+                        // `a > EPS: ratio = rhs / a; ratio < best - EPS`, rows ascending (:144-150)
+                        // (staged in the factor column's buffer, which is idle until the pivot)
+                        for (int i = tid; i < R; i += 256) {
+                            const double a = T[(size_t)i * C + enter];
+                            fcol[i] = (a > kSensBatchEps)
+                                          ? ieee_div(T[(size_t)i * C + rhs], a)
+                                          : (double)NAN;
+                        }
+                        __syncthreads();
+                        leave = staged_eps_fold(fcol, 1, R, INFINITY, slot);
+                        if (leave == -1) outcome = LPR_SENS_UNBOUNDED;  // :151
+                    }
+                }
+            }
+        }
+
+        if (outcome == kSensEditNotRun && leave >= 1 && enter >= 0) {
+            // ---- Pivot :98-119 ----
+            const double piv = T[(size_t)leave * C + enter];
+            if (fabs(piv) < kSensBatchEps) {
+                outcome = LPR_SENS_ZERO_PIVOT;  // :101
+            } else {
+                __syncthreads();  // the staged ratios have been read
+                for (int i = tid; i < R; i += 256) fcol[i] = T[(size_t)i * C + enter];
+                for (int j = tid; j < C; j += 256) prow[j] = ieee_div(T[(size_t)leave * C + j], piv);
+                __syncthreads();
+                // rows with |factor| < EPS are left untouched (:110); element-parallel over the
+                // flattened tableau, four elements in flight per lane
+                {
+                    constexpr int U = 4;
+                    const int di = 256 / C, dj = 256 - (256 / C) * C;
+                    int i = tid / C, j = tid - (tid / C) * C;
+                    for (int base = 0; base < RC; base += U * 256) {
+                        double v[U];
+                        int ii[U], jj[U];
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int x = base + u * 256 + tid;
+                            ii[u] = i;
+                            jj[u] = j;
+                            v[u] = (x < RC) ? T[x] : 0.0;
+                            i += di;
+                            j += dj;
+                            if (j >= C) {
+                                j -= C;
+                                ++i;
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int x = base + u * 256 + tid;
+                            if (x < RC) {
+                                if (ii[u] == leave) {
+                                    T[x] = prow[jj[u]];
+                                } else {
+                                    const double f = fcol[ii[u]];
+                                    if (!(fabs(f) < kSensBatchEps)) {
+                                        const double prod = f * prow[jj[u]];  // rounded: no FMA
+                                        T[x] = v[u] - prod;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+                if (tid == 0) {
+                    const int old = basic[leave - 1];  // basicVars[leaveRow - 1] = enterCol
+                    if (old >= 0) bcount[old] -= 1;
+                    basic[leave - 1] = enter;
+                    bcount[enter] += 1;
+                    if (log_n < vw.log_cap) {
+                        int32_t* e3 = g_log + 3 * log_n;
+                        e3[0] = phase == kPhaseDual ? 0 : 1;
+                        e3[1] = leave;
+                        e3[2] = enter;
+                    }
+                }
+                ++log_n;
+                ++pivots;
+                ++edit_pivots;
+                ++done;
+                __syncthreads();
+                continue;
+            }
+        }
+
+        if (phase == kPhaseEpilogue) {  // :159-165
+            z = T[rhs];
+            for (int j = tid; j < rhs; j += 256) {
+                const int r = lane_basic_row(T, R, C, j);
+                g_sol[j] = (r == -1) ? 0.0 : T[(size_t)r * C + rhs];
+            }
+            nsol = rhs;
+            outcome = LPR_SENS_OK;
+        }
+
+        // ---- the edit has ended ----
+        if (outcome != LPR_SENS_OK && vw.edits[edit_off + edit].op == LPR_SENS_EDIT_RHS) {
+            // catch: restore (:462-469); solutionVector is not restored
+            __syncthreads();
+            if constexpr (kLds) {
+                for (int x = tid; x < RC; x += 256) T[x] = cur[x];
+                dirty = false;
+            } else {
+                for (int x = tid; x < RC; x += 256) T[x] = alt[x];
+            }
+            for (int i = tid; i < m; i += 256) basic[i] = g_snap[i];
+            for (int j = tid; j < C; j += 256) bcount[j] = g_snap[m + j];
+            z = old_z;
+            outcome = LPR_SENS_ROLLED_BACK;
+        }
+        if (tid == 0) {
+            vw.outcome[edit_off + edit] = outcome;
+            vw.edit_piv[edit_off + edit] = edit_pivots;
+        }
+        ++edit;
+        phase = kPhaseApply;
+        __syncthreads();
+    }
+
+    // ---- write the scenario back ----
+    __syncthreads();
+    int in_alt = 0;
+    if constexpr (kLds) {
+        if (phase == kPhaseApply) {  // at an edit boundary: cur is the scenario's state
+            if (dirty)
+                for (int x = tid; x < RC; x += 256) cur[x] = T[x];
+        } else {  // inside an edit: cur may be a ChangeRHS snapshot
+            for (int x = tid; x < RC; x += 256) alt[x] = T[x];
+            in_alt = 1;
+        }
+    }
+    for (int j = tid; j < C; j += 256) g_bcount[j] = bcount[j];
+    for (int i = tid; i < m; i += 256) g_basic[i] = basic[i];
+    if (tid == 0) {
+        d->z = z;
+        d->old_z = old_z;
+        d->pivots = pivots;
+        d->edit_pivots = edit_pivots;
+        d->log_n = log_n;
+        d->edit = edit;
+        d->phase = phase;
+        d->iter_dual = it_d;
+        d->iter_primal = it_p;
+        d->nsol = nsol;
+        d->in_alt = in_alt;
+        d->status = status;
+        if (status == kRunning) idx_out[atomicAdd(n_out, 1)] = k;
+    }
+}
+
+template __global__ void k_sens_batch<true>(SensBatchView, const int32_t*, int, int32_t*,
+                                            int32_t*, int);
+template __global__ void k_sens_batch<false>(SensBatchView, const int32_t*, int, int32_t*,
+                                             int32_t*, int);
+
+// The base state into every scenario: the tableau compact (the base pads its rows to ld) into
+// the cur slice, basicVars and its membership counts as stored, solutionVector.
+__global__ __launch_bounds__(256) void k_sens_batch_init(SensBatchView vw, int count,
+                                                         const double* __restrict__ baseT, int ld,
+                                                         const int32_t* __restrict__ base_basic,
+                                                         const int32_t* __restrict__ base_bcount,
+                                                         const double* __restrict__ base_sol,
+                                                         int nsol) {
+    const int k = blockIdx.x;
+    if (k >= count) return;
+    const int tid = threadIdx.x;
+    const int R = vw.R, C = vw.C, m = R - 1, RC = R * C;
+    double* T = vw.cur + (size_t)k * RC;
+    int i = tid / C, j = tid - (tid / C) * C;
+    const int di = 256 / C, dj = 256 - (256 / C) * C;
+    for (int x = tid; x < RC; x += 256) {
+        T[x] = baseT[(size_t)i * ld + j];
+        i += di;
+        j += dj;
+        if (j >= C) {
+            j -= C;
+            ++i;
+        }
+    }
+    for (int q = tid; q < m; q += 256) vw.basic[(size_t)k * m + q] = base_basic[q];
+    for (int q = tid; q < C; q += 256) vw.bcount[(size_t)k * C + q] = base_bcount[q];
+    for (int q = tid; q < nsol; q += 256) vw.sol[(size_t)k * vw.sol_cap + q] = base_sol[q];
+}
+
+// ------------------------------------------------------------------------------------------
+// Launchers (sens_batch_engine.hip).  Dynamic LDS above 64 KiB needs the attribute once per device.
+int sens_batch_launch(int form, hipStream_t s, const SensBatchView& vw, const int32_t* idx_in,
+                      int n_in, int32_t* idx_out, int32_t* n_out, int chunk) {
+    static unsigned long long g_mask = 0;  // per device bit: the G attribute is set
+    if (n_in <= 0) return LPR_OK_OPTIMAL;
+    if (form == kFormG) {
+        const size_t lds = sens_batch_footprint_g(vw.R, vw.C);
+        if (lds > ((size_t)64 << 10)) {
+            int dev = 0;
+            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LPR_DEVICE_ERROR;
+            const unsigned long long bit = 1ull << dev;
+            if (!(__atomic_load_n(&g_mask, __ATOMIC_ACQUIRE) & bit)) {
+                const hipError_t err = hipFuncSetAttribute(
+                    reinterpret_cast<const void*>(&k_sens_batch<true>),
+                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBatchMaxLdsG);
+                if (err != hipSuccess) {
+                    set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed: %s",
+                              (size_t)kBatchMaxLdsG, hipGetErrorString(err));
+                    return LPR_DEVICE_ERROR;
+                }
+                __atomic_fetch_or(&g_mask, bit, __ATOMIC_ACQ_REL);
+            }
+        }
+        hipLaunchKernelGGL((k_sens_batch<true>), dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in,
+                           idx_out, n_out, chunk);
+    } else {
+        const size_t lds = sens_batch_aux_bytes(vw.R, vw.C);
+        hipLaunchKernelGGL((k_sens_batch<false>), dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in,
+                           idx_out, n_out, chunk);
+    }
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) {
+        set_error("k_sens_batch (form %d, %d scenarios) failed to launch: %s", form, n_in,
+                  hipGetErrorString(err));
+        return LPR_DEVICE_ERROR;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, const double* baseT,
+                           int ld, const int32_t* base_basic, const int32_t* base_bcount,
+                           const double* base_sol, int nsol) {
+    hipLaunchKernelGGL(k_sens_batch_init, dim3(count), dim3(256), 0, s, vw, count, baseT, ld,
+                       base_basic, base_bcount, base_sol, nsol);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) {
+        set_error("k_sens_batch_init failed to launch: %s", hipGetErrorString(err));
+        return LPR_DEVICE_ERROR;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+}  // namespace lpr

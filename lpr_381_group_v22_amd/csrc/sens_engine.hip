@@ -642,6 +642,23 @@ void sens_orphan(lpr_sens* s) {  // lpr_engine_close
     sens_release_device(s);
     s->eng = nullptr;
 }
+// What lpr_sens_batch_create reads of an analyzer: its engine (null once orphaned), the shape, the
+// device tableau with its leading dimension, basicVars and its membership counts on the device,
+// and the host mirrors of solutionVector and finalZ.
+lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,
+                      const int32_t** basic, const int32_t** bcount,
+                      const std::vector<double>** sol, double* z) {
+    if (!s) return nullptr;
+    *R = s->R;
+    *C = s->C;
+    *ld = s->ld;
+    *T = s->T;
+    *basic = s->basic;
+    *bcount = s->bcount;
+    *sol = &s->h_sol;
+    *z = s->z;
+    return s->eng;
+}
 }  // namespace lpr
 
 #define LPR_LIVE_S(s)                                                                       \

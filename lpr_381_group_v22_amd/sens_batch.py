@@ -1,0 +1,211 @@
+"""One solved model, many what-if scripts in one call (lpr_sens_batch_*).
+
+A scenario is a private copy of a base ``SensState`` plus a script: a list of ``(op_name, *args)``
+whose op names are the ``SensState`` method names.  Every script runs on the MI355X with no host
+step per edit or per pivot and ends with the bits the same calls give on a fresh ``SensState``
+holding the base state.  The reference (SensitivityAnalysis/SensitivityAnalyzer.cs) has no batch
+mode: the per-scenario accessors below are named after the single-handle surface (engine.py).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _native as N
+from .engine import SensState
+
+# op name -> (code, number of integer arguments, takes a value)
+EDIT_OPS = {
+    "resolve_all": (N.LPR_SENS_EDIT_RESOLVE_ALL, 0, False),
+    "change_nonbasic_cbar": (N.LPR_SENS_EDIT_NONBASIC_CBAR, 1, True),
+    "change_basic": (N.LPR_SENS_EDIT_BASIC, 1, True),
+    "change_rhs": (N.LPR_SENS_EDIT_RHS, 1, True),
+    "change_nonbasic_column": (N.LPR_SENS_EDIT_NONBASIC_COLUMN, 2, True),
+}
+SHAPE_CHANGING_OPS = ("add_activity", "add_constraint")
+MAX_ROWS_H = 1024
+MAX_COLS_H = 2048
+FORM_G, FORM_H = 1, 2            # lpr_sens_batch_result.form
+VARIANT_G, VARIANT_H = 2, 3      # lpr_sens_batch_opts.variant
+EDIT_NOT_RUN = -100
+MAX_LDS_G = 160 * 1024 - 1024    # kBatchMaxLdsG
+
+
+def footprint_g(rows: int, cols: int) -> int:
+    """Bytes of dynamic LDS a scenario needs in form G (sens_batch_footprint_g): the tableau, the
+    factor column and the pivot row in doubles, the membership counts and basicVars in int32."""
+    aux = 8 * (rows + cols) + 4 * (cols + rows - 1)
+    return 8 * rows * cols + ((aux + 7) & ~7)
+
+
+def fits_g(rows: int, cols: int) -> bool:
+    return footprint_g(rows, cols) <= MAX_LDS_G
+
+
+EDIT_DTYPE = np.dtype([("op", np.int32), ("a", np.int32), ("b", np.int32),
+                       ("reserved", np.int32), ("v", np.float64)])
+
+
+class PackedScripts(NamedTuple):
+    """The packed arrays of lpr_sens_batch_create."""
+    nedits: np.ndarray   # int32, per scenario
+    edits: np.ndarray    # EDIT_DTYPE (the layout of lpr_sens_edit), packed by nedits
+
+
+def _int32(x, what: str) -> int:
+    i = int(x)
+    if i != x:
+        raise ValueError(f"{what}: {x!r} is not an integer")
+    # an index the int32 of lpr_sens_edit cannot hold is out of range on any tableau
+    return max(-2 ** 31, min(2 ** 31 - 1, i))
+
+
+def pack_scripts(scripts: Sequence[Sequence[tuple]]) -> PackedScripts:
+    """Scripts -> the packed ABI arrays, with the checks of lpr_sens_batch_create (raises
+    ValueError where the call would refuse the batch): at least one scenario, known ops, and no op
+    that changes the tableau's shape."""
+    if len(scripts) < 1:
+        raise ValueError("no scenarios")
+    nedits = np.zeros(len(scripts), dtype=np.int32)
+    flat = []
+    for k, script in enumerate(scripts):
+        nedits[k] = len(script)
+        for q, edit in enumerate(script):
+            name, args = edit[0], tuple(edit[1:])
+            if len(args) == 1 and isinstance(args[0], (tuple, list)):
+                args = tuple(args[0])    # (op, (args...)) as the test scripts write it
+            if name in SHAPE_CHANGING_OPS:
+                raise ValueError(f"scenario {k} edit {q}: {name} changes the tableau's shape; "
+                                 f"call SensState.{name} on a single handle")
+            if name not in EDIT_OPS:
+                raise ValueError(f"scenario {k} edit {q}: unknown op {name!r}")
+            code, nint, has_v = EDIT_OPS[name]
+            if len(args) != nint + (1 if has_v else 0):
+                raise ValueError(f"scenario {k} edit {q}: {name} takes {nint + has_v} arguments, "
+                                 f"got {len(args)}")
+            ints = [_int32(a, f"scenario {k} edit {q}") for a in args[:nint]] + [0, 0]
+            flat.append((code, ints[0], ints[1], 0, float(args[nint]) if has_v else 0.0))
+    edits = np.array(flat, dtype=EDIT_DTYPE) if flat else np.zeros(0, dtype=EDIT_DTYPE)
+    return PackedScripts(nedits, edits)
+
+
+class SensitivityBatch:
+    """``len(scripts)`` scenarios over the state ``base`` holds now (lpr_sens_batch_*).  The base
+    is only read and may be destroyed afterwards."""
+
+    def __init__(self, base: SensState, scripts: Sequence[Sequence[tuple]], log_cap: int = 0):
+        p = pack_scripts(scripts)
+        self._h = None
+        self._engine = base.engine
+        h = C.c_void_p()
+        eptr = p.edits.ctypes.data_as(C.POINTER(N.SensEdit)) if p.edits.size else None
+        N.check(N.lib.lpr_sens_batch_create(base._h, len(p.nedits),
+                                            p.nedits.ctypes.data_as(C.POINTER(C.c_int32)), eptr,
+                                            int(log_cap), C.byref(h)), "lpr_sens_batch_create")
+        self._h = h
+        self.Count = len(p.nedits)
+        self.nedits = p.nedits.tolist()
+        self._off = np.concatenate([[0], np.cumsum(p.nedits)]).astype(np.int64)
+        cnt, r, c, lc, f = (C.c_int32() for _ in range(5))
+        te = C.c_int64()
+        N.check(N.lib.lpr_sens_batch_info(self._h, C.byref(cnt), C.byref(r), C.byref(c),
+                                          C.byref(te), C.byref(lc), C.byref(f)),
+                "lpr_sens_batch_info")
+        self.Rows, self.Cols, self.LogCap = r.value, c.value, lc.value
+        self.TotalEdits = te.value
+        self.LastResult: Optional[N.SensBatchResult] = None
+
+    def destroy(self) -> None:
+        if self._h:
+            N.lib.lpr_sens_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    # -- every script, edit after edit ----------------------------------------------------------
+    def Run(self, max_pivots: int = 0, chunk: int = 0, variant: int = 0) -> N.SensBatchResult:
+        opts = N.SensBatchOpts(max_pivots=int(max_pivots), chunk=int(chunk), variant=int(variant))
+        res = N.SensBatchResult()
+        N.check(N.lib.lpr_sens_batch_run(self._h, C.byref(opts), C.byref(res)),
+                "lpr_sens_batch_run")
+        self.LastResult = res
+        return res
+
+    # -- bulk reads -----------------------------------------------------------------------------
+    def outcome_arrays(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(outcome, pivots) per edit, packed as the scripts are."""
+        n = max(self.TotalEdits, 1)
+        oc = np.full(n, EDIT_NOT_RUN, dtype=np.int32)
+        pv = np.zeros(n, dtype=np.int64)
+        N.check(N.lib.lpr_sens_batch_outcomes_read(
+            self._h, oc.ctypes.data_as(C.POINTER(C.c_int32)),
+            pv.ctypes.data_as(C.POINTER(C.c_int64))), "lpr_sens_batch_outcomes_read")
+        return oc[:self.TotalEdits], pv[:self.TotalEdits]
+
+    def state_arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(z, solutionVector.Count, basicVars as a Count x (rows - 1) array)"""
+        m = self.Rows - 1
+        z = np.zeros(self.Count, dtype=np.float64)
+        ns = np.zeros(self.Count, dtype=np.int32)
+        basic = np.zeros(max(self.Count * m, 1), dtype=np.int32)
+        N.check(N.lib.lpr_sens_batch_state_read(
+            self._h, z.ctypes.data_as(C.POINTER(C.c_double)),
+            ns.ctypes.data_as(C.POINTER(C.c_int32)),
+            basic.ctypes.data_as(C.POINTER(C.c_int32))), "lpr_sens_batch_state_read")
+        return z, ns, basic[:self.Count * m].reshape(self.Count, m)
+
+    # -- per-scenario reads ---------------------------------------------------------------------
+    def Outcomes(self, k: int) -> List[int]:
+        oc, _ = self.outcome_arrays()
+        return oc[self._off[k]:self._off[k + 1]].tolist()
+
+    def Pivots(self, k: int) -> List[int]:
+        _, pv = self.outcome_arrays()
+        return pv[self._off[k]:self._off[k + 1]].tolist()
+
+    def Tableau(self, k: int) -> np.ndarray:
+        T = np.empty((self.Rows, self.Cols), dtype=np.float64)
+        N.check(N.lib.lpr_sens_batch_tableau_read(
+            self._h, int(k), T.ctypes.data_as(C.POINTER(C.c_double))),
+            "lpr_sens_batch_tableau_read")
+        return T
+
+    def Solution(self, k: int) -> np.ndarray:
+        cnt = C.c_int32()
+        N.check(N.lib.lpr_sens_batch_solution_read(self._h, int(k), None, 0, C.byref(cnt)),
+                "lpr_sens_batch_solution_read")
+        cap = max(cnt.value, 1)
+        x = np.zeros(cap, dtype=np.float64)
+        N.check(N.lib.lpr_sens_batch_solution_read(
+            self._h, int(k), x.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(cnt)),
+            "lpr_sens_batch_solution_read")
+        return x[:cnt.value]
+
+    def Log(self, k: int, cap: Optional[int] = None) -> List[Tuple[int, int, int]]:
+        """The pivot triples kept for scenario k (at most LogCap); LogCount gives the exact total."""
+        cap = self.LogCap if cap is None else int(cap)
+        buf = np.zeros(max(3 * cap, 3), dtype=np.int32)
+        cnt = C.c_int64()
+        N.check(N.lib.lpr_sens_batch_log_read(
+            self._h, int(k), buf.ctypes.data_as(C.POINTER(C.c_int32)), cap, C.byref(cnt)),
+            "lpr_sens_batch_log_read")
+        n = min(cnt.value, cap, self.LogCap)
+        return [tuple(t) for t in buf[:3 * n].reshape(-1, 3).tolist()]
+
+    def LogCount(self, k: int) -> int:
+        cnt = C.c_int64()
+        N.check(N.lib.lpr_sens_batch_log_read(self._h, int(k), None, 0, C.byref(cnt)),
+                "lpr_sens_batch_log_read")
+        return cnt.value
+
+    def State(self, k: int) -> dict:
+        """Scenario k as ``OracleSens.state()`` lays a state out: T, basic, sol, z."""
+        z, _, basic = self.state_arrays()
+        return dict(T=self.Tableau(k), basic=basic[k].tolist(), sol=self.Solution(k),
+                    z=float(z[k]))

@@ -1,0 +1,201 @@
+"""Measures the sensitivity scenario batch and prints one JSON line per
+workload:
+
+  S   a solved 8 x 14 LP (m = 7, n = 6), 65536 one-edit scenarios: the RHS of every row and the
+      cost of every column (change_nonbasic_cbar or change_basic, by what the column is) at a
+      spread of values
+  G   a solved 33 x 97 LP (m = 32, n = 64), 4096 three-edit scripts (RHS, cost, RHS)
+  H   a solved 257 x 769 LP (m = 256, n = 512), 256 two-edit scripts (RHS, cost): form H
+
+Per workload: scenarios/s end to end (lpr_sens_batch_create, lpr_sens_batch_run, the bulk reads of
+outcomes / pivots / z / basicVars, closed by an engine sync) and for lpr_sens_batch_run alone
+(best of --repeat, after one warm-up pass); launches; pivots; the same scenarios one at a time
+through SensState.create + the edit calls + shape() + destroy in a Python loop (a time-bounded
+prefix); the CPU oracle on one core (a prefix).  256 scenarios per workload (evenly spaced) are
+checked against the oracle bit for bit (outcomes, pivots, log, tableau, basicVars, z, solution);
+any mismatch makes the exit status non-zero.  Inputs are seeded.
+
+The single-handle loop and the oracle loop cover a time-bounded prefix of the scenarios
+(`scenarios` in their records); `speedup_e2e_vs_single` compares the batch's rate over all
+scenarios with the loop's rate over that prefix, and `speedup_prefix_scenarios` says how many it
+covered.  In S the edit kind cycles with period 20, so any prefix of 20 or more has the full mix.
+
+Run it under a time limit:  timeout -k 10 900 python tools/sens_batch_bench.py --out
+profiles/sens_batch_bench.json
+Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python
+tools/sens_batch_bench.py --no-check --repeat 1   (no --out: profiled times stay out of the record)
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+
+CHECK = 256
+SHAPES = {"S": (7, 6, 65536), "G": (32, 64, 4096), "H": (256, 512, 256)}
+
+
+def gen_workload(orc, name: str, seed: int):
+    """(base, scripts): a solved random_dense LP and `count` scripts over it."""
+    import sens_cases
+    m, n, count = SHAPES[name]
+    base = sens_cases.solved_lp(orc, m, n, seed % 1000)
+    T, _, _, basis = base
+    R, C = T.shape
+    rng = np.random.RandomState(seed)
+    bset = set(int(b) for b in basis)
+
+    def rhs_edit(q):
+        k = 1 + q % (R - 1)
+        return ("change_rhs", (k, float(T[k, -1]) * float(rng.uniform(0.25, 2.0))))
+
+    def cost_edit(q):
+        j = q % (C - 1)
+        if j in bset:
+            return ("change_basic", (j, float(rng.uniform(-0.5, 0.5))))
+        return ("change_nonbasic_cbar", (j, float(T[0, j]) + float(rng.uniform(-0.6, 0.4))))
+
+    scripts = []
+    for q in range(count):
+        if name == "S":
+            t = q % (R - 1 + C - 1)
+            scripts.append([rhs_edit(t) if t < R - 1 else cost_edit(t - (R - 1))])
+        elif name == "G":
+            scripts.append([rhs_edit(q), cost_edit(q), rhs_edit(q + 7)])
+        else:
+            scripts.append([rhs_edit(q), cost_edit(3 * q)])
+    return base, scripts
+
+
+def run_batch(pkg, eng, base_handle, scripts):
+    """One end-to-end pass: (seconds end to end, seconds of the run, result, batch)."""
+    eng.sync()
+    t0 = time.perf_counter()
+    b = pkg.SensitivityBatch(base_handle, scripts)
+    t1 = time.perf_counter()
+    res = b.Run()
+    t2 = time.perf_counter()
+    b.outcome_arrays()
+    b.state_arrays()
+    eng.sync()
+    t3 = time.perf_counter()
+    return t3 - t0, t2 - t1, res, b
+
+
+def single_loop(SensState, eng, base, scripts, budget_s: float):
+    T, x, z, _ = base
+    done = 0
+    t0 = time.perf_counter()
+    while done < len(scripts) and time.perf_counter() - t0 < budget_s:
+        d = SensState.create(eng, T, x, z)
+        for op, args in scripts[done]:
+            getattr(d, op)(*args)
+        d.shape()
+        d.destroy()
+        done += 1
+    dt = time.perf_counter() - t0
+    return dict(scenarios=done, seconds=dt, scenarios_per_s=done / dt)
+
+
+def oracle_loop(orc, base, scripts, budget_s: float):
+    T, x, z, basis = base
+    done = 0
+    t0 = time.perf_counter()
+    while done < len(scripts) and time.perf_counter() - t0 < budget_s:
+        o = orc.sens(T, x, z, basis)
+        for op, args in scripts[done]:
+            getattr(o, op)(*args)
+        done += 1
+    dt = time.perf_counter() - t0
+    return dict(scenarios=done, seconds=dt, scenarios_per_s=done / dt)
+
+
+def bit_check(orc, base, scripts, batch) -> int:
+    """Scenarios among CHECK evenly spaced ones that differ from the oracle in any output."""
+    import sens_batch_cases
+    bad = 0
+    step = max(1, len(scripts) // CHECK)
+    for k in list(range(0, len(scripts), step))[:CHECK]:
+        ref = sens_batch_cases.oracle_run(orc, base, scripts[k])
+        try:
+            sens_batch_cases.same_scenario(batch, k, ref, k)
+        except AssertionError:
+            bad += 1
+    return bad
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="S,G,H")
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=20261017)
+    ap.add_argument("--single-seconds", type=float, default=5.0)
+    ap.add_argument("--oracle-seconds", type=float, default=5.0)
+    ap.add_argument("--no-check", action="store_true", help="skip the bit check and the loops")
+    ap.add_argument("--out", default=None,
+                    help="also append the JSON lines to this file (the committed record is "
+                         "profiles/sens_batch_bench.json; never pass it to a profiled run)")
+    args = ap.parse_args()
+
+    import lpr_381_group_v22_amd as pkg
+    from lpr_381_group_v22_amd.engine import SensState
+    from oracle_lib import Oracle
+    orc = Oracle()  # the bases are solved on the CPU, outside every timed region
+    failures = 0
+    lines = []
+    with pkg.Engine(0) as eng:
+        for i, name in enumerate(args.workloads.split(",")):
+            base, scripts = gen_workload(orc, name, args.seed + i)
+            T, x, z, _ = base
+            d = SensState.create(eng, T, x, z)
+            run_batch(pkg, eng, d, scripts)[3].destroy()  # warm-up
+            runs = [run_batch(pkg, eng, d, scripts) for _ in range(max(1, args.repeat))]
+            best_e2e = min(r[0] for r in runs)
+            best_run = min(r[1] for r in runs)
+            res, batch = runs[-1][2], runs[-1][3]
+            oc, pv = batch.outcome_arrays()
+            count = len(scripts)
+            rec = dict(workload=name, scenarios=count, rows=int(T.shape[0]), cols=int(T.shape[1]),
+                       edits=int(len(oc)), form={1: "G", 2: "H"}[res.form],
+                       pivots=int(pv.sum()), launches=res.launches,
+                       outcomes={str(int(c)): int((oc == c).sum()) for c in np.unique(oc)},
+                       e2e_seconds=best_e2e, e2e_scenarios_per_s=count / best_e2e,
+                       run_seconds=best_run, run_scenarios_per_s=count / best_run,
+                       e2e_seconds_all=[r[0] for r in runs],
+                       run_seconds_all=[r[1] for r in runs])
+            if not args.no_check:
+                bad = bit_check(orc, base, scripts, batch)
+                rec["bit_checked"] = min(CHECK, count)
+                rec["bit_mismatches"] = bad
+                failures += bad
+                rec["single_handle"] = single_loop(SensState, eng, base, scripts,
+                                                   args.single_seconds)
+                rec["cpu_oracle_1core"] = oracle_loop(orc, base, scripts, args.oracle_seconds)
+                rec["speedup_e2e_vs_single"] = rec["e2e_scenarios_per_s"] / \
+                    rec["single_handle"]["scenarios_per_s"]
+                rec["speedup_prefix_scenarios"] = rec["single_handle"]["scenarios"]
+            for r in runs:
+                r[3].destroy()
+            d.destroy()
+            line = json.dumps(rec)
+            print(line, flush=True)
+            lines.append(line)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    if failures:
+        print(f"bit check: {failures} scenario(s) differ from the oracle", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
