@@ -715,14 +715,19 @@ int lpr_bb_batch_trace_read(lpr_bb_batch* b, int32_t k, int32_t* quads, int64_t 
  * 2048).  The reference has no batch mode; every call cites the C# lines it repeats per scenario. */
 typedef struct lpr_sens_batch lpr_sens_batch;
 
-/* The edits that keep the tableau's shape.  AddNewActivity (:534-584) and AddNewConstraint
- * (:609-659) change it: they stay with lpr_sens_add_* on a single handle. */
+/* Ops 0..4 keep the tableau's shape and are what lpr_sens_batch_create takes.  AddNewActivity
+ * (:534-584) and AddNewConstraint (:609-659) grow it: a batch from lpr_sens_batch_create_grow
+ * takes them too, with the new column or row in that call's payload pool. */
 enum lpr_sens_edit_op {
     LPR_SENS_EDIT_RESOLVE_ALL = 0,     /* ResolveAll :203-208; no arguments                       */
     LPR_SENS_EDIT_NONBASIC_CBAR = 1,   /* ChangeNonBasicReducedCost :300-321; a = index, v = new  */
     LPR_SENS_EDIT_BASIC = 2,           /* ChangeBasic :362-393; a = col, v = delta                */
     LPR_SENS_EDIT_RHS = 3,             /* ChangeRHS :427-470; a = k, v = new b                    */
-    LPR_SENS_EDIT_NONBASIC_COLUMN = 4  /* ChangeNonBasicColumn :502-531; a = row, b = col, v = new */
+    LPR_SENS_EDIT_NONBASIC_COLUMN = 4, /* ChangeNonBasicColumn :502-531; a = row, b = col, v = new */
+    LPR_SENS_EDIT_ADD_ACTIVITY = 5,    /* AddNewActivity :534-584; v = c_new, the column a_new is
+                                          payload[a .. a + b)                                      */
+    LPR_SENS_EDIT_ADD_CONSTRAINT = 6   /* AddNewConstraint :609-659; v = rhs, tech is
+                                          payload[a .. a + b), b = ntech                           */
 };
 
 typedef struct lpr_sens_edit {
@@ -739,6 +744,23 @@ typedef struct lpr_sens_edit {
  * once this call has returned. */
 int lpr_sens_batch_create(lpr_sens* base, int32_t count, const int32_t* nedits,
                           const lpr_sens_edit* edits, int32_t log_cap, lpr_sens_batch** out);
+/* lpr_sens_batch_create plus ops 5 and 6, so a scenario's tableau can grow as its script runs.
+ * `payload` (npayload doubles, copied; NULL only with npayload 0) holds the vectors those edits
+ * point into.  LPR_BAD_ARGUMENT, naming the scenario and the edit: a payload range outside
+ * [0, npayload), a negative b, npayload above 2^31 - 1, or a script whose largest possible shape
+ * -- the base's rows plus its add-constraint edits, by the base's columns plus its add edits of
+ * both kinds -- is past 1024 x 2048.  Every array of the batch is sized by the largest such
+ * shape over all scripts, and that shape picks the form.
+ *   ADD_ACTIVITY   with b != rows - 1 reports LPR_SENS_INVALID_INDEX and changes nothing (the
+ *                  batch's one rule of its own: lpr_sens_add_activity refuses that call)
+ *   ADD_CONSTRAINT with b != cols - 1 reports LPR_SENS_INVALID_INDEX (:616-617); with a stored
+ *                  basicVars entry outside [0, b) LPR_SENS_INDEX_OUT_OF_RANGE; neither changes
+ *                  anything.  aX (:647-651) reads solutionVector as stored, stale after an edit
+ *                  that did not end OK.
+ * The shape grows before the re-solve and stays grown whatever its outcome. */
+int lpr_sens_batch_create_grow(lpr_sens* base, int32_t count, const int32_t* nedits,
+                               const lpr_sens_edit* edits, const double* payload,
+                               int64_t npayload, int32_t log_cap, lpr_sens_batch** out);
 int lpr_sens_batch_destroy(lpr_sens_batch* b);
 
 typedef struct lpr_sens_batch_opts {
@@ -768,16 +790,22 @@ int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
  * the form of the last run (0 before the first); any may be NULL. */
 int lpr_sens_batch_info(lpr_sens_batch* b, int32_t* count, int32_t* rows, int32_t* cols,
                         int64_t* total_edits, int32_t* log_cap, int32_t* form);
+/* rows[k] x cols[k]: the shape of scenario k as of the last run (the base's, where nothing has
+ * grown it); max_rows x max_cols: the largest shape a script of this batch can reach, which the
+ * strides of the bulk reads are sized by.  Any may be NULL. */
+int lpr_sens_batch_shape_read(lpr_sens_batch* b, int32_t* rows, int32_t* cols, int32_t* max_rows,
+                              int32_t* max_cols);
 /* Per edit, packed as the scripts are: the lpr_sens_outcome (-100 for an edit that has not ended)
  * and its pivots (what lpr_sens_shape's last_pivots gives after that edit); either may be NULL. */
 int lpr_sens_batch_outcomes_read(lpr_sens_batch* b, int32_t* outcome, int64_t* pivots);
 /* CurrentZ :728 and solutionVector.Count per scenario, basicVars packed by rows - 1; any may be
- * NULL. */
+ * NULL.  In a grow batch basicVars is packed by max_rows - 1 (lpr_sens_batch_shape_read), and the
+ * entries past a scenario's own rows - 1 are INT32_MIN. */
 int lpr_sens_batch_state_read(lpr_sens_batch* b, double* z, int32_t* nsol, int32_t* basic);
 /* CurrentSolutionVector :729 of scenario k: *count entries, the first min(*count, cap) copied. */
 int lpr_sens_batch_solution_read(lpr_sens_batch* b, int32_t k, double* x, int32_t cap,
                                  int32_t* count);
-/* CurrentTableau :727 of scenario k: rows x cols row-major. */
+/* CurrentTableau :727 of scenario k: rows x cols row-major, at the scenario's own shape. */
 int lpr_sens_batch_tableau_read(lpr_sens_batch* b, int32_t k, double* rowmajor);
 /* (kind 0 dual / 1 primal, leaveRow, enterCol) of scenario k's pivots, as lpr_sens_log_read:
  * *count = all of them, the first min(*count, log_cap, cap) copied. */

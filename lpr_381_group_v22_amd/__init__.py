@@ -14,7 +14,8 @@ from .knapsack import KnapsackBranchBoundSimplex, KnapsackBranchBoundSolver
 from .primal_batch import PrimalSimplexBatch, pack_models
 from .primal_simplex_solver import PrimalSimplexSolver
 from .revised_primal_simplex_solver import RevisedPrimalSimplexSolver, SolverException
-from .sens_batch import SensitivityBatch, pack_scripts
+from .sens_batch import (SensitivityBatch, SensitivityGrowBatch, pack_grow_scripts,
+                         pack_scripts)
 
 __all__ = [
     "Engine", "Tableau", "default_engine", "Constraint", "InputFileParser",
@@ -22,5 +23,5 @@ __all__ = [
     "BranchAndBoundAdapter", "BranchBoundTree", "solve_level_synchronous", "torch_collectives",
     "Comm", "solve_level_sync_native", "KnapsackBranchBoundSimplex", "KnapsackBranchBoundSolver",
     "PrimalSimplexBatch", "pack_models", "BranchAndBoundBatch", "solve_integer_programs",
-    "SensitivityBatch", "pack_scripts", "_native",
+    "SensitivityBatch", "SensitivityGrowBatch", "pack_scripts", "pack_grow_scripts", "_native",
 ]

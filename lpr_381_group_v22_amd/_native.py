@@ -49,6 +49,8 @@ LPR_SENS_EDIT_NONBASIC_CBAR = 1
 LPR_SENS_EDIT_BASIC = 2
 LPR_SENS_EDIT_RHS = 3
 LPR_SENS_EDIT_NONBASIC_COLUMN = 4
+LPR_SENS_EDIT_ADD_ACTIVITY = 5
+LPR_SENS_EDIT_ADD_CONSTRAINT = 6
 
 
 class SolveOpts(C.Structure):
@@ -355,9 +357,12 @@ SIGNATURES = {
     "lpr_bb_batch_pop_order_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
     "lpr_bb_batch_trace_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
     "lpr_sens_batch_create": (C.c_int, [_P, C.c_int32, _I32, C.POINTER(SensEdit), C.c_int32, _PP]),
+    "lpr_sens_batch_create_grow": (C.c_int, [_P, C.c_int32, _I32, C.POINTER(SensEdit), _D,
+                                             C.c_int64, C.c_int32, _PP]),
     "lpr_sens_batch_destroy": (C.c_int, [_P]),
     "lpr_sens_batch_run": (C.c_int, [_P, C.POINTER(SensBatchOpts), C.POINTER(SensBatchResult)]),
     "lpr_sens_batch_info": (C.c_int, [_P, _I32, _I32, _I32, _I64, _I32, _I32]),
+    "lpr_sens_batch_shape_read": (C.c_int, [_P, _I32, _I32, _I32, _I32]),
     "lpr_sens_batch_outcomes_read": (C.c_int, [_P, _I32, _I64]),
     "lpr_sens_batch_state_read": (C.c_int, [_P, _D, _I32, _I32]),
     "lpr_sens_batch_solution_read": (C.c_int, [_P, C.c_int32, _D, C.c_int32, _I32]),

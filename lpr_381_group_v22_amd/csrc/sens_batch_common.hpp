@@ -10,8 +10,11 @@
 
 namespace lpr {
 
-// Forms of a scenario batch.  Every scenario of a batch has the base's shape, so one call runs
-// one form.  The numbers are those of BatchForm (a wave-per-scenario form W is not built).
+// Forms of a scenario batch.  One call runs one form, chosen by the batch's maximal shape: the
+// base's shape, or in a grow batch (lpr_sens_batch_create_grow) the largest shape a script can
+// reach.  Strides and the LDS carve-up are sized by that shape; a scenario indexes its tableau
+// compactly by its own column count.  The numbers are those of BatchForm (a wave-per-scenario
+// form W is not built).
 //   G: the working state of a scenario lives in dynamic LDS: the tableau (rows x cols, compact),
 //      the factor column (rows), the pivot row (cols), the membership counts (cols, int32) and
 //      basicVars (rows - 1, int32).  Budget: kBatchMaxLdsG, 160 KiB less the workgroup's 1 KiB.
@@ -70,11 +73,12 @@ struct SensScenario {
     int32_t nsol;        // solutionVector.Count
     int32_t in_alt;      // form G, stopped inside an edit: the working tableau is in the alt slice
     int32_t status;      // kRunning, LPR_OK_OPTIMAL (script ended) or LPR_PIVOT_LIMIT (resumable)
+    int32_t R, C;        // the scenario's shape now (AddNewActivity / AddNewConstraint grow it)
 };
 
-// What a launch needs of the batch: shape, strides and the device arrays.
+// What a launch needs of the batch: strides and the device arrays.
 struct SensBatchView {
-    int32_t R, C;        // the base's shape
+    int32_t R, C;        // the maximal shape of a scenario: what every stride below is sized by
     int32_t sol_cap;     // doubles per scenario in `sol`: max(base solutionVector.Count, C - 1)
     int32_t log_cap;     // triples per scenario in `log`
     SensScenario* desc;
@@ -86,6 +90,7 @@ struct SensBatchView {
     double* sol;         // count x sol_cap
     int32_t* log;        // count x 3 * log_cap
     const lpr_sens_edit* edits;
+    const double* payload;  // grow batch: the columns and rows the add edits point into
     int32_t* outcome;    // per edit, packed
     int64_t* edit_piv;   // per edit, packed
 };

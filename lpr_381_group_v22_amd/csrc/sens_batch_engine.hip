@@ -9,11 +9,12 @@
 #include <new>
 
 namespace lpr {
-int sens_batch_launch(int form, hipStream_t s, const SensBatchView& vw, const int32_t* idx_in,
-                      int n_in, int32_t* idx_out, int32_t* n_out, int chunk);
-int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, const double* baseT,
-                           int ld, const int32_t* base_basic, const int32_t* base_bcount,
-                           const double* base_sol, int nsol);
+int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& vw,
+                      const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
+                      int chunk);
+int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, int R, int C,
+                           const double* baseT, int ld, const int32_t* base_basic,
+                           const int32_t* base_bcount, const double* base_sol, int nsol);
 // sens_engine.hip
 lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,
                       const int32_t** basic, const int32_t** bcount,
@@ -27,9 +28,12 @@ struct lpr_sens_batch {
     int32_t count = 0;
     int64_t total_edits = 0;
     int form = 0;  // the form of the last run (0: none yet)
+    bool grow = false;         // from lpr_sens_batch_create_grow: scripts may hold the add edits
+    int32_t base_R = 0, base_C = 0;  // the base's shape (vw.R x vw.C is the maximal one)
     SensBatchView vw{};
     std::vector<SensScenario> h_desc;  // host mirror, current after create and every run
     lpr_sens_edit* d_edits = nullptr;
+    double* d_payload = nullptr;
     int32_t* idx = nullptr;         // 2 x count: the running lists, in and out
     int32_t* counter = nullptr;     // the running count (device)
     int32_t* h_counter = nullptr;   // pinned
@@ -46,14 +50,16 @@ void sb_release_device(lpr_sens_batch* b) {
     SensBatchView& v = b->vw;
     hipFree(v.desc); hipFree(v.cur); hipFree(v.alt); hipFree(v.basic); hipFree(v.bcount);
     hipFree(v.snap); hipFree(v.sol); hipFree(v.log); hipFree(v.outcome); hipFree(v.edit_piv);
-    hipFree(b->d_edits); hipFree(b->idx); hipFree(b->counter);
+    hipFree(b->d_edits); hipFree(b->d_payload); hipFree(b->idx); hipFree(b->counter);
     if (b->h_counter) hipHostFree(b->h_counter);
     v.desc = nullptr;
     v.cur = v.alt = v.sol = nullptr;
     v.basic = v.bcount = v.snap = v.log = v.outcome = nullptr;
     v.edit_piv = nullptr;
     v.edits = nullptr;
+    v.payload = nullptr;
     b->d_edits = nullptr;
+    b->d_payload = nullptr;
     b->idx = b->counter = b->h_counter = nullptr;
 }
 
@@ -61,6 +67,207 @@ int sb_fail(lpr_sens_batch* b, int rc) {
     sb_release_device(b);
     delete b;
     return rc;
+}
+
+// count private copies of the state of `base` (SensitivityAnalyzer.cs:14-18), one script each.
+// W names the call in messages; grow: the scripts may hold the two add edits, whose columns and
+// rows lie in `payload`.
+int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int32_t* nedits,
+              const lpr_sens_edit* edits, const double* payload, int64_t npayload,
+              int32_t log_cap, lpr_sens_batch** out) {
+    int R = 0, C = 0, ld = 0;
+    const double* baseT = nullptr;
+    const int32_t *base_basic = nullptr, *base_bcount = nullptr;
+    const std::vector<double>* base_sol = nullptr;
+    double z = 0.0;
+    lpr_engine* e = sens_view(base, &R, &C, &ld, &baseT, &base_basic, &base_bcount, &base_sol, &z);
+    if (!e) {
+        set_error("%s: the base handle is null or orphaned: its engine has been closed", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (!out || count < 1 || !nedits || log_cap < 0) {
+        set_error("%s: bad arguments (count=%d, log_cap=%d, or a null handle / nedits)", W, count,
+                  log_cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    *out = nullptr;
+    if (R > kBatchMaxRowsH || C > kBatchMaxColsH) {
+        set_error("%s: the base is a %d x %d tableau, beyond the batch limit of %d x %d (form H); "
+                  "edit it alone with lpr_sens_*", W, R, C, kBatchMaxRowsH, kBatchMaxColsH);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (grow && (npayload < 0 || npayload > INT32_MAX || (npayload > 0 && !payload))) {
+        set_error("%s: npayload=%lld must lie in 0..2^31-1, with a payload where it is not 0", W,
+                  (long long)npayload);
+        return LPR_BAD_ARGUMENT;
+    }
+    int64_t total = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        if (nedits[k] < 0) {
+            set_error("%s: scenario %d has nedits=%d; it must be >= 0", W, k, nedits[k]);
+            return LPR_BAD_ARGUMENT;
+        }
+        total += nedits[k];
+    }
+    if (total > 0 && !edits) {
+        set_error("%s: null edits for scripts that have entries", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    int maxR = R, maxC = C;  // the largest shape any script can reach
+    if (!grow) {
+        for (int64_t q = 0; q < total; ++q) {
+            const int op = edits[q].op;
+            if (op < LPR_SENS_EDIT_RESOLVE_ALL || op > LPR_SENS_EDIT_NONBASIC_COLUMN) {
+                set_error("%s: edit %lld has op %d; a batch takes the ops 0..4 that keep the "
+                          "tableau's shape -- AddNewActivity / AddNewConstraint go through "
+                          "lpr_sens_add_activity / lpr_sens_add_constraint on a single handle, or "
+                          "lpr_sens_batch_create_grow", W, (long long)q, op);
+                return LPR_BAD_ARGUMENT;
+            }
+        }
+    } else {
+        int64_t q = 0;
+        for (int32_t k = 0; k < count; ++k) {
+            int rows = R, cols = C;
+            for (int32_t i = 0; i < nedits[k]; ++i, ++q) {
+                const lpr_sens_edit& ed = edits[q];
+                if (ed.op < LPR_SENS_EDIT_RESOLVE_ALL || ed.op > LPR_SENS_EDIT_ADD_CONSTRAINT) {
+                    set_error("%s: scenario %d edit %d has op %d; the ops are 0..6", W, k, i,
+                              ed.op);
+                    return LPR_BAD_ARGUMENT;
+                }
+                if (ed.op < LPR_SENS_EDIT_ADD_ACTIVITY) continue;
+                if (ed.b < 0 || ed.a < 0 || (int64_t)ed.a + ed.b > npayload) {
+                    set_error("%s: scenario %d edit %d (op %d) takes payload [%d, %d + %d), "
+                              "outside [0, %lld)", W, k, i, ed.op, ed.a, ed.a, ed.b,
+                              (long long)npayload);
+                    return LPR_BAD_ARGUMENT;
+                }
+                rows += ed.op == LPR_SENS_EDIT_ADD_CONSTRAINT;
+                cols += 1;
+                if (rows > kBatchMaxRowsH || cols > kBatchMaxColsH) {
+                    set_error("%s: scenario %d edit %d can grow the %d x %d base to %d x %d, "
+                              "beyond the batch limit of %d x %d (form H)", W, k, i, R, C, rows,
+                              cols, kBatchMaxRowsH, kBatchMaxColsH);
+                    return LPR_BAD_ARGUMENT;
+                }
+            }
+            maxR = std::max(maxR, rows);
+            maxC = std::max(maxC, cols);
+        }
+    }
+    LPR_HIP(hipSetDevice(e->device));
+    lpr_sens_batch* b = new (std::nothrow) lpr_sens_batch();
+    if (!b) return sb_oom("handle", 1);
+    b->eng = e;
+    b->count = count;
+    b->total_edits = total;
+    b->grow = grow;
+    b->base_R = R;
+    b->base_C = C;
+    const int nsol = (int)base_sol->size();
+    SensBatchView& v = b->vw;
+    v.R = maxR;
+    v.C = maxC;
+    v.sol_cap = std::max(std::max(nsol, maxC - 1), 1);
+    v.log_cap = log_cap > 0 ? log_cap : std::min<int32_t>(kBatchLogDefaultMax, 4 * (R + C));
+    try {
+        b->h_desc.resize((size_t)count);
+    } catch (...) {
+        delete b;
+        return sb_oom("descriptors", count);
+    }
+    int64_t at = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        SensScenario& d = b->h_desc[(size_t)k];
+        std::memset(&d, 0, sizeof d);
+        d.z = z;
+        d.old_z = z;
+        d.edit_off = at;
+        d.nedits = nedits[k];
+        d.phase = kPhaseApply;
+        d.nsol = nsol;
+        d.status = kRunning;
+        d.R = R;
+        d.C = C;
+        at += nedits[k];
+    }
+    const int64_t n = count, RC = (int64_t)maxR * maxC;
+    const int m = maxR - 1;
+    const int64_t te = std::max<int64_t>(total, 1);
+    int rc = LPR_OK_OPTIMAL;
+    auto get = [&](auto** p, int64_t elems, const char* what) {
+        if (rc != LPR_OK_OPTIMAL) return;
+        if (hipMalloc(reinterpret_cast<void**>(p), (size_t)elems * sizeof(**p)) != hipSuccess) {
+            *p = nullptr;
+            (void)hipGetLastError();
+            rc = sb_oom(what, elems);
+        }
+    };
+    get(&v.desc, n, "descriptors");
+    get(&v.cur, n * RC, "tableau slab");
+    get(&v.alt, n * RC, "second tableau slab");
+    get(&v.basic, n * std::max(m, 1), "basicVars");
+    get(&v.bcount, n * maxC, "membership counts");
+    get(&v.snap, n * (m + maxC), "ChangeRHS snapshots");
+    get(&v.sol, n * v.sol_cap, "solution vectors");
+    get(&v.log, n * 3 * v.log_cap, "pivot logs");
+    get(&v.outcome, te, "outcomes");
+    get(&v.edit_piv, te, "pivot counts");
+    get(&b->d_edits, te, "edits");
+    if (npayload > 0) get(&b->d_payload, npayload, "payload");
+    get(&b->idx, 2 * n, "running lists");
+    get(&b->counter, 1, "counter");
+    if (rc == LPR_OK_OPTIMAL && hipHostMalloc(&b->h_counter, sizeof(int32_t)) != hipSuccess)
+        rc = sb_oom("pinned counter", 1);
+    if (rc != LPR_OK_OPTIMAL) return sb_fail(b, rc);
+    v.edits = b->d_edits;
+    v.payload = b->d_payload;
+    hipStream_t s = e->stream;
+    double* d_sol = nullptr;  // the base's solutionVector is a host mirror
+    hipError_t err = hipSuccess;
+    if (nsol > 0) {
+        if (hipMalloc(&d_sol, (size_t)nsol * sizeof(double)) != hipSuccess)
+            return sb_fail(b, sb_oom("base solution", nsol));
+        err = hipMemcpyAsync(d_sol, base_sol->data(), (size_t)nsol * sizeof(double),
+                             hipMemcpyHostToDevice, s);
+    }
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(v.desc, b->h_desc.data(), (size_t)count * sizeof(SensScenario),
+                             hipMemcpyHostToDevice, s);
+    if (err == hipSuccess && total > 0)
+        err = hipMemcpyAsync(b->d_edits, edits, (size_t)total * sizeof(lpr_sens_edit),
+                             hipMemcpyHostToDevice, s);
+    if (err == hipSuccess && npayload > 0)
+        err = hipMemcpyAsync(b->d_payload, payload, (size_t)npayload * sizeof(double),
+                             hipMemcpyHostToDevice, s);
+    std::vector<int32_t> not_run;  // every outcome starts as kSensEditNotRun
+    try {
+        not_run.assign((size_t)te, kSensEditNotRun);
+    } catch (...) {
+        hipFree(d_sol);
+        return sb_fail(b, sb_oom("outcomes (host)", te));
+    }
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(v.outcome, not_run.data(), (size_t)te * sizeof(int32_t),
+                             hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) err = hipMemsetAsync(v.edit_piv, 0, (size_t)te * sizeof(int64_t), s);
+    if (err == hipSuccess) err = hipMemsetAsync(v.sol, 0, (size_t)(n * v.sol_cap) * sizeof(double), s);
+    rc = LPR_OK_OPTIMAL;
+    if (err == hipSuccess)
+        rc = sens_batch_launch_init(s, v, count, R, C, baseT, ld, base_basic, base_bcount, d_sol,
+                                    nsol);
+    if (err == hipSuccess && rc == LPR_OK_OPTIMAL)
+        err = hipStreamSynchronize(s);  // edits are borrowed, and the base may go after this call
+    hipFree(d_sol);
+    if (err != hipSuccess) {
+        set_error("%s: %s", W, hipGetErrorString(err));
+        rc = LPR_DEVICE_ERROR;
+    }
+    if (rc != LPR_OK_OPTIMAL) return sb_fail(b, rc);
+    e->live_sens_batch.push_back(b);
+    *out = b;
+    return LPR_OK_OPTIMAL;
 }
 
 }  // namespace
@@ -84,153 +291,18 @@ void sens_batch_orphan(lpr_sens_batch* b) {  // lpr_engine_close
 
 extern "C" {
 
-// count private copies of the state of `base` (SensitivityAnalyzer.cs:14-18), one script each
 int lpr_sens_batch_create(lpr_sens* base, int32_t count, const int32_t* nedits,
                           const lpr_sens_edit* edits, int32_t log_cap, lpr_sens_batch** out) {
-    static const char* W = "lpr_sens_batch_create";
-    int R = 0, C = 0, ld = 0;
-    const double* baseT = nullptr;
-    const int32_t *base_basic = nullptr, *base_bcount = nullptr;
-    const std::vector<double>* base_sol = nullptr;
-    double z = 0.0;
-    lpr_engine* e = sens_view(base, &R, &C, &ld, &baseT, &base_basic, &base_bcount, &base_sol, &z);
-    if (!e) {
-        set_error("%s: the base handle is null or orphaned: its engine has been closed", W);
-        return LPR_BAD_ARGUMENT;
-    }
-    if (!out || count < 1 || !nedits || log_cap < 0) {
-        set_error("%s: bad arguments (count=%d, log_cap=%d, or a null handle / nedits)", W, count,
-                  log_cap);
-        return LPR_BAD_ARGUMENT;
-    }
-    *out = nullptr;
-    if (R > kBatchMaxRowsH || C > kBatchMaxColsH) {
-        set_error("%s: the base is a %d x %d tableau, beyond the batch limit of %d x %d (form H); "
-                  "edit it alone with lpr_sens_*", W, R, C, kBatchMaxRowsH, kBatchMaxColsH);
-        return LPR_BAD_ARGUMENT;
-    }
-    int64_t total = 0;
-    for (int32_t k = 0; k < count; ++k) {
-        if (nedits[k] < 0) {
-            set_error("%s: scenario %d has nedits=%d; it must be >= 0", W, k, nedits[k]);
-            return LPR_BAD_ARGUMENT;
-        }
-        total += nedits[k];
-    }
-    if (total > 0 && !edits) {
-        set_error("%s: null edits for scripts that have entries", W);
-        return LPR_BAD_ARGUMENT;
-    }
-    for (int64_t q = 0; q < total; ++q) {
-        const int op = edits[q].op;
-        if (op < LPR_SENS_EDIT_RESOLVE_ALL || op > LPR_SENS_EDIT_NONBASIC_COLUMN) {
-            set_error("%s: edit %lld has op %d; a batch takes the ops 0..4 that keep the tableau's "
-                      "shape -- AddNewActivity / AddNewConstraint go through lpr_sens_add_activity "
-                      "/ lpr_sens_add_constraint on a single handle", W, (long long)q, op);
-            return LPR_BAD_ARGUMENT;
-        }
-    }
-    LPR_HIP(hipSetDevice(e->device));
-    lpr_sens_batch* b = new (std::nothrow) lpr_sens_batch();
-    if (!b) return sb_oom("handle", 1);
-    b->eng = e;
-    b->count = count;
-    b->total_edits = total;
-    const int m = R - 1;
-    const int nsol = (int)base_sol->size();
-    SensBatchView& v = b->vw;
-    v.R = R;
-    v.C = C;
-    v.sol_cap = std::max(std::max(nsol, C - 1), 1);
-    v.log_cap = log_cap > 0 ? log_cap : std::min<int32_t>(kBatchLogDefaultMax, 4 * (R + C));
-    try {
-        b->h_desc.resize((size_t)count);
-    } catch (...) {
-        delete b;
-        return sb_oom("descriptors", count);
-    }
-    int64_t at = 0;
-    for (int32_t k = 0; k < count; ++k) {
-        SensScenario& d = b->h_desc[(size_t)k];
-        std::memset(&d, 0, sizeof d);
-        d.z = z;
-        d.old_z = z;
-        d.edit_off = at;
-        d.nedits = nedits[k];
-        d.phase = kPhaseApply;
-        d.nsol = nsol;
-        d.status = kRunning;
-        at += nedits[k];
-    }
-    const int64_t n = count, RC = (int64_t)R * C;
-    const int64_t te = std::max<int64_t>(total, 1);
-    int rc = LPR_OK_OPTIMAL;
-    auto get = [&](auto** p, int64_t elems, const char* what) {
-        if (rc != LPR_OK_OPTIMAL) return;
-        if (hipMalloc(reinterpret_cast<void**>(p), (size_t)elems * sizeof(**p)) != hipSuccess) {
-            *p = nullptr;
-            (void)hipGetLastError();
-            rc = sb_oom(what, elems);
-        }
-    };
-    get(&v.desc, n, "descriptors");
-    get(&v.cur, n * RC, "tableau slab");
-    get(&v.alt, n * RC, "second tableau slab");
-    get(&v.basic, n * std::max(m, 1), "basicVars");
-    get(&v.bcount, n * C, "membership counts");
-    get(&v.snap, n * (m + C), "ChangeRHS snapshots");
-    get(&v.sol, n * v.sol_cap, "solution vectors");
-    get(&v.log, n * 3 * v.log_cap, "pivot logs");
-    get(&v.outcome, te, "outcomes");
-    get(&v.edit_piv, te, "pivot counts");
-    get(&b->d_edits, te, "edits");
-    get(&b->idx, 2 * n, "running lists");
-    get(&b->counter, 1, "counter");
-    if (rc == LPR_OK_OPTIMAL && hipHostMalloc(&b->h_counter, sizeof(int32_t)) != hipSuccess)
-        rc = sb_oom("pinned counter", 1);
-    if (rc != LPR_OK_OPTIMAL) return sb_fail(b, rc);
-    v.edits = b->d_edits;
-    hipStream_t s = e->stream;
-    double* d_sol = nullptr;  // the base's solutionVector is a host mirror
-    hipError_t err = hipSuccess;
-    if (nsol > 0) {
-        if (hipMalloc(&d_sol, (size_t)nsol * sizeof(double)) != hipSuccess)
-            return sb_fail(b, sb_oom("base solution", nsol));
-        err = hipMemcpyAsync(d_sol, base_sol->data(), (size_t)nsol * sizeof(double),
-                             hipMemcpyHostToDevice, s);
-    }
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(v.desc, b->h_desc.data(), (size_t)count * sizeof(SensScenario),
-                             hipMemcpyHostToDevice, s);
-    if (err == hipSuccess && total > 0)
-        err = hipMemcpyAsync(b->d_edits, edits, (size_t)total * sizeof(lpr_sens_edit),
-                             hipMemcpyHostToDevice, s);
-    std::vector<int32_t> not_run;  // every outcome starts as kSensEditNotRun
-    try {
-        not_run.assign((size_t)te, kSensEditNotRun);
-    } catch (...) {
-        hipFree(d_sol);
-        return sb_fail(b, sb_oom("outcomes (host)", te));
-    }
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(v.outcome, not_run.data(), (size_t)te * sizeof(int32_t),
-                             hipMemcpyHostToDevice, s);
-    if (err == hipSuccess) err = hipMemsetAsync(v.edit_piv, 0, (size_t)te * sizeof(int64_t), s);
-    if (err == hipSuccess) err = hipMemsetAsync(v.sol, 0, (size_t)(n * v.sol_cap) * sizeof(double), s);
-    rc = LPR_OK_OPTIMAL;
-    if (err == hipSuccess)
-        rc = sens_batch_launch_init(s, v, count, baseT, ld, base_basic, base_bcount, d_sol, nsol);
-    if (err == hipSuccess && rc == LPR_OK_OPTIMAL)
-        err = hipStreamSynchronize(s);  // edits are borrowed, and the base may go after this call
-    hipFree(d_sol);
-    if (err != hipSuccess) {
-        set_error("%s: %s", W, hipGetErrorString(err));
-        rc = LPR_DEVICE_ERROR;
-    }
-    if (rc != LPR_OK_OPTIMAL) return sb_fail(b, rc);
-    e->live_sens_batch.push_back(b);
-    *out = b;
-    return LPR_OK_OPTIMAL;
+    return sb_create("lpr_sens_batch_create", false, base, count, nedits, edits, nullptr, 0,
+                     log_cap, out);
+}
+
+// ... whose scripts may also hold AddNewActivity (:534-584) and AddNewConstraint (:609-659)
+int lpr_sens_batch_create_grow(lpr_sens* base, int32_t count, const int32_t* nedits,
+                               const lpr_sens_edit* edits, const double* payload,
+                               int64_t npayload, int32_t log_cap, lpr_sens_batch** out) {
+    return sb_create("lpr_sens_batch_create_grow", true, base, count, nedits, edits, payload,
+                     npayload, log_cap, out);
 }
 
 int lpr_sens_batch_destroy(lpr_sens_batch* b) {
@@ -251,7 +323,7 @@ int lpr_sens_batch_destroy(lpr_sens_batch* b) {
 }
 
 // Every script that has not ended, edit after edit (:203-208, :300-321, :362-393, :427-470,
-// :502-531)
+// :502-531, and in a grow batch :534-584, :609-659)
 int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
                        lpr_sens_batch_result* res) {
     LPR_LIVE_SB(b);
@@ -302,7 +374,7 @@ int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
     int launches = 0;
     while (live > 0) {
         LPR_HIP(hipMemsetAsync(b->counter, 0, sizeof(int32_t), s));
-        const int rc = sens_batch_launch(form, s, v, in, live, outl, b->counter, chunk);
+        const int rc = sens_batch_launch(form, b->grow, s, v, in, live, outl, b->counter, chunk);
         if (rc != LPR_OK_OPTIMAL) return rc;
         ++launches;
         LPR_HIP(hipMemcpyAsync(b->h_counter, b->counter, sizeof(int32_t), hipMemcpyDeviceToHost,
@@ -332,8 +404,8 @@ int lpr_sens_batch_info(lpr_sens_batch* b, int32_t* count, int32_t* rows, int32_
         return LPR_BAD_ARGUMENT;
     }
     if (count) *count = b->count;
-    if (rows) *rows = b->vw.R;
-    if (cols) *cols = b->vw.C;
+    if (rows) *rows = b->base_R;
+    if (cols) *cols = b->base_C;
     if (total_edits) *total_edits = b->total_edits;
     if (log_cap) *log_cap = b->vw.log_cap;
     if (form) *form = b->form;
@@ -362,12 +434,30 @@ int lpr_sens_batch_state_read(lpr_sens_batch* b, double* z, int32_t* nsol, int32
         if (z) z[k] = b->h_desc[(size_t)k].z;
         if (nsol) nsol[k] = b->h_desc[(size_t)k].nsol;
     }
-    const int64_t nb = (int64_t)b->count * (b->vw.R - 1);
+    const int64_t sm = b->vw.R - 1, nb = (int64_t)b->count * sm;
     if (basic && nb > 0) {
         LPR_HIP(hipMemcpyAsync(basic, b->vw.basic, (size_t)nb * sizeof(int32_t),
                                hipMemcpyDeviceToHost, b->eng->stream));
         LPR_HIP(hipStreamSynchronize(b->eng->stream));
+        for (int32_t k = 0; k < b->count; ++k)  // past a scenario's own rows: no entry
+            for (int64_t i = b->h_desc[(size_t)k].R - 1; i < sm; ++i) basic[k * sm + i] = INT32_MIN;
     }
+    return LPR_OK_OPTIMAL;
+}
+
+// The shape of every scenario as of now, and the batch-wide maxima the strides are sized by
+int lpr_sens_batch_shape_read(lpr_sens_batch* b, int32_t* rows, int32_t* cols, int32_t* max_rows,
+                              int32_t* max_cols) {
+    if (!b) {
+        set_error("lpr_sens_batch_shape_read: null handle");
+        return LPR_BAD_ARGUMENT;
+    }
+    for (int32_t k = 0; k < b->count; ++k) {
+        if (rows) rows[k] = b->h_desc[(size_t)k].R;
+        if (cols) cols[k] = b->h_desc[(size_t)k].C;
+    }
+    if (max_rows) *max_rows = b->vw.R;
+    if (max_cols) *max_cols = b->vw.C;
     return LPR_OK_OPTIMAL;
 }
 
@@ -398,8 +488,9 @@ int lpr_sens_batch_tableau_read(lpr_sens_batch* b, int32_t k, double* rowmajor) 
                   k, b->count - 1);
         return LPR_BAD_ARGUMENT;
     }
-    const size_t RC = (size_t)b->vw.R * b->vw.C;
-    const double* src = (b->h_desc[(size_t)k].in_alt ? b->vw.alt : b->vw.cur) + (size_t)k * RC;
+    const SensScenario& d = b->h_desc[(size_t)k];
+    const size_t RC = (size_t)d.R * d.C;  // compact at the scenario's own shape
+    const double* src = (d.in_alt ? b->vw.alt : b->vw.cur) + (size_t)k * b->vw.R * b->vw.C;
     LPR_HIP(hipMemcpyAsync(rowmajor, src, RC * sizeof(double), hipMemcpyDeviceToHost,
                            b->eng->stream));
     LPR_HIP(hipStreamSynchronize(b->eng->stream));

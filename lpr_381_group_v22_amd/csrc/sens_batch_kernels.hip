@@ -3,11 +3,14 @@
 // (SensitivityAnalysis/SensitivityAnalyzer.cs), the same bits as lpr_sens_* calls on a fresh
 // handle and the oracle give for that script alone.
 //
-//   k_sens_batch<kLds>   one 256-lane workgroup per scenario runs its script as a resumable state
+//   k_sens_batch<kLds, kGrow>
+//                        one 256-lane workgroup per scenario runs its script as a resumable state
 //                        machine: the edits (:300-321 :362-393 :427-470 :502-531),
 //                        RebuildBasicsFromTableau (:706-723), DualSimplexIfNeeded (:168-201),
 //                        ReOptimize (:121-166), Pivot (:98-119); at most `chunk` pivots per
-//                        launch; the tableau in LDS (form G) or in the global slab (form H)
+//                        launch; the tableau in LDS (form G) or in the global slab (form H).
+//                        kGrow (lpr_sens_batch_create_grow): the shape is the scenario's own, and
+//                        AddNewActivity (:534-584) / AddNewConstraint (:609-659) grow it in place
 //   k_sens_batch_init    the base state copied into every scenario
 #include "sens_batch_common.hpp"
 #include "select_common.hpp"
@@ -92,7 +95,51 @@ __device__ __forceinline__ int lane_basic_row(const double* T, int R, int C, int
     return -1;
 }
 
-template <bool kLds>
+// The membership counts that shadow basicVars, counted again from its m entries
+__device__ __forceinline__ void block_recount(const int32_t* basic, int m, int32_t* bcount, int C) {
+    for (int j = threadIdx.x; j < C; j += 256) bcount[j] = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < m; i += 256) {
+        const int b = basic[i];
+        if (b >= 0 && b < C) atomicAdd(&bcount[b], 1);
+    }
+    __syncthreads();
+}
+
+// A compact R x C tableau re-strided to R2 x C2 >= R x C where it lies; value(i, j) gives entry
+// (i, j) of the grown tableau from the old one, and reads an old entry only at a flat index at or
+// below the new one's (columns and rows are inserted, never removed).
+//   G: in place in LDS, the new flat indices in chunks of 256 from the last to the first.  A
+//      chunk is loaded into registers, then a barrier, then stored: the stores of a chunk land at
+//      or above its base, and every later chunk loads from below that base.
+//   H: through the scenario's alt slice and back.  No ChangeRHS snapshot is alive at an edit
+//      boundary, so alt is free, and cur stays the live tableau.
+template <bool kLds, class F>
+__device__ __forceinline__ void grow_tableau(double* T, double* alt, int R2, int C2, F value) {
+    const int N2 = R2 * C2, tid = threadIdx.x;
+    if constexpr (kLds) {
+        for (int base = ((N2 - 1) / 256) * 256; base >= 0; base -= 256) {
+            const int y = base + tid;
+            double v = 0.0;
+            if (y < N2) {
+                const int i = y / C2;
+                v = value(i, y - i * C2);
+            }
+            __syncthreads();
+            if (y < N2) T[y] = v;
+        }
+    } else {
+        for (int y = tid; y < N2; y += 256) {
+            const int i = y / C2;
+            alt[y] = value(i, y - i * C2);
+        }
+        __syncthreads();
+        for (int y = tid; y < N2; y += 256) T[y] = alt[y];
+    }
+    __syncthreads();
+}
+
+template <bool kLds, bool kGrow>
 __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
                                                     const int32_t* __restrict__ idx_in, int n_in,
                                                     int32_t* __restrict__ idx_out,
@@ -105,12 +152,19 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
     if ((int)blockIdx.x >= n_in) return;
     const int k = idx_in[blockIdx.x];
     SensScenario* const d = vw.desc + k;
-    const int R = vw.R, C = vw.C, m = R - 1, rhs = C - 1, RC = R * C;
-    double* const cur = vw.cur + (size_t)k * RC;
-    double* const alt = vw.alt + (size_t)k * RC;
-    int32_t* const g_basic = vw.basic + (size_t)k * m;
-    int32_t* const g_bcount = vw.bcount + (size_t)k * C;
-    int32_t* const g_snap = vw.snap + (size_t)k * (m + C);
+    // strides and the LDS carve-up: the batch's maximal shape; indexing: the scenario's own
+    const int SR = vw.R, SC = vw.C;
+    int R = SR, C = SC;
+    if constexpr (kGrow) {
+        R = d->R;
+        C = d->C;
+    }
+    int m = R - 1, rhs = C - 1, RC = R * C;
+    double* const cur = vw.cur + (size_t)k * SR * SC;
+    double* const alt = vw.alt + (size_t)k * SR * SC;
+    int32_t* const g_basic = vw.basic + (size_t)k * (SR - 1);
+    int32_t* const g_bcount = vw.bcount + (size_t)k * SC;
+    int32_t* const g_snap = vw.snap + (size_t)k * (SR - 1 + SC);
     double* const g_sol = vw.sol + (size_t)k * vw.sol_cap;
     int32_t* const g_log = vw.log + (size_t)k * 3 * vw.log_cap;
 
@@ -120,14 +174,14 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
     double* fcol;
     if constexpr (kLds) {
         T = smem;
-        fcol = smem + RC;
+        fcol = smem + SR * SC;
     } else {
         T = cur;
         fcol = smem;
     }
-    double* const prow = fcol + R;
-    int32_t* const bcount = reinterpret_cast<int32_t*>(prow + C);
-    int32_t* const basic = bcount + C;
+    double* const prow = fcol + SR;
+    int32_t* const bcount = reinterpret_cast<int32_t*>(prow + SC);
+    int32_t* const basic = bcount + SC;
 
     // the descriptor, uniform over the workgroup
     double z = d->z, old_z = d->old_z;
@@ -161,6 +215,7 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
             it_d = 0;
             it_p = 0;
             bool valid = true;
+            int refused = LPR_SENS_INVALID_INDEX;  // the outcome of an edit that is not valid
             if (e.op == LPR_SENS_EDIT_RESOLVE_ALL) {
                 phase = kPhaseRebuild;
             } else if (e.op == LPR_SENS_EDIT_NONBASIC_CBAR) {  // :306-318
@@ -208,6 +263,92 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
                     z = T[rhs];
                     phase = kPhaseDual;  // no rebuild (:455-456)
                 }
+            } else if (kGrow && e.op == LPR_SENS_EDIT_ADD_ACTIVITY) {  // :534-584
+                // the batch's one rule of its own: a column that is not R - 1 long changes nothing
+                // (lpr_sens_add_activity refuses the call)
+                valid = e.b == m && C >= R;
+                if (valid) {
+                    const int n = C - R;
+                    const double* a = vw.payload + e.a;
+                    // yTa (:543-551): every product rounded on its own, then one lane adds them
+                    // in index order from 0.0, as the loop does
+                    for (int i = tid; i < m; i += 256) fcol[i] = T[n + i] * a[i];
+                    __syncthreads();
+                    if (tid == 0) {
+                        double yTa = 0.0;
+                        for (int i = 0; i < m; ++i) yTa = yTa + fcol[i];
+                        red_v[0] = yTa - e.v;
+                    }
+                    __syncthreads();
+                    const double cbar = red_v[0];
+                    const int C0 = C;
+                    // the column goes in front of the slacks (:553-570)
+                    grow_tableau<kLds>(T, alt, R, C0 + 1, [&](int i, int j) -> double {
+                        if (j == n) return i == 0 ? cbar : a[i - 1];
+                        return T[(size_t)i * C0 + (j < n ? j : j - 1)];
+                    });
+                    C = C0 + 1;
+                    rhs = C - 1;
+                    RC = R * C;
+                    for (int i = tid; i < m; i += 256)  // :575-577
+                        if (basic[i] >= n) basic[i] += 1;
+                    __syncthreads();
+                    block_recount(basic, m, bcount, C);
+                    phase = kPhaseRebuild;
+                }
+            } else if (kGrow && e.op == LPR_SENS_EDIT_ADD_CONSTRAINT) {  // :609-659
+                valid = e.b == rhs;  // :616-617
+                if (valid && rhs > 0) {  // tech[basicVars[pos]] throws on -1 (:640)
+                    int bad = 0;
+                    for (int i = tid; i < m; i += 256) bad |= basic[i] < 0 || basic[i] >= e.b;
+                    if (__syncthreads_or(bad)) {
+                        valid = false;
+                        refused = LPR_SENS_INDEX_OUT_OF_RANGE;
+                    }
+                }
+                if (valid) {
+                    const double* tech = vw.payload + e.a;
+                    // aX (:647-651) over the stored solutionVector: products, then one lane adds
+                    const int lim = e.b < nsol ? e.b : nsol;
+                    for (int j = tid; j < lim; j += 256) prow[j] = tech[j] * g_sol[j];
+                    if (rhs > 0)  // checked above to lie in [0, ntech)
+                        for (int i = tid; i < m; i += 256) fcol[i] = tech[basic[i]];
+                    __syncthreads();
+                    if (tid == 0) {
+                        double aX = 0.0;
+                        for (int j = 0; j < lim; ++j) aX = aX + prow[j];
+                        red_v[0] = e.v - aX;
+                    }
+                    __syncthreads();
+                    const double newb = red_v[0];
+                    // the new row (:636-645): one lane per column, positions ascending
+                    for (int j = tid; j < rhs; j += 256) {
+                        double coeff = -tech[j];
+                        for (int pos = 0; pos < m; ++pos) {
+                            const double prod = fcol[pos] * T[(size_t)(pos + 1) * C + j];
+                            coeff = coeff + prod;
+                        }
+                        prow[j] = coeff;
+                    }
+                    __syncthreads();
+                    const int R0 = R, C0 = C, s0 = rhs;
+                    // a zero column for the new slack in front of the RHS (:621-631), 1.0 in the
+                    // new row (:652-653)
+                    grow_tableau<kLds>(T, alt, R0 + 1, C0 + 1, [&](int i, int j) -> double {
+                        if (i == R0) return j < s0 ? prow[j] : (j == s0 ? 1.0 : newb);
+                        if (j == s0) return 0.0;
+                        return T[(size_t)i * C0 + (j < s0 ? j : s0)];
+                    });
+                    R = R0 + 1;
+                    C = C0 + 1;
+                    m = R - 1;
+                    rhs = C - 1;
+                    RC = R * C;
+                    if (tid == 0) basic[m - 1] = s0;  // basicVars.Add(newSlackCol) :656
+                    __syncthreads();
+                    block_recount(basic, m, bcount, C);
+                    phase = kPhaseRebuild;
+                }
             } else {  // LPR_SENS_EDIT_NONBASIC_COLUMN :505-526 (the create refused anything else)
                 valid = e.a >= 1 && e.a < R && e.b >= 0 && e.b < rhs && bcount[e.b] == 0;
                 if (valid) {
@@ -227,7 +368,7 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
             __syncthreads();
             if (!valid) {  // the C# prints "Invalid ..." and returns; nothing changed
                 if (tid == 0) {
-                    vw.outcome[edit_off + edit] = LPR_SENS_INVALID_INDEX;
+                    vw.outcome[edit_off + edit] = refused;
                     vw.edit_piv[edit_off + edit] = 0;
                 }
                 ++edit;
@@ -467,18 +608,26 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
         d->nsol = nsol;
         d->in_alt = in_alt;
         d->status = status;
+        if constexpr (kGrow) {
+            d->R = R;
+            d->C = C;
+        }
         if (status == kRunning) idx_out[atomicAdd(n_out, 1)] = k;
     }
 }
 
-template __global__ void k_sens_batch<true>(SensBatchView, const int32_t*, int, int32_t*,
-                                            int32_t*, int);
-template __global__ void k_sens_batch<false>(SensBatchView, const int32_t*, int, int32_t*,
-                                             int32_t*, int);
+template __global__ void k_sens_batch<true, false>(SensBatchView, const int32_t*, int, int32_t*,
+                                                   int32_t*, int);
+template __global__ void k_sens_batch<false, false>(SensBatchView, const int32_t*, int, int32_t*,
+                                                    int32_t*, int);
+template __global__ void k_sens_batch<true, true>(SensBatchView, const int32_t*, int, int32_t*,
+                                                  int32_t*, int);
+template __global__ void k_sens_batch<false, true>(SensBatchView, const int32_t*, int, int32_t*,
+                                                   int32_t*, int);
 
-// The base state into every scenario: the tableau compact (the base pads its rows to ld) into
-// the cur slice, basicVars and its membership counts as stored, solutionVector.
-__global__ __launch_bounds__(256) void k_sens_batch_init(SensBatchView vw, int count,
+// The base state (R x C) into every scenario: the tableau compact (the base pads its rows to ld)
+// into the cur slice, basicVars and its membership counts as stored, solutionVector.
+__global__ __launch_bounds__(256) void k_sens_batch_init(SensBatchView vw, int count, int R, int C,
                                                          const double* __restrict__ baseT, int ld,
                                                          const int32_t* __restrict__ base_basic,
                                                          const int32_t* __restrict__ base_bcount,
@@ -487,8 +636,8 @@ __global__ __launch_bounds__(256) void k_sens_batch_init(SensBatchView vw, int c
     const int k = blockIdx.x;
     if (k >= count) return;
     const int tid = threadIdx.x;
-    const int R = vw.R, C = vw.C, m = R - 1, RC = R * C;
-    double* T = vw.cur + (size_t)k * RC;
+    const int m = R - 1, RC = R * C;
+    double* T = vw.cur + (size_t)k * vw.R * vw.C;
     int i = tid / C, j = tid - (tid / C) * C;
     const int di = 256 / C, dj = 256 - (256 / C) * C;
     for (int x = tid; x < RC; x += 256) {
@@ -500,18 +649,22 @@ __global__ __launch_bounds__(256) void k_sens_batch_init(SensBatchView vw, int c
             ++i;
         }
     }
-    for (int q = tid; q < m; q += 256) vw.basic[(size_t)k * m + q] = base_basic[q];
-    for (int q = tid; q < C; q += 256) vw.bcount[(size_t)k * C + q] = base_bcount[q];
+    for (int q = tid; q < m; q += 256) vw.basic[(size_t)k * (vw.R - 1) + q] = base_basic[q];
+    for (int q = tid; q < C; q += 256) vw.bcount[(size_t)k * vw.C + q] = base_bcount[q];
     for (int q = tid; q < nsol; q += 256) vw.sol[(size_t)k * vw.sol_cap + q] = base_sol[q];
 }
 
 // ------------------------------------------------------------------------------------------
 // Launchers (sens_batch_engine.hip).  Dynamic LDS above 64 KiB needs the attribute once per device.
-int sens_batch_launch(int form, hipStream_t s, const SensBatchView& vw, const int32_t* idx_in,
-                      int n_in, int32_t* idx_out, int32_t* n_out, int chunk) {
-    static unsigned long long g_mask = 0;  // per device bit: the G attribute is set
+int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& vw,
+                      const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
+                      int chunk) {
+    static unsigned long long g_masks[2] = {0, 0};  // per device bit: the G attribute is set
     if (n_in <= 0) return LPR_OK_OPTIMAL;
+    const auto kern_g = grow ? &k_sens_batch<true, true> : &k_sens_batch<true, false>;
+    const auto kern_h = grow ? &k_sens_batch<false, true> : &k_sens_batch<false, false>;
     if (form == kFormG) {
+        unsigned long long& g_mask = g_masks[grow ? 1 : 0];
         const size_t lds = sens_batch_footprint_g(vw.R, vw.C);
         if (lds > ((size_t)64 << 10)) {
             int dev = 0;
@@ -519,7 +672,7 @@ int sens_batch_launch(int form, hipStream_t s, const SensBatchView& vw, const in
             const unsigned long long bit = 1ull << dev;
             if (!(__atomic_load_n(&g_mask, __ATOMIC_ACQUIRE) & bit)) {
                 const hipError_t err = hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(&k_sens_batch<true>),
+                    reinterpret_cast<const void*>(kern_g),
                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBatchMaxLdsG);
                 if (err != hipSuccess) {
                     set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed: %s",
@@ -529,12 +682,12 @@ int sens_batch_launch(int form, hipStream_t s, const SensBatchView& vw, const in
                 __atomic_fetch_or(&g_mask, bit, __ATOMIC_ACQ_REL);
             }
         }
-        hipLaunchKernelGGL((k_sens_batch<true>), dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in,
-                           idx_out, n_out, chunk);
+        hipLaunchKernelGGL(kern_g, dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in, idx_out, n_out,
+                           chunk);
     } else {
         const size_t lds = sens_batch_aux_bytes(vw.R, vw.C);
-        hipLaunchKernelGGL((k_sens_batch<false>), dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in,
-                           idx_out, n_out, chunk);
+        hipLaunchKernelGGL(kern_h, dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in, idx_out, n_out,
+                           chunk);
     }
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) {
@@ -545,10 +698,10 @@ int sens_batch_launch(int form, hipStream_t s, const SensBatchView& vw, const in
     return LPR_OK_OPTIMAL;
 }
 
-int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, const double* baseT,
-                           int ld, const int32_t* base_basic, const int32_t* base_bcount,
-                           const double* base_sol, int nsol) {
-    hipLaunchKernelGGL(k_sens_batch_init, dim3(count), dim3(256), 0, s, vw, count, baseT, ld,
+int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, int R, int C,
+                           const double* baseT, int ld, const int32_t* base_basic,
+                           const int32_t* base_bcount, const double* base_sol, int nsol) {
+    hipLaunchKernelGGL(k_sens_batch_init, dim3(count), dim3(256), 0, s, vw, count, R, C, baseT, ld,
                        base_basic, base_bcount, base_sol, nsol);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) {

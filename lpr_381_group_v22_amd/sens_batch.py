@@ -25,6 +25,7 @@ EDIT_OPS = {
     "change_nonbasic_column": (N.LPR_SENS_EDIT_NONBASIC_COLUMN, 2, True),
 }
 SHAPE_CHANGING_OPS = ("add_activity", "add_constraint")
+NO_BASIC_ENTRY = -2 ** 31        # basicVars past a scenario's own rows in a grow batch's bulk read
 MAX_ROWS_H = 1024
 MAX_COLS_H = 2048
 FORM_G, FORM_H = 1, 2            # lpr_sens_batch_result.form
@@ -62,6 +63,17 @@ def _int32(x, what: str) -> int:
     return max(-2 ** 31, min(2 ** 31 - 1, i))
 
 
+def _pack_edit(name: str, args: tuple, where: str) -> tuple:
+    """One shape-keeping edit as a record of EDIT_DTYPE."""
+    if name not in EDIT_OPS:
+        raise ValueError(f"{where}: unknown op {name!r}")
+    code, nint, has_v = EDIT_OPS[name]
+    if len(args) != nint + (1 if has_v else 0):
+        raise ValueError(f"{where}: {name} takes {nint + has_v} arguments, got {len(args)}")
+    ints = [_int32(a, where) for a in args[:nint]] + [0, 0]
+    return (code, ints[0], ints[1], 0, float(args[nint]) if has_v else 0.0)
+
+
 def pack_scripts(scripts: Sequence[Sequence[tuple]]) -> PackedScripts:
     """Scripts -> the packed ABI arrays, with the checks of lpr_sens_batch_create (raises
     ValueError where the call would refuse the batch): at least one scenario, known ops, and no op
@@ -79,16 +91,66 @@ def pack_scripts(scripts: Sequence[Sequence[tuple]]) -> PackedScripts:
             if name in SHAPE_CHANGING_OPS:
                 raise ValueError(f"scenario {k} edit {q}: {name} changes the tableau's shape; "
                                  f"call SensState.{name} on a single handle")
-            if name not in EDIT_OPS:
-                raise ValueError(f"scenario {k} edit {q}: unknown op {name!r}")
-            code, nint, has_v = EDIT_OPS[name]
-            if len(args) != nint + (1 if has_v else 0):
-                raise ValueError(f"scenario {k} edit {q}: {name} takes {nint + has_v} arguments, "
-                                 f"got {len(args)}")
-            ints = [_int32(a, f"scenario {k} edit {q}") for a in args[:nint]] + [0, 0]
-            flat.append((code, ints[0], ints[1], 0, float(args[nint]) if has_v else 0.0))
+            flat.append(_pack_edit(name, args, f"scenario {k} edit {q}"))
     edits = np.array(flat, dtype=EDIT_DTYPE) if flat else np.zeros(0, dtype=EDIT_DTYPE)
     return PackedScripts(nedits, edits)
+
+
+class PackedGrowScripts(NamedTuple):
+    """The packed arrays of lpr_sens_batch_create_grow."""
+    nedits: np.ndarray   # int32, per scenario
+    edits: np.ndarray    # EDIT_DTYPE; an add edit holds its payload offset in a, its length in b
+    payload: np.ndarray  # float64: the vectors of the add edits, in script order
+
+
+def _vector(x, what: str) -> np.ndarray:
+    try:
+        v = np.asarray(x, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {x!r} is not a vector of numbers") from None
+    if v.ndim != 1:
+        raise ValueError(f"{what}: {x!r} is not a vector of numbers")
+    return v
+
+
+def pack_grow_scripts(scripts: Sequence[Sequence[tuple]]) -> PackedGrowScripts:
+    """Scripts -> the packed arrays of lpr_sens_batch_create_grow.  Besides the five ops of
+    pack_scripts, which pack exactly as there, a script may hold ``("add_activity", c_new, a_new)``
+    and ``("add_constraint", tech, rhs)`` as SensState spells them; their vectors go into one
+    payload pool in script order."""
+    if len(scripts) < 1:
+        raise ValueError("no scenarios")
+    nedits = np.zeros(len(scripts), dtype=np.int32)
+    flat, pool, at = [], [], 0
+    for k, script in enumerate(scripts):
+        nedits[k] = len(script)
+        for q, edit in enumerate(script):
+            where = f"scenario {k} edit {q}"
+            name, args = edit[0], tuple(edit[1:])
+            if len(args) == 1 and isinstance(args[0], (tuple, list)):
+                args = tuple(args[0])    # (op, (args...)) as the test scripts write it
+            if name not in SHAPE_CHANGING_OPS:
+                flat.append(_pack_edit(name, args, where))
+                continue
+            if len(args) != 2:
+                raise ValueError(f"{where}: {name} takes 2 arguments, got {len(args)}")
+            if name == "add_activity":
+                code, value, vec = N.LPR_SENS_EDIT_ADD_ACTIVITY, args[0], args[1]
+            else:
+                code, value, vec = N.LPR_SENS_EDIT_ADD_CONSTRAINT, args[1], args[0]
+            vec = _vector(vec, where)
+            try:
+                value = float(value)
+            except (TypeError, ValueError):
+                raise ValueError(f"{where}: {value!r} is not a number") from None
+            if at + vec.size > 2 ** 31 - 1:
+                raise ValueError(f"{where}: the payload pool is past 2^31 - 1 doubles")
+            flat.append((code, at, vec.size, 0, value))
+            pool.append(vec)
+            at += vec.size
+    edits = np.array(flat, dtype=EDIT_DTYPE) if flat else np.zeros(0, dtype=EDIT_DTYPE)
+    payload = np.concatenate(pool) if pool else np.zeros(0, dtype=np.float64)
+    return PackedGrowScripts(nedits, edits, payload)
 
 
 class SensitivityBatch:
@@ -96,15 +158,10 @@ class SensitivityBatch:
     is only read and may be destroyed afterwards."""
 
     def __init__(self, base: SensState, scripts: Sequence[Sequence[tuple]], log_cap: int = 0):
-        p = pack_scripts(scripts)
         self._h = None
+        p = self._pack(scripts)
         self._engine = base.engine
-        h = C.c_void_p()
-        eptr = p.edits.ctypes.data_as(C.POINTER(N.SensEdit)) if p.edits.size else None
-        N.check(N.lib.lpr_sens_batch_create(base._h, len(p.nedits),
-                                            p.nedits.ctypes.data_as(C.POINTER(C.c_int32)), eptr,
-                                            int(log_cap), C.byref(h)), "lpr_sens_batch_create")
-        self._h = h
+        self._h = self._create(base, p, int(log_cap))
         self.Count = len(p.nedits)
         self.nedits = p.nedits.tolist()
         self._off = np.concatenate([[0], np.cumsum(p.nedits)]).astype(np.int64)
@@ -116,6 +173,17 @@ class SensitivityBatch:
         self.Rows, self.Cols, self.LogCap = r.value, c.value, lc.value
         self.TotalEdits = te.value
         self.LastResult: Optional[N.SensBatchResult] = None
+
+    _pack = staticmethod(pack_scripts)
+
+    @staticmethod
+    def _create(base: SensState, p: PackedScripts, log_cap: int) -> C.c_void_p:
+        h = C.c_void_p()
+        eptr = p.edits.ctypes.data_as(C.POINTER(N.SensEdit)) if p.edits.size else None
+        N.check(N.lib.lpr_sens_batch_create(base._h, len(p.nedits),
+                                            p.nedits.ctypes.data_as(C.POINTER(C.c_int32)), eptr,
+                                            log_cap, C.byref(h)), "lpr_sens_batch_create")
+        return h
 
     def destroy(self) -> None:
         if self._h:
@@ -209,3 +277,70 @@ class SensitivityBatch:
         z, _, basic = self.state_arrays()
         return dict(T=self.Tableau(k), basic=basic[k].tolist(), sol=self.Solution(k),
                     z=float(z[k]))
+
+
+class SensitivityGrowBatch(SensitivityBatch):
+    """A ``SensitivityBatch`` whose scripts may also hold ``add_activity`` and ``add_constraint``
+    (lpr_sens_batch_create_grow): a scenario's tableau grows as its script runs.  ``Rows`` and
+    ``Cols`` stay the base's shape; ``Shape(k)`` is scenario k's own, ``MaxRows`` x ``MaxCols`` the
+    largest any script can reach."""
+
+    _pack = staticmethod(pack_grow_scripts)
+
+    @staticmethod
+    def _create(base: SensState, p: PackedGrowScripts, log_cap: int) -> C.c_void_p:
+        h = C.c_void_p()
+        eptr = p.edits.ctypes.data_as(C.POINTER(N.SensEdit)) if p.edits.size else None
+        pptr = p.payload.ctypes.data_as(C.POINTER(C.c_double)) if p.payload.size else None
+        N.check(N.lib.lpr_sens_batch_create_grow(
+            base._h, len(p.nedits), p.nedits.ctypes.data_as(C.POINTER(C.c_int32)), eptr, pptr,
+            p.payload.size, log_cap, C.byref(h)), "lpr_sens_batch_create_grow")
+        return h
+
+    def shape_arrays(self) -> Tuple[np.ndarray, np.ndarray, int, int]:
+        """(rows, cols) per scenario as of now, and the batch-wide (max_rows, max_cols)."""
+        rows = np.zeros(self.Count, dtype=np.int32)
+        cols = np.zeros(self.Count, dtype=np.int32)
+        mr, mc = C.c_int32(), C.c_int32()
+        N.check(N.lib.lpr_sens_batch_shape_read(
+            self._h, rows.ctypes.data_as(C.POINTER(C.c_int32)),
+            cols.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(mr), C.byref(mc)),
+            "lpr_sens_batch_shape_read")
+        return rows, cols, mr.value, mc.value
+
+    @property
+    def MaxRows(self) -> int:
+        return self.shape_arrays()[2]
+
+    @property
+    def MaxCols(self) -> int:
+        return self.shape_arrays()[3]
+
+    def Shape(self, k: int) -> Tuple[int, int]:
+        rows, cols, _, _ = self.shape_arrays()
+        return int(rows[k]), int(cols[k])
+
+    def state_arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(z, solutionVector.Count, basicVars as a Count x (max_rows - 1) array whose entries
+        past a scenario's own rows - 1 are NO_BASIC_ENTRY)"""
+        m = self.MaxRows - 1
+        z = np.zeros(self.Count, dtype=np.float64)
+        ns = np.zeros(self.Count, dtype=np.int32)
+        basic = np.zeros(max(self.Count * m, 1), dtype=np.int32)
+        N.check(N.lib.lpr_sens_batch_state_read(
+            self._h, z.ctypes.data_as(C.POINTER(C.c_double)),
+            ns.ctypes.data_as(C.POINTER(C.c_int32)),
+            basic.ctypes.data_as(C.POINTER(C.c_int32))), "lpr_sens_batch_state_read")
+        return z, ns, basic[:self.Count * m].reshape(self.Count, m)
+
+    def Tableau(self, k: int) -> np.ndarray:
+        T = np.empty(self.Shape(k), dtype=np.float64)
+        N.check(N.lib.lpr_sens_batch_tableau_read(
+            self._h, int(k), T.ctypes.data_as(C.POINTER(C.c_double))),
+            "lpr_sens_batch_tableau_read")
+        return T
+
+    def State(self, k: int) -> dict:
+        st = super().State(k)
+        st["basic"] = st["basic"][:self.Shape(k)[0] - 1]
+        return st

@@ -7,6 +7,14 @@ workload:
   G   a solved 33 x 97 LP (m = 32, n = 64), 4096 three-edit scripts (RHS, cost, RHS)
   H   a solved 257 x 769 LP (m = 256, n = 512), 256 two-edit scripts (RHS, cost): form H
 
+With --grow the scripts hold the two edits that grow the tableau and run through
+SensitivityGrowBatch (lpr_sens_batch_create_grow); the committed record of that is
+profiles/sens_grow_bench.json:
+
+  S   the 8 x 14 base, 65536 candidate products: one add_activity per scenario
+  G   the 33 x 97 base, 4096 scripts: add_constraint (a cap on one variable), then change_rhs
+  H   the 257 x 769 base, 256 scripts: add_activity, then add_constraint
+
 Per workload: scenarios/s end to end (lpr_sens_batch_create, lpr_sens_batch_run, the bulk reads of
 outcomes / pivots / z / basicVars, closed by an engine sync) and for lpr_sens_batch_run alone
 (best of --repeat, after one warm-up pass); launches; pivots; the same scenarios one at a time
@@ -75,11 +83,46 @@ def gen_workload(orc, name: str, seed: int):
     return base, scripts
 
 
-def run_batch(pkg, eng, base_handle, scripts):
+def gen_grow_workload(orc, name: str, seed: int):
+    """(base, scripts): the base of gen_workload and `count` scripts that grow it."""
+    base, keep = gen_workload(orc, name, seed)
+    T, x, _, _ = base
+    R, C = T.shape
+    n = C - R
+    rng = np.random.RandomState(seed + 1)
+    made = [j for j in range(n) if x[j] > 1e-6] or list(range(n))  # the products in the plan
+
+    def activity(rows):
+        """A candidate product: a sparse-ish column and a cost near its shadow value, so that
+        some candidates enter the basis and some do not."""
+        a = rng.uniform(0.0, 1.0, size=rows - 1) * (rng.uniform(size=rows - 1) < 0.5)
+        y = T[0, n:n + R - 1]
+        worth = float(y @ a[:R - 1])
+        return ("add_activity", (worth * float(rng.uniform(0.6, 1.4)), a.tolist()))
+
+    def cap(q, cols):
+        """x_j <= 0.3 .. 1.3 of its value: most caps bite, some do not."""
+        tech = np.zeros(cols - 1)
+        j = made[q % len(made)]
+        tech[j] = 1.0
+        return ("add_constraint", (tech.tolist(), float(x[j]) * float(rng.uniform(0.3, 1.3))))
+
+    scripts = []
+    for q in range(len(keep)):
+        if name == "S":
+            scripts.append([activity(R)])
+        elif name == "G":
+            scripts.append([cap(q, C), keep[q][0]])
+        else:
+            scripts.append([activity(R), cap(q, C + 1)])
+    return base, scripts
+
+
+def run_batch(pkg, eng, base_handle, scripts, grow=False):
     """One end-to-end pass: (seconds end to end, seconds of the run, result, batch)."""
     eng.sync()
     t0 = time.perf_counter()
-    b = pkg.SensitivityBatch(base_handle, scripts)
+    b = (pkg.SensitivityGrowBatch if grow else pkg.SensitivityBatch)(base_handle, scripts)
     t1 = time.perf_counter()
     res = b.Run()
     t2 = time.perf_counter()
@@ -140,6 +183,9 @@ def main() -> int:
     ap.add_argument("--single-seconds", type=float, default=5.0)
     ap.add_argument("--oracle-seconds", type=float, default=5.0)
     ap.add_argument("--no-check", action="store_true", help="skip the bit check and the loops")
+    ap.add_argument("--grow", action="store_true",
+                    help="the growth workloads (add_activity / add_constraint) through "
+                         "SensitivityGrowBatch")
     ap.add_argument("--out", default=None,
                     help="also append the JSON lines to this file (the committed record is "
                          "profiles/sens_batch_bench.json; never pass it to a profiled run)")
@@ -153,17 +199,19 @@ def main() -> int:
     lines = []
     with pkg.Engine(0) as eng:
         for i, name in enumerate(args.workloads.split(",")):
-            base, scripts = gen_workload(orc, name, args.seed + i)
+            gen = gen_grow_workload if args.grow else gen_workload
+            base, scripts = gen(orc, name, args.seed + i)
             T, x, z, _ = base
             d = SensState.create(eng, T, x, z)
-            run_batch(pkg, eng, d, scripts)[3].destroy()  # warm-up
-            runs = [run_batch(pkg, eng, d, scripts) for _ in range(max(1, args.repeat))]
+            run_batch(pkg, eng, d, scripts, args.grow)[3].destroy()  # warm-up
+            runs = [run_batch(pkg, eng, d, scripts, args.grow)
+                    for _ in range(max(1, args.repeat))]
             best_e2e = min(r[0] for r in runs)
             best_run = min(r[1] for r in runs)
             res, batch = runs[-1][2], runs[-1][3]
             oc, pv = batch.outcome_arrays()
             count = len(scripts)
-            rec = dict(workload=name, scenarios=count, rows=int(T.shape[0]), cols=int(T.shape[1]),
+            rec = dict(workload=name + ("_grow" if args.grow else ""), scenarios=count, rows=int(T.shape[0]), cols=int(T.shape[1]),
                        edits=int(len(oc)), form={1: "G", 2: "H"}[res.form],
                        pivots=int(pv.sum()), launches=res.launches,
                        outcomes={str(int(c)): int((oc == c).sum()) for c in np.unique(oc)},
