@@ -126,7 +126,7 @@ typedef struct lpr_solve_opts {
                               chunks in flight).  0x50tr and 0x60tr named forms since retired and
                               are accepted as aliases of 0x30tr and 0x40tr (so 0x60tr with block > 8
                               now runs `block` pivots per sweep, where it used to cap them at 8).
-                              Bits 16..23, K-pivot paths: 0x10000 diagnostic time stamps of the loop
+                              Bits 16..24, K-pivot paths: 0x10000 diagnostic time stamps of the loop
                               heads, 0x20000 loop heads not confined to one XCD, 0x40000 confined
                               but hand-offs through the memory side, 0x80000 the sweep does not
                               leave the heads' XCD to them, 0x100000 it does so only once this
@@ -141,7 +141,9 @@ typedef struct lpr_solve_opts {
                               is faster than the events any more: opt-in only.
                               0x800000: every tile of the two-stream sweep non-temporal (by
                               default the tiles at both ends of its work queue keep the default
-                              cache policy). */
+                              cache policy).  0x1000000: no 64-row tiles at the head of that queue
+                              (by default the row tiles of its first half are handed out in pairs,
+                              so that a lane loads its pivot-row slices once per 64 rows). */
     int32_t block;         /* pivots decided ahead and applied per sweep of the tableau on large
                               tableaux: 0 auto (16), 1 one pivot per sweep, 2..16 that many.  The bits
                               stored are the same for every value (each element goes through the

@@ -920,7 +920,7 @@ int lpr_primal_solve(lpr_tableau* t, const lpr_solve_opts* opts, lpr_solve_resul
     lpr_solve_opts o;
     std::memset(&o, 0, sizeof o);
     if (opts) o = *opts;
-    const int hflags = (o.variant >> 16) & 255;  // loop-head placement / diagnostics (K-pivot paths)
+    const int hflags = (o.variant >> 16) & 511;  // loop-head placement / diagnostics (K-pivot paths)
     o.variant &= 0xffff;                       // path + tile
     // retired forms, kept as aliases: 0x50tr (the overlap in one launch) runs as the two-stream
     // overlap, 0x60tr (one launch per loop head, K <= 8) as heads-then-sweep

@@ -81,6 +81,11 @@ constexpr int kOvTileRows = LPR_OV_TILE_ROWS;  // rows per sweep workgroup (TR i
 #define LPR_OV_IC_MB 64
 #endif
 constexpr int kOvIcMB = LPR_OV_IC_MB;
+// share of the two-stream sweep's row tiles, from the head of its queue, handed out in pairs as
+// 64-row tiles (ov_tiles), in percent
+#ifndef LPR_OV_TALL_PCT
+#define LPR_OV_TALL_PCT 50
+#endif
 // ov_heads: the unit of a hand-off is the WAVE, not the workgroup -- every wave publishes its
 // own partial once its own stores have drained and collects all G x kOvWPG of them itself: no LDS
 // combine, no workgroup barrier in a head (false: one partial per workgroup, four barriers per head)
@@ -494,7 +499,6 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
     const int64_t log_cap = ci->log_cap;
     const double* __restrict__ Tin = B.Tb[ci->cur];
     const int ld2 = ld >> 1;
-    const int rhs = C - 1;
     const size_t slotP = (size_t)kOvMax * ld, slotF = (size_t)kOvMax * Rp;
     double* prowA = B.prow + (size_t)sa * slotP;
     double* fcolA = B.fcol + (size_t)sa * slotF;
@@ -522,10 +526,8 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
     // being swept, lane 16 + t what belongs to pivot t of this block.  One load per wave fetches a
     // whole operand vector; the chains run on registers and scalars only (no LDS, no barrier).
     const int lane = tid & (kWave - 1);
-    const int rAv = (lane < kb) ? ci->r[lane] : -1;                          // pivot rows, block A
-    const double parhsAv = (lane < kb) ? prowA[(size_t)lane * ld + rhs] : 0.0;  // p_t[rhs], block A
+    const int rAv = (lane < kb) ? ci->r[lane] : -1;  // pivot rows, block A
     int rNv = -1;            // lane t: pivot row of this block's pivot t
-    double prhsNv = 0.0;     // lane t: p_t[rhs] of this block's pivot t
     unsigned maskA = 0u, maskN = 0u;  // bit t: this lane's row is the pivot row of pivot t
 #pragma unroll
     for (int t = 0; t < kOvMax; ++t) {
@@ -768,10 +770,13 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
 
             // ---- row r after all earlier pivots, normalised (:199); next Z row; one trip ----
             // fv: lane t < kb: f_t[r] of the block being swept; lane 16 + t, t < q - 1: f_t[r] of
-            // this block; lane 32: T[r, rhs]; lane 33: the pivot element T[r, e]; lane 34: the Z
-            // row's factor T[0, e]; others +0.0.  The row's RHS entry goes through the same chain
-            // as the lane's own column pair (independent chains, interleaved by the scheduler), so
-            // p_q[rhs] needs neither a lane of its own nor a barrier.
+            // this block; lane 32: row r's RHS entry; lane 33: the pivot element T[r, e]; lane 34:
+            // the Z row's factor T[0, e]; others +0.0.  The RHS entry needs no chain of its own:
+            // T^(q-1)[r, rhs] is the RHS column after the pivots staged so far, entry r -- the very
+            // `myb` (or further-row entry) the ratio test of this head has just divided, taken
+            // through the same rounded steps in the same order.  Head q - 1 (or the launch / the
+            // prologue before) stored it to bvec before its Z partial was published, so it is
+            // visible to every wave that has collected this head's entering column.
             double2 w = have_c ? Tin2[(size_t)r * ld2 + c2_first] : make_double2(0.0, 0.0);
             double fv = 0.0;
             {
@@ -779,7 +784,7 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                 if (lane < kb) src = fcolA + (size_t)lane * Rp + r;
                 else if (lane >= kOvMax && lane - kOvMax < q - 1)
                     src = fcolN + (size_t)(lane - kOvMax) * Rp + r;
-                else if (lane == 32) src = Tin + (size_t)r * ld + rhs;
+                else if (lane == 32) src = bprev + r;
                 else if (lane == 33) src = colq + r;
                 else if (lane == 34) src = colq;
                 if (src) fv = xld(src);
@@ -788,7 +793,7 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                 __builtin_amdgcn_s_waitcnt(0);
                 OV_STAMP(q, 8);  // this wave's row gather has arrived
             }
-            double wr = ov_rl(fv, 32);
+            const double wr = ov_rl(fv, 32);  // T^(q-1)[r, rhs]
             const double p = ov_rl(fv, 33);   // the pivot element T[r, e] ...
             const double f0 = ov_rl(fv, 34);  // ... and the Z row's factor T[0, e]
             // r was the pivot row of earlier pivot t: bit t (wave-uniform)
@@ -800,50 +805,40 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                     const double f = ov_rl(fv, t);
                     const double px = f * pA[t].x;
                     const double py = f * pA[t].y;
-                    const double pr = f * ov_rl(parhsAv, t);
                     w.x = w.x - px;
                     w.y = w.y - py;
-                    wr = wr - pr;
                 }
 #pragma unroll
                 for (int t = 0; t < kOvMax; ++t) {  // through this block's earlier pivots
                     const double f = ov_rl(fv, kOvMax + t);
                     const double px = f * myp[t].x;
                     const double py = f * myp[t].y;
-                    const double pr = f * ov_rl(prhsNv, t);
                     w.x = w.x - px;
                     w.y = w.y - py;
-                    wr = wr - pr;
                 }
             } else {
 #pragma unroll
                 for (int t = 0; t < kOvMax; ++t) {
                     if ((ra >> t) & 1u) {
                         w = pA[t];
-                        wr = ov_rl(parhsAv, t);
                     } else {
                         const double f = ov_rl(fv, t);
                         const double px = f * pA[t].x;
                         const double py = f * pA[t].y;
-                        const double pr = f * ov_rl(parhsAv, t);
                         w.x = w.x - px;
                         w.y = w.y - py;
-                        wr = wr - pr;
                     }
                 }
 #pragma unroll
                 for (int t = 0; t < kOvMax; ++t) {
                     if ((rn >> t) & 1u) {
                         w = myp[t];
-                        wr = ov_rl(prhsNv, t);
                     } else {
                         const double f = ov_rl(fv, kOvMax + t);
                         const double px = f * myp[t].x;
                         const double py = f * myp[t].y;
-                        const double pr = f * ov_rl(prhsNv, t);
                         w.x = w.x - px;
                         w.y = w.y - py;
-                        wr = wr - pr;
                     }
                 }
             }
@@ -855,10 +850,7 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                 ieee_div_n<3>(dn, dd, dq);
             }
             const double prhs = dq[0];
-            if (lane == q - 1) {
-                prhsNv = prhs;
-                rNv = r;
-            }
+            if (lane == q - 1) rNv = r;
             if (have_i && i_first == r) maskN |= 1u << (q - 1);
             Cand n;
             n.v = 0.0;
@@ -1147,49 +1139,53 @@ __device__ __forceinline__ void ov_rows_store(const ov_v2d (&x)[TR], ov_v2d* dst
 // launch's heads have said where they are (B.hx) -- the heads then run as fast as with nothing
 // beside them.  Wrong or missing hints cost time, never correctness: any workgroup may take any
 // tile.  `static_tile` >= 0: one given tile (the in-place sweep runs alone and has no queue).
-// TROWS rows are processed; the row tiles are counted in units of `unit` rows (>= TROWS) and this
-// call takes the TROWS rows at offset `off` inside its unit (the half tiles of the sweep's tail)
-// POL (out of place only): bit 0 loads, bit 1 stores of the tile's rows with the default cache
-// policy instead of non-temporal (the ends of the queue, see ov_tiles)
-template <int TR, bool DB, bool INPLACE, int TROWS = kOvTileRows, int POL = 0>
-__device__ __forceinline__ void ov_one_tile(const OvBuffers& B, const OvCtl* ci,
-                                            const double* __restrict__ fc,
-                                            const ov_v2d* __restrict__ prow2, int tb, int ld,
-                                            int R, int Rp, int K, int cur, int unit = TROWS,
-                                            int off = 0) {
-    typedef ov_v2d v2d;
-    const int ld2 = ld >> 1;
-    const int nct = (ld2 + kOvNT - 1) / kOvNT;
-    const int nrt = (R + unit - 1) / unit;
+//
+// Tile `tb` of the queue (nct column strips x nrt row tiles) -> its column strip and row tile by
+// address; false: there is no such tile.  Odd sweeps walk the tableau the other way round.
+__device__ __forceinline__ bool ov_tile_at(const OvCtl* ci, int tb, int nct, int nrt, int* ct,
+                                           int* rt) {
     if (LPR_OV_DIAG & 16) {  // workgroup b sits on XCD b % 8: give each XCD consecutive tiles
         const int per = (nct * nrt + 7) / 8;
         tb = (tb % 8) * per + tb / 8;
     }
-    int ct = tb % nct, rt = tb / nct;
+    *ct = tb % nct;
+    *rt = tb / nct;
     if (LPR_OV_DIAG & 32) {
-        rt = tb % nrt;
-        ct = tb / nrt;
-        if (ct >= nct) return;
+        *rt = tb % nrt;
+        *ct = tb / nrt;
+        if (*ct >= nct) return false;
     }
-    if (rt >= nrt) return;
+    if (*rt >= nrt) return false;
     if ((ci->sweep & 1) && !(LPR_OV_DIAG & 512)) {
-        ct = nct - 1 - ct;
-        rt = nrt - 1 - rt;
+        *ct = nct - 1 - *ct;
+        *rt = nrt - 1 - *rt;
     }
-    const int c2 = ct * kOvNT + threadIdx.x;
-    if (c2 >= ld2) return;
+    return true;
+}
+
+// this lane's slice of the normalised pivot rows, for a whole tile: all kOvMax loads in flight
+// at once (rows >= K of the staging slot are stale but valid memory; they are not used)
+__device__ __forceinline__ void ov_load_slices(ov_v2d (&p)[kOvMax],
+                                               const ov_v2d* __restrict__ prow2, int ld2, int c2) {
+#pragma unroll
+    for (int s = 0; s < kOvMax; ++s) {
+        if (LPR_OV_DIAG & 2) p[s] = ov_v2d{(double)c2, (double)s};
+        else p[s] = prow2[(size_t)s * ld2 + c2];
+    }
+}
+
+// Rows [ibase, ibase + TROWS) of column pair c2 (at most: the tableau may end first).
+// POL (out of place only): bit 0 loads, bit 1 stores of these rows with the default cache policy
+// instead of non-temporal (the ends of the queue, see ov_tiles)
+template <int TR, bool DB, bool INPLACE, int TROWS, int POL>
+__device__ __forceinline__ void ov_tile_rows(const OvBuffers& B, const OvCtl* ci,
+                                             const double* __restrict__ fc,
+                                             const ov_v2d (&p)[kOvMax], int c2, int ibase, int ld2,
+                                             int R, int Rp, int K, int cur) {
+    typedef ov_v2d v2d;
     // in place every element is read and written by the same lane; out of place the buffers differ
     const v2d* Tin2 = reinterpret_cast<const v2d*>(B.Tb[cur]);
     v2d* Tout2 = reinterpret_cast<v2d*>(B.Tb[INPLACE ? cur : (cur ^ 1)]);
-    // this lane's slice of the normalised pivot rows, for the whole tile: all kOvMax loads in
-    // flight at once (rows >= K of the staging slot are stale but valid memory; they are not used)
-    v2d p[kOvMax];
-#pragma unroll
-    for (int s = 0; s < kOvMax; ++s) {
-        if (LPR_OV_DIAG & 2) p[s] = v2d{(double)c2, (double)s};
-        else p[s] = prow2[(size_t)s * ld2 + c2];
-    }
-    const int ibase = rt * unit + off;
     const int iend = min(R, ibase + TROWS);
     if (ibase >= R) return;
 
@@ -1296,14 +1292,36 @@ __device__ __forceinline__ void ov_one_tile(const OvBuffers& B, const OvCtl* ci,
     }
 }
 
+// One tile of TROWS rows: the row tiles are counted in units of `unit` rows (>= TROWS) and this
+// call takes the TROWS rows at offset `off` inside its unit (the half tiles of the sweep's tail)
+template <int TR, bool DB, bool INPLACE, int TROWS = kOvTileRows, int POL = 0>
+__device__ __forceinline__ void ov_one_tile(const OvBuffers& B, const OvCtl* ci,
+                                            const double* __restrict__ fc,
+                                            const ov_v2d* __restrict__ prow2, int tb, int ld,
+                                            int R, int Rp, int K, int cur, int unit = TROWS,
+                                            int off = 0) {
+    const int ld2 = ld >> 1;
+    int ct, rt;
+    if (!ov_tile_at(ci, tb, (ld2 + kOvNT - 1) / kOvNT, (R + unit - 1) / unit, &ct, &rt)) return;
+    const int c2 = ct * kOvNT + threadIdx.x;
+    if (c2 >= ld2) return;
+    ov_v2d p[kOvMax];
+    ov_load_slices(p, prow2, ld2, c2);
+    ov_tile_rows<TR, DB, INPLACE, TROWS, POL>(B, ci, fc, p, c2, rt * unit + off, ld2, R, Rp, K,
+                                              cur);
+}
+
 // avoid: 0 = never leave an XCD to the heads, 1 = live word only (B.hx), 2 = hint + live word
+// tall_pairs: pairs of row tiles at the head of the queue that are handed out as ONE tile of
+// 2 x TROWS rows each (same 256 lanes, same column strip): a lane loads its pivot-row slices once
+// for both halves -- 64 KB of L2 hits per 128 KB of tableau otherwise
 template <int TR, bool DB, bool INPLACE, int TROWS = kOvTileRows>
 __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __restrict__ fcol,
                                          const double* __restrict__ prow, int ld, int R, int Rp,
                                          int lp, int static_tile, int avoid,
                                          bool write_ctl = true, int sweeps_done = -1,
                                          int wait_heads = -1, int hint_xcc = -1,
-                                         int ic_tiles = 0) {
+                                         int ic_tiles = 0, int tall_pairs = 0) {
     static_assert(TROWS % TR == 0 && (!DB || TROWS % (2 * TR) == 0) && TROWS <= 64,
                   "tile rows: a multiple of the chunks in flight, and one bit each in prmask");
     __shared__ int s_tile;
@@ -1400,16 +1418,25 @@ __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __res
         return;
     }
     const int ld2 = ld >> 1;
-    const int ntiles = ((ld2 + kOvNT - 1) / kOvNT) * ((R + TROWS - 1) / TROWS);
+    const int nct = (ld2 + kOvNT - 1) / kOvNT, nrt = (R + TROWS - 1) / TROWS;
+    const int ntiles = nct * nrt;
     // The workgroups finish their last tiles at different times and the chip drains: the last
     // quarter of the queue is handed out as HALF tiles (a pivot-row slice load per 16 rows instead
     // of 32 there, a shorter tail: 64-row tiles everywhere measured 181 us, 32-row 174, 16-row 172).
+    // The head of the queue, where nothing drains, is handed out as TALL tiles (tall_pairs pairs of
+    // row tiles, by queue position: on odd sweeps they are the last rows of the tableau, and the
+    // ragged last row tile is half of the first pair); full tiles in between.
     constexpr bool kHalfTail = (TROWS / 2) % TR == 0 && TROWS == kOvTileRows && (LPR_OV_DIAG & 256) == 0;
 #ifndef LPR_OV_TAIL_DIV
 #define LPR_OV_TAIL_DIV 4
 #endif
     const int tsplit = kHalfTail ? (ntiles - ntiles / LPR_OV_TAIL_DIV) : ntiles;
-    const int qtiles = tsplit + 2 * (ntiles - tsplit);
+    // (tiles taken in another order than row-major do not pair: LPR_OV_DIAG 16 / 32)
+    const int npairs =
+        (kHalfTail && !(LPR_OV_DIAG & (16 | 32))) ? min(tall_pairs, tsplit / (2 * nct)) : 0;
+    const int ntall = npairs * nct;   // queue entries [0, ntall): tall tiles,
+    const int qsplit = tsplit - ntall;  // [ntall, qsplit): full tiles, [qsplit, qtiles): half tiles
+    const int qtiles = qsplit + 2 * (ntiles - tsplit);
     // do loop heads that stage a block run beside this launch, and where?
     const bool heads_beside = !INPLACE && avoid > 0 && ci->status == kRunning &&
                               ci->pending == kRunning;
@@ -1434,22 +1461,39 @@ __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __res
         const int tile = s_tile;
         __syncthreads();
         if (tile >= qtiles) return;
-        // position in the queue, in full tiles: its first / last ic_tiles keep the default cache
-        // policy for their loads / stores (the previous sweep went the other way round, so the
-        // first tiles read here are the last ones it wrote)
-        const int at = tile < tsplit ? tile : tsplit + ((tile - tsplit) >> 1);
-        const int pol = (at < ic_tiles ? 1 : 0) | (at >= ntiles - ic_tiles ? 2 : 0);
-        if (tile < tsplit) {
-#define LPR_OV_FULL(P) ov_one_tile<TR, DB, INPLACE, TROWS, P>(B, ci, fc, prow2, tile, ld, R, Rp, K, cur)
-            switch (pol) {
-                case 1: LPR_OV_FULL(1); break;
-                case 2: LPR_OV_FULL(2); break;
-                case 3: LPR_OV_FULL(3); break;
-                default: LPR_OV_FULL(0); break;
-            }
+        // position in the queue, in full tiles (`at`): its first / last ic_tiles keep the default
+        // cache policy for their loads / stores (the previous sweep went the other way round, so
+        // the first tiles read here are the last ones it wrote)
+        if (tile < qsplit) {
+            // a tall tile is the full tiles `at` and `at + nct` (the same column strip, the next
+            // row tile): one load of the slices, then each half as the full tile it is, with its
+            // own cache policy, pivot rows and ragged end
+            const int halves = tile < ntall ? 2 : 1;
+            int at = tile < ntall ? (tile / nct) * 2 * nct + tile % nct : tile + ntall;
+            int ct, rt;
+            if (ov_tile_at(ci, at, nct, nrt, &ct, &rt) && ct * kOvNT + (int)threadIdx.x < ld2) {
+                const int c2 = ct * kOvNT + threadIdx.x;
+                ov_v2d p[kOvMax];
+                ov_load_slices(p, prow2, ld2, c2);
+#pragma unroll 1
+                for (int h = 0; h < halves; ++h, at += nct) {
+                    if (h) ov_tile_at(ci, at, nct, nrt, &ct, &rt);
+                    const int pol = (at < ic_tiles ? 1 : 0) | (at >= ntiles - ic_tiles ? 2 : 0);
+#define LPR_OV_FULL(P) \
+    ov_tile_rows<TR, DB, INPLACE, TROWS, P>(B, ci, fc, p, c2, rt * TROWS, ld2, R, Rp, K, cur)
+                    switch (pol) {
+                        case 1: LPR_OV_FULL(1); break;
+                        case 2: LPR_OV_FULL(2); break;
+                        case 3: LPR_OV_FULL(3); break;
+                        default: LPR_OV_FULL(0); break;
+                    }
 #undef LPR_OV_FULL
+                }
+            }
         } else {  // the tail of the queue: half tiles
-            const int u = tile - tsplit;
+            const int u = tile - qsplit;
+            const int at = tsplit + (u >> 1);
+            const int pol = (at < ic_tiles ? 1 : 0) | (at >= ntiles - ic_tiles ? 2 : 0);
 #define LPR_OV_HALF(P)                                                                             \
     ov_one_tile<TR, false, INPLACE, TROWS / 2, P>(B, ci, fc, prow2, tsplit + (u >> 1), ld, R, Rp, \
                                                   K, cur, TROWS, (u & 1) * (TROWS / 2))
@@ -1479,11 +1523,12 @@ __global__ __launch_bounds__(kOvNT) void k_ov2_sweep(const OvBuffers B,
                                                      const double* __restrict__ prow_ro, int ld,
                                                      int R, int Rp, int lp, int avoid,
                                                      int write_ctl, int sweeps_done,
-                                                     int wait_heads, int hint_xcc, int ic_tiles) {
+                                                     int wait_heads, int hint_xcc, int ic_tiles,
+                                                     int tall_pairs) {
     // fcol_ro / prow_ro alias B.fcol / B.prow, which the heads beside this launch write -- but only
     // the OTHER staging slot (ci->slot ^ 1) than the one the tiles read, so the read-only view holds
     ov_tiles<TR, DB, false>(B, fcol_ro, prow_ro, ld, R, Rp, lp, -1, avoid, write_ctl != 0,
-                            sweeps_done, wait_heads, hint_xcc, ic_tiles);
+                            sweeps_done, wait_heads, hint_xcc, ic_tiles, tall_pairs);
 }
 
 // The same two halves as separate launches: all K loop heads of a block in ONE persistent launch
@@ -1816,11 +1861,14 @@ int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t
     // none, every tile non-temporal (the form before)
     const int ic_tiles =
         (flags & 128) ? 0 : (int)(((size_t)kOvIcMB << 20) / ((size_t)kOvTileRows * kOvNT * 16));
+    // 64-row tiles at the head of the queue: the row-tile pairs of its first half (by address
+    // on even sweeps); flags 256: none, the queue before (full tiles, then half tiles)
+    const int tall_pairs = (flags & 256) ? 0 : nrt * LPR_OV_TALL_PCT / 200;
 #define LPR_OV2_SWEEP(TR, DB)                                                                     \
     hipExtLaunchKernelGGL((k_ov2_sweep<TR, DB>), grid, blk, 0, S, ev_start, sweep_done, 0, c->b,   \
                           c->b.fcol, c->b.prow, t->ld, t->rows, c->Rp, lp, avoid, by_event ? 1 : 0, \
                           by_event ? -1 : c->steps, sweep_dev ? c->steps : -1, c->head_xcc_hint,    \
-                          ic_tiles)
+                          ic_tiles, tall_pairs)
     switch (ov_tile_code(tr)) {
         case 0x04: LPR_OV2_SWEEP(4, false); break;
         case 0x10: LPR_OV2_SWEEP(16, false); break;

@@ -5,7 +5,8 @@
 //         -DLPR_OV_DIAG=<bits> -I lpr_381_group_v22_amd/csrc -I include tools/sweep_bench.hip -o ...
 // usage: sweep_bench [reps] [wgs_per_cu] [leave_xcc (-1: none)] [tile code 4|8|16|0x24|0x28]
 //                    [R] [C] [mode] [ic_mb: MB at each end of the queue with default-policy
-//                    loads / stores, 0: all non-temporal]
+//                    loads / stores, 0: all non-temporal] [tall_pct: percent of the row tiles, from
+//                    the head of the queue, handed out in pairs as 64-row tiles; default 0: none]
 // prints one JSON line: average / min launch time by HIP events, GB/s of 2*8*R*ld.
 #include "overlap_kernels.hip"
 
@@ -69,6 +70,7 @@ int main(int argc, char** argv) {
     const int mode = argc > 7 ? std::atoi(argv[7]) : 0;  // 1: linear copy kernel, 2: hipMemcpyDtoD
     const int ic_mb = argc > 8 ? std::atoi(argv[8]) : 0;
     const int ic_tiles = (int)(((size_t)ic_mb << 20) / ((size_t)kOvTileRows * kOvNT * 16));
+    const int tall_pct = argc > 9 ? std::atoi(argv[9]) : 0;
     const int ld = (C + 15) / 16 * 16, Rp = (R + 15) / 16 * 16;
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, 0));
@@ -109,6 +111,7 @@ int main(int argc, char** argv) {
 
     const int nct = (ld / 2 + kOvNT - 1) / kOvNT, nrt = (R + kOvTileRows - 1) / kOvTileRows;
     const int ntiles = nct * nrt;
+    const int tall_pairs = nrt * tall_pct / 200;
     const int cap = wgs_per_cu * cus;
     const dim3 grid(wgs_per_cu > 0 && ntiles > cap ? cap : ntiles), blk(kOvNT);
     const int avoid = leave >= 0 ? 2 : 0;
@@ -130,7 +133,7 @@ int main(int argc, char** argv) {
         }
 #define SW(TR, DB)                                                                               \
     hipLaunchKernelGGL((k_ov2_sweep<TR, DB>), grid, blk, 0, S, b, b.fcol, b.prow, ld, R, Rp, lp, \
-                       avoid, 1, -1, -1, -1, ic_tiles)
+                       avoid, 1, -1, -1, -1, ic_tiles, tall_pairs)
         switch (tile) {
             case 0x04: SW(4, false); break;
             case 0x10: SW(16, false); break;
