@@ -28,7 +28,9 @@ struct CutState {
     int32_t pr, pc;      // pivot (tableau row, column) of the pending update
     int32_t print_steps; // `iter` only advances when printSteps is set (DualSimplex.cs:94)
     int32_t pending;     // a pivot has been staged/applied and not yet counted
-    int32_t pad;
+    int32_t nan_updates; // the staged pivot is PrimalSimplexSolver2's: it skips a row on `|f| <= EPS`
+                         // (:160), so a NaN factor updates its row; the other two pivots update on
+                         // `|f| > EPS` (DualSimplex.cs:166, CuttingPlaneSolver.cs:161), so it does not
     int64_t iter;        // the C# `iter`
     int64_t done;        // pivots performed
     int64_t max_iters;   // maxIters (:108 / :90)
@@ -155,6 +157,7 @@ __global__ __launch_bounds__(1024) void k_cut_select(double* __restrict__ T, int
     if (tid == 0) {
         st->pr = pr;
         st->pc = pc;
+        st->nan_updates = (mode == kCutPrimal2);
         st->pending = 1;  // closed by the next k_cut_select
         if (st->print_steps) st->iter += 1;  // ++iter inside `if (printSteps)` (:94 / :75)
         if (st->log_n < st->log_cap) {
@@ -168,7 +171,8 @@ __global__ __launch_bounds__(1024) void k_cut_select(double* __restrict__ T, int
 }
 
 // Pivot with the row skip (DualSimplex.cs:150-178, PrimalSimplexSolver2.cs:145-164): row i is
-// rewritten only if |f_i| > EPS.  No state is written here: the bookkeeping lives in k_cut_select.
+// rewritten only if |f_i| > EPS; a NaN f_i rewrites its row in PrimalSimplexSolver2's form alone
+// (`if (|f| <= EPS) continue`), st->nan_updates.  No state is written here: the bookkeeping lives in k_cut_select.
 template <int TR>
 __global__ __launch_bounds__(256) void k_cut_update(double* __restrict__ T, int ld, int R,
                                                     const double* __restrict__ rowbuf,
@@ -179,6 +183,7 @@ __global__ __launch_bounds__(256) void k_cut_update(double* __restrict__ T, int 
     const int c2 = blockIdx.x * blockDim.x + threadIdx.x;
     const int i0 = blockIdx.y * TR;
     const int r = st->pr;
+    const bool nan_updates = st->nan_updates != 0;
     if (c2 >= ld2) return;
     const double2 pr2 = reinterpret_cast<const double2*>(rowbuf)[c2];
     double2* __restrict__ T2 = reinterpret_cast<double2*>(T);
@@ -191,7 +196,7 @@ __global__ __launch_bounds__(256) void k_cut_update(double* __restrict__ T, int 
             continue;
         }
         const double f = colbuf[i];
-        if (!(fabs(f) > kCutEps)) continue;  // the row is not touched
+        if (nan_updates ? (fabs(f) <= kCutEps) : !(fabs(f) > kCutEps)) continue;  // not touched
         double2 x = T2[(size_t)i * ld2 + c2];
         const double px = f * pr2.x;
         const double py = f * pr2.y;
@@ -262,6 +267,7 @@ __global__ __launch_bounds__(1024) void k_cut_add(double* __restrict__ T, int ld
     for (int i = tid; i < R + 1; i += nt) colbuf[i] = T[(size_t)i * ld + pc];
     if (tid == 0) {
         st->pr = R;
+        st->nan_updates = 0;
         st->pc = pc;
         if (st->log_n < st->log_cap) {
             int32_t* e = log + 3 * st->log_n;

@@ -51,7 +51,7 @@ static void cl_push(CutLog* l, int kind, int row, int col) {
 
 /* Pivot with the |f| <= EPS row skip: DualSimplex.cs:150-178, PrimalSimplexSolver2.cs:145-164,
  * CuttingPlaneSolver.cs:145-176.  pr is a TABLEAU row.  Returns 0 or CUT_PIVOT_TOO_SMALL. */
-static int pivot_skip(double* T, int R, int C, int pr, int pc) {
+static int pivot_skip(double* T, int R, int C, int pr, int pc, int nan_updates) {
     double* prow = T + (size_t)pr * C;
     double piv = prow[pc];
     if (fabs(piv) <= EPS) return CUT_PIVOT_TOO_SMALL;
@@ -62,7 +62,9 @@ static int pivot_skip(double* T, int R, int C, int pr, int pc) {
         if (i == pr) continue;
         double* row = T + (size_t)i * C;
         double f = row[pc];
-        if (fabs(f) > EPS)
+        /* DualSimplex.cs:166 and CuttingPlaneSolver.cs:161 update on `|f| > EPS`;
+         * PrimalSimplexSolver2.cs:160 skips on `|f| <= EPS`: only there a NaN factor updates */
+        if (nan_updates ? !(fabs(f) <= EPS) : (fabs(f) > EPS))
             for (int j = 0; j < C; j++) {
                 double prod = f * prow[j];
                 row[j] = row[j] - prod;
@@ -109,7 +111,7 @@ static int dual_solve(double* T, int R, int C, int max_iters, int print_steps, i
         if (hard_cap > 0 && done >= hard_cap) { if (pivots) *pivots = done; return CUT_LIMIT; }
         if (print_steps) ++iter; /* :94 */
         cl_push(log, 0, pivotRow, pivotCol);
-        int rc = pivot_skip(T, R, C, pivotRow + 1, pivotCol); /* :98 */
+        int rc = pivot_skip(T, R, C, pivotRow + 1, pivotCol, 0); /* :98 */
         if (rc) { if (pivots) *pivots = done; return rc; }
         done++;
         if (iter >= max_iters) { if (pivots) *pivots = done; return CUT_LIMIT; } /* :108-112 */
@@ -153,7 +155,7 @@ static int primal2_solve(double* T, int R, int C, int max_iters, int print_steps
         if (hard_cap > 0 && done >= hard_cap) { if (pivots) *pivots = done; return CUT_LIMIT; }
         if (print_steps) ++iter; /* :75 */
         cl_push(log, 1, bestRow, pivotCol);
-        int rc = pivot_skip(T, R, C, bestRow, pivotCol); /* :79 */
+        int rc = pivot_skip(T, R, C, bestRow, pivotCol, 1); /* :79 */
         if (rc) { if (pivots) *pivots = done; return rc; }
         done++;
         if (iter >= max_iters) { if (pivots) *pivots = done; return CUT_LIMIT; } /* :90-95 */
@@ -239,7 +241,7 @@ int orc_cutting_plane(double* T, int* R_io, int R_cap, int C, int max_cuts, int6
         /* 7) pivot on the cut */
         if (fabs(AT(T, C, cutRow, pivotCol)) <= EPS) { exitc = 3; break; }
         cl_push(&l, 2, cutRow - 1, pivotCol);
-        pivot_skip(T, R, C, cutRow, pivotCol);
+        pivot_skip(T, R, C, cutRow, pivotCol, 0);
         /* 8) clean-up */
         int needDual = 0, needPrimal = 0;
         for (int i = 1; i < R; i++) if (AT(T, C, i, C - 1) < -EPS) { needDual = 1; break; }

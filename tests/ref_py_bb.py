@@ -39,6 +39,16 @@ def round4(x: float) -> float:
     return x
 
 
+def floor_total(x: float) -> float:
+    """Math.Floor (:837, :871): +-inf and NaN come back unchanged (math.floor raises on them)."""
+    return x if x != x or x in (INF, -INF) else float(math.floor(x))
+
+
+def ceil_total(x: float) -> float:
+    """Math.Ceiling (:870), the same for +-inf and NaN."""
+    return x if x != x or x in (INF, -INF) else float(math.ceil(x))
+
+
 def _div(a: float, b: float) -> float:
     try:
         return a / b
@@ -299,15 +309,15 @@ class BranchAndBound:
             minDist = INF
             for i, v in enumerate(vals):
                 if not self.IsInteger(v):
-                    d = abs((v - math.floor(v)) - 0.5)
+                    d = abs((v - floor_total(v)) - 0.5)
                     if d < minDist:
                         minDist = d
                         best = i
                         bestValue = v
             if best == -1:
                 continue
-            upperInt = to_int32(math.ceil(bestValue))
-            lowerInt = to_int32(math.floor(bestValue))
+            upperInt = to_int32(ceil_total(bestValue))
+            lowerInt = to_int32(floor_total(bestValue))
             kids = []
             for side, (bound, typ) in enumerate(((lowerInt, 0), (upperInt, 1))):
                 con = [1.0 if i == best else 0.0 for i in range(self.nvars)] + [float(bound),

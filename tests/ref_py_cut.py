@@ -138,7 +138,8 @@ def primal2_solve(obj, rows, max_iters=10_000, print_steps=False, log=None, hard
 
 
 def _frac(a):  # CuttingPlaneSolver.cs:12-17
-    f = a - math.floor(a)
+    # Math.Floor hands +-inf and NaN back unchanged (math.floor raises): inf - inf = NaN
+    f = a - (a if a != a or a in (INF, -INF) else math.floor(a))
     if abs(f) < EPS or abs(1 - f) < EPS:
         return 0.0
     return f
@@ -195,7 +196,8 @@ def cutting_plane(obj, rows, max_cuts=64, log=None, hard_cap=0):
                 primal2_solve(obj, rows, print_steps=True, log=log, hard_cap=hard_cap)
         except PivotTooSmall:
             return 7, cuts
-        if all(obj[j] >= -EPS for j in range(n - 1)) and not any(r[-1] < -EPS for r in rows):
+        # IsObjectiveOptimal (:19-25) returns false on `obj[j] < -EPS`: a NaN cost does not object
+        if not any(obj[j] < -EPS for j in range(n - 1)) and not any(r[-1] < -EPS for r in rows):
             if any(_frac(r[-1]) > EPS for r in rows):
                 continue
             return 0, cuts

@@ -43,7 +43,8 @@ class PySens:
         return len(self.t[0])
 
     def _is_pivot_col(self, prow, col):  # :79-84
-        return all(i == prow or abs(self.t[i][col]) <= EPS for i in range(1, self.R))
+        # `if (i != pivotRow && Math.Abs(...) > EPS) return false`: a NaN entry does not object
+        return all(i == prow or not abs(self.t[i][col]) > EPS for i in range(1, self.R))
 
     def _basic_row(self, col):  # :69-77
         for i in range(1, self.R):
