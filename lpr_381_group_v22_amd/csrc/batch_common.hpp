@@ -1,13 +1,19 @@
 // batch_common.hpp -- definitions shared by the batched primal simplex (batch_engine.hip, host)
-// and its kernels (batch_kernels.hip).  Not part of the ABI (include/lpr_engine.h is).
+// and its kernels (batch_kernels.hip), and what the three batch engines (LP, B&B: bb_batch_*,
+// scenarios: sens_batch_*) have in common on the host: the forms and the rule that picks one, the
+// running-list driver, the dynamic-LDS attribute and the handle plumbing.  The device side of what
+// they share is batch_device.hpp.  Not part of the ABI (include/lpr_engine.h is).
 #pragma once
 
 #include "engine_common.hpp"
 
+#include <utility>
+
 namespace lpr {
 
-// Forms of one LP in a batch.  The host picks one per LP by its LDS
-// footprint, (rows * cols + rows) doubles: the tableau, compact, and the staged factor column.
+// Forms of one item (LP, IP, scenario batch) in a batch.  The host picks
+// one per item by its LDS footprint; for an LP that is (rows * cols + rows) doubles: the tableau,
+// compact, and the staged factor column.
 enum BatchForm : int { kFormW = 0, kFormG = 1, kFormH = 2, kNumForms = 3 };
 
 // Every workgroup keeps kBatchWgScratch bytes of LDS for itself (the reduction slots).
@@ -25,6 +31,7 @@ constexpr int kBatchMaxColsH = 2048;
 // Pivots per LP per launch, by form: a launch stays within a few milliseconds, and no launch runs
 // without a bound, even on an LP that cycles.
 constexpr int kBatchChunk[kNumForms] = {256, 128, 16};
+static_assert(sizeof(kBatchChunk) / sizeof(int) == kNumForms, "one chunk per form");
 // Pivot-log pairs kept per LP when the caller passes log_cap = 0: 4 * (rows + cols), at most 4096.
 constexpr int kBatchLogDefaultMax = 4096;
 
@@ -55,4 +62,128 @@ inline size_t batch_footprint(int rows, int cols) {  // doubles of LDS one LP ne
     return (size_t)rows * cols + rows;
 }
 
+// The form of one item by the bytes of LDS it needs: the smallest that holds it, or the forced
+// one (opts.variant 1/2/3) if the item fits it.  allow_w = false: the engine builds no form W.
+inline int batch_pick_form(size_t bytes, int variant, bool allow_w = true) {
+    const bool fitW = allow_w && bytes <= kBatchMaxLdsW, fitG = bytes <= kBatchMaxLdsG;
+    if (variant == 1 && fitW) return kFormW;
+    if (variant == 2 && fitG) return kFormG;
+    if (variant == 3) return kFormH;
+    return fitW ? kFormW : (fitG ? kFormG : kFormH);
+}
+
+// hipMalloc of `elems` elements into *p unless an earlier one has failed (*rc); on failure *p is
+// null and *rc is what oom(what, elems) returns after it has set the message.
+template <class T, class Oom>
+void dev_alloc(T** p, int64_t elems, const char* what, int* rc, Oom oom) {
+    if (*rc != LPR_OK_OPTIMAL) return;
+    if (hipMalloc(reinterpret_cast<void**>(p), (size_t)elems * sizeof(T)) != hipSuccess) {
+        *p = nullptr;
+        (void)hipGetLastError();
+        *rc = oom(what, elems);
+    }
+}
+
+// The running lists of a batch and the launch rounds over them.  The items still running are
+// listed per form, one contiguous range per form in the `in` half of idx.  A round zeroes the
+// counters, launches one bounded kernel per non-empty form (W, G, H) -- an item that is still
+// running when its chunk is used up appends itself to the `out` range of its form and counts
+// itself -- reads the counters into pinned memory, synchronises and swaps in and out.  The rounds
+// end when no item is left.
+struct BatchRunLists {
+    int32_t* idx = nullptr;         // 2 x count: the running lists, in and out, per form
+    int32_t* counters = nullptr;    // kNumForms running counts (device)
+    int32_t* h_counters = nullptr;  // pinned
+    int32_t count = 0;
+    int32_t off[kNumForms] = {0, 0, 0}, live[kNumForms] = {0, 0, 0};
+
+    template <class Oom>
+    void alloc(int32_t n, int* rc, Oom oom) {
+        count = n;
+        dev_alloc(&idx, 2 * (int64_t)n, "running lists", rc, oom);
+        dev_alloc(&counters, kNumForms, "counters", rc, oom);
+        if (*rc == LPR_OK_OPTIMAL &&
+            hipHostMalloc(&h_counters, kNumForms * sizeof(int32_t)) != hipSuccess)
+            *rc = oom("counters", kNumForms);
+    }
+    void release() {
+        hipFree(idx);
+        hipFree(counters);
+        if (h_counters) hipHostFree(h_counters);
+        idx = counters = h_counters = nullptr;
+    }
+    // The host lists into the `in` half.  The engine uploads its descriptors after this.
+    int upload(hipStream_t s, const std::vector<int32_t> (&lists)[kNumForms]) {
+        for (int f = 0, at = 0; f < kNumForms; ++f) {
+            off[f] = at;
+            live[f] = (int32_t)lists[f].size();
+            if (live[f] > 0)
+                LPR_HIP(hipMemcpyAsync(idx + at, lists[f].data(), (size_t)live[f] * sizeof(int32_t),
+                                       hipMemcpyHostToDevice, s));
+            at += live[f];
+        }
+        return LPR_OK_OPTIMAL;
+    }
+    // The rounds.  launch is int(int form, const int32_t* in, int n_in, int32_t* out,
+    // int32_t* n_out); a launch that fails ends the rounds with its code.
+    template <class Launch>
+    int rounds(hipStream_t s, Launch launch, int* launches) {
+        int32_t* in = idx;
+        int32_t* out = idx + count;
+        while (live[kFormW] + live[kFormG] + live[kFormH] > 0) {
+            LPR_HIP(hipMemsetAsync(counters, 0, kNumForms * sizeof(int32_t), s));
+            for (int f = 0; f < kNumForms; ++f) {
+                if (live[f] == 0) continue;
+                const int rc = launch(f, in + off[f], live[f], out + off[f], counters + f);
+                if (rc != LPR_OK_OPTIMAL) return rc;
+                ++*launches;
+            }
+            LPR_HIP(hipMemcpyAsync(h_counters, counters, kNumForms * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, s));
+            LPR_HIP(hipStreamSynchronize(s));
+            for (int f = 0; f < kNumForms; ++f) live[f] = h_counters[f];
+            std::swap(in, out);
+        }
+        return LPR_OK_OPTIMAL;
+    }
+};
+
+// Dynamic LDS above 64 KiB needs the attribute once per kernel and device; *mask keeps one bit
+// per device for one kernel instantiation.
+inline int raise_dynamic_lds(const void* fn, size_t bytes, unsigned long long* mask) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LPR_DEVICE_ERROR;
+    const unsigned long long bit = 1ull << dev;
+    if (__atomic_load_n(mask, __ATOMIC_ACQUIRE) & bit) return LPR_OK_OPTIMAL;
+    const hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)bytes);
+    if (err != hipSuccess) {
+        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed: %s", bytes,
+                  hipGetErrorString(err));
+        return LPR_DEVICE_ERROR;
+    }
+    __atomic_fetch_or(mask, bit, __ATOMIC_ACQ_REL);
+    return LPR_OK_OPTIMAL;
+}
+
+// A batch handle leaves its engine's list of live ones (the *_destroy calls).
+template <class H>
+void unlist(std::vector<H*>& live, H* h) {
+    for (size_t q = 0; q < live.size(); ++q)
+        if (live[q] == h) {
+            live.erase(live.begin() + q);
+            break;
+        }
+}
+
 }  // namespace lpr
+
+// Entry check of every call on a batch handle; noun names the kind of batch in the message.
+#define LPR_LIVE_HANDLE(b, noun)                                                            \
+    do {                                                                                    \
+        if (!(b) || !(b)->eng) {                                                            \
+            ::lpr::set_error(noun " handle is null or orphaned: its engine has been closed"); \
+            return LPR_BAD_ARGUMENT;                                                        \
+        }                                                                                   \
+        LPR_HIP(hipSetDevice((b)->eng->device));                                            \
+    } while (0)

@@ -1,7 +1,8 @@
 // batch_engine.hip -- host side of the batched primal simplex (include/lpr_engine.h, lpr_batch_*;
 // DESIGN.md section 12).  Every LP of a batch is solved on the device with the rules of
 // PrimalSimplexSolver; the host only picks each LP's form, relaunches the bounded solve kernels
-// while LPs are still running (one small counter read per launch round) and copies results out.
+// while LPs are still running (BatchRunLists: one small counter read per launch round) and copies
+// results out.
 #include "batch_common.hpp"
 
 #include <algorithm>
@@ -29,9 +30,7 @@ struct lpr_batch {
     double* slab = nullptr;         // every tableau, packed rows x cols row-major
     int32_t* basis = nullptr;       // packed by rows - 1
     int32_t* logs = nullptr;        // packed by log_cap pairs
-    int32_t* idx = nullptr;         // 2 x count: the running lists, in and out, per form
-    int32_t* counters = nullptr;    // kNumForms running counts (device)
-    int32_t* h_counters = nullptr;  // pinned
+    BatchRunLists run;              // the running lists and their counters
     double* xz = nullptr;           // extract output: x (x_total) then z (count), lazy
     int64_t slab_n = 0, basis_n = 0, log_n = 0, x_total = 0;
 };
@@ -48,18 +47,13 @@ void batch_release_device(lpr_batch* b) {
     hipFree(b->slab);
     hipFree(b->basis);
     hipFree(b->logs);
-    hipFree(b->idx);
-    hipFree(b->counters);
     hipFree(b->xz);
-    if (b->h_counters) hipHostFree(b->h_counters);
+    b->run.release();
     b->desc = nullptr;
     b->slab = nullptr;
     b->basis = nullptr;
     b->logs = nullptr;
-    b->idx = nullptr;
-    b->counters = nullptr;
     b->xz = nullptr;
-    b->h_counters = nullptr;
 }
 
 // Shapes within form H (rows <= kBatchMaxRowsH, cols <= kBatchMaxColsH) and at least a Z row
@@ -120,21 +114,15 @@ int batch_alloc(lpr_engine* e, int32_t count, const std::vector<int32_t>& R,
     b->log_n = lg;
     b->x_total = x;
     int rc = LPR_OK_OPTIMAL;
-    if (hipMalloc(&b->desc, (size_t)count * sizeof(BatchDesc)) != hipSuccess)
-        rc = batch_oom("descriptors", count);
-    else if (hipMalloc(&b->slab, (size_t)std::max<int64_t>(t, 1) * sizeof(double)) != hipSuccess)
-        rc = batch_oom("tableau slab", t);
-    else if (hipMalloc(&b->basis, (size_t)std::max<int64_t>(bs, 1) * sizeof(int32_t)) !=
-             hipSuccess)
-        rc = batch_oom("bases", bs);
-    else if (hipMalloc(&b->logs, (size_t)std::max<int64_t>(lg, 1) * 2 * sizeof(int32_t)) !=
-             hipSuccess)
-        rc = batch_oom("pivot logs", lg);
-    else if (hipMalloc(&b->idx, (size_t)count * 2 * sizeof(int32_t)) != hipSuccess)
-        rc = batch_oom("running lists", count);
-    else if (hipMalloc(&b->counters, kNumForms * sizeof(int32_t)) != hipSuccess ||
-             hipHostMalloc(&b->h_counters, kNumForms * sizeof(int32_t)) != hipSuccess)
-        rc = batch_oom("counters", kNumForms);
+    // the message gives the entries asked for (n), which a padded or paired allocation exceeds
+    auto oom_n = [](int64_t n) {
+        return [n](const char* what, int64_t) { return batch_oom(what, n); };
+    };
+    dev_alloc(&b->desc, count, "descriptors", &rc, batch_oom);
+    dev_alloc(&b->slab, std::max<int64_t>(t, 1), "tableau slab", &rc, oom_n(t));
+    dev_alloc(&b->basis, std::max<int64_t>(bs, 1), "bases", &rc, oom_n(bs));
+    dev_alloc(&b->logs, std::max<int64_t>(lg, 1) * 2, "pivot logs", &rc, oom_n(lg));
+    b->run.alloc(count, &rc, batch_oom);
     if (rc == LPR_OK_OPTIMAL &&
         hipMemcpy(b->desc, b->h_desc.data(), (size_t)count * sizeof(BatchDesc),
                   hipMemcpyHostToDevice) != hipSuccess) {
@@ -148,17 +136,6 @@ int batch_alloc(lpr_engine* e, int32_t count, const std::vector<int32_t>& R,
     }
     *out = b;
     return LPR_OK_OPTIMAL;
-}
-
-// The form of one LP: the smallest that holds it, or the forced one (opts.variant 1/2/3) if the
-// LP fits it.
-int batch_form(const BatchDesc& d, int variant) {
-    const size_t bytes = batch_footprint(d.rows, d.cols) * sizeof(double);
-    const bool fitW = bytes <= kBatchMaxLdsW, fitG = bytes <= kBatchMaxLdsG;
-    if (variant == 1 && fitW) return kFormW;
-    if (variant == 2 && fitG) return kFormG;
-    if (variant == 3) return kFormH;
-    return fitW ? kFormW : (fitG ? kFormG : kFormH);
 }
 
 }  // namespace
@@ -177,15 +154,6 @@ lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const 
     return b->eng;
 }
 }  // namespace lpr
-
-#define LPR_LIVE_B(b)                                                                       \
-    do {                                                                                    \
-        if (!(b) || !(b)->eng) {                                                            \
-            set_error("batch handle is null or orphaned: its engine has been closed");      \
-            return LPR_BAD_ARGUMENT;                                                        \
-        }                                                                                   \
-        LPR_HIP(hipSetDevice((b)->eng->device));                                            \
-    } while (0)
 
 extern "C" {
 
@@ -346,12 +314,7 @@ int lpr_batch_destroy(lpr_batch* b) {
         hipSetDevice(b->eng->device);
         hipStreamSynchronize(b->eng->stream);
         batch_release_device(b);
-        auto& lv = b->eng->live_batch;
-        for (size_t q = 0; q < lv.size(); ++q)
-            if (lv[q] == b) {
-                lv.erase(lv.begin() + q);
-                break;
-            }
+        unlist(b->eng->live_batch, b);
     }
     delete b;
     return LPR_OK_OPTIMAL;
@@ -359,7 +322,7 @@ int lpr_batch_destroy(lpr_batch* b) {
 
 // PrimalSimplexSolver.Solve() (:102-150) for every LP that is not finished
 int lpr_batch_solve(lpr_batch* b, const lpr_batch_opts* opts, lpr_batch_result* res) {
-    LPR_LIVE_B(b);
+    LPR_LIVE_HANDLE(b, "batch");
     if (!res) {
         set_error("lpr_batch_solve: null result");
         return LPR_BAD_ARGUMENT;
@@ -386,7 +349,7 @@ int lpr_batch_solve(lpr_batch* b, const lpr_batch_opts* opts, lpr_batch_result* 
         if (d.status != kRunning && d.status != LPR_PIVOT_LIMIT) continue;  // finished stays so
         d.status = kRunning;
         d.max_iter = o.max_pivots > 0 ? d.iter + o.max_pivots : 0;
-        const int f = batch_form(d, o.variant);
+        const int f = batch_pick_form(batch_footprint(d.rows, d.cols) * sizeof(double), o.variant);
         lists[f].push_back(k);
         if (f == kFormH) {
             max_rows = std::max(max_rows, d.rows);
@@ -396,38 +359,17 @@ int lpr_batch_solve(lpr_batch* b, const lpr_batch_opts* opts, lpr_batch_result* 
             slot[f] = std::max(slot[f], (fp + 1) & ~1);
         }
     }
-    int32_t* in = b->idx;
-    int32_t* outl = b->idx + count;
-    int32_t off[kNumForms], live[kNumForms];
-    for (int f = 0, at = 0; f < kNumForms; ++f) {
-        off[f] = at;
-        live[f] = (int32_t)lists[f].size();
-        if (live[f] > 0)
-            LPR_HIP(hipMemcpyAsync(in + at, lists[f].data(), (size_t)live[f] * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, s));
-        at += live[f];
-    }
+    int rc = b->run.upload(s, lists);
+    if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(b->desc, b->h_desc.data(), (size_t)count * sizeof(BatchDesc),
                            hipMemcpyHostToDevice, s));
     int launches = 0;
-    while (live[kFormW] + live[kFormG] + live[kFormH] > 0) {
-        LPR_HIP(hipMemsetAsync(b->counters, 0, kNumForms * sizeof(int32_t), s));
-        for (int f = 0; f < kNumForms; ++f) {
-            if (live[f] == 0) continue;
-            const int chunk = o.chunk > 0 ? o.chunk : kBatchChunk[f];
-            const int rc = batch_launch_simplex(f, s, b->desc, b->slab, b->basis, b->logs,
-                                                in + off[f], live[f], outl + off[f],
-                                                b->counters + f, chunk, slot[f], max_rows,
-                                                max_cols);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-            ++launches;
-        }
-        LPR_HIP(hipMemcpyAsync(b->h_counters, b->counters, kNumForms * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
-        LPR_HIP(hipStreamSynchronize(s));
-        for (int f = 0; f < kNumForms; ++f) live[f] = b->h_counters[f];
-        std::swap(in, outl);
-    }
+    rc = b->run.rounds(s, [&](int f, const int32_t* in, int n_in, int32_t* out, int32_t* n_out) {
+        return batch_launch_simplex(f, s, b->desc, b->slab, b->basis, b->logs, in, n_in, out,
+                                    n_out, o.chunk > 0 ? o.chunk : kBatchChunk[f], slot[f],
+                                    max_rows, max_cols);
+    }, &launches);
+    if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(b->h_desc.data(), b->desc, (size_t)count * sizeof(BatchDesc),
                            hipMemcpyDeviceToHost, s));
     LPR_HIP(hipStreamSynchronize(s));
@@ -457,7 +399,7 @@ static int batch_extract(lpr_batch* b, bool want_x) {
 
 // Status, pivots (C# `iteration`) and FinalZ = T[0, cols-1] (:113) of every LP; any may be NULL
 int lpr_batch_status_read(lpr_batch* b, int32_t* status, int64_t* pivots, double* z) {
-    LPR_LIVE_B(b);
+    LPR_LIVE_HANDLE(b, "batch");
     for (int32_t k = 0; k < b->count; ++k) {
         if (status) status[k] = b->h_desc[(size_t)k].status;
         if (pivots) pivots[k] = b->h_desc[(size_t)k].iter;
@@ -473,7 +415,7 @@ int lpr_batch_status_read(lpr_batch* b, int32_t* status, int64_t* pivots, double
 
 // ExtractSolution() (:213-252) of every optimal LP, packed by n[k]; 0 for the others
 int lpr_batch_solution_read(lpr_batch* b, double* x) {
-    LPR_LIVE_B(b);
+    LPR_LIVE_HANDLE(b, "batch");
     if (!x) {
         set_error("lpr_batch_solution_read: null x");
         return LPR_BAD_ARGUMENT;
@@ -489,7 +431,7 @@ int lpr_batch_solution_read(lpr_batch* b, double* x) {
 
 // basicVariables (:18-24, :142) of every LP, packed by rows[k] - 1
 int lpr_batch_basis_read(lpr_batch* b, int32_t* basis) {
-    LPR_LIVE_B(b);
+    LPR_LIVE_HANDLE(b, "batch");
     if (!basis) {
         set_error("lpr_batch_basis_read: null basis");
         return LPR_BAD_ARGUMENT;
@@ -504,7 +446,7 @@ int lpr_batch_basis_read(lpr_batch* b, int32_t* basis) {
 // The pivot log of LP k (:138): the first min(pivots, log_cap, cap) (row, col) pairs
 int lpr_batch_log_read(lpr_batch* b, int32_t k, int32_t* rows, int32_t* cols, int64_t cap,
                        int64_t* count) {
-    LPR_LIVE_B(b);
+    LPR_LIVE_HANDLE(b, "batch");
     if (k < 0 || k >= b->count || cap < 0 || !count) {
         set_error("lpr_batch_log_read: LP %d out of range (0..%d), cap %lld or null count", k,
                   b->count - 1, (long long)cap);
@@ -527,7 +469,7 @@ int lpr_batch_log_read(lpr_batch* b, int32_t k, int32_t* rows, int32_t* cols, in
 
 // The tableau of LP k (FinalTableau, :18-24), rows[k] x cols[k] row-major
 int lpr_batch_tableau_read(lpr_batch* b, int32_t k, double* rowmajor) {
-    LPR_LIVE_B(b);
+    LPR_LIVE_HANDLE(b, "batch");
     if (k < 0 || k >= b->count || !rowmajor) {
         set_error("lpr_batch_tableau_read: LP %d out of range (0..%d) or null output", k,
                   b->count - 1);
@@ -543,7 +485,7 @@ int lpr_batch_tableau_read(lpr_batch* b, int32_t k, double* rowmajor) {
 
 // Shape of LP k (rows, cols, n), for callers that size their reads
 int lpr_batch_shape(lpr_batch* b, int32_t k, int32_t* rows, int32_t* cols, int32_t* n) {
-    LPR_LIVE_B(b);
+    LPR_LIVE_HANDLE(b, "batch");
     if (k < 0 || k >= b->count) {
         set_error("lpr_batch_shape: LP %d out of range (0..%d)", k, b->count - 1);
         return LPR_BAD_ARGUMENT;

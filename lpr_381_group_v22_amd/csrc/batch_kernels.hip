@@ -8,39 +8,16 @@
 //   k_batch_build              the constructor (:27-87) for every LP of lpr_batch_from_lps
 //   k_batch_extract            FinalZ (:113) and ExtractSolution() (:213-252) for every LP
 #include "batch_common.hpp"
-#include "select_common.hpp"
+#include "batch_device.hpp"
 
 #pragma clang fp contract(off)
 
 namespace lpr {
 
-// Ordering between the lanes of one LP.  Form W: one wave, no workgroup barrier (the four LPs of
-// a workgroup never wait for each other); a wave's LDS operations complete in order, so a
-// wave-scope fence that keeps the compiler from moving them is enough.
-template <int NT>
-__device__ __forceinline__ void lp_sync() {
-    if constexpr (NT == kWave) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-// Lexicographic (value, index) minimum over the NT lanes of one LP; every lane gets it.
-template <int NT>
-__device__ __forceinline__ Cand lp_cand_min(Cand c, double* red_v, int* red_i) {
-    if constexpr (NT == kWave) {
-        return dpp_wave_cand_min(c);
-    } else {
-        return dpp_block_cand_min(c, red_v, red_i);
-    }
-}
-
-// One LP per NT lanes; 256 / NT LPs per workgroup.  idx_in lists the LPs still running; an LP that
-// is still running when its chunk is used up appends itself to idx_out (n_out counts them: the one
-// word the host reads per launch).
+// One LP per NT lanes; 256 / NT LPs per workgroup.  Everything the lanes of an LP share during a
+// launch is in LDS (W, G) or ordered by workgroup barriers (H), so form W fences at wave scope.
+// idx_in lists the LPs still running; an LP that is still running when its chunk is used up
+// appends itself to idx_out (n_out counts them: the one word the host reads per launch).
 template <int NT, bool kLds>
 __global__ __launch_bounds__(256) void k_batch_simplex(BatchDesc* __restrict__ desc,
                                                        double* __restrict__ slab,
@@ -76,7 +53,7 @@ __global__ __launch_bounds__(256) void k_batch_simplex(BatchDesc* __restrict__ d
         T = smem + (size_t)sub * slot;
         fcol = T + RC;
         for (int x = lane; x < RC; x += NT) T[x] = Tg[x];
-        lp_sync<NT>();
+        group_sync<NT, kFenceWave>();
     } else {
         T = Tg;
         fcol = smem;
@@ -96,7 +73,7 @@ __global__ __launch_bounds__(256) void k_batch_simplex(BatchDesc* __restrict__ d
                 c.i = j;
             }
         }
-        c = lp_cand_min<NT>(c, red_v, red_i);
+        c = group_cand_min<NT>(c, red_v, red_i);
         const int e = c.i;
         if (e < 0) {
             status = LPR_OK_OPTIMAL;
@@ -116,7 +93,7 @@ __global__ __launch_bounds__(256) void k_batch_simplex(BatchDesc* __restrict__ d
                 }
             }
         }
-        l = lp_cand_min<NT>(l, red_v, red_i);
+        l = group_cand_min<NT>(l, red_v, red_i);
         const int r = l.i;
         if (r < 0) {
             status = LPR_UNBOUNDED;
@@ -128,7 +105,7 @@ __global__ __launch_bounds__(256) void k_batch_simplex(BatchDesc* __restrict__ d
         }
         // ---- Pivot  :193-211 ----
         for (int i = lane; i < R; i += NT) fcol[i] = T[(size_t)i * C + e];
-        lp_sync<NT>();
+        group_sync<NT, kFenceWave>();
         const double pe = fcol[r];
         double* const Tr = T + (size_t)r * C;
         for (int j = lane; j < C; j += NT) {  // :198-199, every column, RHS included
@@ -137,7 +114,7 @@ __global__ __launch_bounds__(256) void k_batch_simplex(BatchDesc* __restrict__ d
             if constexpr (!kLds) prow[j] = v;
         }
         if constexpr (kLds) prow = Tr;
-        lp_sync<NT>();
+        group_sync<NT, kFenceWave>();
         // :201-210: every row but r, the Z row included, and no row skipped for a zero factor
         // (+0 * a negative p_j is -0.0, and -0.0 - -0.0 is +0.0; 0 * inf is NaN).  Element-
         // parallel over the flattened tableau, four elements in flight per lane.
@@ -179,7 +156,7 @@ __global__ __launch_bounds__(256) void k_batch_simplex(BatchDesc* __restrict__ d
             }
         }
         ++iter;
-        lp_sync<NT>();
+        group_sync<NT, kFenceWave>();
     }
 
     if constexpr (kLds) {  // the LDS copy goes back to the slab
@@ -286,23 +263,7 @@ __global__ __launch_bounds__(256) void k_batch_extract(const BatchDesc* __restri
 }
 
 // ------------------------------------------------------------------------------------------
-// Launchers (batch_engine.hip).  Dynamic LDS above 64 KiB needs the attribute once per device.
-static int raise_lds(const void* fn, size_t bytes, unsigned long long* mask) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LPR_DEVICE_ERROR;
-    const unsigned long long bit = 1ull << dev;
-    if (__atomic_load_n(mask, __ATOMIC_ACQUIRE) & bit) return LPR_OK_OPTIMAL;
-    const hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)bytes);
-    if (err != hipSuccess) {
-        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed: %s", bytes,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    __atomic_fetch_or(mask, bit, __ATOMIC_ACQ_REL);
-    return LPR_OK_OPTIMAL;
-}
-
+// Launchers (batch_engine.hip).
 int batch_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab, int32_t* basis,
                          int32_t* logs, const int32_t* idx_in, int n_in, int32_t* idx_out,
                          int32_t* n_out, int chunk, int slot_doubles, int max_rows,
@@ -317,8 +278,8 @@ int batch_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab,
     } else if (form == kFormG) {
         const size_t lds = (size_t)slot_doubles * sizeof(double);
         if (lds > ((size_t)64 << 10)) {
-            const int rc = raise_lds(reinterpret_cast<const void*>(&k_batch_simplex<256, true>),
-                                     kBatchMaxLdsG, &g_mask);
+            const int rc = raise_dynamic_lds(
+                reinterpret_cast<const void*>(&k_batch_simplex<256, true>), kBatchMaxLdsG, &g_mask);
             if (rc != LPR_OK_OPTIMAL) return rc;
         }
         hipLaunchKernelGGL((k_batch_simplex<256, true>), dim3(n_in), dim3(256), lds, s, desc,

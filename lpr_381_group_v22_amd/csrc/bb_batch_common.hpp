@@ -2,32 +2,23 @@
 // host) and its kernels (bb_batch_kernels.hip).  Not part of the ABI (include/lpr_engine.h is).
 #pragma once
 
-#include "engine_common.hpp"
+#include "batch_common.hpp"
 
 namespace lpr {
 
-// Forms of one IP in a batch, as those of the LP batch (section 12).  The
-// host picks one per IP by the footprint of its working pair at full depth: two tableaux of
-// (R + c) x (C + c) doubles and the staged factor column of R + c doubles, c the node cap.
-enum BBBatchForm : int { kBBFormW = 0, kBBFormG = 1, kBBFormH = 2, kBBNumForms = 3 };
+// The forms and their limits are those of the LP batch (BatchForm, batch_common.hpp; DESIGN.md
+// sections 12 and 13).  The host picks one per IP by the footprint of its working pair at full
+// depth: two tableaux of (R + c) x (C + c) doubles and the staged factor column of R + c doubles,
+// c the node cap.  W and G keep the pair in LDS; H keeps it in the IP's slice of the global work
+// slab and the factor column in LDS, for shapes at full depth up to kBatchMaxRowsH x
+// kBatchMaxColsH.
 
-// Every workgroup keeps kBBBatchWgScratch bytes of static LDS for itself (the reduction slots).
-constexpr size_t kBBBatchWgScratch = (size_t)1 << 10;
-// W: one wave per IP, four IPs per 256-lane workgroup, each in a quarter of the 64 KiB a
-// workgroup gets without the dynamic-LDS attribute.
-constexpr size_t kBBBatchWgLdsW = (size_t)64 << 10;
-constexpr size_t kBBBatchMaxLdsW = (kBBBatchWgLdsW - kBBBatchWgScratch) / 4;
-// G: one workgroup per IP, the pair in dynamic LDS: 160 KiB less the workgroup's scratch.
-constexpr size_t kBBBatchMaxLdsG = ((size_t)160 << 10) - kBBBatchWgScratch;
-// H: one workgroup per IP, the pair in its slice of the global work slab, the factor column in
-// LDS.  Shapes at full depth up to the limit of the LP batch's form H.
-constexpr int kBBBatchMaxRowsH = 1024;
-constexpr int kBBBatchMaxColsH = 2048;
 // Node cap: <= 0 means the reference's 20 (:1038); more than kBBBatchMaxNodeCap is refused.
 constexpr int kBBBatchDefaultNodeCap = 20;
 constexpr int kBBBatchMaxNodeCap = 64;
 // Pops per IP per launch, by form: a launch stays within a few milliseconds.
-constexpr int kBBBatchChunk[kBBNumForms] = {32, 16, 4};
+constexpr int kBBBatchChunk[kNumForms] = {32, 16, 4};
+static_assert(sizeof(kBBBatchChunk) / sizeof(int) == kNumForms, "one chunk per form");
 // Pivots one child LP may take before its IP ends with LPR_PIVOT_LIMIT (0 in the options): the
 // `1 << 16` guard of bb_expand.
 constexpr int kBBBatchMaxChildPivots = 1 << 16;

@@ -1,8 +1,7 @@
 // bb_batch_engine.hip -- host side of the batched Branch & Bound (include/lpr_engine.h,
 // lpr_bb_batch_*).  Every IP of a batch runs ExecuteBranchAndBound on the
 // device; the host only picks each IP's form, relaunches the bounded search kernels while IPs are
-// still running (one small counter read per launch round) and copies results out.
-#include "batch_common.hpp"
+// still running (BatchRunLists of batch_common.hpp) and copies results out.
 #include "bb_batch_common.hpp"
 
 #include <algorithm>
@@ -28,9 +27,7 @@ struct lpr_bb_batch {
     std::vector<BBBatchDesc> h_desc;  // host mirror, current after every create / run
     BBBatchBufs d{};                  // device buffers (d.work grows on demand)
     int64_t work_n = 0;               // doubles allocated at d.work
-    int32_t* idx = nullptr;           // 2 x count: the running lists, in and out, per form
-    int32_t* counters = nullptr;      // kBBNumForms running counts (device)
-    int32_t* h_counters = nullptr;    // pinned
+    BatchRunLists run;                // the running lists and their counters
     int64_t x_total = 0, rec_total = 0, trace_total = 0;
     bool ran = false;
 };
@@ -55,14 +52,9 @@ void bbb_release_device(lpr_bb_batch* b) {
     hipFree(b->d.trace);
     hipFree(b->d.ints);
     hipFree(b->d.stk);
-    hipFree(b->idx);
-    hipFree(b->counters);
-    if (b->h_counters) hipHostFree(b->h_counters);
+    b->run.release();
     b->d = BBBatchBufs{};
     b->work_n = 0;
-    b->idx = nullptr;
-    b->counters = nullptr;
-    b->h_counters = nullptr;
 }
 
 // A root of rows x cols with nvars decision columns whose shape at full depth stays within form H.
@@ -74,11 +66,11 @@ bool bbb_shape_ok(const char* where, int32_t k, int64_t rows, int64_t cols, int6
                   where, k, (long long)rows, (long long)cols, (long long)nvars);
         return false;
     }
-    if (rows + node_cap > kBBBatchMaxRowsH || cols + node_cap > kBBBatchMaxColsH) {
+    if (rows + node_cap > kBatchMaxRowsH || cols + node_cap > kBatchMaxColsH) {
         set_error("%s: IP %d has a %lld x %lld root, %lld x %lld at the full depth of node cap %d: "
                   "beyond the batch limit of %d x %d (form H); run it alone with lpr_bb_run",
                   where, k, (long long)rows, (long long)cols, (long long)(rows + node_cap),
-                  (long long)(cols + node_cap), node_cap, kBBBatchMaxRowsH, kBBBatchMaxColsH);
+                  (long long)(cols + node_cap), node_cap, kBatchMaxRowsH, kBatchMaxColsH);
         return false;
     }
     return true;
@@ -142,33 +134,28 @@ int bbb_alloc(lpr_engine* e, int32_t count, const std::vector<int32_t>& R,
     b->x_total = x;
     b->rec_total = rec;
     b->trace_total = tr;
-    auto one = [](int64_t n) { return (size_t)std::max<int64_t>(n, 1); };
+    auto one = [](int64_t n) { return std::max<int64_t>(n, 1); };
     int rc = LPR_OK_OPTIMAL;
     BBBatchBufs& D = b->d;
-    if (hipMalloc(&D.desc, (size_t)count * sizeof(BBBatchDesc)) != hipSuccess)
-        rc = bbb_oom("descriptors", count, sizeof(BBBatchDesc));
-    else if (hipMalloc(&D.stack, one(st) * sizeof(double)) != hipSuccess)
-        rc = bbb_oom("DFS stack slab: (node_cap + 2) (rows + node_cap) (cols + node_cap) doubles "
-                     "per IP",
-                     st, sizeof(double));
-    else if (hipMalloc(&D.x, one(x) * sizeof(double)) != hipSuccess ||
-             hipMalloc(&D.vals, one(x) * sizeof(double)) != hipSuccess)
-        rc = bbb_oom("incumbents", 2 * x, sizeof(double));
-    else if (hipMalloc(&D.rec_i, one(rec) * kBBRecInts * sizeof(int32_t)) != hipSuccess ||
-             hipMalloc(&D.rec_d, one(rec) * 2 * sizeof(double)) != hipSuccess)
-        rc = bbb_oom("node records", rec, kBBRecInts * sizeof(int32_t) + 2 * sizeof(double));
-    else if (hipMalloc(&D.pops, one(pop) * sizeof(int32_t)) != hipSuccess)
-        rc = bbb_oom("pop orders", pop, sizeof(int32_t));
-    else if (hipMalloc(&D.trace, one(tr) * 4 * sizeof(int32_t)) != hipSuccess)
-        rc = bbb_oom("pivot traces", tr, 4 * sizeof(int32_t));
-    else if (hipMalloc(&D.ints, one(in) * sizeof(int32_t)) != hipSuccess ||
-             hipMalloc(&D.stk, one(stk) * sizeof(int32_t)) != hipSuccess)
-        rc = bbb_oom("scratch", in + stk, sizeof(int32_t));
-    else if (hipMalloc(&b->idx, (size_t)count * 2 * sizeof(int32_t)) != hipSuccess)
-        rc = bbb_oom("running lists", count, 2 * sizeof(int32_t));
-    else if (hipMalloc(&b->counters, kBBNumForms * sizeof(int32_t)) != hipSuccess ||
-             hipHostMalloc(&b->h_counters, kBBNumForms * sizeof(int32_t)) != hipSuccess)
-        rc = bbb_oom("counters", kBBNumForms, sizeof(int32_t));
+    // the message gives n entries of elem bytes each (one figure for buffers that go together)
+    auto gb = [](int64_t n, size_t elem) {
+        return [=](const char* what, int64_t) { return bbb_oom(what, n, elem); };
+    };
+    dev_alloc(&D.desc, count, "descriptors", &rc, gb(count, sizeof(BBBatchDesc)));
+    dev_alloc(&D.stack, one(st),
+              "DFS stack slab: (node_cap + 2) (rows + node_cap) (cols + node_cap) doubles per IP",
+              &rc, gb(st, sizeof(double)));
+    dev_alloc(&D.x, one(x), "incumbents", &rc, gb(2 * x, sizeof(double)));
+    dev_alloc(&D.vals, one(x), "incumbents", &rc, gb(2 * x, sizeof(double)));
+    const size_t rec_elem = kBBRecInts * sizeof(int32_t) + 2 * sizeof(double);
+    dev_alloc(&D.rec_i, one(rec) * kBBRecInts, "node records", &rc, gb(rec, rec_elem));
+    dev_alloc(&D.rec_d, one(rec) * 2, "node records", &rc, gb(rec, rec_elem));
+    dev_alloc(&D.pops, one(pop), "pop orders", &rc, gb(pop, sizeof(int32_t)));
+    dev_alloc(&D.trace, one(tr) * 4, "pivot traces", &rc, gb(tr, 4 * sizeof(int32_t)));
+    dev_alloc(&D.ints, one(in), "scratch", &rc, gb(in + stk, sizeof(int32_t)));
+    dev_alloc(&D.stk, one(stk), "scratch", &rc, gb(in + stk, sizeof(int32_t)));
+    b->run.alloc(count, &rc,
+                 [](const char* what, int64_t n) { return bbb_oom(what, n, sizeof(int32_t)); });
     if (rc == LPR_OK_OPTIMAL &&
         hipMemcpy(D.desc, b->h_desc.data(), (size_t)count * sizeof(BBBatchDesc),
                   hipMemcpyHostToDevice) != hipSuccess) {
@@ -205,17 +192,6 @@ int bbb_load(lpr_bb_batch* b, const double* d_src, const std::vector<int64_t>& s
     return LPR_OK_OPTIMAL;
 }
 
-// The form of one IP: the smallest that holds its working pair at full depth, or the forced one
-// (opts.variant 1/2/3) if the IP fits it.
-int bbb_form(const BBBatchDesc& d, int variant) {
-    const size_t bytes = bb_batch_footprint(d.rows, d.cols, d.node_cap) * sizeof(double);
-    const bool fitW = bytes <= kBBBatchMaxLdsW, fitG = bytes <= kBBBatchMaxLdsG;
-    if (variant == 1 && fitW) return kBBFormW;
-    if (variant == 2 && fitG) return kBBFormG;
-    if (variant == 3) return kBBFormH;
-    return fitW ? kBBFormW : (fitG ? kBBFormG : kBBFormH);
-}
-
 }  // namespace
 
 namespace lpr {
@@ -224,15 +200,6 @@ void bb_batch_orphan(lpr_bb_batch* b) {  // lpr_engine_close
     b->eng = nullptr;
 }
 }  // namespace lpr
-
-#define LPR_LIVE_BBB(b)                                                                     \
-    do {                                                                                    \
-        if (!(b) || !(b)->eng) {                                                            \
-            set_error("B&B batch handle is null or orphaned: its engine has been closed");  \
-            return LPR_BAD_ARGUMENT;                                                        \
-        }                                                                                   \
-        LPR_HIP(hipSetDevice((b)->eng->device));                                            \
-    } while (0)
 
 extern "C" {
 
@@ -341,12 +308,7 @@ int lpr_bb_batch_destroy(lpr_bb_batch* b) {
         hipSetDevice(b->eng->device);
         hipStreamSynchronize(b->eng->stream);
         bbb_release_device(b);
-        auto& lv = b->eng->live_bb_batch;
-        for (size_t q = 0; q < lv.size(); ++q)
-            if (lv[q] == b) {
-                lv.erase(lv.begin() + q);
-                break;
-            }
+        unlist(b->eng->live_bb_batch, b);
     }
     delete b;
     return LPR_OK_OPTIMAL;
@@ -355,7 +317,7 @@ int lpr_bb_batch_destroy(lpr_bb_batch* b) {
 // ExecuteBranchAndBound (:1006-1233) for every IP, from its root
 int lpr_bb_batch_run(lpr_bb_batch* b, const lpr_bb_batch_opts* opts, lpr_bb_batch_result* res) {
     static const char* W = "lpr_bb_batch_run";
-    LPR_LIVE_BBB(b);
+    LPR_LIVE_HANDLE(b, "B&B batch");
     if (!res) {
         set_error("%s: null result", W);
         return LPR_BAD_ARGUMENT;
@@ -371,18 +333,18 @@ int lpr_bb_batch_run(lpr_bb_batch* b, const lpr_bb_batch_opts* opts, lpr_bb_batc
     std::memset(res, 0, sizeof *res);
     hipStream_t s = b->eng->stream;
     const int32_t count = b->count;
-    std::vector<int32_t> lists[kBBNumForms];
-    int slot[kBBNumForms] = {0, 0, 0};
+    std::vector<int32_t> lists[kNumForms];
+    int slot[kNumForms] = {0, 0, 0};
     int max_rows = 0;
     int64_t work = 0;
     for (int32_t k = 0; k < count; ++k) {
         BBBatchDesc& d = b->h_desc[(size_t)k];
         d.enable_pruning = o.enable_pruning ? 1 : 0;
         d.max_child_pivots = o.max_child_pivots > 0 ? o.max_child_pivots : kBBBatchMaxChildPivots;
-        const int f = bbb_form(d, o.variant);
-        lists[f].push_back(k);
         const int64_t fp = (int64_t)bb_batch_footprint(d.rows, d.cols, d.node_cap);
-        if (f == kBBFormH) {
+        const int f = batch_pick_form((size_t)fp * sizeof(double), o.variant);
+        lists[f].push_back(k);
+        if (f == kFormH) {
             d.work_off = work;
             work += fp;
             max_rows = std::max(max_rows, d.rows + d.node_cap);
@@ -399,38 +361,18 @@ int lpr_bb_batch_run(lpr_bb_batch* b, const lpr_bb_batch_opts* opts, lpr_bb_batc
             return bbb_oom("form H working pairs", work, sizeof(double));
         b->work_n = work;
     }
-    int32_t* in = b->idx;
-    int32_t* outl = b->idx + count;
-    int32_t off[kBBNumForms], live[kBBNumForms];
-    for (int f = 0, at = 0; f < kBBNumForms; ++f) {
-        off[f] = at;
-        live[f] = (int32_t)lists[f].size();
-        if (live[f] > 0)
-            LPR_HIP(hipMemcpyAsync(in + at, lists[f].data(), (size_t)live[f] * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, s));
-        at += live[f];
-    }
+    int rc = b->run.upload(s, lists);
+    if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(b->d.desc, b->h_desc.data(), (size_t)count * sizeof(BBBatchDesc),
                            hipMemcpyHostToDevice, s));
     bb_batch_launch_reset(s, b->d, count);
     LPR_HIP(hipGetLastError());
     int launches = 0;
-    while (live[kBBFormW] + live[kBBFormG] + live[kBBFormH] > 0) {
-        LPR_HIP(hipMemsetAsync(b->counters, 0, kBBNumForms * sizeof(int32_t), s));
-        for (int f = 0; f < kBBNumForms; ++f) {
-            if (live[f] == 0) continue;
-            const int chunk = o.chunk > 0 ? o.chunk : kBBBatchChunk[f];
-            const int rc = bb_batch_launch(f, s, b->d, in + off[f], live[f], outl + off[f],
-                                           b->counters + f, chunk, slot[f], max_rows);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-            ++launches;
-        }
-        LPR_HIP(hipMemcpyAsync(b->h_counters, b->counters, kBBNumForms * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
-        LPR_HIP(hipStreamSynchronize(s));
-        for (int f = 0; f < kBBNumForms; ++f) live[f] = b->h_counters[f];
-        std::swap(in, outl);
-    }
+    rc = b->run.rounds(s, [&](int f, const int32_t* in, int n_in, int32_t* out, int32_t* n_out) {
+        return bb_batch_launch(f, s, b->d, in, n_in, out, n_out,
+                               o.chunk > 0 ? o.chunk : kBBBatchChunk[f], slot[f], max_rows);
+    }, &launches);
+    if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(b->h_desc.data(), b->d.desc, (size_t)count * sizeof(BBBatchDesc),
                            hipMemcpyDeviceToHost, s));
     LPR_HIP(hipStreamSynchronize(s));
@@ -450,7 +392,7 @@ int lpr_bb_batch_run(lpr_bb_batch* b, const lpr_bb_batch_opts* opts, lpr_bb_batc
 int lpr_bb_batch_result_read(lpr_bb_batch* b, int32_t* status, int32_t* found, int64_t* processed,
                              int32_t* best_node, double* z, int64_t* pivots,
                              int64_t* nodes_created) {
-    LPR_LIVE_BBB(b);
+    LPR_LIVE_HANDLE(b, "B&B batch");
     for (int32_t k = 0; k < b->count; ++k) {
         const BBBatchDesc& d = b->h_desc[(size_t)k];
         if (status) status[k] = d.status;
@@ -466,7 +408,7 @@ int lpr_bb_batch_result_read(lpr_bb_batch* b, int32_t* status, int32_t* found, i
 
 // optimalSolution (:1059-1066) of every IP, packed by nvars
 int lpr_bb_batch_solution_read(lpr_bb_batch* b, double* x) {
-    LPR_LIVE_BBB(b);
+    LPR_LIVE_HANDLE(b, "B&B batch");
     if (!x) {
         set_error("lpr_bb_batch_solution_read: null x");
         return LPR_BAD_ARGUMENT;
@@ -495,7 +437,7 @@ static int bbb_ip(lpr_bb_batch* b, const char* where, int32_t k, int64_t cap, in
 int lpr_bb_batch_records_read(lpr_bb_batch* b, int32_t k, int32_t* parent, int32_t* kind,
                               int32_t* depth, int32_t* var, double* bound, int32_t* status,
                               double* z, int64_t cap, int64_t* count) {
-    LPR_LIVE_BBB(b);
+    LPR_LIVE_HANDLE(b, "B&B batch");
     int rc = bbb_ip(b, "lpr_bb_batch_records_read", k, cap, count);
     if (rc != LPR_OK_OPTIMAL) return rc;
     const BBBatchDesc& d = b->h_desc[(size_t)k];
@@ -525,7 +467,7 @@ int lpr_bb_batch_records_read(lpr_bb_batch* b, int32_t k, int32_t* parent, int32
 // Record ids of IP k in pop order, as lpr_bb_pop_order_read
 int lpr_bb_batch_pop_order_read(lpr_bb_batch* b, int32_t k, int32_t* ids, int64_t cap,
                                 int64_t* count) {
-    LPR_LIVE_BBB(b);
+    LPR_LIVE_HANDLE(b, "B&B batch");
     int rc = bbb_ip(b, "lpr_bb_batch_pop_order_read", k, cap, count);
     if (rc != LPR_OK_OPTIMAL) return rc;
     const BBBatchDesc& d = b->h_desc[(size_t)k];
@@ -541,7 +483,7 @@ int lpr_bb_batch_pop_order_read(lpr_bb_batch* b, int32_t k, int32_t* ids, int64_
 // Pivot trace of IP k, as lpr_bb_trace_read
 int lpr_bb_batch_trace_read(lpr_bb_batch* b, int32_t k, int32_t* quads, int64_t cap,
                             int64_t* count) {
-    LPR_LIVE_BBB(b);
+    LPR_LIVE_HANDLE(b, "B&B batch");
     int rc = bbb_ip(b, "lpr_bb_batch_trace_read", k, cap, count);
     if (rc != LPR_OK_OPTIMAL) return rc;
     const BBBatchDesc& d = b->h_desc[(size_t)k];

@@ -8,9 +8,9 @@
 //                         or in the global work slab (H); the DFS stack in HBM
 //   k_bb_batch_load       the roots into their own stack slots (lpr_bb_batch_create / _from_batch)
 //   k_bb_batch_reset      RoundAllTableaux of the root (:1021), record 0, an empty incumbent
+#include "batch_device.hpp"
 #include "bb_batch_common.hpp"
 #include "bb_device_round.hpp"
-#include "select_common.hpp"
 
 #pragma clang fp contract(off)
 
@@ -18,30 +18,8 @@ namespace lpr {
 
 namespace {
 
-// Ordering between the lanes of one IP.  Form W: one wave, no workgroup barrier (the four IPs of a
-// workgroup never wait for each other); the fences make the wave's own LDS and global writes
-// visible to its other lanes.
-template <int NT>
-__device__ __forceinline__ void ip_sync() {
-    if constexpr (NT == kWave) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-
-// Lexicographic (value, index) minimum over the NT lanes of one IP (no NaN candidates); every lane
-// gets it.
-template <int NT>
-__device__ __forceinline__ Cand ip_cand_min(Cand c, double* red_v, int* red_i) {
-    if constexpr (NT == kWave) {
-        return dpp_wave_cand_min(c);
-    } else {
-        return dpp_block_cand_min(c, red_v, red_i);
-    }
-}
+// Ordering between the lanes of one IP is group_sync<NT, kFenceWorkgroup>() throughout: the DFS
+// stack they share is in global memory, so form W fences at workgroup scope.
 
 // Minimum of an int over the NT lanes of one IP; every lane gets it.
 template <int NT>
@@ -72,23 +50,6 @@ __device__ __forceinline__ bool ip_any(bool p, int* red_i) {
     return ip_min_int<NT>(p ? 0 : 1, red_i) == 0;
 }
 
-// f(x, i, j) for every element x = i * cols + j of a rows x cols block, NT lanes apart.
-template <int NT, class F>
-__device__ __forceinline__ void for_each_ij(int rows, int cols, int lane, F&& f) {
-    const int n = rows * cols;
-    const int di = NT / cols, dj = NT - di * cols;
-    int i = lane / cols, j = lane - (lane / cols) * cols;
-    for (int x = lane; x < n; x += NT) {
-        f(x, i, j);
-        i += di;
-        j += dj;
-        if (j >= cols) {
-            j -= cols;
-            ++i;
-        }
-    }
-}
-
 // The pivot of PerformDualPivot :174-190 / PerformPrimalPivot :257-271, out of place (cur -> out):
 // the pivot row divided, then `v == 0.0 ? 0.0`; every other row T - f * p with the product rounded
 // (no FMA) and no row skipped for a zero factor.  Every entry written also gets DoDualSimplex's
@@ -105,7 +66,7 @@ __device__ __forceinline__ void ip_pivot(const double* cur, double* out, double*
         if (v == 0.0) v = 0.0;
         orow[j] = v;
     }
-    ip_sync<NT>();
+    group_sync<NT, kFenceWorkgroup>();
     for_each_ij<NT>(Rc, Cc, lane, [&](int x, int i, int j) {
         if (i == pr) return;
         const double prod = fcol[i] * orow[j];
@@ -113,7 +74,7 @@ __device__ __forceinline__ void ip_pivot(const double* cur, double* out, double*
         if (v == 0.0) v = 0.0;
         out[x] = v;
     });
-    ip_sync<NT>();
+    group_sync<NT, kFenceWorkgroup>();
 }
 
 // Results of one child LP.
@@ -178,7 +139,7 @@ __device__ void add_constraint(const double* P, int Rn, int Cn, int nv, int var,
         }
         A[x] = v;
     });
-    ip_sync<NT>();
+    group_sync<NT, kFenceWorkgroup>();
     // OrderBy(key), a stable sort: the basic columns by (key, column)
     int nb = 0;
     for (int k = 0; k < Cn; ++k) nb += keys[k] >= 0;
@@ -192,7 +153,7 @@ __device__ void add_constraint(const double* P, int Rn, int Cn, int nv, int var,
         }
         list[pos] = k;
     }
-    ip_sync<NT>();
+    group_sync<NT, kFenceWorkgroup>();
     // the sequential eliminations :756-796, every step parallel over the columns
     double* const crow = A + (size_t)Rn * Cc;
     for (int q = 0; q < nb; ++q) {
@@ -221,7 +182,7 @@ __device__ void add_constraint(const double* P, int Rn, int Cn, int nv, int var,
             }
             crow[c] = dn_round4(newVal);
         }
-        ip_sync<NT>();
+        group_sync<NT, kFenceWorkgroup>();
     }
     // RoundTableau :799 of the new row, and the -0 -> +0 of the first DoDualSimplex loop head
     for_each_ij<NT>(Rc, Cc, lane, [&](int x, int i, int j) {
@@ -230,7 +191,7 @@ __device__ void add_constraint(const double* P, int Rn, int Cn, int nv, int var,
         if (v == 0.0) v = 0.0;
         A[x] = v;
     });
-    ip_sync<NT>();
+    group_sync<NT, kFenceWorkgroup>();
 }
 
 // DoDualSimplex :289-468 in tableauOverride mode on the child in *cur (Rc x Cc), ping-ponging with
@@ -255,7 +216,7 @@ __device__ int child_lp(double*& cur, double*& oth, double* fcol, int Rc, int Cc
             }
         }
         if (!ip_any<NT>(bad, red_i)) break;
-        c = ip_cand_min<NT>(c, red_v, red_i);
+        c = group_cand_min<NT>(c, red_v, red_i);
         if (c.i < 0) return kChildInfeasible;  // PerformDualPivot :118-123 -> null optimum
         const int pr = c.i;
         // :126-154: theta = |T0j / Tprj| over Tprj < 0, else +inf; all 0-or-inf -> 0, else the
@@ -283,7 +244,7 @@ __device__ int child_lp(double*& cur, double*& oth, double* fcol, int Rc, int Cc
             pc = ip_min_int<NT>(first0, red_i);
             if (pc == INT_MAX) pc = -1;
         } else {
-            pc = ip_cand_min<NT>(m, red_v, red_i).i;  // no theta > 0: minPos = +inf, none equal
+            pc = group_cand_min<NT>(m, red_v, red_i).i;  // no theta > 0: minPos = +inf, none equal
         }
         if (pc < 0) return kChildInfeasible;  // tableau[rowIndex][-1] -> (tableau, null) :165-172
         if (npiv >= max_piv) return kChildLimit;
@@ -314,7 +275,7 @@ __device__ int child_lp(double*& cur, double*& oth, double* fcol, int Rc, int Cc
             }
         }
         if (!ip_any<NT>(neg, red_i)) break;
-        c = ip_cand_min<NT>(c, red_v, red_i);
+        c = group_cand_min<NT>(c, red_v, red_i);
         if (c.i < 0) break;  // Min() of nothing throws -> (null, null) -> break
         const int pc = c.i;
         // :221-249: theta_i = b_i / T_i,pc over T_i,pc != 0, else +inf
@@ -334,7 +295,7 @@ __device__ int child_lp(double*& cur, double*& oth, double* fcol, int Rc, int Cc
             }
         }
         if (!ip_any<NT>(notneg, red_i)) break;  // every theta < 0 (or none)
-        m = ip_cand_min<NT>(m, red_v, red_i);
+        m = group_cand_min<NT>(m, red_v, red_i);
         int pr = m.i;
         if (pr < 0) {
             pr = ip_min_int<NT>(first0, red_i);
@@ -434,7 +395,7 @@ __global__ __launch_bounds__(256) void k_bb_batch(BBBatchBufs B,
         ++processed;
         // RoundAllTableaux :1047, in place
         for (int x = lane; x < Rn * Cn; x += NT) P[x] = dn_round4(P[x]);
-        ip_sync<NT>();
+        group_sync<NT, kFenceWorkgroup>();
         const double objVal = dn_round4(P[Cn - 1]);  // GetObjective :892-897
         if (pruning && found && objVal <= best_z) continue;  // ShouldPrunebranch :985-1004
         // the decision values of CheckIntegerBasicVar :807-827 / ExtractSolution :899-921, IsInteger
@@ -461,8 +422,8 @@ __global__ __launch_bounds__(256) void k_bb_batch(BBBatchBufs B,
             }
         }
         const bool any_nonint = ip_any<NT>(nonint, red_i);
-        bv = ip_cand_min<NT>(bv, red_v, red_i);
-        ip_sync<NT>();
+        bv = group_cand_min<NT>(bv, red_v, red_i);
+        group_sync<NT, kFenceWorkgroup>();
         if (!any_nonint && objVal > best_z) {  // UpdateOptimalSolution :935-983
             best_z = objVal;
             found = 1;
@@ -504,7 +465,7 @@ __global__ __launch_bounds__(256) void k_bb_batch(BBBatchBufs B,
                 rd[2 * rid] = bound;
                 rd[2 * rid + 1] = z;
             }
-            ip_sync<NT>();
+            group_sync<NT, kFenceWorkgroup>();
             if (rc == kChildLimit) {
                 status = LPR_PIVOT_LIMIT;
                 break;
@@ -531,7 +492,7 @@ __global__ __launch_bounds__(256) void k_bb_batch(BBBatchBufs B,
             }
             ++sp;
         }
-        ip_sync<NT>();
+        group_sync<NT, kFenceWorkgroup>();
     }
 
     if (lane == 0) {
@@ -607,37 +568,21 @@ __global__ __launch_bounds__(256) void k_bb_batch_reset(BBBatchBufs B, int count
 }
 
 // ------------------------------------------------------------------------------------------
-// Launchers (bb_batch_engine.hip).  Dynamic LDS above 64 KiB needs the attribute once per device.
-static int bb_raise_lds(const void* fn, size_t bytes, unsigned long long* mask) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LPR_DEVICE_ERROR;
-    const unsigned long long bit = 1ull << dev;
-    if (__atomic_load_n(mask, __ATOMIC_ACQUIRE) & bit) return LPR_OK_OPTIMAL;
-    const hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)bytes);
-    if (err != hipSuccess) {
-        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed: %s", bytes,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    __atomic_fetch_or(mask, bit, __ATOMIC_ACQ_REL);
-    return LPR_OK_OPTIMAL;
-}
-
+// Launchers (bb_batch_engine.hip).
 int bb_batch_launch(int form, hipStream_t s, const BBBatchBufs& B, const int32_t* idx_in,
                     int n_in, int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles,
                     int max_rows) {
     static unsigned long long g_mask = 0;  // per device bit: the G attribute is set
     if (n_in <= 0) return LPR_OK_OPTIMAL;
-    if (form == kBBFormW) {
+    if (form == kFormW) {
         const size_t lds = (size_t)4 * slot_doubles * sizeof(double);
         hipLaunchKernelGGL((k_bb_batch<kWave, true>), dim3((n_in + 3) / 4), dim3(256), lds, s, B,
                            idx_in, n_in, idx_out, n_out, chunk, slot_doubles);
-    } else if (form == kBBFormG) {
+    } else if (form == kFormG) {
         const size_t lds = (size_t)slot_doubles * sizeof(double);
         if (lds > ((size_t)64 << 10)) {
-            const int rc = bb_raise_lds(reinterpret_cast<const void*>(&k_bb_batch<256, true>),
-                                        kBBBatchMaxLdsG, &g_mask);
+            const int rc = raise_dynamic_lds(
+                reinterpret_cast<const void*>(&k_bb_batch<256, true>), kBatchMaxLdsG, &g_mask);
             if (rc != LPR_OK_OPTIMAL) return rc;
         }
         hipLaunchKernelGGL((k_bb_batch<256, true>), dim3(n_in), dim3(256), lds, s, B, idx_in,

@@ -28,14 +28,12 @@ inline size_t sens_batch_aux_bytes(int rows, int cols) {  // LDS of both forms b
 inline size_t sens_batch_footprint_g(int rows, int cols) {  // bytes of dynamic LDS in form G
     return (size_t)rows * cols * sizeof(double) + sens_batch_aux_bytes(rows, cols);
 }
-inline bool sens_batch_fits_g(int rows, int cols) {
-    return sens_batch_footprint_g(rows, cols) <= kBatchMaxLdsG;
-}
 
 // Pivots per scenario per launch, by form (index kFormG / kFormH), and edits begun per scenario
 // per launch: no launch is unbounded, neither on a scenario that cycles nor on a script of many
 // edits that never pivot.
 constexpr int kSensBatchChunk[kNumForms] = {0, 128, 16};
+static_assert(sizeof(kSensBatchChunk) / sizeof(int) == kNumForms, "one chunk per form");
 constexpr int kSensBatchEditsPerLaunch = 64;
 
 constexpr double kSensBatchEps = kFoldEps;  // SensitivityAnalyzer.cs:20

@@ -1,8 +1,8 @@
 // sens_batch_engine.hip -- host side of the sensitivity scenario batch (include/lpr_engine.h,
 // lpr_sens_batch_*).  Every scenario runs its whole script on the device
 // with the rules of SensitivityAnalyzer; the host copies the base state in, relaunches the
-// bounded script kernel while scenarios are still running (one counter read per launch) and
-// copies results out.
+// bounded script kernel while scenarios are still running (BatchRunLists of batch_common.hpp,
+// with one form per call) and copies results out.
 #include "sens_batch_common.hpp"
 
 #include <algorithm>
@@ -34,9 +34,7 @@ struct lpr_sens_batch {
     std::vector<SensScenario> h_desc;  // host mirror, current after create and every run
     lpr_sens_edit* d_edits = nullptr;
     double* d_payload = nullptr;
-    int32_t* idx = nullptr;         // 2 x count: the running lists, in and out
-    int32_t* counter = nullptr;     // the running count (device)
-    int32_t* h_counter = nullptr;   // pinned
+    BatchRunLists run;  // the running lists and their counters; one form per call
 };
 
 namespace {
@@ -50,8 +48,8 @@ void sb_release_device(lpr_sens_batch* b) {
     SensBatchView& v = b->vw;
     hipFree(v.desc); hipFree(v.cur); hipFree(v.alt); hipFree(v.basic); hipFree(v.bcount);
     hipFree(v.snap); hipFree(v.sol); hipFree(v.log); hipFree(v.outcome); hipFree(v.edit_piv);
-    hipFree(b->d_edits); hipFree(b->d_payload); hipFree(b->idx); hipFree(b->counter);
-    if (b->h_counter) hipHostFree(b->h_counter);
+    hipFree(b->d_edits); hipFree(b->d_payload);
+    b->run.release();
     v.desc = nullptr;
     v.cur = v.alt = v.sol = nullptr;
     v.basic = v.bcount = v.snap = v.log = v.outcome = nullptr;
@@ -60,7 +58,6 @@ void sb_release_device(lpr_sens_batch* b) {
     v.payload = nullptr;
     b->d_edits = nullptr;
     b->d_payload = nullptr;
-    b->idx = b->counter = b->h_counter = nullptr;
 }
 
 int sb_fail(lpr_sens_batch* b, int rc) {
@@ -197,12 +194,7 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
     const int64_t te = std::max<int64_t>(total, 1);
     int rc = LPR_OK_OPTIMAL;
     auto get = [&](auto** p, int64_t elems, const char* what) {
-        if (rc != LPR_OK_OPTIMAL) return;
-        if (hipMalloc(reinterpret_cast<void**>(p), (size_t)elems * sizeof(**p)) != hipSuccess) {
-            *p = nullptr;
-            (void)hipGetLastError();
-            rc = sb_oom(what, elems);
-        }
+        dev_alloc(p, elems, what, &rc, sb_oom);
     };
     get(&v.desc, n, "descriptors");
     get(&v.cur, n * RC, "tableau slab");
@@ -216,10 +208,7 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
     get(&v.edit_piv, te, "pivot counts");
     get(&b->d_edits, te, "edits");
     if (npayload > 0) get(&b->d_payload, npayload, "payload");
-    get(&b->idx, 2 * n, "running lists");
-    get(&b->counter, 1, "counter");
-    if (rc == LPR_OK_OPTIMAL && hipHostMalloc(&b->h_counter, sizeof(int32_t)) != hipSuccess)
-        rc = sb_oom("pinned counter", 1);
+    b->run.alloc(count, &rc, sb_oom);
     if (rc != LPR_OK_OPTIMAL) return sb_fail(b, rc);
     v.edits = b->d_edits;
     v.payload = b->d_payload;
@@ -279,16 +268,6 @@ void sens_batch_orphan(lpr_sens_batch* b) {  // lpr_engine_close
 }
 }  // namespace lpr
 
-#define LPR_LIVE_SB(b)                                                                      \
-    do {                                                                                    \
-        if (!(b) || !(b)->eng) {                                                            \
-            set_error("scenario batch handle is null or orphaned: its engine has been "     \
-                      "closed");                                                            \
-            return LPR_BAD_ARGUMENT;                                                        \
-        }                                                                                   \
-        LPR_HIP(hipSetDevice((b)->eng->device));                                            \
-    } while (0)
-
 extern "C" {
 
 int lpr_sens_batch_create(lpr_sens* base, int32_t count, const int32_t* nedits,
@@ -311,12 +290,7 @@ int lpr_sens_batch_destroy(lpr_sens_batch* b) {
         hipSetDevice(b->eng->device);
         hipStreamSynchronize(b->eng->stream);
         sb_release_device(b);
-        auto& lv = b->eng->live_sens_batch;
-        for (size_t q = 0; q < lv.size(); ++q)
-            if (lv[q] == b) {
-                lv.erase(lv.begin() + q);
-                break;
-            }
+        unlist(b->eng->live_sens_batch, b);
     }
     delete b;
     return LPR_OK_OPTIMAL;
@@ -326,7 +300,7 @@ int lpr_sens_batch_destroy(lpr_sens_batch* b) {
 // :502-531, and in a grow batch :534-584, :609-659)
 int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
                        lpr_sens_batch_result* res) {
-    LPR_LIVE_SB(b);
+    LPR_LIVE_HANDLE(b, "scenario batch");
     if (!res) {
         set_error("lpr_sens_batch_run: null result");
         return LPR_BAD_ARGUMENT;
@@ -343,6 +317,7 @@ int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
     hipStream_t s = b->eng->stream;
     const int32_t count = b->count;
     const SensBatchView& v = b->vw;
+    std::vector<int32_t> lists[kNumForms];  // one form per call: one list is filled
     std::vector<int32_t> list;
     int64_t before = 0;
     bool inside = false;  // a scenario is stopped inside an edit: its slices belong to one form
@@ -355,34 +330,21 @@ int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
         d.pivot_stop = o.max_pivots > 0 ? d.pivots + o.max_pivots : 0;
         list.push_back(k);
     }
-    const bool fitG = sens_batch_fits_g(v.R, v.C);
-    int form = fitG ? kFormG : kFormH;
-    if (o.variant == 2 && fitG) form = kFormG;
-    if (o.variant == 3) form = kFormH;
+    int form = batch_pick_form(sens_batch_footprint_g(v.R, v.C), o.variant, false);
     if (inside && b->form != 0) form = b->form;
     b->form = form;
     res->form = form;
-    int32_t live = (int32_t)list.size();
-    int32_t* in = b->idx;
-    int32_t* outl = b->idx + count;
-    if (live > 0)
-        LPR_HIP(hipMemcpyAsync(in, list.data(), (size_t)live * sizeof(int32_t),
-                               hipMemcpyHostToDevice, s));
+    lists[form].swap(list);
+    int rc = b->run.upload(s, lists);
+    if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(v.desc, b->h_desc.data(), (size_t)count * sizeof(SensScenario),
                            hipMemcpyHostToDevice, s));
     const int chunk = o.chunk > 0 ? o.chunk : kSensBatchChunk[form];
     int launches = 0;
-    while (live > 0) {
-        LPR_HIP(hipMemsetAsync(b->counter, 0, sizeof(int32_t), s));
-        const int rc = sens_batch_launch(form, b->grow, s, v, in, live, outl, b->counter, chunk);
-        if (rc != LPR_OK_OPTIMAL) return rc;
-        ++launches;
-        LPR_HIP(hipMemcpyAsync(b->h_counter, b->counter, sizeof(int32_t), hipMemcpyDeviceToHost,
-                               s));
-        LPR_HIP(hipStreamSynchronize(s));
-        live = *b->h_counter;
-        std::swap(in, outl);
-    }
+    rc = b->run.rounds(s, [&](int f, const int32_t* in, int n_in, int32_t* out, int32_t* n_out) {
+        return sens_batch_launch(f, b->grow, s, v, in, n_in, out, n_out, chunk);
+    }, &launches);
+    if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(b->h_desc.data(), v.desc, (size_t)count * sizeof(SensScenario),
                            hipMemcpyDeviceToHost, s));
     LPR_HIP(hipStreamSynchronize(s));
@@ -414,7 +376,7 @@ int lpr_sens_batch_info(lpr_sens_batch* b, int32_t* count, int32_t* rows, int32_
 
 // The outcome of every edit and its pivots, packed as the scripts are
 int lpr_sens_batch_outcomes_read(lpr_sens_batch* b, int32_t* outcome, int64_t* pivots) {
-    LPR_LIVE_SB(b);
+    LPR_LIVE_HANDLE(b, "scenario batch");
     if (b->total_edits == 0) return LPR_OK_OPTIMAL;
     hipStream_t s = b->eng->stream;
     if (outcome)
@@ -429,7 +391,7 @@ int lpr_sens_batch_outcomes_read(lpr_sens_batch* b, int32_t* outcome, int64_t* p
 
 // CurrentZ :728, solutionVector.Count and basicVars of every scenario
 int lpr_sens_batch_state_read(lpr_sens_batch* b, double* z, int32_t* nsol, int32_t* basic) {
-    LPR_LIVE_SB(b);
+    LPR_LIVE_HANDLE(b, "scenario batch");
     for (int32_t k = 0; k < b->count; ++k) {
         if (z) z[k] = b->h_desc[(size_t)k].z;
         if (nsol) nsol[k] = b->h_desc[(size_t)k].nsol;
@@ -464,7 +426,7 @@ int lpr_sens_batch_shape_read(lpr_sens_batch* b, int32_t* rows, int32_t* cols, i
 // CurrentSolutionVector :729 of scenario k
 int lpr_sens_batch_solution_read(lpr_sens_batch* b, int32_t k, double* x, int32_t cap,
                                  int32_t* count) {
-    LPR_LIVE_SB(b);
+    LPR_LIVE_HANDLE(b, "scenario batch");
     if (k < 0 || k >= b->count || cap < 0 || !count) {
         set_error("lpr_sens_batch_solution_read: scenario %d out of range (0..%d), cap %d or null "
                   "count", k, b->count - 1, cap);
@@ -482,7 +444,7 @@ int lpr_sens_batch_solution_read(lpr_sens_batch* b, int32_t k, double* x, int32_
 
 // CurrentTableau :727 of scenario k
 int lpr_sens_batch_tableau_read(lpr_sens_batch* b, int32_t k, double* rowmajor) {
-    LPR_LIVE_SB(b);
+    LPR_LIVE_HANDLE(b, "scenario batch");
     if (k < 0 || k >= b->count || !rowmajor) {
         set_error("lpr_sens_batch_tableau_read: scenario %d out of range (0..%d) or null output",
                   k, b->count - 1);
@@ -500,7 +462,7 @@ int lpr_sens_batch_tableau_read(lpr_sens_batch* b, int32_t k, double* rowmajor) 
 // The pivot log of scenario k, as lpr_sens_log_read
 int lpr_sens_batch_log_read(lpr_sens_batch* b, int32_t k, int32_t* triples, int64_t cap,
                             int64_t* count) {
-    LPR_LIVE_SB(b);
+    LPR_LIVE_HANDLE(b, "scenario batch");
     if (k < 0 || k >= b->count || cap < 0 || !count) {
         set_error("lpr_sens_batch_log_read: scenario %d out of range (0..%d), cap %lld or null "
                   "count", k, b->count - 1, (long long)cap);

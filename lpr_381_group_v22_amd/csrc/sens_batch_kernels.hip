@@ -12,8 +12,8 @@
 //                        kGrow (lpr_sens_batch_create_grow): the shape is the scenario's own, and
 //                        AddNewActivity (:534-584) / AddNewConstraint (:609-659) grow it in place
 //   k_sens_batch_init    the base state copied into every scenario
+#include "batch_device.hpp"
 #include "sens_batch_common.hpp"
-#include "select_common.hpp"
 
 #pragma clang fp contract(off)
 
@@ -636,26 +636,16 @@ __global__ __launch_bounds__(256) void k_sens_batch_init(SensBatchView vw, int c
     const int k = blockIdx.x;
     if (k >= count) return;
     const int tid = threadIdx.x;
-    const int m = R - 1, RC = R * C;
+    const int m = R - 1;
     double* T = vw.cur + (size_t)k * vw.R * vw.C;
-    int i = tid / C, j = tid - (tid / C) * C;
-    const int di = 256 / C, dj = 256 - (256 / C) * C;
-    for (int x = tid; x < RC; x += 256) {
-        T[x] = baseT[(size_t)i * ld + j];
-        i += di;
-        j += dj;
-        if (j >= C) {
-            j -= C;
-            ++i;
-        }
-    }
+    for_each_ij<256>(R, C, tid, [&](int x, int i, int j) { T[x] = baseT[(size_t)i * ld + j]; });
     for (int q = tid; q < m; q += 256) vw.basic[(size_t)k * (vw.R - 1) + q] = base_basic[q];
     for (int q = tid; q < C; q += 256) vw.bcount[(size_t)k * vw.C + q] = base_bcount[q];
     for (int q = tid; q < nsol; q += 256) vw.sol[(size_t)k * vw.sol_cap + q] = base_sol[q];
 }
 
 // ------------------------------------------------------------------------------------------
-// Launchers (sens_batch_engine.hip).  Dynamic LDS above 64 KiB needs the attribute once per device.
+// Launchers (sens_batch_engine.hip).
 int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& vw,
                       const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
                       int chunk) {
@@ -664,23 +654,11 @@ int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& v
     const auto kern_g = grow ? &k_sens_batch<true, true> : &k_sens_batch<true, false>;
     const auto kern_h = grow ? &k_sens_batch<false, true> : &k_sens_batch<false, false>;
     if (form == kFormG) {
-        unsigned long long& g_mask = g_masks[grow ? 1 : 0];
         const size_t lds = sens_batch_footprint_g(vw.R, vw.C);
         if (lds > ((size_t)64 << 10)) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LPR_DEVICE_ERROR;
-            const unsigned long long bit = 1ull << dev;
-            if (!(__atomic_load_n(&g_mask, __ATOMIC_ACQUIRE) & bit)) {
-                const hipError_t err = hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(kern_g),
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBatchMaxLdsG);
-                if (err != hipSuccess) {
-                    set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed: %s",
-                              (size_t)kBatchMaxLdsG, hipGetErrorString(err));
-                    return LPR_DEVICE_ERROR;
-                }
-                __atomic_fetch_or(&g_mask, bit, __ATOMIC_ACQ_REL);
-            }
+            const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kern_g), kBatchMaxLdsG,
+                                             &g_masks[grow ? 1 : 0]);
+            if (rc != LPR_OK_OPTIMAL) return rc;
         }
         hipLaunchKernelGGL(kern_g, dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in, idx_out, n_out,
                            chunk);

@@ -227,6 +227,63 @@ def test_max_pivots_resume_and_chunk(engine, oracle):
     assert [b.PivotLog(k).tobytes() for k in range(b.Count)] == want_log
 
 
+def _mixed_form_models():
+    """LPs of all three forms: W (m 3-6, n 3-8), G (m = 32, n = 64: rows * (cols + 1) = 3234
+    doubles) and H (m = 100, n = 120: 22 422 > 20 352), tie-heavy and dense."""
+    return [lp_cases.tie_heavy(4, 6, 1), lp_cases.random_dense(5, 8, 2), lp_cases.tie_heavy(6, 3, 3),
+            lp_cases.random_dense(32, 64, 5), lp_cases.tie_heavy(32, 64, 6),
+            lp_cases.random_dense(100, 120, 7)]
+
+
+def _form_of(ref):
+    R, Cc = ref["T"].shape
+    doubles = R * (Cc + 1)
+    return 0 if doubles <= 2016 else (1 if doubles <= 20352 else 2)
+
+
+def expected_launches(forms, pivots, chunk):
+    """Launches of one Solve call: the sum over the forms of max over the form's LPs of
+    P // chunk + 1, P the pivots the LP makes in the call.  A launch runs at most `chunk`
+    iterations of the Solve() loop per LP, the iteration that ends the LP -- it finds no entering
+    column or no leaving row, or meets max_pivots in front of a pivot -- is one of them, so an LP
+    needs P + 1 iterations; every round launches each form that still has an LP once."""
+    total = 0
+    for f in set(forms):
+        total += max(p // chunk + 1 for ff, p in zip(forms, pivots) if ff == f)
+    return total
+
+
+def test_exact_launch_counts_through_mixed_forms(engine, oracle):
+    from lpr_381_group_v22_amd import PrimalSimplexBatch
+    cases = _mixed_form_models()
+    refs = [oracle_from_model(oracle, *c) for c in cases]
+    forms = [_form_of(r) for r in refs]
+    P = [r["pivots"] for r in refs]
+    assert forms == [0, 0, 0, 1, 1, 2] and max(P) < CAP and all(r["status"] == 0 for r in refs)
+    for chunk in (1, 3):
+        b = PrimalSimplexBatch(models_of(cases), engine=engine, log_cap=CAP)
+        res = b.Solve(max_pivots=CAP, chunk=chunk)
+        print("chunk", chunk, "launches", res.launches, "pivots", res.pivots)
+        check_batch(b, refs)
+        assert res.pivots == sum(P)
+        assert res.launches == expected_launches(forms, P, chunk), (chunk, res.launches)
+        b.destroy()
+    # two calls of at most two pivots each, the second resuming the LPs stopped at the limit
+    b = PrimalSimplexBatch(models_of(cases), engine=engine, log_cap=CAP)
+    left = list(P)
+    for call in range(2):
+        alive = [k for k in range(len(P)) if call == 0 or P[k] > 2 * call]
+        step = [min(left[k], 2) for k in alive]
+        res = b.Solve(max_pivots=2, chunk=1)
+        print("call", call, "launches", res.launches, "pivots", res.pivots)
+        assert res.pivots == sum(step)
+        assert res.launches == expected_launches([forms[k] for k in alive], step, 1), call
+        for k, d in zip(alive, step):
+            left[k] -= d
+    check_batch(b, [oracle_from_model(oracle, *c, max_pivots=4) for c in cases])
+    b.destroy()
+
+
 # ------------------------------------------------------------------------------ 5. short log
 def test_log_cap_keeps_the_prefix(engine, oracle):
     from lpr_381_group_v22_amd import PrimalSimplexBatch

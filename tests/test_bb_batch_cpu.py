@@ -73,7 +73,7 @@ def test_bb_batch_kernels_build_without_scratch(tmp_path):
         priv = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1))
         lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1))
         assert priv == 0, (name, priv)
-        assert lds <= 1024, (name, lds)  # the reserved workgroup scratch (kBBBatchWgScratch)
+        assert lds <= 1024, (name, lds)  # the reserved workgroup scratch (kBatchWgScratch)
         assert lds + 159 * 1024 <= 160 * 1024
 
 
@@ -82,8 +82,9 @@ def test_sample_model_takes_form_w():
     2 * 28 * 34 + 28 doubles, within a quarter of 63 KiB."""
     fp = 8 * (2 * 28 * 34 + 28)
     assert fp <= (64 * 1024 - 1024) // 4
-    src = open(os.path.join(CSRC, "bb_batch_common.hpp")).read()
-    assert "constexpr size_t kBBBatchMaxLdsW = (kBBBatchWgLdsW - kBBBatchWgScratch) / 4;" in src
+    assert '#include "batch_common.hpp"' in open(os.path.join(CSRC, "bb_batch_common.hpp")).read()
+    src = open(os.path.join(CSRC, "batch_common.hpp")).read()  # the one owner of the form limits
+    assert "constexpr size_t kBatchMaxLdsW = (kBatchWgLdsW - kBatchWgScratch) / 4;" in src
 
 
 def test_pack_roots_packs_and_refuses():

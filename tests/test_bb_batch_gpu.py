@@ -13,7 +13,7 @@ import bb_cases
 pytestmark = pytest.mark.gpu
 
 PIV_CAP = 1 << 16
-W_MAX, G_MAX = (64 * 1024 - 1024) // 4, 160 * 1024 - 1024  # kBBBatchMaxLdsW / kBBBatchMaxLdsG
+W_MAX, G_MAX = (64 * 1024 - 1024) // 4, 160 * 1024 - 1024  # kBatchMaxLdsW / kBatchMaxLdsG
 
 
 def footprint_bytes(T, cap):
@@ -167,6 +167,55 @@ def test_chunk_one_short_trace_and_second_run(engine, oracle):
     second = bb.result_arrays()
     for key in first:
         assert first[key].tobytes() == second[key].tobytes(), key
+    bb.destroy()
+
+
+def _optimal_roots(oracle):
+    """IPs of all three forms at node cap 20 whose search ends by emptying its stack: neither the
+    node cap nor a child pivot limit is met.  Form H: a product-route root made tall."""
+    if "optimal" not in _ROOTS:
+        keep = ("knapsack_sample", "binary_4v1c_s0", "frac_4v2c_s10", "tall_frac6x3_nv_all",
+                "tall_bin8x3_nv_all")
+        out = [r for r in bb_roots(oracle) + edge_roots(oracle, 20) if r[0] in keep]
+        T, _ = bb_cases._product_root(oracle, bb_cases.fractional_program, 6, 3, 11)
+        t = bb_cases._tall(T, 270, 0)
+        out.append(("tall_frac6x3_280_rows", t, t.shape[1] - 1))
+        T, _ = bb_cases._product_root(oracle, bb_cases.random_binary_program, 8, 3, 3)
+        t = bb_cases._tall(T, 300, 1)
+        out.append(("tall_bin8x3_312_rows", t, t.shape[1] - 1))
+        _ROOTS["optimal"] = out
+    return _ROOTS["optimal"]
+
+
+def expected_launches(forms, processed, chunk):
+    """Launches of one Run call: the sum over the forms of max over the form's IPs of
+    processed // chunk + 1.  A launch runs at most `chunk` iterations of the DFS loop per IP; an
+    iteration pops one node, and the one that finds the stack empty ends the IP, so an IP needs
+    processed + 1 iterations; every round launches each form that still has an IP once.  (A run
+    always starts from the roots, so there is no resumed call to count.)"""
+    total = 0
+    for f in set(forms):
+        total += max(p // chunk + 1 for ff, p in zip(forms, processed) if ff == f)
+    return total
+
+
+def test_exact_launch_counts_through_mixed_forms(engine, oracle):
+    cap = 20
+    roots = _optimal_roots(oracle)
+    refs = [oracle.bb_solve(T, nv, node_cap=cap, piv_cap=PIV_CAP) for _, T, nv in roots]
+    forms = [form_of(T, cap) for _, T, _ in roots]
+    pops = [r["processed"] for r in refs]
+    assert sorted(set(forms)) == [0, 1, 2] and all(r["status"] == 0 for r in refs)
+    assert all(rec["status"] != 5 for r in refs for rec in r["records"])  # no child pivot limit
+    assert len(set(pops)) > 3
+    bb = make(engine, roots, cap)
+    for chunk in (1, 3):
+        res = bb.Run(chunk=chunk)
+        print("chunk", chunk, "launches", res.launches, "pops", res.pops)
+        assert res.done == len(roots) and res.node_cap == 0 and res.pivot_limit == 0
+        check_batch(bb, roots, oracle, cap, refs=refs)
+        assert res.pops == sum(pops) and res.pivots == sum(len(r["trace"]) for r in refs)
+        assert res.launches == expected_launches(forms, pops, chunk), (chunk, res.launches)
     bb.destroy()
 
 

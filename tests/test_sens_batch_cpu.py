@@ -94,8 +94,10 @@ def test_pack_scripts_packs_and_refuses():
 def test_form_rule_matches_the_header():
     """footprint_g is sens_batch_footprint_g, and G's budget is kBatchMaxLdsG."""
     from lpr_381_group_v22_amd import sens_batch as sb
-    src = open(os.path.join(CSRC, "sens_batch_common.hpp")).read()
-    assert "sens_batch_footprint_g(rows, cols) <= kBatchMaxLdsG" in src
+    src = open(os.path.join(CSRC, "sens_batch_engine.hip")).read()
+    assert "batch_pick_form(sens_batch_footprint_g(v.R, v.C), o.variant, false)" in src
+    src = open(os.path.join(CSRC, "batch_common.hpp")).read()
+    assert "fitG = bytes <= kBatchMaxLdsG" in src
     assert sb.MAX_LDS_G == 160 * 1024 - 1024
     assert sb.fits_g(8, 14) and sb.fits_g(33, 97) and not sb.fits_g(257, 769)
     ne = sens_batch_cases.largest_g_extra(60)

@@ -142,6 +142,86 @@ def test_resumption_one_pivot_per_call(engine, sweep, variant):
     b.destroy()
 
 
+def pivot_attempts(ref):
+    """The pivots a script asks for, in order: 'p' for one that is made, 'f' for one that fails
+    (no entering column, no leaving row, a zero pivot: the edit ends with an outcome other than 0,
+    which ChangeRHS reports as rolled back).  An edit that is refused (-1) asks for none."""
+    _, outs, pivs, _ = ref
+    return "".join("p" * n + ("f" if o not in (0, -1) else "") for o, n in zip(outs, pivs))
+
+
+def expected_launches(seqs, chunk, max_pivots=0):
+    """(launches of one Run call, where each scenario stands after it), from where the scenarios
+    stand in their pivot_attempts (None: not in this call).
+
+    A launch goes on until a scenario's script has ended or the scenario asks for a pivot after
+    it has made `chunk` of them in this launch; a pivot that fails is asked for like any other but
+    is not counted.  So a scenario that makes P pivots in a call takes max(1, ceil(P / chunk))
+    launches, and one more when P is a multiple of chunk, not 0, and a failing pivot follows the
+    last one made.  The pivot limit of the call is looked at after the chunk, in front of every
+    pivot asked for: the scenario leaves the call there.  The call takes the maximum over its
+    scenarios (one form, so one launch per round)."""
+    most, after = 0, []
+    for seq, pos in seqs:
+        if pos is None:
+            after.append(None)
+            continue
+        launches, done, made = 1, 0, 0
+        while pos < len(seq):
+            if done >= chunk:
+                launches, done = launches + 1, 0
+            if max_pivots > 0 and made >= max_pivots:
+                break
+            if seq[pos] == "p":
+                done, made = done + 1, made + 1
+            pos += 1
+        most = max(most, launches)
+        after.append(pos if pos < len(seq) else None)
+    return most, after
+
+
+def test_exact_launch_counts(engine, sweep):
+    base, scripts, refs = sweep
+    seqs = [pivot_attempts(r) for r in refs]
+    assert any(q.endswith("pf") for q in seqs) and any(q.endswith("p") for q in seqs)
+    assert sum(q.count("p") for q in seqs) == 59 and "" in seqs
+    for chunk in (1, 3):
+        b = _batch(engine, base, scripts)
+        res = b.Run(chunk=chunk, variant=VARIANT_G)
+        want, _ = expected_launches([(q, 0) for q in seqs], chunk)
+        print("chunk", chunk, "launches", res.launches, "expected", want)
+        assert res.finished == 32 and res.pivots == 59
+        _check_all(b, refs, ("launch counts", chunk))
+        assert res.launches == want, (chunk, res.launches, want)
+        b.destroy()
+    # calls of at most two pivots each, every call resuming the scenarios stopped at the limit
+    b = _batch(engine, base, scripts)
+    at = [(q, 0) for q in seqs]
+    for call in range(2):
+        want, after = expected_launches(at, 1, max_pivots=2)
+        res = b.Run(max_pivots=2, chunk=1, variant=VARIANT_G)
+        print("call", call, "launches", res.launches, "expected", want)
+        assert res.running == sum(a is not None for a in after)
+        assert res.launches == want, (call, res.launches, want)
+        at = [(q, a) for q, a in zip(seqs, after)]
+    assert res.running > 0  # the second call resumed scenarios and stopped some again
+    b.Run()
+    _check_all(b, refs, "launch counts, resumed")
+    b.destroy()
+
+
+def test_form_g_above_64_kib_twice(engine, oracle):
+    """A 64 x 129 base (68 360 bytes of dynamic LDS in form G, above the 64 KiB a kernel gets
+    without the attribute) with a three-edit script, twice: the second batch finds the attribute
+    set."""
+    from lpr_381_group_v22_amd.sens_batch import footprint_g
+    base, scripts = cases.threshold_case(63, 2, 43)
+    assert base[0].shape == (64, 129) and 64 * 1024 < footprint_g(64, 129) <= 159 * 1024
+    for run in range(2):
+        _run_and_check(engine, oracle, ("G above 64 KiB", run), base, [scripts[0][:3]],
+                       form=FORM_G, variant=VARIANT_G)
+
+
 def test_stale_base(engine, oracle):
     """The base is a handle on which a change_rhs with a pivot has run, so its basicVars were last
     written by that pivot, not by a rebuild: it stores column 9 for row 3 where a rebuild would

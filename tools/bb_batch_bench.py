@@ -38,7 +38,7 @@ import numpy as np  # noqa: E402
 CHECK = 256
 NODE_CAP = 20
 TRACE_CAP = 256
-W_MAX, G_MAX = (64 * 1024 - 1024) // 4, 160 * 1024 - 1024  # kBBBatchMaxLdsW / kBBBatchMaxLdsG
+W_MAX, G_MAX = (64 * 1024 - 1024) // 4, 160 * 1024 - 1024  # kBatchMaxLdsW / kBatchMaxLdsG
 
 
 def gen_models(name: str, seed: int):
