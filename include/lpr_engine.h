@@ -814,6 +814,85 @@ int lpr_sens_batch_tableau_read(lpr_sens_batch* b, int32_t k, double* rowmajor);
 int lpr_sens_batch_log_read(lpr_sens_batch* b, int32_t k, int32_t* triples, int64_t cap,
                             int64_t* count);
 
+
+/* ------------------------------------------------------------- cutting-plane batch */
+
+/* Many option-4 tableaux per device call.  One handle holds `count`
+ * independent tableaux (row 0 = objectiveRow, rows 1.. = constraintRows, what lpr_cutting_plane
+ * takes); one run call takes every item through the whole CuttingPlaneSolution recursion
+ * (IntegerProgramming/CuttingPlaneSolver.cs:64-229) on the device: the Gomory cut, the pivot on
+ * it, the dual and primal clean-up solves and the decision to cut again, with no host step per
+ * cut or per pivot.  Item k ends with the exit code, the cuts, the log and the grown tableau that
+ * lpr_cutting_plane gives for it alone on a fresh lpr_tableau.  One 256-lane workgroup per item,
+ * its tableau in LDS (form G) or in its slice of a global slab (form H), picked per item by the
+ * tableau at full row capacity.  The reference has no batch mode; every call cites the C# lines
+ * it repeats per item. */
+typedef struct lpr_cut_batch lpr_cut_batch;
+
+/* objectiveRow and constraintRows per item (:64-70): packed rows[k] x cols[k] row-major blocks.
+ * max_cuts is the row capacity added per item over the handle's life (<= 0: 64, as in
+ * lpr_cutting_plane).  rows[k] >= 2 (ArgumentException :68), cols[k] >= 2, rows[k] + max_cuts <=
+ * 1024 and cols[k] <= 2048; anything else is LPR_BAD_ARGUMENT naming the item (a larger tableau
+ * goes through lpr_cutting_plane).  log_cap: triples kept per item (0: 4 * (rows + max_cuts +
+ * cols), at most 4096; the count is always exact). */
+int lpr_cut_batch_create(lpr_engine* e, int32_t count, const int32_t* rows, const int32_t* cols,
+                         const double* tableaux, int32_t max_cuts, int32_t log_cap,
+                         lpr_cut_batch** out);
+/* The same from the FinalTableau of every LP of a solved lpr_batch (what option 4 cuts,
+ * Program.cs:417-428), device to device.  An LP that was never solved or stopped at
+ * LPR_PIVOT_LIMIT has none: LPR_BAD_ARGUMENT naming it.  The new handle does not depend on
+ * `lps`. */
+int lpr_cut_batch_from_batch(lpr_batch* lps, int32_t max_cuts, int32_t log_cap,
+                             lpr_cut_batch** out);
+/* After lpr_engine_close the handle is orphaned: every call but this one is LPR_BAD_ARGUMENT. */
+int lpr_cut_batch_destroy(lpr_cut_batch* b);
+
+typedef struct lpr_cut_batch_opts {
+    int32_t mode;         /* 0 CuttingPlaneSolution :64-229; 1 DualSimplexSolver.Solve
+                             (DualSimplex.cs:14-114); 2 PrimalSimplexSolver2.Solve
+                             (PrimalSimplexSolver2.cs:46-97)                                     */
+    int32_t max_cuts;     /* mode 0: cuts per item for this call (<= 0: all the capacity left)   */
+    int64_t hard_cap;     /* extra pivot limit per inner solver run, as in the single calls
+                             (<= 0: none)                                                        */
+    int32_t max_iters;    /* modes 1, 2: maxIters (:108 / :90); mode 0 uses 10000 (:190, :200)   */
+    int32_t print_steps;  /* modes 1, 2: `iter` advances only when set (:94 / :75); mode 0: set  */
+    int32_t chunk;        /* pivots per item per launch (0: by form)       */
+    int32_t variant;      /* 0 auto; 2 / 3 force form G / H on the items that fit (tests and
+                             tuning only, same bits)                                             */
+} lpr_cut_batch_opts;
+
+typedef struct lpr_cut_batch_result {
+    int32_t by_code[8];  /* items per exit code 0..7 (mode 0) or per lpr_status (modes 1, 2)     */
+    int32_t launches;    /* kernels launched by this call                                        */
+    int32_t items_g;     /* items this call ran in form G ...                                    */
+    int32_t items_h;     /* ... and in form H                                                    */
+    int32_t reserved;
+    int64_t cuts;        /* cuts added by this call, all items                                   */
+    int64_t pivots;      /* pivots performed by this call, all items and all three kinds         */
+} lpr_cut_batch_result;
+
+/* One call of lpr_cutting_plane (mode 0), lpr_dual_solve (mode 1) or lpr_primal2_solve (mode 2)
+ * per item, on the tableau the last call left: logs append, rows stay grown, and a mode-0 call
+ * adds at most min(opts.max_cuts, capacity left) cuts per item -- an item with none left ends
+ * with exit 1 if all RHS are integral and with exit 6 otherwise, in that order.  opts may be NULL
+ * (mode 0, every default).  Returns LPR_OK_OPTIMAL unless the call itself failed. */
+int lpr_cut_batch_run(lpr_cut_batch* b, const lpr_cut_batch_opts* opts, lpr_cut_batch_result* res);
+/* Per item: the exit code of lpr_cutting_plane (0..7, mode 0) or the lpr_status (modes 1, 2) of
+ * the last call, its cuts, the rows now and the exact number of log triples; any may be NULL. */
+int lpr_cut_batch_result_read(lpr_cut_batch* b, int32_t* code, int32_t* cuts, int32_t* rows,
+                              int64_t* log_count);
+/* Item k: rows now x cols, its row capacity and its log capacity; any may be NULL. */
+int lpr_cut_batch_shape(lpr_cut_batch* b, int32_t k, int32_t* rows, int32_t* cols,
+                        int32_t* row_cap, int32_t* log_cap);
+/* Item k's own grown tableau: rows x cols row-major (lpr_cut_batch_shape). */
+int lpr_cut_batch_tableau_read(lpr_cut_batch* b, int32_t k, double* rowmajor);
+/* (kind 0 dual / 1 primal2 / 2 cut, row in the C#'s own numbering, column) of item k's pivots,
+ * as lpr_cut_log_read: *count = all of them, the first min(*count, log_cap, cap) copied. */
+int lpr_cut_batch_log_read(lpr_cut_batch* b, int32_t k, int32_t* triples, int64_t cap,
+                           int64_t* count);
+/* T[0, cols - 1] of every item (what lpr_solve_result.z is in lpr_dual_solve). */
+int lpr_cut_batch_z_read(lpr_cut_batch* b, double* z);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,12 @@ namespace LPR_381_Group_V22.Native
     internal struct LprSensBatchResult { public int finished, running, launches, form; public long pivots; }
 
     [StructLayout(LayoutKind.Sequential)]
+    internal struct LprCutBatchOpts { public int mode, max_cuts; public long hard_cap; public int max_iters, print_steps, chunk, variant; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprCutBatchResult { public int code0, code1, code2, code3, code4, code5, code6, code7, launches, items_g, items_h, reserved; public long cuts, pivots; }
+
+    [StructLayout(LayoutKind.Sequential)]
     internal struct LprBbBatchResult { public int done, node_cap, pivot_limit, launches; public long pops, pivots; }
 
     [StructLayout(LayoutKind.Sequential)]
@@ -253,6 +259,17 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_solution_read(IntPtr sensBatch, int k, double[] x, int cap, out int count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_tableau_read(IntPtr sensBatch, int k, [Out] double[,] rowmajor);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_log_read(IntPtr sensBatch, int k, int[] triples, long cap, out long count);
+
+        // ---- Cutting-plane batch (DESIGN.md section 15): many option-4 tableaux per call ----
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_create(IntPtr engine, int count, int[] rows, int[] cols, double[] tableaux, int max_cuts, int log_cap, out IntPtr cutBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_from_batch(IntPtr batch, int max_cuts, int log_cap, out IntPtr cutBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_destroy(IntPtr cutBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_run(IntPtr cutBatch, ref LprCutBatchOpts opts, out LprCutBatchResult res);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_result_read(IntPtr cutBatch, int[] code, int[] cuts, int[] rows, long[] log_count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_shape(IntPtr cutBatch, int k, out int rows, out int cols, out int row_cap, out int log_cap);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_tableau_read(IntPtr cutBatch, int k, [Out] double[,] rowmajor);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_log_read(IntPtr cutBatch, int k, int[] triples, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_z_read(IntPtr cutBatch, double[] z);
 
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 

@@ -9,6 +9,7 @@ from .bb_batch import BranchAndBoundBatch, solve_integer_programs
 from .branch_and_bound import (BranchAndBoundAdapter, BranchBoundTree, Comm,
                                solve_level_sync_native, solve_level_synchronous,
                                torch_collectives)
+from .cut_batch import CuttingPlaneBatch, pack_tableaux
 from .input_file_parser import Constraint, InputFileParser
 from .knapsack import KnapsackBranchBoundSimplex, KnapsackBranchBoundSolver
 from .primal_batch import PrimalSimplexBatch, pack_models
@@ -23,5 +24,6 @@ __all__ = [
     "BranchAndBoundAdapter", "BranchBoundTree", "solve_level_synchronous", "torch_collectives",
     "Comm", "solve_level_sync_native", "KnapsackBranchBoundSimplex", "KnapsackBranchBoundSolver",
     "PrimalSimplexBatch", "pack_models", "BranchAndBoundBatch", "solve_integer_programs",
-    "SensitivityBatch", "SensitivityGrowBatch", "pack_scripts", "pack_grow_scripts", "_native",
+    "SensitivityBatch", "SensitivityGrowBatch", "pack_scripts", "pack_grow_scripts",
+    "CuttingPlaneBatch", "pack_tableaux", "_native",
 ]

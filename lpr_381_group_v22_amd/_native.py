@@ -222,6 +222,30 @@ class SensBatchResult(C.Structure):
     ]
 
 
+class CutBatchOpts(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("max_cuts", C.c_int32),
+        ("hard_cap", C.c_int64),
+        ("max_iters", C.c_int32),
+        ("print_steps", C.c_int32),
+        ("chunk", C.c_int32),
+        ("variant", C.c_int32),
+    ]
+
+
+class CutBatchResult(C.Structure):
+    _fields_ = [
+        ("by_code", C.c_int32 * 8),
+        ("launches", C.c_int32),
+        ("items_g", C.c_int32),
+        ("items_h", C.c_int32),
+        ("reserved", C.c_int32),
+        ("cuts", C.c_int64),
+        ("pivots", C.c_int64),
+    ]
+
+
 class BBResult(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -368,6 +392,15 @@ SIGNATURES = {
     "lpr_sens_batch_solution_read": (C.c_int, [_P, C.c_int32, _D, C.c_int32, _I32]),
     "lpr_sens_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
     "lpr_sens_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
+    "lpr_cut_batch_create": (C.c_int, [_P, C.c_int32, _I32, _I32, _D, C.c_int32, C.c_int32, _PP]),
+    "lpr_cut_batch_from_batch": (C.c_int, [_P, C.c_int32, C.c_int32, _PP]),
+    "lpr_cut_batch_destroy": (C.c_int, [_P]),
+    "lpr_cut_batch_run": (C.c_int, [_P, C.POINTER(CutBatchOpts), C.POINTER(CutBatchResult)]),
+    "lpr_cut_batch_result_read": (C.c_int, [_P, _I32, _I32, _I32, _I64]),
+    "lpr_cut_batch_shape": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32, _I32]),
+    "lpr_cut_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
+    "lpr_cut_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
+    "lpr_cut_batch_z_read": (C.c_int, [_P, _D]),
 }
 
 

@@ -1,6 +1,6 @@
 // batch_common.hpp -- definitions shared by the batched primal simplex (batch_engine.hip, host)
-// and its kernels (batch_kernels.hip), and what the three batch engines (LP, B&B: bb_batch_*,
-// scenarios: sens_batch_*) have in common on the host: the forms and the rule that picks one, the
+// and its kernels (batch_kernels.hip), and what the four batch engines (LP, B&B: bb_batch_*,
+// scenarios: sens_batch_*, cutting plane: cut_batch_*) have in common on the host: the forms and the rule that picks one, the
 // running-list driver, the dynamic-LDS attribute and the handle plumbing.  The device side of what
 // they share is batch_device.hpp.  Not part of the ABI (include/lpr_engine.h is).
 #pragma once

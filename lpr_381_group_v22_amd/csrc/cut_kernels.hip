@@ -9,8 +9,7 @@
 // and in one pass by eps_fold (fold_common.hpp), as in the sensitivity re-solve.  Not pipelined:
 // this path is dead code in the reference's menu (Program.cs:417-428); parity is the bar here, not
 // the roofline.
-#include "engine_common.hpp"
-#include "fold_common.hpp"
+#include "cut_common.hpp"
 #include "select_common.hpp"
 
 #include <new>
@@ -19,8 +18,6 @@
 
 namespace lpr {
 
-constexpr double kCutEps = 1e-9;  // DualSimplex.cs:8, PrimalSimplexSolver2.cs, CuttingPlaneSolver.cs:10
-static_assert(kCutEps == kFoldEps, "eps_fold replays the cut path's EPS band");
 constexpr int kCutK = 16;  // eps_fold candidates cached per lane: 16 384 rows / columns in one pass
 
 struct CutState {
@@ -59,8 +56,6 @@ __device__ __forceinline__ int fold_dual_column(const double* __restrict__ T, in
     return eps_fold<kCutK>(
         0, C - 1, INFINITY, [&](int j) { return dual_ratio(T, ld, prow, j); }, lds, lds_v);
 }
-
-enum : int { kCutDual = 0, kCutPrimal2 = 1 };
 
 // One loop head of DualSimplexSolver.Solve (:24-112) or PrimalSimplexSolver2.Solve (:49-96).
 __global__ __launch_bounds__(1024) void k_cut_select(double* __restrict__ T, int ld, int R, int C,
@@ -204,12 +199,6 @@ __global__ __launch_bounds__(256) void k_cut_update(double* __restrict__ T, int 
         x.y = x.y - py;
         T2[(size_t)i * ld2 + c2] = x;
     }
-}
-
-__device__ __forceinline__ double cut_frac(double a) {  // CuttingPlaneSolver.cs:12-17
-    const double f = a - floor(a);
-    if (fabs(f) < kCutEps || fabs(1 - f) < kCutEps) return 0.0;
-    return f;
 }
 
 // CuttingPlaneSolution steps 1-6 (:76-138): choose the constraint whose fractional RHS is closest

@@ -81,6 +81,8 @@ void batch_orphan(lpr_batch* b);
 void bb_batch_orphan(lpr_bb_batch* b);
 // sens_batch_engine.hip
 void sens_batch_orphan(lpr_sens_batch* b);
+// cut_batch_engine.hip
+void cut_batch_orphan(lpr_cut_batch* b);
 }  // namespace lpr
 // cut_kernels.hip
 void lpr_cut_release(lpr_tableau* t);
@@ -753,6 +755,8 @@ int lpr_engine_close(lpr_engine* e) {
     e->live_bb_batch.clear();
     for (lpr_sens_batch* b : e->live_sens_batch) sens_batch_orphan(b);
     e->live_sens_batch.clear();
+    for (lpr_cut_batch* b : e->live_cut_batch) cut_batch_orphan(b);
+    e->live_cut_batch.clear();
     if (e->stream) {
         hipStreamSynchronize(e->stream);
         hipStreamDestroy(e->stream);

@@ -19,39 +19,6 @@
 
 namespace lpr {
 
-// The C#'s "take idx when val(idx) < best - EPS" fold over ascending idx, replayed as it is
-// written: the whole workgroup has staged val(idx) for idx in [lo, hi) (NaN = not a candidate) in
-// LDS, and one wave walks the values 64 at a time; a ballot finds the first lane after the last
-// take with val < best - EPS, which is what the sequential loop takes next.  This is the replay
-// stage of eps_fold (fold_common.hpp) without its prefix-minimum compaction: eps_fold keeps 12 KiB
-// of static LDS per instantiation for the compacted candidates, and form G leaves a workgroup
-// 1 KiB besides its tableau.  Returns the last index taken (-1: none), to every lane.
-__device__ __forceinline__ int staged_eps_fold(const double* stage, int lo, int hi, double best,
-                                               int* slot) {
-    if (threadIdx.x < kWave) {
-        const int lane = threadIdx.x;
-        int cur = -1;
-        for (int b0 = lo; b0 < hi; b0 += kWave) {
-            const int idx = b0 + lane;
-            const double x = (idx < hi) ? stage[idx] : (double)NAN;
-            unsigned long long alive = ~0ull;
-            for (;;) {
-                const unsigned long long hit = __ballot(x < best - kFoldEps) & alive;
-                if (hit == 0ull) break;
-                const int fl = __builtin_amdgcn_readfirstlane(__builtin_ctzll(hit));
-                best = readlane_f64(x, fl);
-                cur = b0 + fl;
-                alive = (fl == kWave - 1) ? 0ull : (~0ull << (fl + 1));
-            }
-        }
-        if (lane == 0) *slot = cur;
-    }
-    __syncthreads();
-    const int r = *slot;
-    __syncthreads();  // the slot is free for the next fold
-    return r;
-}
-
 // GetBasicRow (:69-84) of one column, by the whole workgroup: exactly one row of 1.. holds
 // |v| > EPS, and that row is within EPS of 1.
 __device__ __forceinline__ int block_basic_row(const double* T, int R, int C, int col, int* slot) {
