@@ -893,6 +893,76 @@ int lpr_cut_batch_log_read(lpr_cut_batch* b, int32_t k, int32_t* triples, int64_
 /* T[0, cols - 1] of every item (what lpr_solve_result.z is in lpr_dual_solve). */
 int lpr_cut_batch_z_read(lpr_cut_batch* b, double* z);
 
+
+/* ------------------------------------------------------------------ knapsack batch */
+
+/* Many option-5 instances per device call.  One handle holds `count`
+ * independent 0/1 knapsack instances; one solve call runs the whole level-synchronous search of
+ * section 11 for every instance on the device, with no host step per level, and one DP call runs
+ * the 0/1 DP of every instance, which together are option 5's B&B-against-DP comparison
+ * (Program.cs:430-470) for the whole batch.  PARITY: instance k ends with exactly what
+ * lpr_knap_bb_solve gives for it alone AT THE SAME node_cap -- status, found, Z*, the selected
+ * items, the rank, evaluated / levels / widest and every node record kept, the bound by bits.
+ * The default cap differs (1024 here, 2^22 there), so pass the cap to both when comparing.
+ * Forms, picked per instance by node_cap x (32 x ceil(n / 64) + 32) + 8 n bytes: W one wave per
+ * instance (four per workgroup), G one workgroup with everything in LDS, H one workgroup with
+ * the frontier in a global slab.  The reference has no batch mode. */
+typedef struct lpr_knap_batch lpr_knap_batch;
+
+/* capacity[count], n[count]; weights and values are doubles packed by n[k].  Per instance the
+ * checks of lpr_knap_bb_create: integral doubles, 1 <= w <= 2^31-1, 0 <= v <= 2^31-1,
+ * capacity >= 0, 1 <= n <= 8192; a violation is LPR_BAD_ARGUMENT and the message names the
+ * instance and the index.  node_cap[count] (evaluated nodes per instance) or NULL; NULL or an
+ * entry <= 0 means 1024, an entry over 2^22 is LPR_BAD_ARGUMENT.  narrate: node records kept per
+ * instance (0: none; at most node_cap are ever written).  A failed device allocation is
+ * LPR_OUT_OF_MEMORY and the message gives the footprint. */
+int lpr_knap_batch_create(lpr_engine* e, int32_t count, const int64_t* capacity, const int32_t* n,
+                          const double* weights, const double* values, const int64_t* node_cap,
+                          int32_t narrate, lpr_knap_batch** out);
+/* After lpr_engine_close the handle is orphaned: every call but this one is LPR_BAD_ARGUMENT. */
+int lpr_knap_batch_destroy(lpr_knap_batch* b);
+
+typedef struct lpr_knap_batch_opts {
+    int32_t chunk;    /* nodes an instance may evaluate per launch, checked at level boundaries
+                         (0: by form)                                      */
+    int32_t variant;  /* 0 auto; 1 / 2 / 3 force form W / G / H on the instances that fit it
+                         (tests and tuning only, same bits)                                      */
+} lpr_knap_batch_opts;
+
+typedef struct lpr_knap_batch_result {
+    int32_t finished;  /* instances whose search ended (LPR_OK_OPTIMAL)                          */
+    int32_t capped;    /* instances stopped by their node_cap (LPR_BB_NODE_CAP)                  */
+    int32_t launches;  /* search kernels launched by this call                                   */
+    int32_t items_w;   /* instances this call ran in form W ...                                  */
+    int32_t items_g;   /* ... G ...                                                              */
+    int32_t items_h;   /* ... and H                                                              */
+    int64_t nodes;     /* nodes evaluated, all instances                                         */
+} lpr_knap_batch_result;
+
+/* The search of every instance, from the roots (a second call repeats the first).  opts may be
+ * NULL.  Returns LPR_OK_OPTIMAL unless the call itself failed. */
+int lpr_knap_batch_solve(lpr_knap_batch* b, const lpr_knap_batch_opts* opts,
+                         lpr_knap_batch_result* res);
+/* Per instance, as lpr_knap_bb_result: LPR_OK_OPTIMAL or LPR_BB_NODE_CAP, found, Z* (0 when not
+ * found), evaluated, widest, levels; count entries each, any may be NULL. */
+int lpr_knap_batch_result_read(lpr_knap_batch* b, int32_t* status, int32_t* found, double* z,
+                               int64_t* evaluated, int64_t* widest, int32_t* levels);
+/* rank[p] of every instance (lpr_knap_bb_rank_read), packed by n[k]. */
+int lpr_knap_batch_rank_read(lpr_knap_batch* b, int32_t* rank);
+/* The incumbents' items as ascending original indices, packed by n[k]: counts[k] entries of
+ * instance k's block are valid, the rest of the block is -1. */
+int lpr_knap_batch_selected_read(lpr_knap_batch* b, int32_t* ids, int32_t* counts);
+/* Node records of instance k, as lpr_knap_bb_nodes_read: *count = records kept, the first
+ * min(*count, cap) copied; kitem holds ORIGINAL indices. */
+int lpr_knap_batch_nodes_read(lpr_knap_batch* b, int32_t k, int32_t* parent, int32_t* branch,
+                              int32_t* status, double* bound, int32_t* kitem, int64_t* value,
+                              int64_t cap, int64_t* count);
+/* best[k] = dp[capacity[k]] of the 0/1 DP of lpr_knap_dp over an int64 row initialised to 0, for
+ * every instance; which[count] or NULL: instances with 0 are skipped and get best[k] = -1.  An
+ * instance that is not skipped and needs more than 2^22 cells (capacity + 1 > 4 194 304) makes
+ * the call fail with LPR_BAD_ARGUMENT naming it: solve that one alone with lpr_knap_dp. */
+int lpr_knap_batch_dp(lpr_knap_batch* b, const uint8_t* which, int64_t* best);
+
 #ifdef __cplusplus
 }
 #endif

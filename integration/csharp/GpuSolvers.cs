@@ -537,6 +537,76 @@ namespace LPR_381_Group_V22.IntegerProgramming
             return best;
         }
     }
+
+    /// <summary>
+    /// Option 5 for many instances per device call (DESIGN.md section 16): the branch-and-bound of every instance in one
+    /// Solve(), the DP of every instance in one DP().  Instance k gets what KnapsackBranchBoundSimplex gives at the same NodeCap.
+    /// </summary>
+    public class KnapsackBatch : IDisposable
+    {
+        private IntPtr h;
+        private readonly int[] n, off;
+        public int Count => n.Length;
+        public int[] Status { get; private set; }
+        public double[] Z { get; private set; }
+        public long[] Evaluated { get; private set; }
+
+        /// <param name="nodeCap">evaluated nodes per instance; null or an entry &lt;= 0: 1024</param>
+        /// <param name="narrate">node records kept per instance</param>
+        public KnapsackBatch(long[] capacities, double[][] weights, double[][] values, long[] nodeCap = null, int narrate = 0)
+        {
+            n = weights.Select(w => w.Length).ToArray();
+            off = new int[n.Length];
+            for (int k = 1; k < n.Length; k++) off[k] = off[k - 1] + n[k - 1];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_create(Engine.Handle, n.Length, capacities, n,
+                weights.SelectMany(w => w).ToArray(), values.SelectMany(v => v).ToArray(), nodeCap, narrate, out h), "lpr_knap_batch_create");
+        }
+
+        public void Solve(int chunk = 0, int variant = 0)
+        {
+            var opts = new LprKnapBatchOpts { chunk = chunk, variant = variant };
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_solve(h, ref opts, out _), "lpr_knap_batch_solve");
+            Status = new int[Count]; Z = new double[Count]; Evaluated = new long[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_result_read(h, Status, null, Z, Evaluated, null, null), "lpr_knap_batch_result_read");
+        }
+
+        public int[] Rank(int k)
+        {
+            var all = new int[n.Sum()];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_rank_read(h, all), "lpr_knap_batch_rank_read");
+            return all.Skip(off[k]).Take(n[k]).ToArray();
+        }
+
+        /// <summary>The incumbent's items of every instance, ascending original indices.</summary>
+        public int[][] SelectedIds()
+        {
+            var ids = new int[n.Sum()];
+            var counts = new int[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_selected_read(h, ids, counts), "lpr_knap_batch_selected_read");
+            return Enumerable.Range(0, Count).Select(k => ids.Skip(off[k]).Take(counts[k]).ToArray()).ToArray();
+        }
+
+        /// <summary>Records kept of instance k: (parent, branch, status, bound, k as an original index, V).</summary>
+        public (int[] parent, int[] branch, int[] status, double[] bound, int[] kitem, long[] value) Nodes(int k)
+        {
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_nodes_read(h, k, null, null, null, null, null, null, 0, out long m), "lpr_knap_batch_nodes_read");
+            int[] par = new int[m], br = new int[m], st = new int[m], kk = new int[m];
+            double[] bd = new double[m];
+            long[] V = new long[m];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_nodes_read(h, k, par, br, st, bd, kk, V, m, out m), "lpr_knap_batch_nodes_read");
+            return (par, br, st, bd, kk, V);
+        }
+
+        /// <summary>dp[capacity] of every instance; -1 where which[k] is 0.</summary>
+        public long[] DP(byte[] which = null)
+        {
+            var best = new long[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_dp(h, which, best), "lpr_knap_batch_dp");
+            return best;
+        }
+
+        public void Dispose() { if (h != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_knap_batch_destroy(h), "lpr_knap_batch_destroy"); h = IntPtr.Zero; } }
+    }
 }
 
 namespace LPR_381_Group_V22.SensitivityAnalysis

@@ -52,6 +52,12 @@ namespace LPR_381_Group_V22.Native
     internal struct LprSensBatchResult { public int finished, running, launches, form; public long pivots; }
 
     [StructLayout(LayoutKind.Sequential)]
+    internal struct LprKnapBatchOpts { public int chunk, variant; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprKnapBatchResult { public int finished, capped, launches, items_w, items_g, items_h; public long nodes; }
+
+    [StructLayout(LayoutKind.Sequential)]
     internal struct LprCutBatchOpts { public int mode, max_cuts; public long hard_cap; public int max_iters, print_steps, chunk, variant; }
 
     [StructLayout(LayoutKind.Sequential)]
@@ -270,6 +276,16 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_tableau_read(IntPtr cutBatch, int k, [Out] double[,] rowmajor);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_log_read(IntPtr cutBatch, int k, int[] triples, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_z_read(IntPtr cutBatch, double[] z);
+
+        // ---- Knapsack batch (DESIGN.md section 16): many option-5 instances per call ----
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_create(IntPtr engine, int count, long[] capacity, int[] n, double[] weights, double[] values, long[] node_cap, int narrate, out IntPtr knapBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_destroy(IntPtr knapBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_solve(IntPtr knapBatch, ref LprKnapBatchOpts opts, out LprKnapBatchResult res);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_result_read(IntPtr knapBatch, int[] status, int[] found, double[] z, long[] evaluated, long[] widest, int[] levels);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_rank_read(IntPtr knapBatch, int[] rank);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_selected_read(IntPtr knapBatch, int[] ids, int[] counts);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_nodes_read(IntPtr knapBatch, int k, int[] parent, int[] branch, int[] status, double[] bound, int[] kitem, long[] value, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_dp(IntPtr knapBatch, byte[] which, long[] best);
 
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 

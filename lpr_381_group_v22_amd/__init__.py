@@ -12,6 +12,7 @@ from .branch_and_bound import (BranchAndBoundAdapter, BranchBoundTree, Comm,
 from .cut_batch import CuttingPlaneBatch, pack_tableaux
 from .input_file_parser import Constraint, InputFileParser
 from .knapsack import KnapsackBranchBoundSimplex, KnapsackBranchBoundSolver
+from .knapsack_batch import KnapsackBatch, pack_knapsacks, solve_knapsacks
 from .primal_batch import PrimalSimplexBatch, pack_models
 from .primal_simplex_solver import PrimalSimplexSolver
 from .revised_primal_simplex_solver import RevisedPrimalSimplexSolver, SolverException
@@ -25,5 +26,6 @@ __all__ = [
     "Comm", "solve_level_sync_native", "KnapsackBranchBoundSimplex", "KnapsackBranchBoundSolver",
     "PrimalSimplexBatch", "pack_models", "BranchAndBoundBatch", "solve_integer_programs",
     "SensitivityBatch", "SensitivityGrowBatch", "pack_scripts", "pack_grow_scripts",
-    "CuttingPlaneBatch", "pack_tableaux", "_native",
+    "CuttingPlaneBatch", "pack_tableaux", "KnapsackBatch", "pack_knapsacks", "solve_knapsacks",
+    "_native",
 ]

@@ -246,6 +246,25 @@ class CutBatchResult(C.Structure):
     ]
 
 
+class KnapBatchOpts(C.Structure):
+    _fields_ = [
+        ("chunk", C.c_int32),
+        ("variant", C.c_int32),
+    ]
+
+
+class KnapBatchResult(C.Structure):
+    _fields_ = [
+        ("finished", C.c_int32),
+        ("capped", C.c_int32),
+        ("launches", C.c_int32),
+        ("items_w", C.c_int32),
+        ("items_g", C.c_int32),
+        ("items_h", C.c_int32),
+        ("nodes", C.c_int64),
+    ]
+
+
 class BBResult(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -401,6 +420,15 @@ SIGNATURES = {
     "lpr_cut_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
     "lpr_cut_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
     "lpr_cut_batch_z_read": (C.c_int, [_P, _D]),
+    "lpr_knap_batch_create": (C.c_int, [_P, C.c_int32, _I64, _I32, _D, _D, _I64, C.c_int32, _PP]),
+    "lpr_knap_batch_destroy": (C.c_int, [_P]),
+    "lpr_knap_batch_solve": (C.c_int, [_P, C.POINTER(KnapBatchOpts), C.POINTER(KnapBatchResult)]),
+    "lpr_knap_batch_result_read": (C.c_int, [_P, _I32, _I32, _D, _I64, _I64, _I32]),
+    "lpr_knap_batch_rank_read": (C.c_int, [_P, _I32]),
+    "lpr_knap_batch_selected_read": (C.c_int, [_P, _I32, _I32]),
+    "lpr_knap_batch_nodes_read": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32, _D, _I32, _I64,
+                                            C.c_int64, _I64]),
+    "lpr_knap_batch_dp": (C.c_int, [_P, C.POINTER(C.c_uint8), _I64]),
 }
 
 

@@ -127,6 +127,7 @@ struct lpr_batch;
 struct lpr_bb_batch;
 struct lpr_sens_batch;
 struct lpr_cut_batch;
+struct lpr_knap_batch;
 
 struct lpr_engine {
     int device = 0;
@@ -145,6 +146,7 @@ struct lpr_engine {
     std::vector<lpr_bb_batch*> live_bb_batch;  // batched B&B handles (bb_batch_engine.hip)
     std::vector<lpr_sens_batch*> live_sens_batch;  // scenario batches (sens_batch_engine.hip)
     std::vector<lpr_cut_batch*> live_cut_batch;  // cutting-plane batches (cut_batch_engine.hip)
+    std::vector<lpr_knap_batch*> live_knap_batch;  // knapsack batches (knapsack_batch_engine.hip)
 };
 
 struct lpr_tableau {

@@ -147,11 +147,6 @@ int knap_ensure_log(lpr_knap* k, int64_t cap) {
     return LPR_OK_OPTIMAL;
 }
 
-// B&B inputs: integral doubles, 1 <= w <= 2^31-1, 0 <= v <= 2^31-1
-bool knap_integral_in(double x, double lo) {
-    return std::isfinite(x) && x == std::floor(x) && x >= lo && x <= 2147483647.0;
-}
-
 }  // namespace
 
 namespace lpr {
@@ -284,18 +279,7 @@ int lpr_knap_bb_create(lpr_engine* e, int64_t capacity, const double* weights,
         set_error("lpr_knap_bb_create: capacity %lld < 0", (long long)capacity);
         return LPR_BAD_ARGUMENT;
     }
-    for (int32_t i = 0; i < n; ++i) {
-        if (!knap_integral_in(weights[i], 1.0)) {
-            set_error("lpr_knap_bb_create: weights[%d] = %.17g is not an integer in 1..2^31-1", i,
-                      weights[i]);
-            return LPR_BAD_ARGUMENT;
-        }
-        if (!knap_integral_in(values[i], 0.0)) {
-            set_error("lpr_knap_bb_create: values[%d] = %.17g is not an integer in 0..2^31-1", i,
-                      values[i]);
-            return LPR_BAD_ARGUMENT;
-        }
-    }
+    if (!knap_items_ok("lpr_knap_bb_create", weights, values, n)) return LPR_BAD_ARGUMENT;
     LPR_HIP(hipSetDevice(e->device));
     lpr_knap* k = new (std::nothrow) lpr_knap();
     if (!k) return LPR_OUT_OF_MEMORY;
@@ -304,17 +288,8 @@ int lpr_knap_bb_create(lpr_engine* e, int64_t capacity, const double* weights,
     k->nw = (n + kWave - 1) / kWave;
     k->C = capacity;
     std::vector<uint64_t> ow(n), ov(n);
-    for (int i = 0; i < n; ++i) {
-        ow[i] = (uint64_t)weights[i];
-        ov[i] = (uint64_t)values[i];
-    }
-    // v/w descending as exact cross products (< 2^62), ties to the lower original index
     k->rank.resize(n);
-    for (int i = 0; i < n; ++i) k->rank[i] = i;
-    std::sort(k->rank.begin(), k->rank.end(), [&](int32_t i, int32_t j) {
-        const uint64_t a = ov[i] * ow[j], b = ov[j] * ow[i];
-        return a != b ? a > b : i < j;
-    });
+    knap_rank_items(weights, values, n, ow.data(), ov.data(), k->rank.data());
     k->hw.resize(n);
     k->hv.resize(n);
     for (int p = 0; p < n; ++p) {

@@ -91,32 +91,6 @@ void knap_launch_dp_stream(hipStream_t s, const int64_t* in, int64_t* out, int64
 }
 
 // ================================================================ branch-and-bound
-__device__ __forceinline__ int64_t knap_pack(int lo, int hi) {
-    return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-__device__ __forceinline__ int64_t shfl_xor64(int64_t x, int m) {
-    return knap_pack(__shfl_xor((int)x, m, kWave), __shfl_xor((int)(x >> 32), m, kWave));
-}
-__device__ __forceinline__ int64_t shfl_up64(int64_t x, int d) {
-    return knap_pack(__shfl_up((int)x, d, kWave), __shfl_up((int)(x >> 32), d, kWave));
-}
-__device__ __forceinline__ int64_t shfl64(int64_t x, int lane) {
-    return knap_pack(__shfl((int)x, lane, kWave), __shfl((int)(x >> 32), lane, kWave));
-}
-__device__ __forceinline__ int64_t wave_sum64(int64_t x) {
-#pragma unroll
-    for (int m = kWave / 2; m > 0; m >>= 1) x += shfl_xor64(x, m);
-    return x;
-}
-__device__ __forceinline__ int64_t wave_scan64(int64_t x, int lane) {  // inclusive
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int64_t y = shfl_up64(x, d);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
 // One wave per node.  Node i's bitmaps are nodes[i * 2nw, +nw) = F1 and the next nw words = F0,
 // over rank positions.  w, v are in rank order.
 __global__ __launch_bounds__(kKnapEvalWaves * kWave) void k_knap_eval(
@@ -128,62 +102,13 @@ __global__ __launch_bounds__(kKnapEvalWaves * kWave) void k_knap_eval(
     if (node >= W) return;  // whole waves
     const uint64_t* F1 = nodes + (size_t)node * 2 * nw;
     const uint64_t* F0 = F1 + nw;
-    int64_t w1 = 0, v1 = 0;
-    for (int c = 0; c < nw; ++c) {
-        const int p = c * kWave + lane;
-        if (p < n && ((F1[c] >> lane) & 1ull)) {
-            w1 += w[p];
-            v1 += v[p];
-        }
-    }
-    w1 = wave_sum64(w1);
-    v1 = wave_sum64(v1);
-    int64_t R = C - w1, V = v1;
-    if (R < 0) {
-        if (lane == 0) {
-            st[node] = kKnapInfeasible;
-            kp[node] = -1;
-            stop[node] = n;
-            Vout[node] = 0;
-            bd[node] = 0.0;
-        }
-        return;
-    }
-    int k = -1;
-    for (int c = 0; c < nw; ++c) {
-        const int p = c * kWave + lane;
-        const bool fr = p < n && !(((F1[c] | F0[c]) >> lane) & 1ull);
-        const int64_t fw = fr ? w[p] : 0, fv = fr ? v[p] : 0;
-        const int64_t pw = wave_scan64(fw, lane);
-        // the first free item whose weight exceeds what is left after the free items before it
-        const uint64_t hit = __ballot(fr && pw > R);
-        if (hit) {
-            const int kl = __builtin_ctzll(hit);
-            R -= shfl64(pw - fw, kl);
-            V += wave_sum64(lane < kl ? fv : 0);
-            k = c * kWave + kl;
-            break;
-        }
-        R -= shfl64(pw, kWave - 1);
-        V += wave_sum64(fv);
-    }
+    const KnapEval e = knap_eval_wave(F1, F0, nw, n, C, w, v, lane);
     if (lane != 0) return;
-    if (k < 0 || R == 0) {
-        st[node] = kKnapIntegral;
-        kp[node] = -1;
-        stop[node] = k < 0 ? n : k;
-        Vout[node] = V;
-        bd[node] = (double)V;
-        return;
-    }
-    const double q = ieee_div((double)R, (double)w[k]);
-    const double t = (double)v[k] * q;
-    const double b = (double)V + t;
-    st[node] = kKnapFractional;
-    kp[node] = k;
-    stop[node] = k;
-    Vout[node] = V;
-    bd[node] = b;
+    st[node] = e.st;
+    kp[node] = e.kp;
+    stop[node] = e.stop;
+    Vout[node] = e.V;
+    bd[node] = e.bd;
 }
 
 void knap_launch_eval(hipStream_t s, const uint64_t* nodes, int nw, int n, int64_t C,

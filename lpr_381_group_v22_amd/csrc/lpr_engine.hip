@@ -83,6 +83,8 @@ void bb_batch_orphan(lpr_bb_batch* b);
 void sens_batch_orphan(lpr_sens_batch* b);
 // cut_batch_engine.hip
 void cut_batch_orphan(lpr_cut_batch* b);
+// knapsack_batch_engine.hip
+void knap_batch_orphan(lpr_knap_batch* b);
 }  // namespace lpr
 // cut_kernels.hip
 void lpr_cut_release(lpr_tableau* t);
@@ -757,6 +759,8 @@ int lpr_engine_close(lpr_engine* e) {
     e->live_sens_batch.clear();
     for (lpr_cut_batch* b : e->live_cut_batch) cut_batch_orphan(b);
     e->live_cut_batch.clear();
+    for (lpr_knap_batch* b : e->live_knap_batch) knap_batch_orphan(b);
+    e->live_knap_batch.clear();
     if (e->stream) {
         hipStreamSynchronize(e->stream);
         hipStreamDestroy(e->stream);
