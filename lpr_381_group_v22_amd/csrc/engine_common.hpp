@@ -170,6 +170,7 @@ struct lpr_tableau {
     double* xbuf = nullptr;          // extract-solution output (lazy)
     int xbuf_n = 0;
     int64_t total_pivots = 0;
+    int poll_lead = 0;               // K-pivot driver, test hook: steps queued behind a snapshot (0: by time)
     // kernel timing (opts.time_kernels)
     std::vector<hipEvent_t> ev;      // pairs (start, stop)
     int64_t timed_launches = 0;

@@ -4,6 +4,7 @@
 // word per batch.  There is no CPU fallback: without a gfx950 device lpr_engine_open fails.
 #include "engine_common.hpp"
 
+#include <cmath>
 #include <cstdlib>
 
 #include <cstdarg>
@@ -55,7 +56,7 @@ int ov_set_log(lpr_tableau* t, int parity);
 void ov_launch_heads(lpr_tableau* t, int K, int flags);
 int ov2_begin(lpr_tableau* t);
 int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t ev_start,
-                    hipEvent_t ev_stop);
+                    hipEvent_t ev_stop, int snap_slot);
 int ov_read_stamps(lpr_tableau* t, uint64_t* out, int64_t cap, int64_t* count);
 int ov2_join(lpr_tableau* t);
 void ov_launch_sweep(lpr_tableau* t, int tr);
@@ -64,7 +65,9 @@ struct OvPoll {
     int64_t applied;
     double z[2];  // RHS column entry 0 (= T[0, cols-1]) after an even / odd number of pivots
 };
-int ov_poll(lpr_tableau* t, int parity, OvPoll* out);
+int ov_poll(lpr_tableau* t, int parity, bool with_flags, OvPoll* out);
+int ov_snapshot(lpr_tableau* t, int slot);
+int ov_snapshot_wait(lpr_tableau* t, int slot, OvPoll* out);
 void ov_adopt_buffer(lpr_tableau* t, int cur);
 // revised_engine.hip
 void rev_orphan(lpr_revised* s);
@@ -114,6 +117,14 @@ static int alloc_tableau(lpr_engine* e, int rows, int cols, lpr_tableau** out) {
     if (const char* lc = std::getenv("LPR_TEST_LOG_CAP")) {
         const long v = std::strtol(lc, nullptr, 10);
         if (v >= 16 && v <= (1 << 16)) t->log_cap = v;
+    }
+    // Test hook: the number of steps the K-pivot driver (solve_overlapped) queues behind a mid-call
+    // snapshot (LPR_TEST_POLL_LEAD, 1..64 steps; clipped to half a batch there) instead of the value
+    // it derives from its step estimate, so that a short oracle-checked solve can end on every side
+    // of a snapshot (tests/test_poll_ahead_gpu.py).
+    if (const char* pl = std::getenv("LPR_TEST_POLL_LEAD")) {
+        const long v = std::strtol(pl, nullptr, 10);
+        if (v >= 1 && v <= 64) t->poll_lead = (int)v;
     }
     const size_t tbytes = (size_t)rows * t->ld * sizeof(double);
     hipError_t err = hipSuccess;
@@ -506,6 +517,11 @@ static constexpr int kDefaultBlock = 16;
 // 67 MB 99.6 k vs 104.2 k pivots/s for heads-then-sweep, 101 MB 98.7 k vs 92.2 k, 227 MB 93.6 k vs
 // 78.6 k; round 1's crossover was ~300 MB)
 static constexpr size_t kOverlapBytes = (size_t)80 << 20;
+// Device work queued behind a mid-call snapshot of the K-pivot driver, in microseconds.  At the
+// headline size (a step is 161 us by the driver's estimate) ONE step behind the snapshot already
+// leaves no idle stretch at a batch boundary in a kernel trace (profiles/r07_poll_gaps_lead1.json);
+// the value kept is twice that.
+static constexpr double kOvLeadUs = 320.0;
 
 static int block_size(const lpr_tableau* t, const lpr_solve_opts& o) {
     // a specific one-pivot update-kernel variant was asked for
@@ -533,6 +549,29 @@ static int block_size(const lpr_tableau* t, const lpr_solve_opts& o) {
 // opts.time_kernels: HIP events on the sweep's own stream bracket EVERY sweep launch (start =
 // both kernels of the previous step done); sweep time = stop - start, step time = start of the
 // next step - start of this one.  Only steps that swept a full block are counted.
+//
+// Polling ahead.  The host does not wait for the queue to run dry before it learns the state: in a
+// batch of nb steps a SNAPSHOT of the control block (ov2_launch_step / ov_snapshot: one copy into a
+// pinned slot and an event) is queued `lead` steps before the end, the host waits for that event
+// alone and, while the device works through the last `lead` steps, queues the next batch behind
+// them -- no join, no stream synchronisation, no idle device.  A snapshot is `lead` steps stale when
+// the next batch is sized, so the driver assumes that every step queued so far applied a full
+// block: exact unless a step met the end of the solve, and then the steps queued for nothing return
+// at once, as idle steps always have (at most `lead` of them when the snapshot itself shows the end,
+// one more batch when the end falls in the `lead` steps behind a snapshot).  With a pivot limit the
+// bound is exact, so a call queues ceil(max_pivots / K) + 1 steps whatever the batch length.  Once a
+// snapshot shows anything but a running solve -- the end found, an error -- and whenever the log has
+// to grow, the driver DRAINS (join, synchronous ov_poll) and carries on from the exact state the
+// way it always did, one step at a time while an end is pending.  What a call returns (z, the live
+// buffer, the sweep direction for the next call) comes from that final poll only.
+struct OvTimedBatch {  // a queued batch whose timing events have not been read yet
+    bool live = false;
+    bool own_close = false;  // its last window closes at its own event 2 * nb (else: at the first
+                             // start event of the batch queued behind it, in the other event set)
+    int nb = 0;
+    int64_t g0 = 0;          // index of its first step in the call
+};
+
 static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int tr,
                             bool two_streams, int hflags, lpr_solve_result* res) {
     lpr_engine* e = t->eng;
@@ -543,18 +582,25 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
     // opts.time_kernels = n > 1: events around every n-th step only (two event records per step
     // cost the two-stream pipeline ~3 % -- they sit on the sweep's stream, on the critical cycle)
     const int tstride = o.time_kernels > 1 ? (o.time_kernels < 16 ? o.time_kernels : 16) : 1;
-    // steps between host polls: about 5 ms of device work (a step = one sweep at ~5 TB/s, or K loop
-    // heads at ~8 us, whichever is longer); a poll costs the device ~0.1 ms of idling
+    // steps between snapshots: about 5 ms of device work (a step = one sweep at ~5 TB/s, or K loop
+    // heads at ~8 us, whichever is longer)
+    const double sweep_us = 16.0 * t->rows * (double)t->ld / 5.0e6;
+    const double step_us = sweep_us > 8.0 * K ? sweep_us : 8.0 * K;
     int nlaunch;
     if (o.batch > 0) {
         nlaunch = (o.batch + K - 1) / K;
     } else {
-        const double sweep_us = 16.0 * t->rows * (double)t->ld / 5.0e6;
-        const double step_us = sweep_us > 8.0 * K ? sweep_us : 8.0 * K;
         nlaunch = (int)(5000.0 / step_us);
         if (nlaunch > 64) nlaunch = 64;
     }
     if (nlaunch < 2) nlaunch = 2;
+    // steps queued behind a snapshot: kOvLeadUs of device work by the same estimate (DESIGN 4b
+    // "Control": where the figure comes from), at least 1, at most half the batch
+    const int lead_steps = t->poll_lead > 0 ? t->poll_lead : (int)std::ceil(kOvLeadUs / step_us);
+    // (the opt-in forms whose kernels order themselves on the device, variant bits 21 / 22, keep
+    // the synchronous polls: ov2_launch_step's consistency argument is made for the event form)
+    const bool ahead = (hflags & (32 | 64)) == 0;
+    const bool poll_flags = (hflags & 64) != 0;
     const int64_t start_iter = t->total_pivots;
     const int64_t max_iter = o.max_pivots > 0 ? start_iter + o.max_pivots : 0;
     rc = ov_begin(t, start_iter, max_iter);
@@ -569,59 +615,58 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
     pl.pending = kRunning;
     pl.applied = start_iter;
     int32_t status = kRunning;
-    int64_t applied = start_iter;
-    int64_t step = 0;            // launches (pairs) queued by this call; parity = control block
-    int64_t swept_full = 0;      // full blocks swept so far by this call (for the event windows)
+    int64_t applied = start_iter;  // pivots applied at the latest poll or snapshot
+    int64_t step = 0;              // launches (pairs) queued by this call; parity = control block
     int idle_batches = 0;
-    while (status == kRunning) {
-        int nb = nlaunch;
-        if (pl.pending != kRunning) {
-            nb = 1;  // the end has been found: the staged tail is swept, the outcome published
-        } else if (max_iter > 0) {  // the blocks the limit allows (+ the step that only decides)
-            const int64_t left = max_iter - applied;
-            const int64_t need = (left + K - 1) / K + (step == 0 ? 1 : 0);
-            if (need < nb) nb = (int)need;
-        }
-        if (nb < 1) nb = 1;
-        const int64_t log_before = t->log_cap;
-        const int32_t* log_ptr = t->log;
-        rc = ensure_log(t, applied + (int64_t)(nb + 1) * K + 1);
-        if (rc != LPR_OK_OPTIMAL) return rc;
-        if (t->log_cap != log_before || t->log != log_ptr) {
-            rc = ov_set_log(t, two_streams ? (int)(step & 1) : 0);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        // One or two launches per K pivots: plain launches keep the device busy (measured: a
-        // captured graph is no faster here, and capturing one costs milliseconds per solve call).
-        if (timed) {  // (sized for a full batch at once: creating an event costs ~10 us)
-            while ((int)t->ev.size() < 2 * (nb > nlaunch ? nb : nlaunch) + 2) {
-                hipEvent_t ev;
-                LPR_HIP(hipEventCreate(&ev));
-                t->ev.push_back(ev);
+    bool exact = true;   // `pl` is a synchronous poll and nothing has been queued since
+    int64_t nbatch = 0;  // batches queued; parity = event set and snapshot slot
+    OvTimedBatch tb[2];  // by event set
+    int last_set = -1;   // event set of the batch queued last
+    const int first_full = two_streams ? 1 : 0;  // the first step of a two-stream call sweeps nothing
+    const int evset = 2 * nlaunch + 1;           // events per set: (start, stop) per step + closing
+
+    // Reads the events of batch `b`.  Steps sweep full blocks in order: first (two streams) the step
+    // that sweeps nothing, then full blocks, then at most one partial block and idle steps -- so the
+    // sampled steps that count are those with a call-wide index in [first_full, full_end).
+    auto read_events = [&](int b, int64_t full_end) -> int {
+        OvTimedBatch& B = tb[b];
+        hipEvent_t* ev = t->ev.data() + (size_t)b * evset;
+        hipEvent_t close = B.own_close ? ev[2 * B.nb] : t->ev[(size_t)(b ^ 1) * evset];
+        for (int k = 0; k < B.nb && B.g0 + k < full_end; k += tstride) {
+            if (B.g0 + k < first_full) continue;  // (the sampled steps are the multiples of tstride)
+            float ms = 0.f;
+            LPR_HIP(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
+            t->timed_total_ms += ms;
+            t->timed_launches += 1;
+            // start of this step to the start of the next SAMPLED one (or the closing event):
+            // that many steps, all of them full as long as they lie before full_end
+            const int kn = (k + tstride < B.nb) ? k + tstride : B.nb;
+            if (B.g0 + kn <= full_end) {
+                float st = 0.f;
+                LPR_HIP(hipEventElapsedTime(&st, ev[2 * k], kn < B.nb ? ev[2 * kn] : close));
+                t->timed_step_ms += st;
+                t->timed_steps += kn - k;
             }
         }
-        for (int k = 0; k < nb; ++k, ++step) {
-            const int lp = (int)(step & 1);
-            const bool tk = timed && (k % tstride == 0);
-            if (two_streams) {
-                rc = ov2_launch_step(t, K, tr, lp, hflags, tk ? t->ev[2 * k] : nullptr,
-                                     tk ? t->ev[2 * k + 1] : nullptr);
-                if (rc != LPR_OK_OPTIMAL) return rc;
-                continue;
-            }
-            ov_launch_heads(t, K, hflags);
-            if (tk) LPR_HIP(hipEventRecord(t->ev[2 * k], s));
-            ov_launch_sweep(t, tr);
-            if (tk) LPR_HIP(hipEventRecord(t->ev[2 * k + 1], s));
-        }
+        B.live = false;
+        return LPR_OK_OPTIMAL;
+    };
+
+    // The synchronous poll: both streams joined, the control block and z read back, the events of
+    // every batch still pending read against the exact count of full blocks.
+    auto drain = [&]() -> int {
         if (two_streams) {
-            rc = ov2_join(t);
-            if (rc != LPR_OK_OPTIMAL) return rc;
+            int jr = ov2_join(t);
+            if (jr != LPR_OK_OPTIMAL) return jr;
         }
-        if (timed) LPR_HIP(hipEventRecord(t->ev[2 * nb], s));  // closes the last step's window
+        if (timed && last_set >= 0 && tb[last_set].live && !tb[last_set].own_close) {
+            // closes the last step's window
+            LPR_HIP(hipEventRecord(t->ev[(size_t)last_set * evset + 2 * tb[last_set].nb], s));
+            tb[last_set].own_close = true;
+        }
         LPR_HIP(hipGetLastError());
-        rc = ov_poll(t, two_streams ? (int)(step & 1) : 0, &pl);
-        if (rc != LPR_OK_OPTIMAL) return rc;
+        int pr = ov_poll(t, two_streams ? (int)(step & 1) : 0, poll_flags, &pl);
+        if (pr != LPR_OK_OPTIMAL) return pr;
         if (pl.error || pl.status == LPR_DEVICE_ERROR) {
             // the staging state is unusable (a head group never arrived): the handle is poisoned
             t->poisoned = true;
@@ -632,36 +677,131 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
         status = pl.status;
         if (status == kRunning && pl.pending != kRunning && pl.kdone == 0)
             status = pl.pending;  // the end was found and nothing is left to sweep
-        if (timed) {
-            // steps of this batch sweep full blocks in order: first (only in the very first batch
-            // of a two-stream call) the step that sweeps nothing, then full blocks, then at most
-            // one partial block and idle steps
-            const int64_t full_now = (pl.applied - start_iter) / K - swept_full;
-            const int first = (step == nb && two_streams) ? 1 : 0;
-            for (int k = 0; k < nb && k < first + full_now; k += tstride) {
-                if (k < first) continue;  // (the sampled steps are the multiples of tstride)
-                float ms = 0.f;
-                LPR_HIP(hipEventElapsedTime(&ms, t->ev[2 * k], t->ev[2 * k + 1]));
-                t->timed_total_ms += ms;
-                t->timed_launches += 1;
-                // start of this step to the start of the next SAMPLED one (or the closing event):
-                // that many steps, all of them full as long as they lie before first + full_now
-                const int kn = (k + tstride < nb) ? k + tstride : nb;
-                if (kn <= first + full_now) {
-                    float st = 0.f;
-                    LPR_HIP(hipEventElapsedTime(&st, t->ev[2 * k], t->ev[2 * kn]));
-                    t->timed_step_ms += st;
-                    t->timed_steps += kn - k;
+        if (timed && last_set >= 0) {
+            const int64_t full_end = first_full + (pl.applied - start_iter) / K;
+            for (int b : {last_set ^ 1, last_set})  // the older batch first
+                if (tb[b].live) {
+                    int er = read_events(b, full_end);
+                    if (er != LPR_OK_OPTIMAL) return er;
                 }
-            }
-            swept_full += full_now;
         }
         idle_batches = (pl.applied == applied) ? idle_batches + 1 : 0;
         applied = pl.applied;
+        exact = true;
         if (status == kRunning && idle_batches >= 3) {
             set_error("overlapped pivot loop made no progress (device status still running)");
             return LPR_DEVICE_ERROR;
         }
+        return LPR_OK_OPTIMAL;
+    };
+
+    while (status == kRunning) {
+        // pivots applied once everything queued so far has run, if no step has met the end
+        int64_t base = applied;
+        if (!exact) {
+            base = start_iter + (step - first_full) * K;
+            if (max_iter > 0 && base > max_iter) base = max_iter;
+        }
+        int nb = nlaunch;
+        bool to_limit = false;  // this batch takes the call to its pivot limit
+        if (exact && pl.pending != kRunning) {
+            nb = 1;  // the end has been found: the staged tail is swept, the outcome published
+        } else if (max_iter > 0) {  // the blocks the limit allows (+ the step that only decides)
+            const int64_t left = max_iter - base;
+            const int64_t need = (left + K - 1) / K + (step == 0 ? 1 : 0);
+            if (need <= nb) {
+                nb = (int)need;
+                to_limit = true;
+            }
+        }
+        if (nb < 1) nb = 1;
+        if (base + (int64_t)(nb + 1) * K + 1 > t->log_cap) {
+            if (!exact) {
+                // The heads write B.log from their own stream: the old buffer must be out of use
+                // before it is replaced.  Drain, then size the batch again from the exact state.
+                rc = drain();
+                if (rc != LPR_OK_OPTIMAL) return rc;
+                continue;
+            }
+            const int64_t log_before = t->log_cap;
+            const int32_t* log_ptr = t->log;
+            rc = ensure_log(t, base + (int64_t)(nb + 1) * K + 1);
+            if (rc != LPR_OK_OPTIMAL) return rc;
+            if (t->log_cap != log_before || t->log != log_ptr) {
+                rc = ov_set_log(t, two_streams ? (int)(step & 1) : 0);
+                if (rc != LPR_OK_OPTIMAL) return rc;
+            }
+        }
+        // A snapshot `lead` steps before the end of the batch -- unless the batch is known to be
+        // the call's last (it reaches the pivot limit, or an end is pending): the drain follows.
+        int lead = 0;
+        if (ahead && !to_limit && nb >= 2 && !(exact && pl.pending != kRunning)) {
+            lead = lead_steps < nb / 2 ? lead_steps : nb / 2;
+            if (lead < 1) lead = 1;
+        }
+        const int set = (int)(nbatch & 1);
+        // One or two launches per K pivots: plain launches keep the device busy (measured: a
+        // captured graph is no faster here, and capturing one costs milliseconds per solve call).
+        hipEvent_t* ev = nullptr;
+        if (timed) {  // (two sets, sized for full batches at once: creating an event costs ~10 us)
+            while ((int)t->ev.size() < 2 * evset) {
+                hipEvent_t x;
+                LPR_HIP(hipEventCreate(&x));
+                t->ev.push_back(x);
+            }
+            ev = t->ev.data() + (size_t)set * evset;
+            tb[set].live = true;
+            tb[set].own_close = false;
+            tb[set].nb = nb;
+            tb[set].g0 = step;
+        }
+        for (int k = 0; k < nb; ++k, ++step) {
+            const int lp = (int)(step & 1);
+            const bool tk = timed && (k % tstride == 0);
+            const bool snap = lead > 0 && k == nb - lead;
+            if (two_streams) {
+                rc = ov2_launch_step(t, K, tr, lp, hflags, tk ? ev[2 * k] : nullptr,
+                                     tk ? ev[2 * k + 1] : nullptr, snap ? set : -1);
+                if (rc != LPR_OK_OPTIMAL) return rc;
+                continue;
+            }
+            if (snap) {
+                rc = ov_snapshot(t, set);
+                if (rc != LPR_OK_OPTIMAL) return rc;
+            }
+            ov_launch_heads(t, K, hflags);
+            if (tk) LPR_HIP(hipEventRecord(ev[2 * k], s));
+            ov_launch_sweep(t, tr);
+            if (tk) LPR_HIP(hipEventRecord(ev[2 * k + 1], s));
+        }
+        last_set = set;
+        nbatch += 1;
+        exact = false;
+        if (lead > 0) {
+            LPR_HIP(hipGetLastError());
+            OvPoll sp;
+            rc = ov_snapshot_wait(t, set, &sp);
+            if (rc != LPR_OK_OPTIMAL) return rc;
+            idle_batches = (sp.applied == applied) ? idle_batches + 1 : 0;
+            if (sp.status == kRunning && sp.pending == kRunning && !sp.error && idle_batches < 3) {
+                applied = sp.applied;
+                // The batch before this one is complete (its last step precedes the snapshot on
+                // the engine stream, and so does the start event that closes its last window) and
+                // every step of it came before a snapshot that shows no end: all its blocks were
+                // full.  hipEventQuery confirms; if it ever did not, the drain below would wait.
+                if (!timed || !tb[set ^ 1].live) continue;
+                const hipError_t q = hipEventQuery(ev[0]);
+                if (q == hipSuccess) {
+                    rc = read_events(set ^ 1, INT64_MAX);
+                    if (rc != LPR_OK_OPTIMAL) return rc;
+                    continue;
+                }
+                if (q != hipErrorNotReady) LPR_HIP(q);
+                (void)hipGetLastError();
+            }
+        }
+        rc = drain();
+        if (rc != LPR_OK_OPTIMAL) return rc;
     }
     ov_adopt_buffer(t, pl.cur);
     t->total_pivots = applied;

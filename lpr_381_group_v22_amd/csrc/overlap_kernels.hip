@@ -1572,6 +1572,11 @@ struct lpr_overlap_ctx {
     int head_xcc_hint = -1;         // the XCD the loop heads shared at the last poll (-1: unknown)
     int sweep_dir = 0;              // direction of the next sweep (OvCtl::sweep) at the last poll
     bool batch_first = true;        // the next step is the first after the streams were joined
+    // Mid-call snapshots (ov_snapshot / ov2_launch_step): one control-block entry each, copied into a
+    // pinned slot of its own (NOT h_ctl: ov_begin and ov_set_log upload from that), and the event
+    // that says the copy has landed.  Two of each, used alternately.
+    lpr::OvCtl* h_snap = nullptr;
+    hipEvent_t ev_snap[2] = {nullptr, nullptr};
 };
 
 namespace lpr {
@@ -1594,6 +1599,7 @@ void ov_release(lpr_tableau* t) {
     for (int k = 0; k < 2; ++k) {
         if (c->ev_h[k]) hipEventDestroy(c->ev_h[k]);
         if (c->ev_s[k]) hipEventDestroy(c->ev_s[k]);
+        if (c->ev_snap[k]) hipEventDestroy(c->ev_snap[k]);
     }
     hipFree(c->T2);
     hipFree(c->b.prow);
@@ -1613,6 +1619,7 @@ void ov_release(lpr_tableau* t) {
     if (c->h_ctl) hipHostFree(c->h_ctl);
     if (c->h_z) hipHostFree(c->h_z);
     if (c->h_flags) hipHostFree(c->h_flags);
+    if (c->h_snap) hipHostFree(c->h_snap);
     delete c;
     t->ov = nullptr;
 }
@@ -1660,6 +1667,8 @@ int ov_ensure(lpr_tableau* t, bool second_buffer) {
     chk(hipHostMalloc(&c->h_ctl, 2 * sizeof(OvCtl)));
     chk(hipHostMalloc(&c->h_z, 2 * sizeof(double)));
     chk(hipHostMalloc(&c->h_flags, 4 * sizeof(unsigned)));
+    chk(hipHostMalloc(&c->h_snap, 2 * sizeof(OvCtl)));
+    for (int k = 0; k < 2; ++k) chk(hipEventCreateWithFlags(&c->ev_snap[k], hipEventDisableTiming));
     t->ov = c;
     if (err != hipSuccess) {
         set_error("overlapped-pivot scratch allocation failed: %s", hipGetErrorString(err));
@@ -1677,6 +1686,7 @@ int ov_ensure(lpr_tableau* t, bool second_buffer) {
     LPR_HIP(hipMemsetAsync(c->b.sflag, 0, kOvFlagWords * sizeof(unsigned), s));
     std::memset(c->h_ctl, 0, 2 * sizeof(OvCtl));
     std::memset(c->h_flags, 0, 4 * sizeof(unsigned));
+    std::memset(c->h_snap, 0, 2 * sizeof(OvCtl));
     return LPR_OK_OPTIMAL;
 }
 
@@ -1811,8 +1821,25 @@ int ov2_begin(lpr_tableau* t) {
     return LPR_OK_OPTIMAL;
 }
 
+// snap_slot >= 0: a snapshot of the control block for the host goes on the engine stream S at this
+// step boundary -- behind the wait for the heads of the step before, in front of this step's sweep
+// -- into pinned slot snap_slot (ov_snapshot_wait reads it).  Call this step s, lp = s & 1.  The copy
+// reads ctl[lp], the entry step s only READS, and every field of it is final there:
+//   * status, pending, kdone, slot, r[], staged, max_iter, log_cap, error, head_xcc were written by
+//     the heads of step s-1 (ov_heads, co = ctl[(s-1 & 1) ^ 1] = ctl[lp]); S has waited for their
+//     completion event ev_h[prev] just above the copy;
+//   * applied, cur, sweep were written by the sweep of step s-1 (ov_tiles, write_ctl), which
+//     precedes the copy on S;
+//   * the heads and the sweep of step s itself (the heads may already be running on H) write only
+//     ctl[lp ^ 1];
+//   * the next writers of ctl[lp] are the kernels of step s+1: its sweep follows on S, and its heads
+//     wait for the completion event of sweep s, which is behind the copy on S.
+// So the host sees the state exactly as it was after s steps.  It does NOT get the RHS column's
+// entry 0 this way: the heads rewrite bvec at every pivot, beside the copy.  The driver asks for no
+// snapshot in the opt-in forms whose kernels order themselves on the device (flags 32 / 64): a
+// step that carries one always orders the sweep by the event.
 int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t ev_start,
-                    hipEvent_t ev_stop) {
+                    hipEvent_t ev_stop, int snap_slot) {
     lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
     hipStream_t S = t->eng->stream, H = c->hstream;
     const int cur = c->ev_idx, prev = cur ^ 1;
@@ -1830,13 +1857,18 @@ int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t
     // first two steps of a call (the heads it would wait for may not be resident yet: they
     // could find the chip full of polling sweep workgroups), nor while the heads' XCD is unknown.
     const bool sweep_dev = (flags & 64) != 0 && !c->batch_first && c->steps >= 2 &&
-                           c->head_xcc_hint >= 0;
+                           c->head_xcc_hint >= 0 && snap_slot < 0;
     const int heads_done = (flags & 64) ? c->steps + 1 : -1;
     // The events that order the two streams (and the ones that time a sampled step) are the
     // completion signals of the kernels themselves (hipExtLaunchKernelGGL's stop event): a separate
     // hipEventRecord is a packet of its own on the stream, ~3 us each on the critical cycle.
     if (by_event) LPR_HIP(hipStreamWaitEvent(H, c->last_sweep, 0));
     if (!sweep_dev) LPR_HIP(hipStreamWaitEvent(S, c->ev_h[prev], 0));
+    if (snap_slot >= 0) {
+        LPR_HIP(hipMemcpyAsync(&c->h_snap[snap_slot], &c->b.ctl[lp], sizeof(OvCtl),
+                               hipMemcpyDeviceToHost, S));
+        LPR_HIP(hipEventRecord(c->ev_snap[snap_slot], S));
+    }
     const int G = ov_groups(t);
     const int spread = ov_spread(G, flags);
     const int no_l2 = (flags & 6) ? 1 : 0;
@@ -1892,16 +1924,50 @@ int ov2_join(lpr_tableau* t) {
     return LPR_OK_OPTIMAL;
 }
 
+// In-place form: a snapshot of the control block for the host, queued on the engine stream between
+// two steps (behind a sweep, in front of the next heads) into pinned slot `slot`.  It reads entry
+// 0, the one the sweep has just written and ov_poll reads in this form; everything is one stream.
+int ov_snapshot(lpr_tableau* t, int slot) {
+    lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
+    hipStream_t s = t->eng->stream;
+    LPR_HIP(hipMemcpyAsync(&c->h_snap[slot], &c->b.ctl[0], sizeof(OvCtl), hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipEventRecord(c->ev_snap[slot], s));
+    return LPR_OK_OPTIMAL;
+}
+
+// Waits for the snapshot in `slot` alone -- not for the steps queued behind it -- and hands its
+// control fields on.  No z, cur or sweep direction: what a call returns and leaves for the next
+// one comes from the synchronous poll at its end; the XCD hint for the next launches is refreshed.
+int ov_snapshot_wait(lpr_tableau* t, int slot, OvPoll* out) {
+    lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
+    LPR_HIP(hipEventSynchronize(c->ev_snap[slot]));
+    const OvCtl& h = c->h_snap[slot];
+    c->head_xcc_hint = h.head_xcc;
+    out->status = h.status;
+    out->pending = h.pending;
+    out->kdone = h.kdone;
+    out->cur = h.cur;
+    out->error = h.error;
+    out->applied = h.applied;
+    out->z[0] = out->z[1] = 0.0;
+    return LPR_OK_OPTIMAL;
+}
+
 // reads control block `parity` back, and entry 0 of both RHS-column buffers (= T[0, cols-1] after
-// an even / odd number of pivots): one synchronisation per poll
-int ov_poll(lpr_tableau* t, int parity, OvPoll* out) {
+// an even / odd number of pivots): one synchronisation per poll.  with_flags: also B.sflag, whose
+// word 3 only the device-side hand-over of the sweep (flags 64) ever sets.
+int ov_poll(lpr_tableau* t, int parity, bool with_flags, OvPoll* out) {
     lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
     hipStream_t s = t->eng->stream;
     LPR_HIP(hipMemcpyAsync(c->h_ctl, c->b.ctl, 2 * sizeof(OvCtl), hipMemcpyDeviceToHost, s));
     LPR_HIP(hipMemcpyAsync(&c->h_z[0], c->b.bvec, sizeof(double), hipMemcpyDeviceToHost, s));
     LPR_HIP(hipMemcpyAsync(&c->h_z[1], c->b.bvec + c->Rp, sizeof(double), hipMemcpyDeviceToHost,
                            s));
-    LPR_HIP(hipMemcpyAsync(c->h_flags, c->b.sflag, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (with_flags)
+        LPR_HIP(hipMemcpyAsync(c->h_flags, c->b.sflag, 4 * sizeof(unsigned), hipMemcpyDeviceToHost,
+                               s));
+    else
+        c->h_flags[3] = 0u;
     LPR_HIP(hipStreamSynchronize(s));
     const OvCtl& h = c->h_ctl[parity];
     c->head_xcc_hint = h.head_xcc;
