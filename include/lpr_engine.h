@@ -963,6 +963,77 @@ int lpr_knap_batch_nodes_read(lpr_knap_batch* b, int32_t k, int32_t* parent, int
  * the call fail with LPR_BAD_ARGUMENT naming it: solve that one alone with lpr_knap_dp. */
 int lpr_knap_batch_dp(lpr_knap_batch* b, const uint8_t* which, int64_t* best);
 
+/* ------------------------------------------------------------------ revised simplex batch */
+
+/* Many option-2 LPs per device call.  One handle holds `count` independent
+ * LPs in (c, A, b) form; one solve call runs RevisedPrimalSimplexSolver.Solve() (:82-251) and
+ * ExtractSolution (:277-287) for every LP on the device.  PARITY: LP k ends with exactly what
+ * lpr_revised_solve gives for it alone at the same max_pivots -- status, iterations, the (row,
+ * enter, leave) log, the basis, the bytes of B^-1 and of the last x_B, and x and Z on the optimal
+ * exit.  Forms, picked per LP by the bytes it keeps resident (B^-1 and A with odd leading
+ * dimensions, six vectors of m, c, the n + m staged candidates, the basis and the non-basic
+ * flags): W one wave per LP (four per workgroup), G one workgroup with everything in LDS, H one
+ * workgroup with B^-1 and A in a global slab.  IterationSnapshots are not kept: a caller who
+ * wants the text uses lpr_revised_step on one model.  The reference has no batch mode. */
+typedef struct lpr_rev_batch lpr_rev_batch;
+
+/* new RevisedPrimalSimplexSolver(objective, constraints, isMin) per LP (:41-80): c = -objective
+ * when is_min (:51), B^-1 = I, basis[i] = n + i, c_B = 0 (:72-78); Relation is never read.
+ * n[count], m[count]; objective packed by n[k], A as packed m[k] x n[k] row-major blocks, b
+ * packed by m[k], is_min[count].  LPR_BAD_ARGUMENT with a message: count <= 0, a null array,
+ * n[k] < 1 or m[k] < 1 (the two ArgumentExceptions of :43-44), log_cap < 0, or an LP beyond
+ * m <= 1023 and n + m <= 2047 (what lpr_batch_from_lps takes; solve that one alone with
+ * lpr_revised_solve).  log_cap: (row, enter, leave) triples kept per LP; 0 means
+ * 4 * (n + 2 m), at most 4096.  A failed device allocation is LPR_OUT_OF_MEMORY and the message
+ * names the buffer and its size. */
+int lpr_rev_batch_create(lpr_engine* e, int32_t count, const int32_t* n, const int32_t* m,
+                         const double* objective, const double* A, const double* b,
+                         const int8_t* is_min, int32_t log_cap, lpr_rev_batch** out);
+/* After lpr_engine_close the handle is orphaned: every call but this one is LPR_BAD_ARGUMENT. */
+int lpr_rev_batch_destroy(lpr_rev_batch* b);
+
+typedef struct lpr_rev_batch_opts {
+    int64_t max_pivots;  /* iterations per LP per call, tested where lpr_revised_solve tests it:
+                            after the entering choice (0: no limit)                              */
+    int32_t chunk;       /* passes of the loop (:87) per LP per launch (0: by form, section 17)  */
+    int32_t variant;     /* 0 auto; 1 / 2 / 3 force form W / G / H on the LPs that fit it (tests
+                            and tuning only, same bits)                                          */
+} lpr_rev_batch_opts;
+
+typedef struct lpr_rev_batch_result {
+    int32_t optimal;     /* LPs in each state after this call: LPR_OK_OPTIMAL (:124-146) ...     */
+    int32_t unbounded;   /* ... LPR_UNBOUNDED (:178-179) ...                                     */
+    int32_t infeasible;  /* ... LPR_INFEASIBLE_BASIS (:90-91) ...                                */
+    int32_t other;       /* ... LPR_ENTERING_ALREADY_BASIC (:182-183), LPR_PIVOT_TOO_SMALL (:267) */
+    int32_t limit;       /* ... and LPR_PIVOT_LIMIT (no C# counterpart)                          */
+    int32_t launches;    /* solve kernels launched by this call                                  */
+    int64_t iterations;  /* iterations (:249) performed by this call, all LPs                    */
+} lpr_rev_batch_result;
+
+/* Solve() (:82-251) for every LP that is not finished: an LP at LPR_PIVOT_LIMIT resumes with the
+ * bits an uninterrupted solve has, a finished one stays as it is.  opts may be NULL.  Returns
+ * LPR_OK_OPTIMAL unless the call itself failed (a bad variant or a negative chunk is
+ * LPR_BAD_ARGUMENT). */
+int lpr_rev_batch_solve(lpr_rev_batch* b, const lpr_rev_batch_opts* opts,
+                        lpr_rev_batch_result* res);
+/* Per LP: status, iterations (:249) and FinalZ = Dot(cOrig, x) (:284; 0 unless optimal); count
+ * entries each, any may be NULL. */
+int lpr_rev_batch_status_read(lpr_rev_batch* b, int32_t* status, int64_t* iterations, double* z);
+/* SolutionVector (:277-283) of every LP, packed by n[k]; 0 unless optimal. */
+int lpr_rev_batch_solution_read(lpr_rev_batch* b, double* x);
+/* basicVariables (:28, :195) of every LP, packed by m[k]. */
+int lpr_rev_batch_basis_read(lpr_rev_batch* b, int32_t* basis);
+/* The log of LP k: leavingRow (:177, 0-based), enteringIdx (:122), leavingVar (:181) of the first
+ * min(iterations, log_cap) iterations; *count = triples kept, the first min(*count, cap) copied. */
+int lpr_rev_batch_log_read(lpr_rev_batch* b, int32_t k, int32_t* row, int32_t* enter,
+                           int32_t* leave, int64_t cap, int64_t* count);
+/* BInverse (:29, :274) of LP k, m x m row-major. */
+int lpr_rev_batch_binv_read(lpr_rev_batch* b, int32_t k, double* out);
+/* The last x_B = BInverse b (:89) of LP k, m entries. */
+int lpr_rev_batch_xb_read(lpr_rev_batch* b, int32_t k, double* out);
+/* n (:45) and m (:46) of LP k; either may be NULL. */
+int lpr_rev_batch_shape(lpr_rev_batch* b, int32_t k, int32_t* n, int32_t* m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,95 @@ namespace LPR_381_Group_V22.Simplex
         public void Dispose() { if (batch != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_batch_destroy(batch), "lpr_batch_destroy"); batch = IntPtr.Zero; } }
     }
 
+    /// <summary>RevisedPrimalSimplexSolver.Solve() + ExtractSolution (RevisedPrimalSimplexSolver.cs:82-251, :277-287) for many
+    /// LPs in one device call (DESIGN.md section 17); each LP gives the bits of RevisedPrimalSimplexSolver alone.  No
+    /// IterationSnapshots: solve that one model with RevisedPrimalSimplexSolver for the text.</summary>
+    public class RevisedSimplexBatch : IDisposable
+    {
+        private IntPtr batch;                           // lpr_rev_batch*
+        private readonly int[] nvars, ncons;
+        public int Count { get; }
+        public List<int> Status { get; } = new List<int>();
+        public List<long> Iterations { get; } = new List<long>();
+        public List<double> FinalZ { get; } = new List<double>();
+        public List<List<double>> SolutionVector { get; } = new List<List<double>>();
+
+        public RevisedSimplexBatch(List<(List<double> objective, List<IOConstraint> constraints, bool isMinimization)> models, int logCap = 0)
+        {
+            Count = models.Count;
+            nvars = new int[Count]; ncons = new int[Count]; var isMin = new sbyte[Count];
+            var obj = new List<double>(); var A = new List<double>(); var b = new List<double>();
+            for (int k = 0; k < Count; k++)
+            {
+                var (objective, constraints, isMinimization) = models[k];
+                if (objective == null || objective.Count == 0) throw new ArgumentException($"model {k}: Objective cannot be null or empty.");          // :43
+                if (constraints == null || constraints.Count == 0) throw new ArgumentException($"model {k}: Constraints cannot be null or empty.");  // :44
+                nvars[k] = objective.Count; ncons[k] = constraints.Count; isMin[k] = (sbyte)(isMinimization ? 1 : 0);
+                obj.AddRange(objective);
+                for (int i = 0; i < constraints.Count; i++)
+                {
+                    if (constraints[i].Coefficients.Count != nvars[k]) throw new ArgumentException($"model {k}: Constraint {i + 1} has incorrect number of coefficients.");  // :57-58
+                    A.AddRange(constraints[i].Coefficients); b.Add(constraints[i].RHS);   // Relation is never read (:55-61)
+                }
+            }
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_create(Engine.Handle, Count, nvars, ncons, obj.ToArray(), A.ToArray(),
+                b.ToArray(), isMin, logCap, out batch), "lpr_rev_batch_create");
+        }
+
+        /// <summary>Solve() of every unfinished LP; an LP stopped by maxPivots resumes on the next call.</summary>
+        public void Solve(long maxPivots = 0)
+        {
+            var opts = new LprRevBatchOpts { max_pivots = maxPivots };
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_solve(batch, ref opts, out _), "lpr_rev_batch_solve");
+            var st = new int[Count]; var it = new long[Count]; var z = new double[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_status_read(batch, st, it, z), "lpr_rev_batch_status_read");
+            var x = new double[nvars.Sum()];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_solution_read(batch, x), "lpr_rev_batch_solution_read");
+            Status.Clear(); Iterations.Clear(); FinalZ.Clear(); SolutionVector.Clear();
+            for (int k = 0, at = 0; k < Count; at += nvars[k], k++)
+            {
+                Status.Add(st[k]); Iterations.Add(it[k]);
+                bool optimal = st[k] == (int)LprStatus.Optimal;
+                FinalZ.Add(optimal ? z[k] : 0.0);                                  // :284, set on the optimal exit only
+                SolutionVector.Add(optimal ? x.Skip(at).Take(nvars[k]).ToList() : null);
+            }
+        }
+
+        public List<int> BasicVariables(int k)
+        {
+            var all = new int[ncons.Sum()];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_basis_read(batch, all), "lpr_rev_batch_basis_read");
+            return all.Skip(ncons.Take(k).Sum()).Take(ncons[k]).ToList();
+        }
+
+        public List<(int row, int enter, int leave)> PivotLog(int k)
+        {
+            const int cap = 1 << 12;
+            var r = new int[cap]; var e = new int[cap]; var l = new int[cap];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_log_read(batch, k, r, e, l, cap, out long count), "lpr_rev_batch_log_read");
+            var log = new List<(int, int, int)>();
+            for (long q = 0; q < Math.Min(count, cap); q++) log.Add((r[q], e[q], l[q]));
+            return log;
+        }
+
+        public double[,] BInverse(int k)
+        {
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_shape(batch, k, out _, out int m), "lpr_rev_batch_shape");
+            var t = new double[m, m];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_binv_read(batch, k, t), "lpr_rev_batch_binv_read");
+            return t;
+        }
+
+        public double[] XB(int k)
+        {
+            var xb = new double[ncons[k]];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_xb_read(batch, k, xb), "lpr_rev_batch_xb_read");
+            return xb;
+        }
+
+        public void Dispose() { if (batch != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_destroy(batch), "lpr_rev_batch_destroy"); batch = IntPtr.Zero; } }
+    }
+
     /// <summary>BranchAndBoundAdapter.SolveFromPrimal + ExecuteBranchAndBound (BranchBoundSimplexSolver.cs:1006-1233)
     /// for many IPs in one device call (DESIGN.md section 13); each IP gives the bits of BranchAndBound alone.</summary>
     public class BranchAndBoundBatch : IDisposable

@@ -58,6 +58,12 @@ namespace LPR_381_Group_V22.Native
     internal struct LprKnapBatchResult { public int finished, capped, launches, items_w, items_g, items_h; public long nodes; }
 
     [StructLayout(LayoutKind.Sequential)]
+    internal struct LprRevBatchOpts { public long max_pivots; public int chunk; public int variant; }
+
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct LprRevBatchResult { public int optimal, unbounded, infeasible, other, limit, launches; public long iterations; }
+
+    [StructLayout(LayoutKind.Sequential)]
     internal struct LprCutBatchOpts { public int mode, max_cuts; public long hard_cap; public int max_iters, print_steps, chunk, variant; }
 
     [StructLayout(LayoutKind.Sequential)]
@@ -286,6 +292,16 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_selected_read(IntPtr knapBatch, int[] ids, int[] counts);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_nodes_read(IntPtr knapBatch, int k, int[] parent, int[] branch, int[] status, double[] bound, int[] kitem, long[] value, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_dp(IntPtr knapBatch, byte[] which, long[] best);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_create(IntPtr engine, int count, int[] n, int[] m, double[] objective, double[] A, double[] b, sbyte[] is_min, int log_cap, out IntPtr revBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_destroy(IntPtr revBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_solve(IntPtr revBatch, ref LprRevBatchOpts opts, out LprRevBatchResult res);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_status_read(IntPtr revBatch, int[] status, long[] iterations, double[] z);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_solution_read(IntPtr revBatch, double[] x);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_basis_read(IntPtr revBatch, int[] basis);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_log_read(IntPtr revBatch, int k, int[] row, int[] enter, int[] leave, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_binv_read(IntPtr revBatch, int k, [Out] double[,] rowmajor);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_xb_read(IntPtr revBatch, int k, double[] xB);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_shape(IntPtr revBatch, int k, out int n, out int m);
 
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 

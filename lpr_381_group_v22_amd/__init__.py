@@ -15,6 +15,7 @@ from .knapsack import KnapsackBranchBoundSimplex, KnapsackBranchBoundSolver
 from .knapsack_batch import KnapsackBatch, pack_knapsacks, solve_knapsacks
 from .primal_batch import PrimalSimplexBatch, pack_models
 from .primal_simplex_solver import PrimalSimplexSolver
+from .revised_batch import RevisedSimplexBatch, pack_revised_models
 from .revised_primal_simplex_solver import RevisedPrimalSimplexSolver, SolverException
 from .sens_batch import (SensitivityBatch, SensitivityGrowBatch, pack_grow_scripts,
                          pack_scripts)
@@ -27,5 +28,6 @@ __all__ = [
     "PrimalSimplexBatch", "pack_models", "BranchAndBoundBatch", "solve_integer_programs",
     "SensitivityBatch", "SensitivityGrowBatch", "pack_scripts", "pack_grow_scripts",
     "CuttingPlaneBatch", "pack_tableaux", "KnapsackBatch", "pack_knapsacks", "solve_knapsacks",
+    "RevisedSimplexBatch", "pack_revised_models",
     "_native",
 ]

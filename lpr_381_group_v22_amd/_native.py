@@ -265,6 +265,26 @@ class KnapBatchResult(C.Structure):
     ]
 
 
+class RevBatchOpts(C.Structure):
+    _fields_ = [
+        ("max_pivots", C.c_int64),
+        ("chunk", C.c_int32),
+        ("variant", C.c_int32),
+    ]
+
+
+class RevBatchResult(C.Structure):
+    _fields_ = [
+        ("optimal", C.c_int32),
+        ("unbounded", C.c_int32),
+        ("infeasible", C.c_int32),
+        ("other", C.c_int32),
+        ("limit", C.c_int32),
+        ("launches", C.c_int32),
+        ("iterations", C.c_int64),
+    ]
+
+
 class BBResult(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -429,6 +449,17 @@ SIGNATURES = {
     "lpr_knap_batch_nodes_read": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32, _D, _I32, _I64,
                                             C.c_int64, _I64]),
     "lpr_knap_batch_dp": (C.c_int, [_P, C.POINTER(C.c_uint8), _I64]),
+    "lpr_rev_batch_create": (C.c_int, [_P, C.c_int32, _I32, _I32, _D, _D, _D, _I8, C.c_int32,
+                                       _PP]),
+    "lpr_rev_batch_destroy": (C.c_int, [_P]),
+    "lpr_rev_batch_solve": (C.c_int, [_P, C.POINTER(RevBatchOpts), C.POINTER(RevBatchResult)]),
+    "lpr_rev_batch_status_read": (C.c_int, [_P, _I32, _I64, _D]),
+    "lpr_rev_batch_solution_read": (C.c_int, [_P, _D]),
+    "lpr_rev_batch_basis_read": (C.c_int, [_P, _I32]),
+    "lpr_rev_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32, C.c_int64, _I64]),
+    "lpr_rev_batch_binv_read": (C.c_int, [_P, C.c_int32, _D]),
+    "lpr_rev_batch_xb_read": (C.c_int, [_P, C.c_int32, _D]),
+    "lpr_rev_batch_shape": (C.c_int, [_P, C.c_int32, _I32, _I32]),
 }
 
 

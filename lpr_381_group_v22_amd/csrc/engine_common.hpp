@@ -128,6 +128,7 @@ struct lpr_bb_batch;
 struct lpr_sens_batch;
 struct lpr_cut_batch;
 struct lpr_knap_batch;
+struct lpr_rev_batch;
 
 struct lpr_engine {
     int device = 0;
@@ -147,6 +148,7 @@ struct lpr_engine {
     std::vector<lpr_sens_batch*> live_sens_batch;  // scenario batches (sens_batch_engine.hip)
     std::vector<lpr_cut_batch*> live_cut_batch;  // cutting-plane batches (cut_batch_engine.hip)
     std::vector<lpr_knap_batch*> live_knap_batch;  // knapsack batches (knapsack_batch_engine.hip)
+    std::vector<lpr_rev_batch*> live_rev_batch;  // revised simplex batches (rev_batch_engine.hip)
 };
 
 struct lpr_tableau {

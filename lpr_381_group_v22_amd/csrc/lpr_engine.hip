@@ -88,6 +88,7 @@ void sens_batch_orphan(lpr_sens_batch* b);
 void cut_batch_orphan(lpr_cut_batch* b);
 // knapsack_batch_engine.hip
 void knap_batch_orphan(lpr_knap_batch* b);
+void rev_batch_orphan(lpr_rev_batch* b);
 }  // namespace lpr
 // cut_kernels.hip
 void lpr_cut_release(lpr_tableau* t);
@@ -901,6 +902,8 @@ int lpr_engine_close(lpr_engine* e) {
     e->live_cut_batch.clear();
     for (lpr_knap_batch* b : e->live_knap_batch) knap_batch_orphan(b);
     e->live_knap_batch.clear();
+    for (lpr_rev_batch* b : e->live_rev_batch) rev_batch_orphan(b);
+    e->live_rev_batch.clear();
     if (e->stream) {
         hipStreamSynchronize(e->stream);
         hipStreamDestroy(e->stream);

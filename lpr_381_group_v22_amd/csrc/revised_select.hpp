@@ -549,5 +549,18 @@ __device__ __forceinline__ void rev_ratio_body(const double* __restrict__ u,
     for (int i = m + tid; i < ldb; i += nt) browbuf[i] = 0.0;
 }
 
+// ------------------------------------------------------------------------------------------
+// The per-candidate tests of the two selections, for the batch kernels (rev_batch_kernels.hip),
+// whose operands are in LDS and whose group is a wave or a workgroup.
+// Entering (:105-121): the value the "v < best - EPS" fold sees, NaN = not a candidate.
+__device__ __forceinline__ double rev_enter_value(double rc, bool basic) {
+    return (!basic && rc > kRevEps) ? -rc : (double)NAN;
+}
+// Ratio (:154-176): does the loop take row i (ratio, basic variable bi) over its current choice
+// (best, basic variable brow; none: no row yet)?  A NaN ratio (u_i <= EPS) fails both clauses.
+__device__ __forceinline__ bool rev_ratio_take(double ratio, double best, bool none, int bi,
+                                               int brow) {
+    return ratio < best - kRevEps || (fabs(ratio - best) <= kRevEps && (none || bi < brow));
+}
 
 }  // namespace lpr
