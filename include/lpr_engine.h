@@ -513,6 +513,41 @@ int lpr_sens_add_activity(lpr_sens* s, double c_new, const double* a_new, int32_
 int lpr_sens_add_constraint(lpr_sens* s, const double* tech, int32_t ntech, double rhs,
                             int32_t* outcome);
 
+/* The sensitivity report: what DisplayRangeNonBasic (:276-297), DisplayRangeBasic (:324-359),
+ * DisplayRangeRHS (:396-424) and ShadowPrices (:212-222) compute, for every column and every
+ * constraint of the analyzer's current state, from one read of the tableau on the device
+ * (DESIGN.md section 18).  Max / Min are .NET Framework's Math.Max / Math.Min (a NaN sticks, of
+ * equal values the later one in scan order is kept: +0 against -0), every quotient is IEEE
+ * division.  What column j is: */
+enum lpr_sens_range_kind {
+    LPR_SENS_RANGE_NONBASIC_RANGE = 0,       /* cbar > EPS: "can DECREASE by at most" :291-292     */
+    LPR_SENS_RANGE_NONBASIC_BOUNDARY = 1,    /* |cbar| <= EPS: "at boundary" :293-294              */
+    LPR_SENS_RANGE_NONBASIC_NOT_OPTIMAL = 2, /* otherwise (negative or NaN cbar): "Warning" :295-296 */
+    LPR_SENS_RANGE_BASIC = 3,                /* in basicVars, with a basic row :330-336            */
+    LPR_SENS_RANGE_BASIC_ROW_NOT_FOUND = 4   /* in basicVars, GetBasicRow gives -1 :337            */
+};
+/* Per column j < cols - 1 (each array cols - 1 long):
+ *   kind          an lpr_sens_range_kind; basicVars.Contains(j) decides basic (:282 :330)
+ *   var_row       GetBasicRow(j) (:69-84) when j is in basicVars, else -1
+ *   reduced_cost  tableau[0, j] (:288)
+ *   cost_lo / hi  deltaLower / deltaUpper of :340-355 over row var_row for kind BASIC;
+ *                 -inf / +inf for every other kind
+ * Per constraint k = 1 .. rows - 1, at index k - 1 (each array rows - 1 long), slack column
+ * s = n + k - 1 (:62-67):
+ *   shadow        tableau[0, s] (:212-222, :404)
+ *   rhs_lo / hi   deltaLower / deltaUpper of :406-418 down column s
+ *   rhs_now       tableau[k, cols - 1] (:420)
+ * Any output pointer may be NULL.  The call changes nothing of the analyzer: tableau, basicVars,
+ * pivot log, solution vector and Z stay as they are.  A shape with n = cols - rows < 0 (the C#
+ * would index out of range) is LPR_BAD_ARGUMENT and nothing is written. */
+int lpr_sens_ranging(lpr_sens* s, int32_t* kind, int32_t* var_row, double* reduced_cost,
+                     double* cost_lo, double* cost_hi, double* shadow, double* rhs_lo,
+                     double* rhs_hi, double* rhs_now);
+/* Device time in milliseconds of the two kernels of the last lpr_sens_ranging call on this handle
+ * (the sweep over the tableau, the finish that folds the partials), from events; LPR_BAD_ARGUMENT
+ * before the first call.  Either may be NULL. */
+int lpr_sens_ranging_times(lpr_sens* s, double* sweep_ms, double* finish_ms);
+
 /* ------------------------------------------------------------------------------------------
  * Knapsack, menu option 5 (Program.cs:430-470).  The reference calls two classes it never
  * defines (KnapsackBranchBoundSimplex; KnapsackBranchBoundSolver.cs is an empty class), so the

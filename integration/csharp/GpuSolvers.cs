@@ -779,6 +779,27 @@ namespace LPR_381_Group_V22.SensitivityAnalysis
         // A-tilde^T y of RecoverObjectiveC / PerformDuality (:236-245, :690-694), summed in the C#'s order on the device
         internal double[] ATy(double[] y, int n) { var o = new double[Math.Max(1, n)]; NativeMethods.ThrowIfError(NativeMethods.lpr_sens_column_fold(h, y, y.Length, null, n, o), "lpr_sens_column_fold"); return o; }
 
+        // What DisplayRangeNonBasic (:276-297), DisplayRangeBasic (:324-359), DisplayRangeRHS (:396-424) and ShadowPrices (:212-222)
+        // compute, for every column and every constraint, from one read of the tableau on the device.  Kind: 0 non-basic with a range,
+        // 1 non-basic at the boundary, 2 non-basic and not optimal, 3 basic, 4 basic without a basic row (:337).
+        internal sealed class Ranging
+        {
+            public int[] Kind, VarRow;                      // per column 0 .. numCols - 2
+            public double[] ReducedCost, CostLo, CostHi;
+            public double[] Shadow, RhsLo, RhsHi, RhsNow;   // per constraint k at k - 1
+        }
+        internal Ranging RangingReport()
+        {
+            NativeMethods.lpr_sens_shape(h, out int R, out int C, out _, out _, out _, out _);
+            var r = new Ranging
+            {
+                Kind = new int[C - 1], VarRow = new int[C - 1], ReducedCost = new double[C - 1], CostLo = new double[C - 1], CostHi = new double[C - 1],
+                Shadow = new double[R - 1], RhsLo = new double[R - 1], RhsHi = new double[R - 1], RhsNow = new double[R - 1],
+            };
+            NativeMethods.ThrowIfError(NativeMethods.lpr_sens_ranging(h, r.Kind, r.VarRow, r.ReducedCost, r.CostLo, r.CostHi, r.Shadow, r.RhsLo, r.RhsHi, r.RhsNow), "lpr_sens_ranging");
+            return r;
+        }
+
         public void Dispose() { if (h != IntPtr.Zero) { NativeMethods.lpr_sens_destroy(h); h = IntPtr.Zero; } }
     }
 }

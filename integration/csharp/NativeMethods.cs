@@ -225,6 +225,9 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_change_nonbasic_column(IntPtr sens, int row, int col, double newVal, out int outcome);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_add_activity(IntPtr sens, double cNew, double[] aNew, int na, out int outcome);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_add_constraint(IntPtr sens, double[] tech, int ntech, double rhs, out int outcome);
+        // the sensitivity report: every cost range (cols - 1 entries) and RHS range (rows - 1 entries) in one call; any array may be null
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_ranging(IntPtr sens, int[] kind, int[] varRow, double[] reducedCost, double[] costLo, double[] costHi, double[] shadow, double[] rhsLo, double[] rhsHi, double[] rhsNow);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_ranging_times(IntPtr sens, out double sweepMs, out double finishMs);
 
         // ---- Knapsack, menu option 5 (Program.cs:430-470): KnapsackBranchBoundSolver.Solve, KnapsackBranchBoundSimplex ----
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_dp(IntPtr engine, long capacity, int[] weights, int[] values, int n, ref LprKnapDpOpts opts, out long best);

@@ -43,6 +43,13 @@ LPR_SENS_ROLLED_BACK = 8
 LPR_SENS_INDEX_OUT_OF_RANGE = 9
 LPR_SENS_INVALID_INDEX = -1
 
+# lpr_sens_range_kind
+LPR_SENS_RANGE_NONBASIC_RANGE = 0
+LPR_SENS_RANGE_NONBASIC_BOUNDARY = 1
+LPR_SENS_RANGE_NONBASIC_NOT_OPTIMAL = 2
+LPR_SENS_RANGE_BASIC = 3
+LPR_SENS_RANGE_BASIC_ROW_NOT_FOUND = 4
+
 # lpr_sens_edit_op
 LPR_SENS_EDIT_RESOLVE_ALL = 0
 LPR_SENS_EDIT_NONBASIC_CBAR = 1
@@ -389,6 +396,8 @@ SIGNATURES = {
     "lpr_sens_change_nonbasic_column": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _I32]),
     "lpr_sens_add_activity": (C.c_int, [_P, C.c_double, _D, C.c_int32, _I32]),
     "lpr_sens_add_constraint": (C.c_int, [_P, _D, C.c_int32, C.c_double, _I32]),
+    "lpr_sens_ranging": (C.c_int, [_P, _I32, _I32, _D, _D, _D, _D, _D, _D, _D]),
+    "lpr_sens_ranging_times": (C.c_int, [_P, _D, _D]),
     "lpr_knap_dp": (C.c_int, [_P, C.c_int64, _I32, _I32, C.c_int32, C.POINTER(KnapDpOpts), _I64]),
     "lpr_knap_bb_create": (C.c_int, [_P, C.c_int64, _D, _D, C.c_int32, _PP]),
     "lpr_knap_bb_destroy": (C.c_int, [_P]),

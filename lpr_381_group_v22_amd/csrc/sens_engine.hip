@@ -11,6 +11,7 @@
 #include "engine_common.hpp"
 #include "fold_common.hpp"
 #include "select_common.hpp"
+#include "sens_ranging_common.hpp"
 
 #include <algorithm>
 #include <new>
@@ -43,6 +44,14 @@ struct lpr_sens {
     std::vector<double> h_sol;
     double z = 0.0;
     int64_t pivots = 0;         // pivots of the last edit
+    // lpr_sens_ranging: partial slabs + output block (device), its pinned mirror, both grown on
+    // demand; events around the two kernels of the last call
+    char* rng_ws = nullptr;
+    size_t rng_ws_cap = 0;
+    char* rng_pin = nullptr;
+    size_t rng_pin_cap = 0;
+    hipEvent_t rng_ev[3] = {nullptr, nullptr, nullptr};
+    bool rng_timed = false;
 };
 
 namespace lpr {
@@ -429,6 +438,15 @@ void sens_release_device(lpr_sens* s) {
     if (s->h_state) hipHostFree(s->h_state);
     s->log = nullptr;
     s->state = s->h_state = nullptr;
+    hipFree(s->rng_ws);
+    if (s->rng_pin) hipHostFree(s->rng_pin);
+    s->rng_ws = s->rng_pin = nullptr;
+    s->rng_ws_cap = s->rng_pin_cap = 0;
+    for (hipEvent_t& ev : s->rng_ev) {
+        if (ev) hipEventDestroy(ev);
+        ev = nullptr;
+    }
+    s->rng_timed = false;
 }
 
 // allocate everything that depends on the shape except T (zeroed); on failure nothing is kept
@@ -659,6 +677,10 @@ lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,
     *z = s->z;
     return s->eng;
 }
+// sens_ranging_kernels.hip: the sweep and the finish of lpr_sens_ranging on `st`
+int sens_ranging_launch(hipStream_t st, const double* T, int ld, int R, int C,
+                        const int32_t* bcount, const int32_t* cand, char* ws,
+                        const SensRangingPlan& pl, hipEvent_t ev_mid);
 }  // namespace lpr
 
 #define LPR_LIVE_S(s)                                                                       \
@@ -832,6 +854,89 @@ int lpr_sens_column_fold(lpr_sens* s, const double* w, int32_t nw, const double*
     LPR_HIP(hipMemcpyAsync(out, s->fold_io, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost,
                            st));
     LPR_HIP(hipStreamSynchronize(st));
+    return LPR_OK_OPTIMAL;
+}
+
+int lpr_sens_ranging(lpr_sens* s, int32_t* kind, int32_t* var_row, double* reduced_cost,
+                     double* cost_lo, double* cost_hi, double* shadow, double* rhs_lo,
+                     double* rhs_hi, double* rhs_now) {
+    LPR_LIVE_S(s);
+    SensRangingPlan pl;
+    if (!sens_ranging_plan(s->R, s->C, &pl)) {
+        set_error("lpr_sens_ranging: a %d x %d tableau has no slack block (n < 0)", s->R, s->C);
+        return LPR_BAD_ARGUMENT;
+    }
+    hipStream_t st = s->eng->stream;
+    if (s->rng_ws_cap < pl.total) {
+        hipFree(s->rng_ws);
+        s->rng_ws = nullptr;
+        s->rng_ws_cap = 0;
+        if (hipMalloc(&s->rng_ws, pl.total) != hipSuccess) {
+            s->rng_ws = nullptr;
+            set_error("lpr_sens_ranging: workspace allocation (%zu bytes) failed", pl.total);
+            return LPR_OUT_OF_MEMORY;
+        }
+        s->rng_ws_cap = pl.total;
+    }
+    const size_t out_bytes = pl.total - pl.out_off;
+    if (s->rng_pin_cap < out_bytes) {
+        if (s->rng_pin) hipHostFree(s->rng_pin);
+        s->rng_pin = nullptr;
+        s->rng_pin_cap = 0;
+        if (hipHostMalloc(&s->rng_pin, out_bytes) != hipSuccess) {
+            s->rng_pin = nullptr;
+            set_error("lpr_sens_ranging: pinned buffer allocation (%zu bytes) failed", out_bytes);
+            return LPR_OUT_OF_MEMORY;
+        }
+        s->rng_pin_cap = out_bytes;
+    }
+    for (hipEvent_t& ev : s->rng_ev)
+        if (!ev) LPR_HIP(hipEventCreate(&ev));
+    s->rng_timed = false;
+    // GetBasicRow of every column on zeroed scratch: a cand left by an earlier call is not trusted
+    int rc = sens_colscan(s);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    hipLaunchKernelGGL(k_sens_cand, dim3((pl.nc + 255) / 256), dim3(256), 0, st, s->T, s->ld, s->C,
+                       s->cnt, s->rowsum, s->cand, (int32_t*)nullptr, (double*)nullptr);
+    LPR_HIP(hipGetLastError());
+    LPR_HIP(hipEventRecord(s->rng_ev[0], st));
+    rc = sens_ranging_launch(st, s->T, s->ld, s->R, s->C, s->bcount, s->cand, s->rng_ws, pl,
+                             s->rng_ev[1]);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    LPR_HIP(hipEventRecord(s->rng_ev[2], st));
+    // one copy of the whole output block, then plain host copies to whatever the caller asked for
+    LPR_HIP(hipMemcpyAsync(s->rng_pin, s->rng_ws + pl.out_off, out_bytes, hipMemcpyDeviceToHost,
+                           st));
+    LPR_HIP(hipStreamSynchronize(st));
+    s->rng_timed = true;
+    const size_t nd = (size_t)pl.nc * sizeof(double), md = (size_t)pl.m * sizeof(double);
+    const size_t ni = (size_t)pl.nc * sizeof(int32_t);
+    auto put = [&](void* dst, size_t off, size_t bytes) {  // off: the plan's, from the buffer start
+        if (dst) std::memcpy(dst, s->rng_pin + (off - pl.out_off), bytes);
+    };
+    put(kind, pl.o_kind, ni);
+    put(var_row, pl.o_row, ni);
+    put(reduced_cost, pl.o_rc, nd);
+    put(cost_lo, pl.o_clo, nd);
+    put(cost_hi, pl.o_chi, nd);
+    put(shadow, pl.o_shadow, md);
+    put(rhs_lo, pl.o_rlo, md);
+    put(rhs_hi, pl.o_rhi, md);
+    put(rhs_now, pl.o_now, md);
+    return LPR_OK_OPTIMAL;
+}
+
+int lpr_sens_ranging_times(lpr_sens* s, double* sweep_ms, double* finish_ms) {
+    LPR_LIVE_S(s);
+    if (!s->rng_timed) {
+        set_error("lpr_sens_ranging_times: no lpr_sens_ranging call has completed on this handle");
+        return LPR_BAD_ARGUMENT;
+    }
+    float a = 0.f, b = 0.f;
+    LPR_HIP(hipEventElapsedTime(&a, s->rng_ev[0], s->rng_ev[1]));
+    LPR_HIP(hipEventElapsedTime(&b, s->rng_ev[1], s->rng_ev[2]));
+    if (sweep_ms) *sweep_ms = a;
+    if (finish_ms) *finish_ms = b;
     return LPR_OK_OPTIMAL;
 }
 

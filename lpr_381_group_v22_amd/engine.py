@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -356,6 +357,23 @@ class RevisedState:
         return out
 
 
+@dataclass
+class RangingReport:
+    """What lpr_sens_ranging writes: per column j < cols - 1 the kind (an lpr_sens_range_kind),
+    GetBasicRow(j) for a column of basicVars (else -1), the reduced cost and the cost range (finite
+    bounds only for kind BASIC); per constraint k at index k - 1 the shadow price, the RHS range
+    and the current RHS."""
+    kind: np.ndarray          # int32, cols - 1
+    var_row: np.ndarray       # int32, cols - 1
+    reduced_cost: np.ndarray  # float64, cols - 1
+    cost_lo: np.ndarray
+    cost_hi: np.ndarray
+    shadow: np.ndarray        # float64, rows - 1
+    rhs_lo: np.ndarray
+    rhs_hi: np.ndarray
+    rhs_now: np.ndarray
+
+
 class SensState:
     """Device-resident tableau of a SensitivityAnalyzer (lpr_sens_*).  Edits return the
     lpr_sens_outcome of the re-solve."""
@@ -439,6 +457,23 @@ class SensState:
         N.check(N.lib.lpr_sens_column_fold(self._h, _dptr(ww), ww.shape[0], _dptr(ii), ncols,
                                            _dptr(out)), "lpr_sens_column_fold")
         return out[:ncols]
+
+    def ranging(self) -> RangingReport:
+        """Every cost range and RHS range of the current state in one device call."""
+        r, c = self.shape()[:2]
+        ints = [np.zeros(c - 1, dtype=np.int32) for _ in range(2)]
+        cols = [np.zeros(c - 1, dtype=np.float64) for _ in range(3)]
+        rows = [np.zeros(r - 1, dtype=np.float64) for _ in range(4)]
+        N.check(N.lib.lpr_sens_ranging(self._h, *[_i32ptr(a) for a in ints],
+                                       *[_dptr(a) for a in cols + rows]), "lpr_sens_ranging")
+        return RangingReport(*ints, *cols, *rows)
+
+    def ranging_times(self) -> Tuple[float, float]:
+        """(sweep, finish) device milliseconds of the last ranging() call, from events."""
+        a, b = C.c_double(), C.c_double()
+        N.check(N.lib.lpr_sens_ranging_times(self._h, C.byref(a), C.byref(b)),
+                "lpr_sens_ranging_times")
+        return a.value, b.value
 
     def _edit(self, name: str, *args) -> int:
         oc = C.c_int32()

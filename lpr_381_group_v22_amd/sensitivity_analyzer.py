@@ -244,6 +244,55 @@ class SensitivityAnalyzer:
         self._say(f"So b_{k} may vary within [{F(cur + lo)}, {F(cur + hi)}] without changing the "
                   "basis.")
 
+    def RangingReport(self):
+        """Every range of the model from one device call (lpr_sens_ranging):
+        an ``engine.RangingReport`` of numpy arrays.  Not in the C#, which answers one index per
+        prompt; the folds are .NET's Math.Max / Math.Min, where BasicRange / RHSRange above use
+        Python's max / min (they differ on NaN and on a +0 / -0 tie)."""
+        return self._s.ranging()
+
+    def DisplayRangingReport(self) -> None:
+        """For every column in index order the lines DisplayRangeNonBasic (:289-296) or
+        DisplayRangeBasic (:337-358) writes for it -- whichever of the two accepts the column, so
+        no "Invalid index" line -- then for every constraint the lines of DisplayRangeRHS
+        (:421-423), all built from one RangingReport()."""
+        rep = self.RangingReport()
+        m = len(rep.shadow)
+        n = len(rep.kind) - m
+
+        def label(col: int) -> str:  # ColLabel :55-60
+            return f"x{col + 1}" if col < n else f"s{col - n + 1}"
+
+        for j, kind in enumerate(rep.kind.tolist()):
+            if kind == N.LPR_SENS_RANGE_BASIC:
+                lo, hi = float(rep.cost_lo[j]), float(rep.cost_hi[j])
+                self._say(f"Allowable change Δ for {label(j)}’s objective coeff that keeps "
+                          f"basis optimal: [{F(lo)}, {F(hi)}]")
+                self._say("Interpretation: set c_B(new) = c_B(old) + Δ within this interval to "
+                          "preserve basis.")
+                continue
+            if kind == N.LPR_SENS_RANGE_BASIC_ROW_NOT_FOUND:
+                self._say("Error: Basic variable not found in tableau.")
+                continue
+            cbar = float(rep.reduced_cost[j])
+            self._say(f"Reduced Cost for {label(j)}: {F(cbar)}")
+            if kind == N.LPR_SENS_RANGE_NONBASIC_RANGE:
+                self._say(f"Range for c{j + 1}: can DECREASE by at most {F(cbar)}, INCREASE "
+                          "without bound.")
+            elif kind == N.LPR_SENS_RANGE_NONBASIC_BOUNDARY:
+                self._say(f"Range for c{j + 1}: at boundary (c̄=0). Any decrease makes "
+                          f"{label(j)} enter; any increase is fine.")
+            else:
+                self._say("Warning: tableau not optimal (negative reduced cost found). Consider "
+                          "re-optimizing.")
+        for i in range(m):
+            k = i + 1
+            lo, hi, cur = float(rep.rhs_lo[i]), float(rep.rhs_hi[i]), float(rep.rhs_now[i])
+            self._say(f"Shadow Price y_{k} = {F(float(rep.shadow[i]))}")
+            self._say(f"Allowable RHS change Δ for constraint {k}: [{F(lo)}, {F(hi)}]")
+            self._say(f"So b_{k} may vary within [{F(cur + lo)}, {F(cur + hi)}] without changing "
+                      "the basis.")
+
     def DisplayRangeNonBasicColumn(self, row: int, colRaw: int) -> None:  # :473-499
         if row < 1 or row >= self.numRows:
             self._say("Invalid row.")
