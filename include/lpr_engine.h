@@ -848,6 +848,25 @@ int lpr_sens_batch_tableau_read(lpr_sens_batch* b, int32_t k, double* rowmajor);
  * *count = all of them, the first min(*count, log_cap, cap) copied. */
 int lpr_sens_batch_log_read(lpr_sens_batch* b, int32_t k, int32_t* triples, int64_t cap,
                             int64_t* count);
+/* The sensitivity report of every scenario in one call: per scenario the
+ * nine outputs of lpr_sens_ranging -- DisplayRangeNonBasic :276-297, DisplayRangeBasic :324-359,
+ * DisplayRangeRHS :396-424, ShadowPrices :212-222, GetBasicRow / IsPivotColumn :69-84 -- on the
+ * state the batch holds for it now: the tableau lpr_sens_batch_tableau_read gives, basicVars as
+ * stored (lpr_sens_batch_state_read; stale entries are kept, nothing is rebuilt) and the
+ * scenario's own shape.  Valid before the first run (every scenario is the base state), after a
+ * run, and between two runs on scenarios stopped inside an edit (LPR_PIVOT_LIMIT).
+ * kind, var_row, reduced_cost, cost_lo, cost_hi are count x (max_cols - 1), shadow, rhs_lo,
+ * rhs_hi, rhs_now are count x (max_rows - 1), max_rows / max_cols those of
+ * lpr_sens_batch_shape_read (the base's shape in a fixed-shape batch); scenario k owns row k of
+ * each.  Entries past scenario k's own cols[k] - 1 or rows[k] - 1 are INT32_MIN in the int arrays
+ * and a quiet NaN in the double arrays.  Any output pointer may be NULL.  The call changes nothing
+ * of the batch: a following lpr_sens_batch_run resumes as if it had not been made. */
+int lpr_sens_batch_ranging(lpr_sens_batch* b, int32_t* kind, int32_t* var_row,
+                           double* reduced_cost, double* cost_lo, double* cost_hi, double* shadow,
+                           double* rhs_lo, double* rhs_hi, double* rhs_now);
+/* Device time in milliseconds of the kernel of the last lpr_sens_batch_ranging call on this
+ * handle, from events; LPR_BAD_ARGUMENT before the first call. */
+int lpr_sens_batch_ranging_time(lpr_sens_batch* b, double* kernel_ms);
 
 
 /* ------------------------------------------------------------- cutting-plane batch */

@@ -274,6 +274,10 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_solution_read(IntPtr sensBatch, int k, double[] x, int cap, out int count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_tableau_read(IntPtr sensBatch, int k, [Out] double[,] rowmajor);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_log_read(IntPtr sensBatch, int k, int[] triples, long cap, out long count);
+        // the report of every scenario: count x (max_cols - 1) per column, count x (max_rows - 1) per constraint,
+        // int.MinValue / NaN past a scenario's own shape; any array may be null
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_ranging(IntPtr sensBatch, int[] kind, int[] varRow, double[] reducedCost, double[] costLo, double[] costHi, double[] shadow, double[] rhsLo, double[] rhsHi, double[] rhsNow);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_ranging_time(IntPtr sensBatch, out double kernelMs);
 
         // ---- Cutting-plane batch (DESIGN.md section 15): many option-4 tableaux per call ----
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_create(IntPtr engine, int count, int[] rows, int[] cols, double[] tableaux, int max_cuts, int log_cap, out IntPtr cutBatch);

@@ -440,6 +440,8 @@ SIGNATURES = {
     "lpr_sens_batch_solution_read": (C.c_int, [_P, C.c_int32, _D, C.c_int32, _I32]),
     "lpr_sens_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
     "lpr_sens_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
+    "lpr_sens_batch_ranging": (C.c_int, [_P, _I32, _I32, _D, _D, _D, _D, _D, _D, _D]),
+    "lpr_sens_batch_ranging_time": (C.c_int, [_P, _D]),
     "lpr_cut_batch_create": (C.c_int, [_P, C.c_int32, _I32, _I32, _D, C.c_int32, C.c_int32, _PP]),
     "lpr_cut_batch_from_batch": (C.c_int, [_P, C.c_int32, C.c_int32, _PP]),
     "lpr_cut_batch_destroy": (C.c_int, [_P]),

@@ -4,6 +4,7 @@
 // bounded script kernel while scenarios are still running (BatchRunLists of batch_common.hpp,
 // with one form per call) and copies results out.
 #include "sens_batch_common.hpp"
+#include "sens_batch_ranging_common.hpp"
 
 #include <algorithm>
 #include <new>
@@ -15,6 +16,9 @@ int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& v
 int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, int R, int C,
                            const double* baseT, int ld, const int32_t* base_basic,
                            const int32_t* base_bcount, const double* base_sol, int nsol);
+// sens_batch_ranging_kernels.hip: the report of every scenario into `out`, laid out by `pl`
+int sens_batch_ranging_launch(hipStream_t s, const SensBatchView& vw, char* out,
+                              const SensBatchRangingPlan& pl);
 // sens_engine.hip
 lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,
                       const int32_t** basic, const int32_t** bcount,
@@ -35,6 +39,12 @@ struct lpr_sens_batch {
     lpr_sens_edit* d_edits = nullptr;
     double* d_payload = nullptr;
     BatchRunLists run;  // the running lists and their counters; one form per call
+    // lpr_sens_batch_ranging: the output block (device) and its pinned mirror, allocated at the
+    // first call (the batch's maximal shape never changes), and the events around the kernel
+    char* rng_out = nullptr;
+    char* rng_pin = nullptr;
+    hipEvent_t rng_ev[2] = {nullptr, nullptr};
+    bool rng_timed = false;
 };
 
 namespace {
@@ -50,6 +60,14 @@ void sb_release_device(lpr_sens_batch* b) {
     hipFree(v.snap); hipFree(v.sol); hipFree(v.log); hipFree(v.outcome); hipFree(v.edit_piv);
     hipFree(b->d_edits); hipFree(b->d_payload);
     b->run.release();
+    hipFree(b->rng_out);
+    if (b->rng_pin) hipHostFree(b->rng_pin);
+    b->rng_out = b->rng_pin = nullptr;
+    for (hipEvent_t& ev : b->rng_ev) {
+        if (ev) hipEventDestroy(ev);
+        ev = nullptr;
+    }
+    b->rng_timed = false;
     v.desc = nullptr;
     v.cur = v.alt = v.sol = nullptr;
     v.basic = v.bcount = v.snap = v.log = v.outcome = nullptr;
@@ -476,6 +494,73 @@ int lpr_sens_batch_log_read(lpr_sens_batch* b, int32_t k, int32_t* triples, int6
                            (size_t)n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost,
                            b->eng->stream));
     LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// DisplayRangeNonBasic :276-297, DisplayRangeBasic :324-359, DisplayRangeRHS :396-424,
+// ShadowPrices :212-222, GetBasicRow :69-84 of every scenario on the state the batch holds now
+int lpr_sens_batch_ranging(lpr_sens_batch* b, int32_t* kind, int32_t* var_row,
+                           double* reduced_cost, double* cost_lo, double* cost_hi, double* shadow,
+                           double* rhs_lo, double* rhs_hi, double* rhs_now) {
+    LPR_LIVE_HANDLE(b, "scenario batch");
+    SensBatchRangingPlan pl;
+    if (!sens_batch_ranging_plan(b->count, b->base_R, b->base_C, b->vw.R, b->vw.C, &pl)) {
+        set_error("lpr_sens_batch_ranging: a %d x %d base has no slack block (n < 0)", b->base_R,
+                  b->base_C);
+        return LPR_BAD_ARGUMENT;
+    }
+    hipStream_t s = b->eng->stream;
+    if (!b->rng_out && hipMalloc(&b->rng_out, pl.total) != hipSuccess) {
+        b->rng_out = nullptr;
+        (void)hipGetLastError();
+        set_error("lpr_sens_batch_ranging: output block allocation (%zu bytes) failed", pl.total);
+        return LPR_OUT_OF_MEMORY;
+    }
+    if (!b->rng_pin && hipHostMalloc(&b->rng_pin, pl.total) != hipSuccess) {
+        b->rng_pin = nullptr;
+        (void)hipGetLastError();
+        set_error("lpr_sens_batch_ranging: pinned buffer allocation (%zu bytes) failed", pl.total);
+        return LPR_OUT_OF_MEMORY;
+    }
+    for (hipEvent_t& ev : b->rng_ev)
+        if (!ev) LPR_HIP(hipEventCreate(&ev));
+    b->rng_timed = false;
+    // the kernel takes shapes and in_alt from the device descriptors, which are current after
+    // create and after every run (a run uploads h_desc before its first launch)
+    LPR_HIP(hipEventRecord(b->rng_ev[0], s));
+    const int rc = sens_batch_ranging_launch(s, b->vw, b->rng_out, pl);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    LPR_HIP(hipEventRecord(b->rng_ev[1], s));
+    // one copy of the whole output block, then plain host copies to whatever the caller asked for
+    LPR_HIP(hipMemcpyAsync(b->rng_pin, b->rng_out, pl.total, hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    b->rng_timed = true;
+    const size_t nc = (size_t)pl.count * pl.mc, nr = (size_t)pl.count * pl.mr;
+    auto put = [&](void* dst, size_t off, size_t bytes) {
+        if (dst && bytes) std::memcpy(dst, b->rng_pin + off, bytes);
+    };
+    put(kind, pl.o_kind, nc * sizeof(int32_t));
+    put(var_row, pl.o_row, nc * sizeof(int32_t));
+    put(reduced_cost, pl.o_rc, nc * sizeof(double));
+    put(cost_lo, pl.o_clo, nc * sizeof(double));
+    put(cost_hi, pl.o_chi, nc * sizeof(double));
+    put(shadow, pl.o_shadow, nr * sizeof(double));
+    put(rhs_lo, pl.o_rlo, nr * sizeof(double));
+    put(rhs_hi, pl.o_rhi, nr * sizeof(double));
+    put(rhs_now, pl.o_now, nr * sizeof(double));
+    return LPR_OK_OPTIMAL;
+}
+
+int lpr_sens_batch_ranging_time(lpr_sens_batch* b, double* kernel_ms) {
+    LPR_LIVE_HANDLE(b, "scenario batch");
+    if (!b->rng_timed) {
+        set_error("lpr_sens_batch_ranging_time: no lpr_sens_batch_ranging call has completed on "
+                  "this handle");
+        return LPR_BAD_ARGUMENT;
+    }
+    float ms = 0.f;
+    LPR_HIP(hipEventElapsedTime(&ms, b->rng_ev[0], b->rng_ev[1]));
+    if (kernel_ms) *kernel_ms = ms;
     return LPR_OK_OPTIMAL;
 }
 

@@ -11,30 +11,13 @@
 // NaN sticks once met, and the combine keeps both properties.  Everything below is that one rule:
 // a lane folds its two adjacent columns, lanes are combined in lane order (= column order), tiles
 // in tile order by the second launch.  No atomics, nothing depends on arrival order.
+#include "dotnet_minmax.hpp"  // dn_max / dn_min, kRngEps
 #include "engine_common.hpp"
 #include "sens_ranging_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace lpr {
-
-namespace {
-
-constexpr double kRngEps = 1e-9;  // SensitivityAnalyzer.cs:20
-
-// .NET Framework Math.Max / Math.Min on doubles (oracle/oracle_revised.c:90 quotes Max)
-__device__ __forceinline__ double dn_max(double a, double b) {
-    if (a > b) return a;
-    if (a != a) return a;
-    return b;
-}
-__device__ __forceinline__ double dn_min(double a, double b) {
-    if (a < b) return a;
-    if (a != a) return a;
-    return b;
-}
-
-}  // namespace
 
 // One pass over rows 1..m.  Grid (tile columns, tile rows), tile = kRngTileRows x kRngTileCols.
 // Every element is read from HBM once (one dwordx4 per lane and row); it feeds its row's partial

@@ -14,7 +14,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
-from .engine import SensState
+from .engine import RangingReport, SensState
 
 # op name -> (code, number of integer arguments, takes a value)
 EDIT_OPS = {
@@ -153,6 +153,29 @@ def pack_grow_scripts(scripts: Sequence[Sequence[tuple]]) -> PackedGrowScripts:
     return PackedGrowScripts(nedits, edits, payload)
 
 
+RANGING_COLUMN_FIELDS = ("kind", "var_row", "reduced_cost", "cost_lo", "cost_hi")
+RANGING_ROW_FIELDS = ("shadow", "rhs_lo", "rhs_hi", "rhs_now")
+
+
+def trim_ranging(padded: RangingReport, k: int, rows: int, cols: int) -> RangingReport:
+    """Row k of the padded arrays of ``ranging_arrays()`` cut to a rows x cols scenario: the
+    per-column fields keep cols - 1 entries, the per-constraint fields rows - 1.  What is cut off
+    must be the padding fill (NO_BASIC_ENTRY / NaN) and nothing else."""
+    out = {}
+    for fields, keep in ((RANGING_COLUMN_FIELDS, cols - 1), (RANGING_ROW_FIELDS, rows - 1)):
+        for f in fields:
+            row = getattr(padded, f)[k]
+            if keep < 0 or keep > row.shape[0]:
+                raise ValueError(f"{f}: a {rows} x {cols} scenario does not fit a padded row of "
+                                 f"{row.shape[0]}")
+            tail = row[keep:]
+            fill = (tail == NO_BASIC_ENTRY) if row.dtype == np.int32 else np.isnan(tail)
+            if not fill.all():
+                raise ValueError(f"{f}: scenario {k} has data past its own shape {rows} x {cols}")
+            out[f] = row[:keep].copy()
+    return RangingReport(**out)
+
+
 class SensitivityBatch:
     """``len(scripts)`` scenarios over the state ``base`` holds now (lpr_sens_batch_*).  The base
     is only read and may be destroyed afterwards."""
@@ -227,6 +250,46 @@ class SensitivityBatch:
             ns.ctypes.data_as(C.POINTER(C.c_int32)),
             basic.ctypes.data_as(C.POINTER(C.c_int32))), "lpr_sens_batch_state_read")
         return z, ns, basic[:self.Count * m].reshape(self.Count, m)
+
+    def _shape_read(self) -> Tuple[np.ndarray, np.ndarray, int, int]:
+        """(rows, cols) per scenario as of now and the batch-wide (max_rows, max_cols); in a
+        fixed-shape batch every entry is the base's shape."""
+        rows = np.zeros(self.Count, dtype=np.int32)
+        cols = np.zeros(self.Count, dtype=np.int32)
+        mr, mc = C.c_int32(), C.c_int32()
+        N.check(N.lib.lpr_sens_batch_shape_read(
+            self._h, rows.ctypes.data_as(C.POINTER(C.c_int32)),
+            cols.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(mr), C.byref(mc)),
+            "lpr_sens_batch_shape_read")
+        return rows, cols, mr.value, mc.value
+
+    def ranging_arrays(self) -> RangingReport:
+        """The sensitivity report of every scenario from one device call (lpr_sens_batch_ranging):
+        the nine arrays of ``SensState.ranging()``, scenario k in row k.  The per-column arrays are
+        Count x (max_cols - 1), the per-constraint arrays Count x (max_rows - 1); entries past a
+        scenario's own shape are NO_BASIC_ENTRY (int) or NaN (float)."""
+        _, _, mr, mc = self._shape_read()
+        # the call writes every cell, the padding included
+        ints = [np.empty((self.Count, mc - 1), dtype=np.int32) for _ in range(2)]
+        cols = [np.empty((self.Count, mc - 1), dtype=np.float64) for _ in range(3)]
+        rows = [np.empty((self.Count, mr - 1), dtype=np.float64) for _ in range(4)]
+        N.check(N.lib.lpr_sens_batch_ranging(
+            self._h, *[a.ctypes.data_as(C.POINTER(C.c_int32)) for a in ints],
+            *[a.ctypes.data_as(C.POINTER(C.c_double)) for a in cols + rows]),
+            "lpr_sens_batch_ranging")
+        return RangingReport(*ints, *cols, *rows)
+
+    def Ranging(self, k: int) -> RangingReport:
+        """Scenario k's report at its own shape, as ``SensState.ranging()`` returns one."""
+        rows, cols, _, _ = self._shape_read()
+        return trim_ranging(self.ranging_arrays(), int(k), int(rows[k]), int(cols[k]))
+
+    def RangingTime(self) -> float:
+        """Device milliseconds of the last ranging_arrays() / Ranging() call's kernel, from events."""
+        ms = C.c_double()
+        N.check(N.lib.lpr_sens_batch_ranging_time(self._h, C.byref(ms)),
+                "lpr_sens_batch_ranging_time")
+        return ms.value
 
     # -- per-scenario reads ---------------------------------------------------------------------
     def Outcomes(self, k: int) -> List[int]:
