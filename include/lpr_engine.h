@@ -798,6 +798,34 @@ int lpr_sens_batch_create(lpr_sens* base, int32_t count, const int32_t* nedits,
 int lpr_sens_batch_create_grow(lpr_sens* base, int32_t count, const int32_t* nedits,
                                const lpr_sens_edit* edits, const double* payload,
                                int64_t npayload, int32_t log_cap, lpr_sens_batch** out);
+/* Many solved models, one script each: scenario k is a fresh analyzer on LP item[k] of a solved
+ * lpr_batch -- new SensitivityAnalyzer(GetFinalTableau(), SolutionVector, FinalZ, BasicVariables)
+ * (Program.cs:147-151, SensitivityAnalyzer.cs:22-39), run per scenario on the device -- followed by
+ * script k (ops 0..6, payload rules as in lpr_sens_batch_create_grow).  The state it starts from:
+ * the LP's final tableau; solutionVector = ExtractSolution() over the LP's n
+ * (PrimalSimplexSolver.cs:213-249), so solutionVector.Count = n; finalZ = tableau[0, cols - 1];
+ * basicVars from RebuildBasicsFromTableau (:35, :706-723: the first qualifying column per row, -1
+ * where none), not the LP batch's stored basis.  item == NULL means item[k] = k, and count must
+ * then be the LP batch's count; otherwise an index may repeat (several scripts on one model) and
+ * the order is free.
+ * The handle is an ordinary lpr_sens_batch whose scenarios have their own shapes, reported as in
+ * a grow batch (lpr_sens_batch_shape_read; state_read packs basicVars by max_rows - 1).  Every
+ * array is sized by the largest shape any scenario can reach, so one large LP sizes every slice
+ * and picks the form: group mixed batches by size.  lpr_sens_batch_info's rows and cols report the
+ * largest base shape over the chosen LPs.
+ * LPR_BAD_ARGUMENT, naming the scenario and the item, with nothing allocated: a null or orphaned
+ * LP batch, count < 1, an item outside the batch, an item whose status is not LPR_OK_OPTIMAL (an
+ * unbounded LP has no SolutionVector, PrimalSimplexSolver.cs:129-135; a running or pivot-limited
+ * one no final tableau), an item with cols < rows (as lpr_sens_create), a script that can grow its
+ * own base past 1024 x 2048, and the payload and op errors of lpr_sens_batch_create_grow.
+ * Synchronous: the LP batch (only read), the edits and the payload may go once it has returned. */
+int lpr_sens_batch_from_batch(lpr_batch* lps, int32_t count, const int32_t* item,
+                              const int32_t* nedits, const lpr_sens_edit* edits,
+                              const double* payload, int64_t npayload, int32_t log_cap,
+                              lpr_sens_batch** out);
+/* Device time in milliseconds of the constructor kernel of the lpr_sens_batch_from_batch call that
+ * made this handle, from events; LPR_BAD_ARGUMENT on a handle of another create. */
+int lpr_sens_batch_from_batch_time(lpr_sens_batch* b, double* kernel_ms);
 int lpr_sens_batch_destroy(lpr_sens_batch* b);
 
 typedef struct lpr_sens_batch_opts {
@@ -824,7 +852,8 @@ typedef struct lpr_sens_batch_result {
 int lpr_sens_batch_run(lpr_sens_batch* b, const lpr_sens_batch_opts* opts,
                        lpr_sens_batch_result* res);
 /* count, numRows, numCols, edits of all scripts together, the pivot-log capacity per scenario and
- * the form of the last run (0 before the first); any may be NULL. */
+ * the form of the last run (0 before the first); any may be NULL.  rows x cols is the base's shape;
+ * in a batch from lpr_sens_batch_from_batch the largest base shape over the chosen LPs. */
 int lpr_sens_batch_info(lpr_sens_batch* b, int32_t* count, int32_t* rows, int32_t* cols,
                         int64_t* total_edits, int32_t* log_cap, int32_t* form);
 /* rows[k] x cols[k]: the shape of scenario k as of the last run (the base's, where nothing has

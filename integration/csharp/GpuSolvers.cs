@@ -802,4 +802,51 @@ namespace LPR_381_Group_V22.SensitivityAnalysis
 
         public void Dispose() { if (h != IntPtr.Zero) { NativeMethods.lpr_sens_destroy(h); h = IntPtr.Zero; } }
     }
+
+    /// One analyzer per solved model of a PrimalSimplexBatch, each with its own script of edits (lpr_sens_batch_from_batch): what
+    /// Program.cs:147-151 builds from GetFinalTableau(), SolutionVector, FinalZ and BasicVariables, for every model on the device.
+    /// items[k] is the model of scenario k (null: model k); every one must be optimal.  A thin wrapper: the reads are the
+    /// lpr_sens_batch_* calls of NativeMethods.
+    internal sealed class GpuSensitivityModelBatch : IDisposable
+    {
+        private IntPtr h;
+        internal readonly int Count;
+
+        internal GpuSensitivityModelBatch(PrimalSimplexBatch primal, int[] items, int[] nedits, LprSensEdit[] edits, double[] payload, int logCap = 0)
+        {
+            Count = nedits.Length;
+            NativeMethods.ThrowIfError(NativeMethods.lpr_sens_batch_from_batch(primal.Handle, Count, items, nedits, edits, payload,
+                payload == null ? 0 : payload.LongLength, logCap, out h), "lpr_sens_batch_from_batch");
+        }
+
+        internal LprSensBatchResult Run(long maxPivots = 0)
+        {
+            var opts = new LprSensBatchOpts { max_pivots = maxPivots };
+            NativeMethods.ThrowIfError(NativeMethods.lpr_sens_batch_run(h, ref opts, out LprSensBatchResult res), "lpr_sens_batch_run");
+            return res;
+        }
+
+        /// rows[k] x cols[k] of every scenario and the maxima the bulk reads are packed by
+        internal void Shapes(out int[] rows, out int[] cols, out int maxRows, out int maxCols)
+        {
+            rows = new int[Count]; cols = new int[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_sens_batch_shape_read(h, rows, cols, out maxRows, out maxCols), "lpr_sens_batch_shape_read");
+        }
+
+        /// The ranging report of every scenario, scenario k in row k of each array (padded to the maxima of Shapes)
+        internal GpuSensitivity.Ranging RangingReport()
+        {
+            Shapes(out _, out _, out int R, out int C);
+            int nc = Count * (C - 1), nr = Count * (R - 1);
+            var r = new GpuSensitivity.Ranging
+            {
+                Kind = new int[nc], VarRow = new int[nc], ReducedCost = new double[nc], CostLo = new double[nc], CostHi = new double[nc],
+                Shadow = new double[nr], RhsLo = new double[nr], RhsHi = new double[nr], RhsNow = new double[nr],
+            };
+            NativeMethods.ThrowIfError(NativeMethods.lpr_sens_batch_ranging(h, r.Kind, r.VarRow, r.ReducedCost, r.CostLo, r.CostHi, r.Shadow, r.RhsLo, r.RhsHi, r.RhsNow), "lpr_sens_batch_ranging");
+            return r;
+        }
+
+        public void Dispose() { if (h != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_sens_batch_destroy(h), "lpr_sens_batch_destroy"); h = IntPtr.Zero; } }
+    }
 }

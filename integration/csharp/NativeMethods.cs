@@ -265,6 +265,8 @@ namespace LPR_381_Group_V22.Native
         // ---- Sensitivity scenario batch (DESIGN.md section 14): one solved model, many what-if scripts per call ----
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_create(IntPtr sens, int count, int[] nedits, LprSensEdit[] edits, int log_cap, out IntPtr sensBatch);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_create_grow(IntPtr sens, int count, int[] nedits, LprSensEdit[] edits, double[] payload, long npayload, int log_cap, out IntPtr sensBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_from_batch(IntPtr batch, int count, int[] item, int[] nedits, LprSensEdit[] edits, double[] payload, long npayload, int log_cap, out IntPtr sensBatch);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_from_batch_time(IntPtr sensBatch, out double kernelMs);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_destroy(IntPtr sensBatch);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_run(IntPtr sensBatch, ref LprSensBatchOpts opts, out LprSensBatchResult res);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_info(IntPtr sensBatch, out int count, out int rows, out int cols, out long total_edits, out int log_cap, out int form);

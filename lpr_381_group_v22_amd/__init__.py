@@ -17,8 +17,8 @@ from .primal_batch import PrimalSimplexBatch, pack_models
 from .primal_simplex_solver import PrimalSimplexSolver
 from .revised_batch import RevisedSimplexBatch, pack_revised_models
 from .revised_primal_simplex_solver import RevisedPrimalSimplexSolver, SolverException
-from .sens_batch import (SensitivityBatch, SensitivityGrowBatch, pack_grow_scripts,
-                         pack_scripts)
+from .sens_batch import (SensitivityBatch, SensitivityGrowBatch, SensitivityModelBatch,
+                         optimal_items, pack_grow_scripts, pack_scripts)
 
 __all__ = [
     "Engine", "Tableau", "default_engine", "Constraint", "InputFileParser",
@@ -27,6 +27,7 @@ __all__ = [
     "Comm", "solve_level_sync_native", "KnapsackBranchBoundSimplex", "KnapsackBranchBoundSolver",
     "PrimalSimplexBatch", "pack_models", "BranchAndBoundBatch", "solve_integer_programs",
     "SensitivityBatch", "SensitivityGrowBatch", "pack_scripts", "pack_grow_scripts",
+    "SensitivityModelBatch", "optimal_items",
     "CuttingPlaneBatch", "pack_tableaux", "KnapsackBatch", "pack_knapsacks", "solve_knapsacks",
     "RevisedSimplexBatch", "pack_revised_models",
     "_native",

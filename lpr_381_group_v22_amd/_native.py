@@ -431,6 +431,9 @@ SIGNATURES = {
     "lpr_sens_batch_create": (C.c_int, [_P, C.c_int32, _I32, C.POINTER(SensEdit), C.c_int32, _PP]),
     "lpr_sens_batch_create_grow": (C.c_int, [_P, C.c_int32, _I32, C.POINTER(SensEdit), _D,
                                              C.c_int64, C.c_int32, _PP]),
+    "lpr_sens_batch_from_batch": (C.c_int, [_P, C.c_int32, _I32, _I32, C.POINTER(SensEdit), _D,
+                                            C.c_int64, C.c_int32, _PP]),
+    "lpr_sens_batch_from_batch_time": (C.c_int, [_P, _D]),
     "lpr_sens_batch_destroy": (C.c_int, [_P]),
     "lpr_sens_batch_run": (C.c_int, [_P, C.POINTER(SensBatchOpts), C.POINTER(SensBatchResult)]),
     "lpr_sens_batch_info": (C.c_int, [_P, _I32, _I32, _I32, _I64, _I32, _I32]),

@@ -74,6 +74,15 @@ struct SensScenario {
     int32_t R, C;        // the scenario's shape now (AddNewActivity / AddNewConstraint grow it)
 };
 
+// lpr_sens_batch_from_batch: the LP a scenario is constructed on, as the LP batch's descriptor
+// (BatchDesc) has it.  rows <= cols, 0 <= n <= cols - 1.
+struct SensModelSrc {
+    int64_t t_off;  // the LP's final tableau: rows x cols row-major, compact, at slab + t_off
+    int32_t rows, cols;
+    int32_t n;      // decision variables: solutionVector.Count
+    int32_t item;   // the LP's index in its batch
+};
+
 // What a launch needs of the batch: strides and the device arrays.
 struct SensBatchView {
     int32_t R, C;        // the maximal shape of a scenario: what every stride below is sized by

@@ -2,12 +2,16 @@
 // lpr_sens_batch_*).  Every scenario runs its whole script on the device
 // with the rules of SensitivityAnalyzer; the host copies the base state in, relaunches the
 // bounded script kernel while scenarios are still running (BatchRunLists of batch_common.hpp,
-// with one form per call) and copies results out.
+// with one form per call) and copies results out.  lpr_sens_batch_from_batch (section 20) starts
+// every scenario from an LP of a solved LP batch instead: the analyzer's constructor runs per
+// scenario on the device.
 #include "sens_batch_common.hpp"
 #include "sens_batch_ranging_common.hpp"
 
 #include <algorithm>
+#include <cstdio>
 #include <new>
+#include <string>
 
 namespace lpr {
 int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& vw,
@@ -16,6 +20,10 @@ int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& v
 int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, int R, int C,
                            const double* baseT, int ld, const int32_t* base_basic,
                            const int32_t* base_bcount, const double* base_sol, int nsol);
+int sens_batch_launch_from_models(hipStream_t s, const SensBatchView& vw, int count,
+                                  const SensModelSrc* src, const double* slab);
+// batch_engine.hip
+lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
 // sens_batch_ranging_kernels.hip: the report of every scenario into `out`, laid out by `pl`
 int sens_batch_ranging_launch(hipStream_t s, const SensBatchView& vw, char* out,
                               const SensBatchRangingPlan& pl);
@@ -33,7 +41,10 @@ struct lpr_sens_batch {
     int64_t total_edits = 0;
     int form = 0;  // the form of the last run (0: none yet)
     bool grow = false;         // from lpr_sens_batch_create_grow: scripts may hold the add edits
-    int32_t base_R = 0, base_C = 0;  // the base's shape (vw.R x vw.C is the maximal one)
+    int32_t base_R = 0, base_C = 0;  // the base's shape (vw.R x vw.C is the maximal one); from an
+                                     // LP batch: the largest base shape over the chosen LPs
+    int32_t min_R = 0;         // the least row count of a base (base_R unless from an LP batch)
+    double ctor_ms = -1.0;     // lpr_sens_batch_from_batch: the constructor kernel, from events
     SensBatchView vw{};
     std::vector<SensScenario> h_desc;  // host mirror, current after create and every run
     lpr_sens_edit* d_edits = nullptr;
@@ -84,18 +95,81 @@ int sb_fail(lpr_sens_batch* b, int rc) {
     return rc;
 }
 
-// count private copies of the state of `base` (SensitivityAnalyzer.cs:14-18), one script each.
-// W names the call in messages; grow: the scripts may hold the two add edits, whose columns and
-// rows lie in `payload`.
-int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int32_t* nedits,
-              const lpr_sens_edit* edits, const double* payload, int64_t npayload,
-              int32_t log_cap, lpr_sens_batch** out) {
-    int R = 0, C = 0, ld = 0;
+// lpr_sens_batch_from_batch: what the scenarios are constructed on instead of a base analyzer
+struct SbModels {
+    lpr_engine* eng;                    // the LP batch's engine
+    const std::vector<BatchDesc>* bd;   // its descriptors (host mirror) and tableau slab
+    const double* slab;
+    const int32_t* item;                // the LP of scenario k; null: LP k
+};
+
+// The LP of every scenario checked and listed; *R x *C is the largest base shape, *min_R the
+// least row count and *nsol the longest solutionVector.
+int sb_models(const char* W, const SbModels& md, int32_t count, std::vector<SensModelSrc>* srcs,
+              int* R, int* C, int* min_R, int* nsol) {
+    const int32_t have = (int32_t)md.bd->size();
+    if (!md.item && count != have) {
+        set_error("%s: count=%d without an item list; the LP batch holds %d LPs", W, count, have);
+        return LPR_BAD_ARGUMENT;
+    }
+    try {
+        srcs->resize((size_t)count);
+    } catch (...) {
+        return sb_oom("item list (host)", count);
+    }
+    *R = *C = *nsol = 0;
+    *min_R = INT32_MAX;
+    for (int32_t k = 0; k < count; ++k) {
+        const int32_t it = md.item ? md.item[k] : k;
+        if (it < 0 || it >= have) {
+            set_error("%s: scenario %d names item %d, outside the LP batch's 0..%d", W, k, it,
+                      have - 1);
+            return LPR_BAD_ARGUMENT;
+        }
+        const BatchDesc& d = (*md.bd)[(size_t)it];
+        if (d.status != LPR_OK_OPTIMAL) {
+            set_error("%s: scenario %d names item %d, which has no optimal final tableau (status "
+                      "%d: %s); the analyzer takes the SolutionVector of an optimal solve", W, k, it,
+                      d.status,
+                      d.status == kRunning ? "not solved"
+                      : d.status == LPR_PIVOT_LIMIT ? "stopped at its pivot limit"
+                      : d.status == LPR_UNBOUNDED ? "unbounded" : "not optimal");
+            return LPR_BAD_ARGUMENT;
+        }
+        if (d.cols < d.rows || d.n < 0 || d.n > d.cols - 1) {
+            set_error("%s: scenario %d names item %d, a %d x %d tableau with n=%d; an analyzer "
+                      "needs cols >= rows (lpr_sens_create) and 0 <= n < cols", W, k, it, d.rows,
+                      d.cols, d.n);
+            return LPR_BAD_ARGUMENT;
+        }
+        SensModelSrc& s = (*srcs)[(size_t)k];
+        s.t_off = d.t_off;
+        s.rows = d.rows;
+        s.cols = d.cols;
+        s.n = d.n;
+        s.item = it;
+        *R = std::max(*R, (int)d.rows);
+        *C = std::max(*C, (int)d.cols);
+        *min_R = std::min(*min_R, (int)d.rows);
+        *nsol = std::max(*nsol, (int)d.n);
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// count scenarios, one script each: private copies of the state of `base`
+// (SensitivityAnalyzer.cs:14-18), or with `md` (base null) a fresh analyzer per scenario on an LP of
+// a solved LP batch.  W names the call in messages; grow: the scripts may hold the two add edits,
+// whose columns and rows lie in `payload`.
+int sb_create(const char* W, bool grow, lpr_sens* base, const SbModels* md, int32_t count,
+              const int32_t* nedits, const lpr_sens_edit* edits, const double* payload,
+              int64_t npayload, int32_t log_cap, lpr_sens_batch** out) {
+    int R = 0, C = 0, ld = 0;  // the base's shape; with md the largest one
     const double* baseT = nullptr;
     const int32_t *base_basic = nullptr, *base_bcount = nullptr;
     const std::vector<double>* base_sol = nullptr;
     double z = 0.0;
-    lpr_engine* e = sens_view(base, &R, &C, &ld, &baseT, &base_basic, &base_bcount, &base_sol, &z);
+    lpr_engine* e = md ? md->eng : sens_view(base, &R, &C, &ld, &baseT, &base_basic, &base_bcount,
+                                             &base_sol, &z);
     if (!e) {
         set_error("%s: the base handle is null or orphaned: its engine has been closed", W);
         return LPR_BAD_ARGUMENT;
@@ -106,6 +180,24 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
         return LPR_BAD_ARGUMENT;
     }
     *out = nullptr;
+    std::vector<SensModelSrc> srcs;  // md: the LP of every scenario
+    int min_R = 0, nsol = 0;
+    if (md) {
+        const int rc = sb_models(W, *md, count, &srcs, &R, &C, &min_R, &nsol);
+        if (rc != LPR_OK_OPTIMAL) return rc;
+    } else {
+        min_R = R;
+        nsol = (int)base_sol->size();
+    }
+    // "scenario k", with the LP it names where there is one
+    auto who = [&](int32_t k) {
+        char buf[64];
+        if (md)
+            std::snprintf(buf, sizeof buf, "scenario %d (item %d)", k, srcs[(size_t)k].item);
+        else
+            std::snprintf(buf, sizeof buf, "scenario %d", k);
+        return std::string(buf);
+    };
     if (R > kBatchMaxRowsH || C > kBatchMaxColsH) {
         set_error("%s: the base is a %d x %d tableau, beyond the batch limit of %d x %d (form H); "
                   "edit it alone with lpr_sens_*", W, R, C, kBatchMaxRowsH, kBatchMaxColsH);
@@ -143,27 +235,28 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
     } else {
         int64_t q = 0;
         for (int32_t k = 0; k < count; ++k) {
-            int rows = R, cols = C;
+            const int R0 = md ? srcs[(size_t)k].rows : R, C0 = md ? srcs[(size_t)k].cols : C;
+            int rows = R0, cols = C0;
             for (int32_t i = 0; i < nedits[k]; ++i, ++q) {
                 const lpr_sens_edit& ed = edits[q];
                 if (ed.op < LPR_SENS_EDIT_RESOLVE_ALL || ed.op > LPR_SENS_EDIT_ADD_CONSTRAINT) {
-                    set_error("%s: scenario %d edit %d has op %d; the ops are 0..6", W, k, i,
+                    set_error("%s: %s edit %d has op %d; the ops are 0..6", W, who(k).c_str(), i,
                               ed.op);
                     return LPR_BAD_ARGUMENT;
                 }
                 if (ed.op < LPR_SENS_EDIT_ADD_ACTIVITY) continue;
                 if (ed.b < 0 || ed.a < 0 || (int64_t)ed.a + ed.b > npayload) {
-                    set_error("%s: scenario %d edit %d (op %d) takes payload [%d, %d + %d), "
-                              "outside [0, %lld)", W, k, i, ed.op, ed.a, ed.a, ed.b,
+                    set_error("%s: %s edit %d (op %d) takes payload [%d, %d + %d), "
+                              "outside [0, %lld)", W, who(k).c_str(), i, ed.op, ed.a, ed.a, ed.b,
                               (long long)npayload);
                     return LPR_BAD_ARGUMENT;
                 }
                 rows += ed.op == LPR_SENS_EDIT_ADD_CONSTRAINT;
                 cols += 1;
                 if (rows > kBatchMaxRowsH || cols > kBatchMaxColsH) {
-                    set_error("%s: scenario %d edit %d can grow the %d x %d base to %d x %d, "
-                              "beyond the batch limit of %d x %d (form H)", W, k, i, R, C, rows,
-                              cols, kBatchMaxRowsH, kBatchMaxColsH);
+                    set_error("%s: %s edit %d can grow the %d x %d base to %d x %d, "
+                              "beyond the batch limit of %d x %d (form H)", W, who(k).c_str(), i,
+                              R0, C0, rows, cols, kBatchMaxRowsH, kBatchMaxColsH);
                     return LPR_BAD_ARGUMENT;
                 }
             }
@@ -180,7 +273,7 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
     b->grow = grow;
     b->base_R = R;
     b->base_C = C;
-    const int nsol = (int)base_sol->size();
+    b->min_R = min_R;
     SensBatchView& v = b->vw;
     v.R = maxR;
     v.C = maxC;
@@ -201,10 +294,10 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
         d.edit_off = at;
         d.nedits = nedits[k];
         d.phase = kPhaseApply;
-        d.nsol = nsol;
+        d.nsol = md ? srcs[(size_t)k].n : nsol;  // md: z and old_z come from the device
         d.status = kRunning;
-        d.R = R;
-        d.C = C;
+        d.R = md ? srcs[(size_t)k].rows : R;
+        d.C = md ? srcs[(size_t)k].cols : C;
         at += nedits[k];
     }
     const int64_t n = count, RC = (int64_t)maxR * maxC;
@@ -232,8 +325,25 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
     v.payload = b->d_payload;
     hipStream_t s = e->stream;
     double* d_sol = nullptr;  // the base's solutionVector is a host mirror
+    SensModelSrc* d_src = nullptr;  // md: the LP of every scenario
+    hipEvent_t ev[2] = {nullptr, nullptr};  // md: around the constructor kernel
+    auto drop = [&]() {
+        hipFree(d_sol);
+        hipFree(d_src);
+        for (hipEvent_t& x : ev)
+            if (x) hipEventDestroy(x);
+    };
     hipError_t err = hipSuccess;
-    if (nsol > 0) {
+    if (md) {
+        if (hipMalloc(&d_src, (size_t)count * sizeof(SensModelSrc)) != hipSuccess) {
+            (void)hipGetLastError();
+            return sb_fail(b, sb_oom("item list", count));
+        }
+        err = hipMemcpyAsync(d_src, srcs.data(), (size_t)count * sizeof(SensModelSrc),
+                             hipMemcpyHostToDevice, s);
+        for (hipEvent_t& x : ev)
+            if (err == hipSuccess) err = hipEventCreate(&x);
+    } else if (nsol > 0) {
         if (hipMalloc(&d_sol, (size_t)nsol * sizeof(double)) != hipSuccess)
             return sb_fail(b, sb_oom("base solution", nsol));
         err = hipMemcpyAsync(d_sol, base_sol->data(), (size_t)nsol * sizeof(double),
@@ -252,7 +362,7 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
     try {
         not_run.assign((size_t)te, kSensEditNotRun);
     } catch (...) {
-        hipFree(d_sol);
+        drop();
         return sb_fail(b, sb_oom("outcomes (host)", te));
     }
     if (err == hipSuccess)
@@ -261,12 +371,26 @@ int sb_create(const char* W, bool grow, lpr_sens* base, int32_t count, const int
     if (err == hipSuccess) err = hipMemsetAsync(v.edit_piv, 0, (size_t)te * sizeof(int64_t), s);
     if (err == hipSuccess) err = hipMemsetAsync(v.sol, 0, (size_t)(n * v.sol_cap) * sizeof(double), s);
     rc = LPR_OK_OPTIMAL;
-    if (err == hipSuccess)
+    if (err == hipSuccess && md) {
+        // :22-39 per scenario on the device; the descriptors come back with z and old_z
+        err = hipEventRecord(ev[0], s);
+        if (err == hipSuccess) rc = sens_batch_launch_from_models(s, v, count, d_src, md->slab);
+        if (err == hipSuccess && rc == LPR_OK_OPTIMAL) err = hipEventRecord(ev[1], s);
+        if (err == hipSuccess && rc == LPR_OK_OPTIMAL)
+            err = hipMemcpyAsync(b->h_desc.data(), v.desc, (size_t)count * sizeof(SensScenario),
+                                 hipMemcpyDeviceToHost, s);
+    } else if (err == hipSuccess) {
         rc = sens_batch_launch_init(s, v, count, R, C, baseT, ld, base_basic, base_bcount, d_sol,
                                     nsol);
+    }
     if (err == hipSuccess && rc == LPR_OK_OPTIMAL)
         err = hipStreamSynchronize(s);  // edits are borrowed, and the base may go after this call
-    hipFree(d_sol);
+    if (err == hipSuccess && rc == LPR_OK_OPTIMAL && md) {
+        float ms = 0.f;
+        err = hipEventElapsedTime(&ms, ev[0], ev[1]);
+        b->ctor_ms = ms;
+    }
+    drop();
     if (err != hipSuccess) {
         set_error("%s: %s", W, hipGetErrorString(err));
         rc = LPR_DEVICE_ERROR;
@@ -290,16 +414,48 @@ extern "C" {
 
 int lpr_sens_batch_create(lpr_sens* base, int32_t count, const int32_t* nedits,
                           const lpr_sens_edit* edits, int32_t log_cap, lpr_sens_batch** out) {
-    return sb_create("lpr_sens_batch_create", false, base, count, nedits, edits, nullptr, 0,
-                     log_cap, out);
+    return sb_create("lpr_sens_batch_create", false, base, nullptr, count, nedits, edits, nullptr,
+                     0, log_cap, out);
 }
 
 // ... whose scripts may also hold AddNewActivity (:534-584) and AddNewConstraint (:609-659)
 int lpr_sens_batch_create_grow(lpr_sens* base, int32_t count, const int32_t* nedits,
                                const lpr_sens_edit* edits, const double* payload,
                                int64_t npayload, int32_t log_cap, lpr_sens_batch** out) {
-    return sb_create("lpr_sens_batch_create_grow", true, base, count, nedits, edits, payload,
-                     npayload, log_cap, out);
+    return sb_create("lpr_sens_batch_create_grow", true, base, nullptr, count, nedits, edits,
+                     payload, npayload, log_cap, out);
+}
+
+// new SensitivityAnalyzer(GetFinalTableau(), SolutionVector, FinalZ, BasicVariables)
+// (Program.cs:147-151, SensitivityAnalyzer.cs:22-39) per scenario, on LP item[k] of a solved LP
+// batch, device to device; the scripts are those of a grow batch
+int lpr_sens_batch_from_batch(lpr_batch* lps, int32_t count, const int32_t* item,
+                              const int32_t* nedits, const lpr_sens_edit* edits,
+                              const double* payload, int64_t npayload, int32_t log_cap,
+                              lpr_sens_batch** out) {
+    static const char* W = "lpr_sens_batch_from_batch";
+    if (out) *out = nullptr;
+    SbModels md;
+    md.bd = nullptr;
+    md.slab = nullptr;
+    md.item = item;
+    md.eng = batch_view(lps, &md.bd, &md.slab);
+    if (!md.eng) {
+        set_error("%s: the LP batch is null or orphaned: its engine has been closed", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    return sb_create(W, true, nullptr, &md, count, nedits, edits, payload, npayload, log_cap, out);
+}
+
+int lpr_sens_batch_from_batch_time(lpr_sens_batch* b, double* kernel_ms) {
+    LPR_LIVE_HANDLE(b, "scenario batch");
+    if (b->ctor_ms < 0.0) {
+        set_error("lpr_sens_batch_from_batch_time: the batch was not made by "
+                  "lpr_sens_batch_from_batch");
+        return LPR_BAD_ARGUMENT;
+    }
+    if (kernel_ms) *kernel_ms = b->ctor_ms;
+    return LPR_OK_OPTIMAL;
 }
 
 int lpr_sens_batch_destroy(lpr_sens_batch* b) {
@@ -504,9 +660,10 @@ int lpr_sens_batch_ranging(lpr_sens_batch* b, int32_t* kind, int32_t* var_row,
                            double* rhs_lo, double* rhs_hi, double* rhs_now) {
     LPR_LIVE_HANDLE(b, "scenario batch");
     SensBatchRangingPlan pl;
-    if (!sens_batch_ranging_plan(b->count, b->base_R, b->base_C, b->vw.R, b->vw.C, &pl)) {
-        set_error("lpr_sens_batch_ranging: a %d x %d base has no slack block (n < 0)", b->base_R,
-                  b->base_C);
+    if (b->min_R < 2 ||
+        !sens_batch_ranging_plan(b->count, b->base_R, b->base_C, b->vw.R, b->vw.C, &pl)) {
+        set_error("lpr_sens_batch_ranging: a %d x %d base has no slack block (n < 0), or a base "
+                  "has no constraint row (least rows %d)", b->base_R, b->base_C, b->min_R);
         return LPR_BAD_ARGUMENT;
     }
     hipStream_t s = b->eng->stream;

@@ -12,6 +12,9 @@
 //                        kGrow (lpr_sens_batch_create_grow): the shape is the scenario's own, and
 //                        AddNewActivity (:534-584) / AddNewConstraint (:609-659) grow it in place
 //   k_sens_batch_init    the base state copied into every scenario
+//   k_sens_batch_from_models
+//                        lpr_sens_batch_from_batch: the analyzer's constructor (:22-39) per
+//                        scenario on the final tableau of an LP of a solved LP batch
 #include "batch_device.hpp"
 #include "sens_batch_common.hpp"
 
@@ -69,6 +72,30 @@ __device__ __forceinline__ void block_recount(const int32_t* basic, int m, int32
     for (int i = threadIdx.x; i < m; i += 256) {
         const int b = basic[i];
         if (b >= 0 && b < C) atomicAdd(&bcount[b], 1);
+    }
+    __syncthreads();
+}
+
+// RebuildBasicsFromTableau (:706-723) by the whole workgroup: basicVars[i] is the first column
+// whose GetBasicRow is i + 1, -1 where there is none, and the membership counts are counted again
+// from it.  basic (R - 1 entries) and bcount (C entries) may lie in LDS or in global memory.
+__device__ __forceinline__ void block_rebuild_basics(const double* T, int R, int C, int32_t* basic,
+                                                     int32_t* bcount) {
+    const int tid = threadIdx.x, m = R - 1, rhs = C - 1;
+    for (int i = tid; i < m; i += 256) basic[i] = kSensNoBasic;
+    for (int j = tid; j < C; j += 256) bcount[j] = 0;
+    __syncthreads();
+    for (int j = tid; j < rhs; j += 256) {  // the first such column per row
+        const int r = lane_basic_row(T, R, C, j);
+        if (r >= 1) atomicMin(&basic[r - 1], j);
+    }
+    __syncthreads();
+    for (int i = tid; i < m; i += 256) {
+        const int b = basic[i];
+        if (b == kSensNoBasic)
+            basic[i] = -1;
+        else
+            atomicAdd(&bcount[b], 1);
     }
     __syncthreads();
 }
@@ -344,23 +371,8 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
             dirty = true;
         }
 
-        if (phase == kPhaseRebuild) {  // RebuildBasicsFromTableau :706-723
-            for (int i = tid; i < m; i += 256) basic[i] = kSensNoBasic;
-            for (int j = tid; j < C; j += 256) bcount[j] = 0;
-            __syncthreads();
-            for (int j = tid; j < rhs; j += 256) {  // the first such column per row
-                const int r = lane_basic_row(T, R, C, j);
-                if (r >= 1) atomicMin(&basic[r - 1], j);
-            }
-            __syncthreads();
-            for (int i = tid; i < m; i += 256) {
-                const int b = basic[i];
-                if (b == kSensNoBasic)
-                    basic[i] = -1;
-                else
-                    atomicAdd(&bcount[b], 1);
-            }
-            __syncthreads();
+        if (phase == kPhaseRebuild) {
+            block_rebuild_basics(T, R, C, basic, bcount);
             phase = kPhaseDual;
         }
 
@@ -611,8 +623,77 @@ __global__ __launch_bounds__(256) void k_sens_batch_init(SensBatchView vw, int c
     for (int q = tid; q < nsol; q += 256) vw.sol[(size_t)k * vw.sol_cap + q] = base_sol[q];
 }
 
+// new SensitivityAnalyzer(GetFinalTableau(), SolutionVector, FinalZ, BasicVariables)
+// (Program.cs:147-151, SensitivityAnalyzer.cs:22-39) for every scenario of a batch made from an LP
+// batch: one workgroup per scenario, on the LP src[k] names.  In order:
+//   1. the LP's compact rows x cols tableau into the scenario's cur slice (:24), compact by the
+//      scenario's own cols; row 0's last cell already holds finalZ, so :32 stores what is there
+//   2. solutionVector = ExtractSolution() over the LP's n (PrimalSimplexSolver.cs:213-249: the
+//      first entry within 1e-9 of 1 is the basic row, a second one or any other entry above 1e-9
+//      gives 0), one lane per decision column; finalZ = tableau[0, cols - 1]
+//   3. RebuildBasicsFromTableau (:35), not the LP batch's stored basis
+//   4. the membership counts of basicVars
+//   5. the descriptor fields that depend on the LP: R, C, nsol, z, old_z
+// Steps 2 and 3 read the LP batch's slab, which nothing writes, so they do not wait for step 1.
+// No division; nothing depends on arrival order (atomicMin / atomicAdd on int32 in LDS).
+__global__ __launch_bounds__(256) void k_sens_batch_from_models(SensBatchView vw, int count,
+                                                                const SensModelSrc* __restrict__ src,
+                                                                const double* __restrict__ slab) {
+    __shared__ int32_t s_basic[kBatchMaxRowsH];  // R - 1 entries used
+    __shared__ int32_t s_bcount[kBatchMaxColsH];
+    const int k = blockIdx.x;
+    if (k >= count) return;
+    const int tid = threadIdx.x;
+    const SensModelSrc s = src[k];
+    const int R = s.rows, C = s.cols, m = R - 1, rhs = C - 1, RC = R * C;
+    const double* const S = slab + s.t_off;
+    double* const T = vw.cur + (size_t)k * vw.R * vw.C;
+    for (int x = tid; x < RC; x += 256) T[x] = S[x];
+    double* const sol = vw.sol + (size_t)k * vw.sol_cap;
+    for (int j = tid; j < s.n; j += 256) {
+        int basicRow = -1;
+        bool isBasic = true;
+        for (int i = 1; i < R && isBasic; ++i) {
+            const double t = S[(size_t)i * C + j];
+            if (fabs(t - 1.0) < 1e-9) {
+                if (basicRow == -1) basicRow = i;
+                else isBasic = false;
+            } else if (fabs(t) > 1e-9) {
+                isBasic = false;
+            }
+        }
+        sol[j] = (isBasic && basicRow != -1) ? S[(size_t)basicRow * C + rhs] : 0.0;
+    }
+    block_rebuild_basics(S, R, C, s_basic, s_bcount);
+    int32_t* const g_basic = vw.basic + (size_t)k * (vw.R - 1);
+    int32_t* const g_bcount = vw.bcount + (size_t)k * vw.C;
+    for (int i = tid; i < m; i += 256) g_basic[i] = s_basic[i];
+    for (int j = tid; j < C; j += 256) g_bcount[j] = s_bcount[j];
+    if (tid == 0) {
+        SensScenario* const d = vw.desc + k;
+        const double z = S[rhs];
+        d->R = R;
+        d->C = C;
+        d->nsol = s.n;
+        d->z = z;
+        d->old_z = z;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Launchers (sens_batch_engine.hip).
+int sens_batch_launch_from_models(hipStream_t s, const SensBatchView& vw, int count,
+                                  const SensModelSrc* src, const double* slab) {
+    hipLaunchKernelGGL(k_sens_batch_from_models, dim3(count), dim3(256), 0, s, vw, count, src, slab);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) {
+        set_error("k_sens_batch_from_models (%d scenarios) failed to launch: %s", count,
+                  hipGetErrorString(err));
+        return LPR_DEVICE_ERROR;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
 int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& vw,
                       const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
                       int chunk) {

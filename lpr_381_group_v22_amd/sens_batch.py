@@ -184,7 +184,10 @@ class SensitivityBatch:
         self._h = None
         p = self._pack(scripts)
         self._engine = base.engine
-        self._h = self._create(base, p, int(log_cap))
+        self._attach(self._create(base, p, int(log_cap)), p)
+
+    def _attach(self, h: C.c_void_p, p) -> None:
+        self._h = h
         self.Count = len(p.nedits)
         self.nedits = p.nedits.tolist()
         self._off = np.concatenate([[0], np.cumsum(p.nedits)]).astype(np.int64)
@@ -407,3 +410,54 @@ class SensitivityGrowBatch(SensitivityBatch):
         st = super().State(k)
         st["basic"] = st["basic"][:self.Shape(k)[0] - 1]
         return st
+
+
+def optimal_items(lp_batch) -> List[int]:
+    """The indices of a solved ``PrimalSimplexBatch`` whose status is optimal: the LPs a
+    ``SensitivityModelBatch`` can be built on."""
+    st, _, _ = lp_batch.status_arrays()
+    return [int(k) for k in np.flatnonzero(st == N.LPR_OK_OPTIMAL)]
+
+
+class SensitivityModelBatch(SensitivityGrowBatch):
+    """Many solved models, one script each (lpr_sens_batch_from_batch): scenario k is a fresh
+    analyzer on LP ``items[k]`` of a solved ``PrimalSimplexBatch`` -- what Program.cs:147-151 builds
+    from ``GetFinalTableau()``, ``SolutionVector``, ``FinalZ`` and ``BasicVariables`` -- followed by
+    ``scripts[k]`` (``pack_grow_scripts`` form).  ``items`` may repeat an index and come in any
+    order; None means LP k for scenario k.  Every item must be optimal (``optimal_items``).  The LP
+    batch is only read and may be destroyed afterwards.  ``Rows`` x ``Cols`` is the largest base
+    shape over the chosen LPs; ``Shape(k)`` is scenario k's own."""
+
+    def __init__(self, lp_batch, scripts: Sequence[Sequence[tuple]],
+                 items: Optional[Sequence[int]] = None, log_cap: int = 0):
+        self._h = None
+        p = pack_grow_scripts(scripts)
+        count = len(p.nedits)
+        if items is None:
+            self._items = list(range(count))
+            iptr = None
+        else:
+            self._items = [_int32(i, "items") for i in items]
+            if len(self._items) != count:
+                raise ValueError(f"{len(self._items)} items for {count} scripts")
+            arr = np.asarray(self._items, dtype=np.int32)
+            iptr = arr.ctypes.data_as(C.POINTER(C.c_int32))
+        self._engine = lp_batch._engine
+        h = C.c_void_p()
+        eptr = p.edits.ctypes.data_as(C.POINTER(N.SensEdit)) if p.edits.size else None
+        pptr = p.payload.ctypes.data_as(C.POINTER(C.c_double)) if p.payload.size else None
+        N.check(N.lib.lpr_sens_batch_from_batch(
+            lp_batch._h, count, iptr, p.nedits.ctypes.data_as(C.POINTER(C.c_int32)), eptr, pptr,
+            p.payload.size, int(log_cap), C.byref(h)), "lpr_sens_batch_from_batch")
+        self._attach(h, p)
+
+    def Item(self, k: int) -> int:
+        """The LP of the batch this one was built from that scenario k started on."""
+        return self._items[k]
+
+    def ConstructTime(self) -> float:
+        """Device milliseconds of the constructor kernel of this batch, from events."""
+        ms = C.c_double()
+        N.check(N.lib.lpr_sens_batch_from_batch_time(self._h, C.byref(ms)),
+                "lpr_sens_batch_from_batch_time")
+        return ms.value

@@ -15,6 +15,16 @@ profiles/sens_grow_bench.json:
   G   the 33 x 97 base, 4096 scripts: add_constraint (a cap on one variable), then change_rhs
   H   the 257 x 769 base, 256 scripts: add_activity, then add_constraint
 
+With --models the scenarios start from different solved models (SensitivityModelBatch,
+lpr_sens_batch_from_batch); the committed record of that is
+profiles/sens_model_batch_bench.json.  The LP workloads are those of tools/batch_bench.py (W: 65536
+textbook LPs, G: 4096 of 32 x 64, H: 256 of 256 x 512), solved with PrimalSimplexBatch; the optimal
+ones are kept.  Two runs are timed separately: from_batch + ranging_arrays() (a report per model),
+and from_batch with one change_rhs per model + Run + ranging_arrays().  The baseline is the loop
+this replaces: per model GetFinalTableau(k), SensState.create, the edit, ranging(), destroy, over a
+time-bounded prefix and scaled (marked extrapolated).  256 evenly spaced scenarios per workload
+are compared with that per-handle path in every output.
+
 Per workload: scenarios/s end to end (lpr_sens_batch_create, lpr_sens_batch_run, the bulk reads of
 outcomes / pivots / z / basicVars, closed by an engine sync) and for lpr_sens_batch_run alone
 (best of --repeat, after one warm-up pass); launches; pivots; the same scenarios one at a time
@@ -175,6 +185,150 @@ def bit_check(orc, base, scripts, batch) -> int:
     return bad
 
 
+# ---- --models: scenarios that start from different solved models ---------------------------------
+def solved_lp_batch(pkg, N, eng, w):
+    """A solved PrimalSimplexBatch over the packed workload w of tools/batch_bench.py."""
+    import ctypes as C
+    import batch_bench as bb
+    h = C.c_void_p()
+    count = len(w["n"])
+    N.check(N.lib.lpr_batch_from_lps(
+        eng._h, count, bb.ptr(w["n"], C.c_int32), bb.ptr(w["m"], C.c_int32),
+        bb.ptr(w["obj"], C.c_double), bb.ptr(w["A"], C.c_double), bb.ptr(w["ncoef"], C.c_int32),
+        bb.ptr(w["rel"], C.c_int8), bb.ptr(w["rhs"], C.c_double), bb.ptr(w["is_max"], C.c_int8),
+        0, C.byref(h)), "lpr_batch_from_lps")
+    lps = pkg.PrimalSimplexBatch.__new__(pkg.PrimalSimplexBatch)
+    lps._init(eng)
+    lps._attach(h, [(int(m) + 1, int(n) + int(m) + 1, int(n)) for n, m in zip(w["n"], w["m"])], 0)
+    opts, res = N.BatchOpts(max_pivots=0, chunk=0, variant=0), N.BatchResult()
+    N.check(N.lib.lpr_batch_solve(h, C.byref(opts), C.byref(res)), "lpr_batch_solve")
+    return lps
+
+
+def run_models(pkg, eng, lps, items, scripts, run: bool):
+    """One pass: (seconds end to end, constructor kernel ms, ranging kernel ms, batch, report)."""
+    eng.sync()
+    t0 = time.perf_counter()
+    b = pkg.SensitivityModelBatch(lps, scripts, items=items)
+    if run:
+        b.Run()
+    rep = b.ranging_arrays()
+    eng.sync()
+    t1 = time.perf_counter()
+    return t1 - t0, b.ConstructTime(), b.RangingTime(), b, rep
+
+
+def models_handle(SensState, eng, lps, x_at, x, z, k, script):
+    """The per-handle path for LP k: (handle after the script, outcomes)."""
+    T = lps.GetFinalTableau(k)
+    n = lps.Shape(k)[2]
+    d = SensState.create(eng, T, x[x_at[k]:x_at[k] + n], float(z[k]))
+    return d, [getattr(d, op)(*args) for op, args in script]
+
+
+def models_loop(SensState, eng, lps, x_at, x, z, items, scripts, budget_s: float):
+    done = 0
+    t0 = time.perf_counter()
+    while done < len(items) and time.perf_counter() - t0 < budget_s:
+        d, _ = models_handle(SensState, eng, lps, x_at, x, z, items[done], scripts[done])
+        d.ranging()
+        d.destroy()
+        done += 1
+    dt = time.perf_counter() - t0
+    return dict(scenarios=done, seconds=dt, scenarios_per_s=done / dt,
+                extrapolated=done < len(items))
+
+
+def models_check(SensState, eng, lps, x_at, x, z, items, scripts, batch, rep) -> int:
+    """Scenarios among CHECK evenly spaced ones that differ from the per-handle path in any output:
+    outcomes, tableau, basicVars, solution, z and the nine ranging arrays."""
+    from lpr_381_group_v22_amd.sens_batch import (RANGING_COLUMN_FIELDS, RANGING_ROW_FIELDS,
+                                                  trim_ranging)
+    import special_values as sv
+    bad = 0
+    step = max(1, len(items) // CHECK)
+    rows, cols, _, _ = batch.shape_arrays()
+    for q in list(range(0, len(items), step))[:CHECK]:
+        d, outs = models_handle(SensState, eng, lps, x_at, x, z, items[q], scripts[q])
+        T, basic, sol = d.read()
+        want = d.ranging()
+        st = batch.State(q)
+        got = trim_ranging(rep, q, int(rows[q]), int(cols[q]))
+        ok = (batch.Outcomes(q) == outs and st["T"].shape == T.shape
+              and st["T"].tobytes() == T.tobytes() and st["basic"] == basic.tolist()
+              and st["sol"].tobytes() == sol.tobytes() and sv.same(st["z"], d.shape()[4])
+              and all(sv.same(getattr(got, f), getattr(want, f)) for f in RANGING_COLUMN_FIELDS + RANGING_ROW_FIELDS))
+        bad += not ok
+        d.destroy()
+    return bad
+
+
+def main_models(args) -> int:
+    import batch_bench as bb
+    import lpr_381_group_v22_amd as pkg
+    from lpr_381_group_v22_amd import _native as N
+    from lpr_381_group_v22_amd.engine import SensState
+    failures, lines = 0, []
+    names = {"S": "W", "G": "G", "H": "H"}
+    with pkg.Engine(0) as eng:
+        for i, name in enumerate(args.workloads.split(",")):
+            w = bb.gen_workload(names[name], args.seed + i)
+            offs = bb.offsets(w)
+            lps = solved_lp_batch(pkg, N, eng, w)
+            items = pkg.optimal_items(lps)
+            _, _, z = lps.status_arrays()
+            x = lps.solution_packed()
+            x_at = offs[0]
+            shapes = [lps.Shape(k) for k in items]
+            edit = [[("change_rhs", (1, float(w["rhs"][offs[2][k]]) * 1.25))] for k in items]
+            none = [[] for _ in items]
+            rec = dict(workload=name + "_models", lps=int(lps.Count), scenarios=len(items),
+                       max_rows=max(s[0] for s in shapes), max_cols=max(s[1] for s in shapes))
+            # what the constructor kernel has to move at the least: every tableau read and written
+            rec["ctor_bytes_min"] = int(sum(2 * 8 * s[0] * s[1] for s in shapes))
+            for tag, scripts, run in (("report", none, False), ("edit_report", edit, True)):
+                run_models(pkg, eng, lps, items, scripts, run)[3].destroy()  # warm-up
+                runs = [run_models(pkg, eng, lps, items, scripts, run)
+                        for _ in range(max(1, args.repeat))]
+                best = min(runs, key=lambda r: r[0])
+                r = dict(e2e_seconds=best[0], e2e_scenarios_per_s=len(items) / best[0],
+                         e2e_seconds_all=[q[0] for q in runs],
+                         ctor_kernel_ms=min(q[1] for q in runs),
+                         ranging_kernel_ms=min(q[2] for q in runs))
+                r["ctor_gbytes_per_s"] = rec["ctor_bytes_min"] / (r["ctor_kernel_ms"] * 1e-3) / 1e9
+                batch, rep = runs[-1][3], runs[-1][4]
+                if run:
+                    oc, pv = batch.outcome_arrays()
+                    r["form"] = {1: "G", 2: "H"}[batch.LastResult.form]
+                    r["pivots"] = int(pv.sum())
+                    r["outcomes"] = {str(int(c)): int((oc == c).sum()) for c in np.unique(oc)}
+                if not args.no_check:
+                    if run:
+                        bad = models_check(SensState, eng, lps, x_at, x, z, items, scripts, batch,
+                                           rep)
+                        rec["checked"] = min(CHECK, len(items))
+                        rec["mismatches"] = bad
+                        failures += bad
+                    r["per_handle_loop"] = models_loop(SensState, eng, lps, x_at, x, z, items,
+                                                       scripts, args.single_seconds)
+                    r["ratio_to_loop"] = r["e2e_scenarios_per_s"] / \
+                        r["per_handle_loop"]["scenarios_per_s"]
+                for q in runs:
+                    q[3].destroy()
+                rec[tag] = r
+            lps.destroy()
+            line = json.dumps(rec)
+            print(line, flush=True)
+            lines.append(line)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    if failures:
+        print(f"check: {failures} scenario(s) differ from the per-handle path", file=sys.stderr)
+        return 1
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="S,G,H")
@@ -186,10 +340,15 @@ def main() -> int:
     ap.add_argument("--grow", action="store_true",
                     help="the growth workloads (add_activity / add_constraint) through "
                          "SensitivityGrowBatch")
+    ap.add_argument("--models", action="store_true",
+                    help="scenarios that start from different solved models, through "
+                         "SensitivityModelBatch (record: profiles/sens_model_batch_bench.json)")
     ap.add_argument("--out", default=None,
                     help="also append the JSON lines to this file (the committed record is "
                          "profiles/sens_batch_bench.json; never pass it to a profiled run)")
     args = ap.parse_args()
+    if args.models:
+        return main_models(args)
 
     import lpr_381_group_v22_amd as pkg
     from lpr_381_group_v22_amd.engine import SensState
