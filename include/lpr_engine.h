@@ -143,7 +143,12 @@ typedef struct lpr_solve_opts {
                               default the tiles at both ends of its work queue keep the default
                               cache policy).  0x1000000: no 64-row tiles at the head of that queue
                               (by default the row tiles of its first half are handed out in pairs,
-                              so that a lane loads its pivot-row slices once per 64 rows). */
+                              so that a lane loads its pivot-row slices once per 64 rows).
+                              0x2000000: the two-stream path never uses the condensed working
+                              layout (by default a call with a budget of 1 024 pivots or more, or
+                              none, works on buffers that leave out the unit columns of its start
+                              basis); 0x4000000: it uses it whatever the size of the
+                              tableau or the length of the call (tests).  Same bits either way. */
     int32_t block;         /* pivots decided ahead and applied per sweep of the tableau on large
                               tableaux: 0 auto (16), 1 one pivot per sweep, 2..16 that many.  The bits
                               stored are the same for every value (each element goes through the

@@ -24,6 +24,11 @@ namespace lpr {
 constexpr int kWave = 64;
 constexpr int kLdAlign = 16;          // tableau rows padded to 16 doubles = 128 B
 constexpr int32_t kRunning = -100;    // device status word while the pivot loop is live
+// K-pivot path, condensed layout: `pending` codes that never leave the driver.  The block ends
+// before the pivot that cannot be staged in that layout; the driver writes the full tableau back
+// and goes on from there.
+constexpr int32_t kOvLeaveNonFinite = -101;  // a factor is inf / NaN: omitted columns would change
+constexpr int32_t kOvLeaveSpares = -102;     // an omitted variable leaves and no spare slot is free
 constexpr int kMaxHeadGroups = 32;    // k_pivot_head workgroups (partials per bank)
 
 void set_error(const char* fmt, ...);
@@ -198,6 +203,7 @@ struct lpr_tableau {
         }
     } graph_key;
     void* ov = nullptr;               // lpr_overlap_ctx of the overlapped K-pivot path (overlap_kernels.hip)
+    void* ovc = nullptr;              // its condensed working layout (OvcCtx, overlap_kernels.hip)
     void* cut = nullptr;              // lpr_cut_ctx of the cutting-plane side path (cut_kernels.hip)
     void* small = nullptr;            // lpr_small_ctx of the cache-resident path (small_kernels.hip)
 };

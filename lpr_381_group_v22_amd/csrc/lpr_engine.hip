@@ -69,6 +69,14 @@ int ov_poll(lpr_tableau* t, int parity, bool with_flags, OvPoll* out);
 int ov_snapshot(lpr_tableau* t, int slot);
 int ov_snapshot_wait(lpr_tableau* t, int slot, OvPoll* out);
 void ov_adopt_buffer(lpr_tableau* t, int cur);
+void ovc_release(lpr_tableau* t);
+bool ovc_fits(const lpr_tableau* t, int spares);
+int ovc_width(const lpr_tableau* t, int spares);
+int ovc_ensure(lpr_tableau* t, int spares);
+int ovc_condense(lpr_tableau* t, bool* ok);
+void ovc_enter(lpr_tableau* t);
+void ovc_leave(lpr_tableau* t);
+int ovc_expand(lpr_tableau* t);
 // revised_engine.hip
 void rev_orphan(lpr_revised* s);
 // bb_engine.hip
@@ -260,6 +268,7 @@ static void release_device(lpr_tableau* t) {
     if (t->eng->stream) hipStreamSynchronize(t->eng->stream);
     drop_graph(t);
     lpr_cut_release(t);
+    ovc_release(t);
     ov_release(t);
     small_release(t);
     for (hipEvent_t ev : t->ev) hipEventDestroy(ev);
@@ -814,6 +823,78 @@ static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int 
     return status;
 }
 
+// The two-stream path on the condensed working layout (DESIGN 4b "Condensed layout"): for the
+// length of a call the kernels work on buffers that leave out the columns basic when it began --
+// exact unit columns that no pivot changes -- so a sweep moves (n + S + 1) / (n + m + 1) of the
+// bytes.  opts.variant bit 25: the form before (never condensed); bit 26: condensed whatever the
+// size or the length of the call (tests).
+//
+// kOvcMinPivots: a call with a pivot budget below it stays on the full layout -- condensing and
+// expanding cost one pass over the tableau each (the measured break-even).
+static constexpr int64_t kOvcMinPivots = 1024;
+
+// spare columns: an omitted variable that leaves takes one, and when none is left the driver
+// expands and condenses again.  Test hook LPR_TEST_OV_SPARES (1..4096): a small number, so that a
+// short oracle-checked solve re-condenses every few pivots (tests/test_condensed_gpu.py).
+static int ovc_spares(const lpr_tableau* t) {
+    if (const char* sp = std::getenv("LPR_TEST_OV_SPARES")) {
+        const long v = std::strtol(sp, nullptr, 10);
+        if (v >= 1 && v <= 4096) return (int)v;
+    }
+    // m / 8 - 1 (255 .. 4095 measured at m = 4096; 511 makes the buffers 17 column
+    // strips of the sweep exactly): a narrower sweep also leaves the heads beside it more of the
+    // chip, which outweighs expanding and condensing again every few hundred pivots
+    const int s = (t->rows - 1) / 8 - 1;
+    return s < 1 ? 1 : s;
+}
+
+static bool use_condensed(const lpr_tableau* t, const lpr_solve_opts& o, int cflags, int hflags) {
+    if (cflags & 1) return false;
+    // the diagnostic build of the heads and the opt-in forms that order themselves on the device
+    // exist for the full layout only
+    if (hflags & (1 | 32 | 64)) return false;
+    const int S = ovc_spares(t);
+    if (!ovc_fits(t, S)) return false;
+    if (cflags & 2) return true;
+    if (o.max_pivots > 0 && o.max_pivots < kOvcMinPivots) return false;
+    return ovc_width(t, S) < t->ld;
+}
+
+static int solve_condensed(lpr_tableau* t, const lpr_solve_opts& o, int K, int tr, int hflags,
+                           lpr_solve_result* res) {
+    const int64_t first = t->total_pivots;
+    lpr_solve_opts oc = o;
+    for (;;) {
+        const int64_t done = t->total_pivots - first;
+        if (o.max_pivots > 0) oc.max_pivots = o.max_pivots - done;
+        bool ok = false;
+        int rc = ovc_ensure(t, ovc_spares(t));
+        if (rc == LPR_OK_OPTIMAL) rc = ovc_condense(t, &ok);
+        if (rc != LPR_OK_OPTIMAL && rc != LPR_OUT_OF_MEMORY) return rc;
+        int status;
+        if (rc != LPR_OK_OPTIMAL || !ok) {
+            // a basic column is not the exact unit column (or there is no room): the full layout
+            status = solve_overlapped(t, oc, K, tr, true, hflags, res);
+        } else {
+            ovc_enter(t);
+            status = solve_overlapped(t, oc, K, tr, true, hflags, res);
+            ovc_leave(t);
+            if (status == LPR_DEVICE_ERROR || status == LPR_OUT_OF_MEMORY ||
+                status == LPR_BAD_ARGUMENT)
+                return status;
+            rc = ovc_expand(t);
+            if (rc != LPR_OK_OPTIMAL) return rc;
+            if (status == kOvLeaveSpares) continue;
+            if (status == kOvLeaveNonFinite) {
+                if (o.max_pivots > 0) oc.max_pivots = o.max_pivots - (t->total_pivots - first);
+                status = solve_overlapped(t, oc, K, tr, true, hflags, res);
+            }
+        }
+        res->pivots = t->total_pivots - first;
+        return status;
+    }
+}
+
 }  // namespace lpr
 
 using namespace lpr;
@@ -1072,6 +1153,7 @@ int lpr_primal_solve(lpr_tableau* t, const lpr_solve_opts* opts, lpr_solve_resul
     std::memset(&o, 0, sizeof o);
     if (opts) o = *opts;
     const int hflags = (o.variant >> 16) & 511;  // loop-head placement / diagnostics (K-pivot paths)
+    const int cflags = (o.variant >> 25) & 3;    // condensed layout: 1 = never, 2 = always
     o.variant &= 0xffff;                       // path + tile
     // retired forms, kept as aliases: 0x50tr (the overlap in one launch) runs as the two-stream
     // overlap, 0x60tr (one launch per loop head, K <= 8) as heads-then-sweep
@@ -1097,6 +1179,15 @@ int lpr_primal_solve(lpr_tableau* t, const lpr_solve_opts* opts, lpr_solve_resul
             bool two_streams = (o.variant & 0xff00) == 0x3000 || big;
             const int tr = (o.variant & 0xff00) ? (o.variant & 0xff) : 8;
             if (two_streams && ov_ensure(t, true) != LPR_OK_OPTIMAL) two_streams = false;
+            if (two_streams && (big || (cflags & 2)) && !(cflags & 1) &&
+                ovc_fits(t, ovc_spares(t)) && ovc_width(t, ovc_spares(t)) < t->ld) {
+                // the buffers of the condensed layout come with the handle's first two-stream
+                // call, whichever layout that call itself uses
+                const int er = ovc_ensure(t, ovc_spares(t));
+                if (er != LPR_OK_OPTIMAL && er != LPR_OUT_OF_MEMORY) return er;
+            }
+            if (two_streams && use_condensed(t, o, cflags, hflags))
+                return solve_condensed(t, o, K, tr, hflags, res);
             return solve_overlapped(t, o, K, tr, two_streams, hflags, res);
         }
     }

@@ -35,6 +35,11 @@
 //                              row they fetch through the block being swept plus their own earlier
 //                              pivots.  A step lasts max(sweep, heads).
 //
+// For the length of a solve call the two-stream form works on CONDENSED buffers that leave out the
+// unit columns of the call's start basis (k_ov_condense / k_ov_expand at the ends of the call, the
+// COND instantiation of ov_heads; DESIGN.md section 4b "Condensed layout"): the sweep is the same
+// code on a narrower tableau.
+//
 // Control state that a launch both reads and updates exists twice (`OvCtl ctl[2]`): the launch
 // with parity p reads ctl[p] and its two lead workgroups write ctl[p ^ 1] -- so no workgroup can
 // see a field change under it.  Same for the barrier counter.
@@ -107,6 +112,8 @@ struct OvCtl {
     int32_t r[kOvMax]; // pivot rows of that block
     int32_t error;     // a grid barrier timed out
     int32_t head_xcc;  // XCD the loop heads of the previous launch shared (-1: none / spread)
+    int32_t spares;    // condensed layout: spare columns handed out so far in this call
+    int32_t pad_;
     int64_t staged;    // pivots decided so far (index of the next one)
     int64_t applied;   // pivots swept into the tableau so far
     int64_t max_iter;  // <= 0: no limit
@@ -135,6 +142,13 @@ struct OvBuffers {      // everything the step kernel touches, passed by value
     unsigned* bar;      // [2]
     int32_t* basis;
     int32_t* log;
+    // Condensed working layout (DESIGN 4b "Condensed layout"; all null in the full layout): the
+    // buffers hold [columns not basic when the call began | spare columns | RHS] and
+    int32_t* colid;               // [ld] the original column a slot holds (-1: free spare, padding)
+    unsigned long long* rowvar;   // [R - 1] {original column << 32 | slot} of the variable basic in
+                                  // row i + 1; slot -1: it has no column in the buffers (omitted)
+    unsigned long long* cstate;   // [0] sticky: a head met a non-finite factor
+    int spare0, nspare;           // the spare slots are [spare0, spare0 + nspare)
 };
 
 constexpr int kOvStampsPerPivot = 12;   // diagnostic build of the heads (opts.variant bit 16)
@@ -157,7 +171,8 @@ __global__ __launch_bounds__(1024) void k_ov_prologue(const double* __restrict__
                                                       unsigned* __restrict__ bar,
                                                       unsigned* __restrict__ tileq,
                                                       unsigned long long* __restrict__ hx,
-                                                      unsigned* __restrict__ sflag) {
+                                                      unsigned* __restrict__ sflag,
+                                                      const int32_t* __restrict__ colid) {
     __shared__ double lds_v[16];
     __shared__ int lds_i[16];
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -178,7 +193,7 @@ __global__ __launch_bounds__(1024) void k_ov_prologue(const double* __restrict__
         zrow[j] = v;
         if (j < C - 1 && v < c.v) {
             c.v = v;
-            c.i = j;
+            c.i = colid ? ((colid[j] << 16) | j) : j;  // condensed: ties go by the original index
         }
     }
     c = block_cand_min(c, lds_v, lds_i);
@@ -463,7 +478,11 @@ __device__ __forceinline__ void ov_publish_min(Cand c, double* lds_v, int* lds_i
 // step, on the critical path whenever the heads end last) is gone.  In this form the heads also own
 // the control-block fields the sweep used to write (applied / cur / sweep parity): the sweep of the
 // same step only reads the control block.
-template <int NT, bool STAMP>
+// COND: the condensed layout.  An entering candidate is {original column << 16 | slot}; a leaving
+// variable that has no column in the buffers gets the next spare slot, whose lane puts the 1.0 the
+// unit column holds in the pivot row in front of the division -- the rest is the ordinary
+// arithmetic on a column that was all +0.0 until now.
+template <int NT, bool STAMP, bool COND = false>
 __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K, int G, int lp,
                          bool solo, int spread, int no_l2, int wait_sweeps, int heads_done = -1) {
     if ((int)blockIdx.x % spread != 0) return;
@@ -521,6 +540,15 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
     }
     double2 myz = have_c ? zrow2[c2_first] : make_double2(0.0, 0.0);
     double myb = have_i ? B.bvec[(size_t)(staged0 & 1) * Rp + i_first] : 0.0;
+    // condensed: the original columns of this lane's pair, and the spares handed out so far
+    int idx = -1, idy = -1, used = 0;
+    if (COND) {
+        if (have_c) {
+            idx = B.colid[2 * c2_first];
+            idy = B.colid[2 * c2_first + 1];
+        }
+        used = ci->spares;
+    }
     // Workgroup-uniform operands are kept ONE PER LANE (the same in every wave) and read with
     // v_readlane where a chain needs them: lane t < 16 holds what belongs to pivot t of the block
     // being swept, lane 16 + t what belongs to pivot t of this block.  One load per wave fetches a
@@ -641,6 +669,8 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                 pend_out = LPR_OK_OPTIMAL;
                 break;
             }
+            const int e_id = COND ? (e >> 16) : e;  // the original column (basis, pivot log)
+            if (COND) e &= 0xffff;                  // where it lives
             // ---- column e after all earlier pivots, this lane's row(s); one trip ----
             // pv: lane t < kb: p_t[e] of the block being swept; lane 16 + t, t < q - 1: p_t[e] of
             // this block's earlier pivots; every other lane +0.0.  Steps of unused pivots are exact
@@ -676,6 +706,8 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
             Cand rc;
             rc.v = DBL_MAX;
             rc.i = -1;
+            // condensed: x - (f * (+0)) = x holds for the omitted columns only while f is finite
+            bool badf = COND && have_i && !(fabs(cq) <= DBL_MAX);
             if (have_i) {
                 hst(&colq[i_first], cq, l2);
                 if (i_first >= 1 && cq > 1e-9) {
@@ -713,6 +745,7 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                     }
                 }
                 hst(&colq[i], c, l2);
+                if (COND && !(fabs(c) <= DBL_MAX)) badf = true;
                 if (c > 1e-9) {
                     const double ratio = ieee_div(bprev[i], c);
                     if (ratio >= 0 && ratio < rc.v) {
@@ -725,6 +758,8 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
             // has drained; then wave 0 collects the G partials: the leaving row (:169-191)
             OV_STAMP(q, 4);
             OV_STAMP(q, 5);
+            if (COND && badf)  // ahead of the ratio partial: whoever holds all partials sees it
+                __hip_atomic_store(B.cstate, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             int r;
             if (kOvWaveHandoff) {
                 ov_publish_wave_min(rc, B.gran + ((size_t)2 * kOvParts + g * kOvWPG + tid / kWave) * 3,
@@ -787,7 +822,28 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                 else if (lane == 32) src = bprev + r;
                 else if (lane == 33) src = colq + r;
                 else if (lane == 34) src = colq;
+                else if (COND && lane == 35) src = reinterpret_cast<const double*>(B.cstate);
+                else if (COND && lane == 36)
+                    src = reinterpret_cast<const double*>(B.rowvar + (r - 1));
                 if (src) fv = xld(src);
+            }
+            int sigma = -1;  // condensed: the spare slot the leaving variable takes
+            int leave_id = -1;
+            if (COND) {
+                if (__double2loint(ov_rl(fv, 35)) != 0) {
+                    pend_out = kOvLeaveNonFinite;
+                    break;
+                }
+                const double lv = ov_rl(fv, 36);
+                if (__double2loint(lv) < 0) {  // it has no column here
+                    if (used >= B.nspare) {
+                        pend_out = kOvLeaveSpares;
+                        break;
+                    }
+                    sigma = B.spare0 + used;
+                    leave_id = __double2hiint(lv);
+                    used += 1;
+                }
             }
             if (STAMP) {
                 __builtin_amdgcn_s_waitcnt(0);
@@ -842,6 +898,17 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                     }
                 }
             }
+            if (COND && sigma >= 0 && have_c && (sigma >> 1) == c2_first) {
+                // the leaving variable's column before this pivot is unit(r): 1.0 in the pivot row
+                if (sigma & 1) {
+                    w.y = 1.0;
+                    idy = leave_id;
+                } else {
+                    w.x = 1.0;
+                    idx = leave_id;
+                }
+                B.colid[sigma] = leave_id;  // (read by the next launch and by the expansion)
+            }
             // p_q[rhs] (every lane works it out for itself) and this lane's pair of the normalised
             // row (:199 true division): three quotients behind one check
             double dq[3];
@@ -870,13 +937,23 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
                 myz.x = myz.x - mxp;
                 myz.y = myz.y - myp2;
                 zrow2[c2_first] = myz;  // read again by the next launch
-                if (j < C - 1 && myz.x < n.v) {
-                    n.v = myz.x;
-                    n.i = j;
-                }
-                if (j + 1 < C - 1 && myz.y < n.v) {
-                    n.v = myz.y;
-                    n.i = j + 1;
+                if (COND) {  // by value, then by the ORIGINAL index (a spare slot holds any column)
+                    Cand a, b;
+                    a.v = myz.x;
+                    a.i = (j < C - 1 && myz.x < 0.0) ? ((idx << 16) | j) : -1;
+                    b.v = myz.y;
+                    b.i = (j + 1 < C - 1 && myz.y < 0.0) ? ((idy << 16) | (j + 1)) : -1;
+                    const Cand m = ov_cand_min_sel(a, b);
+                    if (m.i >= 0) n = m;
+                } else {
+                    if (j < C - 1 && myz.x < n.v) {
+                        n.v = myz.x;
+                        n.i = j;
+                    }
+                    if (j + 1 < C - 1 && myz.y < n.v) {
+                        n.v = myz.y;
+                        n.i = j + 1;
+                    }
                 }
             }
             for (int c2 = c2_first + G * nt; c2 < ld2; c2 += G * nt) {  // further column pairs
@@ -947,11 +1024,14 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
             OV_STAMP(q, 9);
             if (lead && tid == 0) {
                 co->r[q - 1] = r;
-                B.basis[r - 1] = e;  // :142
+                B.basis[r - 1] = e_id;  // :142
                 if (pidx < log_cap) {
                     B.log[2 * pidx] = r;
-                    B.log[2 * pidx + 1] = e;
+                    B.log[2 * pidx + 1] = e_id;
                 }
+                if (COND)  // read by the heads that take row r next, in this launch or a later one
+                    hst(B.rowvar + (r - 1),
+                        ((unsigned long long)(unsigned)e_id << 32) | (unsigned)e, l2);
             }
             count = q;
             // this workgroup's Z-row partial, published once its row slice / RHS entries have
@@ -997,6 +1077,8 @@ __device__ void ov_heads(const OvBuffers B, int ld, int R, int C, int Rp, int K,
         co->log_cap = log_cap;
         co->error = err | ci->error;
         co->head_xcc = l2 ? (int)my_xcc : (staging ? -1 : ci->head_xcc);
+        co->spares = used;
+        co->pad_ = 0;
         B.bar[lp ^ 1] = 0u;
         if (wait_sweeps >= 0) {  // the fields of the sweep running beside this launch
             const int ks = (status == kRunning) ? ci->kdone : 0;
@@ -1405,6 +1487,8 @@ __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __res
             co->log_cap = ci->log_cap;
             co->error = ci->error;
             co->head_xcc = ci->head_xcc;
+            co->spares = ci->spares;
+            co->pad_ = 0;
             B.bar[lp ^ 1] = 0u;
         }
     }
@@ -1510,11 +1594,11 @@ __device__ __forceinline__ void ov_tiles(const OvBuffers& B, const double* __res
 
 // The overlap: the heads of the next block and the sweep of the current one as two kernels on two
 // streams, running concurrently (variant 0x30tr), each with its own register budget.
-template <int NT, bool STAMP>
+template <int NT, bool STAMP, bool COND = false>
 __global__ __launch_bounds__(NT) void k_ov2_heads(const OvBuffers B, int ld, int R, int C, int Rp,
                                                   int K, int G, int lp, int spread, int no_l2,
                                                   int wait_sweeps, int heads_done) {
-    ov_heads<NT, STAMP>(B, ld, R, C, Rp, K, G, lp, false, spread, no_l2, wait_sweeps, heads_done);
+    ov_heads<NT, STAMP, COND>(B, ld, R, C, Rp, K, G, lp, false, spread, no_l2, wait_sweeps, heads_done);
 }
 
 template <int TR, bool DB>
@@ -1549,6 +1633,154 @@ __global__ __launch_bounds__(kOvNT) void k_ov_sweep(const OvBuffers B,
     // queue's counter costs a burst of ~1000 atomics on one word at the start of every sweep).
     // TROWS = 8: small tableaux, where 32-row tiles would leave most CUs without a tile
     ov_tiles<TR, DB, true, TROWS>(B, fcol_ro, prow_ro, ld, R, Rp, 1, (int)blockIdx.x, 0);
+}
+
+// ------------------------------------------------------------------------------------------
+// The condensed layout at the ends of a solve call (DESIGN 4b "Condensed layout").
+//
+// k_ov_cond_map (one workgroup): from `basis`, where every column of the full tableau goes.
+//   rowof[j]  the row column j is basic in (0: in none)
+//   slotof[j] its slot in the condensed buffers (-1: omitted); the RHS column takes the last one
+//   colid[s]  the inverse (-1: spare slot, padding), rowvar[i]: every basic variable is omitted
+// fail[0] != 0: the basis names a column twice or one out of range -- the layout is not used.
+__global__ __launch_bounds__(1024) void k_ov_cond_map(const int32_t* __restrict__ basis, int R,
+                                                      int C, int Wc, int Wp,
+                                                      int32_t* __restrict__ rowof,
+                                                      int32_t* __restrict__ slotof,
+                                                      int32_t* __restrict__ colid,
+                                                      unsigned long long* __restrict__ rowvar,
+                                                      unsigned long long* __restrict__ cstate,
+                                                      unsigned* __restrict__ fail) {
+    __shared__ int s_cnt[1024];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int j = tid; j < C; j += nt) rowof[j] = 0;
+    for (int s = tid; s < Wp; s += nt) colid[s] = -1;
+    if (tid == 0) {
+        cstate[0] = 0ull;
+        fail[0] = 0u;
+    }
+    __syncthreads();
+    for (int i = 1 + tid; i < R; i += nt) {
+        const int b = basis[i - 1];
+        if (b < 0 || b >= C - 1) {
+            fail[0] = 1u;
+        } else {
+            if (atomicExch(&rowof[b], i) != 0) fail[0] = 1u;
+            rowvar[i - 1] = ((unsigned long long)(unsigned)b << 32) | 0xffffffffull;
+        }
+    }
+    __syncthreads();
+    // slots of the resident columns, in the original order: a lane counts its run of columns, the
+    // runs are summed in order, then every lane numbers its own
+    const int per = (C - 1 + nt - 1) / nt;
+    const int j0 = min(tid * per, C - 1), j1 = min(j0 + per, C - 1);
+    int cnt = 0;
+    for (int j = j0; j < j1; ++j) cnt += (rowof[j] == 0) ? 1 : 0;
+    s_cnt[tid] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0;
+        for (int k = 0; k < nt; ++k) {
+            const int c = s_cnt[k];
+            s_cnt[k] = acc;
+            acc += c;
+        }
+        if (acc != C - R) fail[0] = 1u;  // (the slots behind it are the spares)
+        slotof[C - 1] = Wc - 1;
+        colid[Wc - 1] = C - 1;
+    }
+    __syncthreads();
+    int s = s_cnt[tid];
+    for (int j = j0; j < j1; ++j) {
+        if (rowof[j] == 0) {
+            if (s < Wc - 1) colid[s] = j;
+            slotof[j] = s++;
+        } else {
+            slotof[j] = -1;
+        }
+    }
+}
+
+// Full tableau -> condensed buffer, one lane per column pair of the full row (grid.y = row) and,
+// behind them, one per pair of spare / padding slots.  An omitted column must be the unit column of its row bit for
+// bit (+0.0 elsewhere, the Z row included): anything else sets fail[1].
+__global__ __launch_bounds__(256) void k_ov_condense(const double* __restrict__ T, int ld, int C,
+                                                     double* __restrict__ Tc, int Wp, int Wc,
+                                                     int nres, const int32_t* __restrict__ slotof,
+                                                     const int32_t* __restrict__ rowof,
+                                                     unsigned* __restrict__ fail) {
+    if (fail[0]) return;  // no valid map
+    const int k = blockIdx.y;
+    const int j0 = 2 * (blockIdx.x * blockDim.x + threadIdx.x);  // (ld is even: a pair per lane)
+    if (j0 < ld) {
+        if (j0 >= C) return;
+        const ov_v2d v2 = __builtin_nontemporal_load(
+            reinterpret_cast<const ov_v2d*>(&T[(size_t)k * ld + j0]));
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = j0 + h;
+            if (j >= C) break;
+            const double v = h ? v2.y : v2.x;
+            const int s = slotof[j];
+            if (s >= 0) {
+                if (s < Wp) Tc[(size_t)k * Wp + s] = v;
+            } else {
+                const long long want = (rowof[j] == k) ? 0x3ff0000000000000ll : 0ll;
+                if (__double_as_longlong(v) != want) fail[1] = 1u;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int s = nres + (j0 + h - ld);
+            if (s < Wp && s != Wc - 1) Tc[(size_t)k * Wp + s] = 0.0;
+        }
+    }
+}
+
+// k_ov_expand_map (one workgroup): the same maps for the state a call ends in -- slots by `colid`
+// (the spares handed out included), rows of the variables still omitted by `rowvar`.
+__global__ __launch_bounds__(1024) void k_ov_expand_map(int R, int C, int Wp,
+                                                        const int32_t* __restrict__ colid,
+                                                        const unsigned long long* __restrict__ rowvar,
+                                                        int32_t* __restrict__ rowof,
+                                                        int32_t* __restrict__ slotof) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int j = tid; j < C; j += nt) {
+        rowof[j] = 0;
+        slotof[j] = -1;
+    }
+    __syncthreads();
+    for (int s = tid; s < Wp; s += nt) {
+        const int id = colid[s];
+        if (id >= 0 && id < C) slotof[id] = s;
+    }
+    for (int i = 1 + tid; i < R; i += nt) {
+        const unsigned long long rv = rowvar[i - 1];
+        if ((int)(unsigned)rv < 0) rowof[(int)(rv >> 32)] = i;
+    }
+}
+
+// Condensed buffer -> full tableau: resident columns by their slot, unit columns for the variables
+// still omitted, +0.0 in the padding.
+__global__ __launch_bounds__(256) void k_ov_expand(const double* __restrict__ Tc, int Wp,
+                                                   double* __restrict__ T, int ld, int C,
+                                                   const int32_t* __restrict__ slotof,
+                                                   const int32_t* __restrict__ rowof) {
+    const int k = blockIdx.y;
+    const int j0 = 2 * (blockIdx.x * blockDim.x + threadIdx.x);  // (ld is even: a pair per lane)
+    if (j0 >= ld) return;
+    double v[2] = {0.0, 0.0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = j0 + h;
+        if (j < C) {
+            const int s = slotof[j];
+            if (s >= 0) v[h] = __builtin_nontemporal_load(&Tc[(size_t)k * Wp + s]);
+            else if (k > 0 && rowof[j] == k) v[h] = 1.0;
+        }
+    }
+    *reinterpret_cast<ov_v2d*>(&T[(size_t)k * ld + j0]) = ov_v2d{v[0], v[1]};
 }
 
 }  // namespace lpr
@@ -1742,7 +1974,8 @@ int ov_begin(lpr_tableau* t, int64_t iter, int64_t max_iter) {
                        c->b.zrow, c->b.bvec + (size_t)(iter & 1) * c->Rp,
                        c->b.zparts + (iter & 1) * kOvGroups, ov_groups(t),
                        c->b.gran + (size_t)(iter & 1) * 3 * kOvParts, (unsigned)(2 * iter + 1),
-                       c->b.gran, c->b.xgran, c->b.bar, c->b.tileq, c->b.hx, c->b.sflag);
+                       c->b.gran, c->b.xgran, c->b.bar, c->b.tileq, c->b.hx, c->b.sflag,
+                       (const int32_t*)c->b.colid);
     LPR_HIP(hipGetLastError());
     return LPR_OK_OPTIMAL;
 }
@@ -1872,7 +2105,11 @@ int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t
     const int G = ov_groups(t);
     const int spread = ov_spread(G, flags);
     const int no_l2 = (flags & 6) ? 1 : 0;
-    if (flags & 1)
+    if (c->b.colid)  // the condensed layout (no diagnostic build of it)
+        hipExtLaunchKernelGGL((k_ov2_heads<kOvNT, false, true>), dim3(G * spread), dim3(kOvNT), 0,
+                              H, nullptr, c->ev_h[cur], 0, c->b, t->ld, t->rows, t->cols, c->Rp, K,
+                              G, lp, spread, no_l2, wait_sweeps, heads_done);
+    else if (flags & 1)
         hipExtLaunchKernelGGL((k_ov2_heads<kOvNT, true>), dim3(G * spread), dim3(kOvNT), 0, H,
                               nullptr, c->ev_h[cur], 0, c->b, t->ld, t->rows, t->cols, c->Rp, K, G,
                               lp, spread, no_l2, wait_sweeps, heads_done);
@@ -2009,6 +2246,158 @@ void ov_adopt_buffer(lpr_tableau* t, int cur) {
         t->T = c->T2;
         c->T2 = tmp;
     }
+}
+
+// ---- the condensed layout (driver: solve_condensed in lpr_engine.hip) ---------------------------
+// It is a second lpr_overlap_ctx, built for a tableau of the same rows and the narrower width, with
+// the maps beside it.  Inside the regime the handle's T / ld / cols / ov name the condensed buffers,
+// so the two-stream driver and every ov_* call above run unchanged on the narrower geometry.
+struct OvcCtx {
+    int rows = 0, cols = 0, ld = 0, spares = 0;  // what it was built for
+    int nres = 0, Wc = 0, Wp = 0;                // resident columns, logical / physical width
+    void* ov = nullptr;                          // the lpr_overlap_ctx of the condensed geometry
+    double* Tc = nullptr;                        // the condensed buffer the handle does not hold
+    int32_t *colid = nullptr, *slotof = nullptr, *rowof = nullptr;
+    unsigned long long *rowvar = nullptr, *cstate = nullptr;
+    unsigned *fail = nullptr, *h_fail = nullptr;
+    double* T_full = nullptr;  // the handle's own fields while it is inside the regime
+    int ld_full = 0, cols_full = 0;
+    void* ov_full = nullptr;
+};
+
+void ovc_release(lpr_tableau* t) {
+    OvcCtx* x = static_cast<OvcCtx*>(t->ovc);
+    if (!x) return;
+    void* keep = t->ov;
+    t->ov = x->ov;
+    ov_release(t);
+    t->ov = keep;
+    hipFree(x->Tc);
+    hipFree(x->colid);
+    hipFree(x->slotof);
+    hipFree(x->rowof);
+    hipFree(x->rowvar);
+    hipFree(x->cstate);
+    hipFree(x->fail);
+    if (x->h_fail) hipHostFree(x->h_fail);
+    delete x;
+    t->ovc = nullptr;
+}
+
+// can this tableau use the condensed layout at all, with `spares` spare columns?
+bool ovc_fits(const lpr_tableau* t, int spares) {
+    const int nres = t->cols - t->rows;
+    if (t->rows < 2 || nres < 1 || spares < 1) return false;
+    // an entering candidate is {original column << 16 | slot} in a non-negative int
+    if (t->cols > 32767) return false;
+    const long Wp = align_up(nres + spares + 1, kLdAlign);
+    // every column pair has a lane of its own in the loop heads
+    return Wp <= 32767 && Wp / 2 <= (long)kOvGroups * kOvNT;
+}
+
+// physical width of the condensed buffers
+int ovc_width(const lpr_tableau* t, int spares) {
+    return align_up(t->cols - t->rows + spares + 1, kLdAlign);
+}
+
+void ovc_enter(lpr_tableau* t) {
+    OvcCtx* x = static_cast<OvcCtx*>(t->ovc);
+    x->T_full = t->T;
+    x->ld_full = t->ld;
+    x->cols_full = t->cols;
+    x->ov_full = t->ov;
+    t->T = x->Tc;
+    t->ld = x->Wp;
+    t->cols = x->Wc;
+    t->ov = x->ov;
+    x->Tc = nullptr;
+}
+
+void ovc_leave(lpr_tableau* t) {
+    OvcCtx* x = static_cast<OvcCtx*>(t->ovc);
+    x->Tc = t->T;  // (the live condensed buffer: ov_adopt_buffer may have swapped the two)
+    x->ov = t->ov;
+    t->T = x->T_full;
+    t->ld = x->ld_full;
+    t->cols = x->cols_full;
+    t->ov = x->ov_full;
+}
+
+int ovc_ensure(lpr_tableau* t, int spares) {
+    OvcCtx* x = static_cast<OvcCtx*>(t->ovc);
+    if (x && x->rows == t->rows && x->cols == t->cols && x->ld == t->ld && x->spares == spares)
+        return LPR_OK_OPTIMAL;
+    ovc_release(t);
+    x = new (std::nothrow) OvcCtx();
+    if (!x) return LPR_OUT_OF_MEMORY;
+    x->rows = t->rows;
+    x->cols = t->cols;
+    x->ld = t->ld;
+    x->spares = spares;
+    x->nres = t->cols - t->rows;
+    x->Wc = x->nres + spares + 1;
+    x->Wp = align_up(x->Wc, kLdAlign);
+    t->ovc = x;
+    hipError_t err = hipSuccess;
+    auto chk = [&](hipError_t e) { if (err == hipSuccess) err = e; };
+    chk(hipMalloc(&x->Tc, (size_t)t->rows * x->Wp * sizeof(double)));
+    chk(hipMalloc(&x->colid, (size_t)x->Wp * sizeof(int32_t)));
+    chk(hipMalloc(&x->slotof, (size_t)t->cols * sizeof(int32_t)));
+    chk(hipMalloc(&x->rowof, (size_t)t->cols * sizeof(int32_t)));
+    chk(hipMalloc(&x->rowvar, (size_t)t->rows * sizeof(unsigned long long)));
+    chk(hipMalloc(&x->cstate, 2 * sizeof(unsigned long long)));
+    chk(hipMalloc(&x->fail, 2 * sizeof(unsigned)));
+    chk(hipHostMalloc(&x->h_fail, 2 * sizeof(unsigned)));
+    int rc = LPR_OK_OPTIMAL;
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        rc = err == hipErrorOutOfMemory ? LPR_OUT_OF_MEMORY : LPR_DEVICE_ERROR;
+    } else {
+        // the scratch of the narrower geometry: ov_ensure, on the handle as the regime sees it
+        ovc_enter(t);
+        t->ov = nullptr;
+        rc = ov_ensure(t, true);
+        if (rc == LPR_OK_OPTIMAL) {
+            lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
+            c->b.colid = x->colid;
+            c->b.rowvar = x->rowvar;
+            c->b.cstate = x->cstate;
+            c->b.spare0 = x->nres;
+            c->b.nspare = spares;
+        }
+        ovc_leave(t);
+    }
+    if (rc != LPR_OK_OPTIMAL) ovc_release(t);
+    return rc;
+}
+
+// full tableau -> x->Tc.  *ok: every basic column is the exact unit column of its row and no
+// column is basic twice; otherwise nothing the solve reads has been touched.
+int ovc_condense(lpr_tableau* t, bool* ok) {
+    OvcCtx* x = static_cast<OvcCtx*>(t->ovc);
+    hipStream_t s = t->eng->stream;
+    hipLaunchKernelGGL(k_ov_cond_map, dim3(1), dim3(1024), 0, s, t->basis, t->rows, t->cols, x->Wc,
+                       x->Wp, x->rowof, x->slotof, x->colid, x->rowvar, x->cstate, x->fail);
+    const int span = (t->ld + (x->Wp - x->nres) + 1) / 2;  // a lane takes two columns
+    hipLaunchKernelGGL(k_ov_condense, dim3((span + 255) / 256, t->rows), dim3(256), 0, s, t->T,
+                       t->ld, t->cols, x->Tc, x->Wp, x->Wc, x->nres, x->slotof, x->rowof, x->fail);
+    LPR_HIP(hipGetLastError());
+    LPR_HIP(hipMemcpyAsync(x->h_fail, x->fail, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    *ok = x->h_fail[0] == 0u && x->h_fail[1] == 0u;
+    return LPR_OK_OPTIMAL;
+}
+
+// x->Tc (the live condensed buffer, after ovc_leave) -> the full tableau t->T
+int ovc_expand(lpr_tableau* t) {
+    OvcCtx* x = static_cast<OvcCtx*>(t->ovc);
+    hipStream_t s = t->eng->stream;
+    hipLaunchKernelGGL(k_ov_expand_map, dim3(1), dim3(1024), 0, s, t->rows, t->cols, x->Wp,
+                       x->colid, x->rowvar, x->rowof, x->slotof);
+    hipLaunchKernelGGL(k_ov_expand, dim3((t->ld / 2 + 255) / 256, t->rows), dim3(256), 0, s, x->Tc,
+                       x->Wp, t->T, t->ld, t->cols, x->slotof, x->rowof);
+    LPR_HIP(hipGetLastError());
+    return LPR_OK_OPTIMAL;
 }
 
 }  // namespace lpr
