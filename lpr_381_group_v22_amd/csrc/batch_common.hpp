@@ -176,6 +176,10 @@ void unlist(std::vector<H*>& live, H* h) {
         }
 }
 
+// batch_engine.hip: what an engine that starts from a solved LP batch reads of it: its engine (null
+// once orphaned, or with no handle), the descriptors' host mirror and the tableau slab
+lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
+
 }  // namespace lpr
 
 // Entry check of every call on a batch handle; noun names the kind of batch in the message.

@@ -243,22 +243,7 @@ __global__ __launch_bounds__(256) void k_batch_extract(const BatchDesc* __restri
     if (!x) return;
     const bool opt = d.status == LPR_OK_OPTIMAL;
     for (int j = lane; j < d.n; j += kWave) {
-        double v = 0.0;
-        if (opt) {
-            int basicRow = -1;
-            bool isBasic = true;
-            for (int i = 1; i < R && isBasic; ++i) {
-                const double t = T[(size_t)i * C + j];
-                if (fabs(t - 1.0) < 1e-9) {
-                    if (basicRow == -1) basicRow = i;
-                    else isBasic = false;
-                } else if (fabs(t) > 1e-9) {
-                    isBasic = false;
-                }
-            }
-            if (isBasic && basicRow != -1) v = T[(size_t)basicRow * C + (C - 1)];
-        }
-        x[d.x_off + j] = v;
+        x[d.x_off + j] = opt ? extract_solution(T, C, R, C, j) : 0.0;
     }
 }
 

@@ -1,13 +1,11 @@
-// dotnet_minmax.hpp -- .NET Framework's Math.Max / Math.Min on doubles and the EPS of the
-// sensitivity reports, shared by sens_ranging_kernels.hip (lpr_sens_ranging)
+// dotnet_minmax.hpp -- .NET Framework's Math.Max / Math.Min on doubles, shared by
+// sens_ranging_kernels.hip (lpr_sens_ranging)
 // and sens_batch_ranging_kernels.hip (lpr_sens_batch_ranging, section 19).  Device code only.
 #pragma once
 
 #include "engine_common.hpp"
 
 namespace lpr {
-
-constexpr double kRngEps = 1e-9;  // SensitivityAnalyzer.cs:20
 
 // .NET Framework Math.Max / Math.Min on doubles (oracle/oracle_revised.c:90 quotes Max)
 __device__ __forceinline__ double dn_max(double a, double b) {

@@ -211,4 +211,15 @@ struct lpr_tableau {
 namespace lpr {
 // lpr_engine.hip: make room for `rows_needed` tableau rows on a live handle
 int tableau_reserve_rows(lpr_tableau* t, int rows_needed);
+// sens_engine.hip: what lpr_sens_batch_create reads of an analyzer (null: no handle); the engine is
+// null once the handle is orphaned
+lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,
+                      const int32_t** basic, const int32_t** bcount,
+                      const std::vector<double>** sol, double* z);
+// sens_ranging_kernels.hip: the sweep and the finish of lpr_sens_ranging on `st`; ws is the buffer
+// laid out by `pl` (sens_ranging_common.hpp), ev_mid (may be null) is recorded between the two
+struct SensRangingPlan;
+int sens_ranging_launch(hipStream_t st, const double* T, int ld, int R, int C,
+                        const int32_t* bcount, const int32_t* cand, char* ws,
+                        const SensRangingPlan& pl, hipEvent_t ev_mid);
 }  // namespace lpr

@@ -621,25 +621,12 @@ __global__ __launch_bounds__(256) void k_pivot_fused(const double* __restrict__ 
 
 // ------------------------------------------------------------------------------------------
 // ExtractSolution  PrimalSimplexSolver.cs:213-252.  One lane per decision column j < n (coalesced
-// across j), serial over rows.  The C# early `break`s only stop the scan; the verdict
-// "exactly one entry within 1e-9 of 1 and every other entry within 1e-9 of 0" does not depend on
-// where the scan stops, so the full scan gives the same x_j.
+// across j); the rule is extract_solution (select_common.hpp).
 __global__ __launch_bounds__(256) void k_extract(const double* __restrict__ T, int ld, int R,
                                                  int C, int n, double* __restrict__ x) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    int basicRow = -1;
-    bool isBasic = true;
-    for (int i = 1; i < R; ++i) {
-        const double v = T[(size_t)i * ld + j];
-        if (fabs(v - 1.0) < 1e-9) {
-            if (basicRow == -1) basicRow = i;
-            else isBasic = false;
-        } else if (fabs(v) > 1e-9) {
-            isBasic = false;
-        }
-    }
-    x[j] = (isBasic && basicRow != -1) ? T[(size_t)basicRow * ld + (C - 1)] : 0.0;
+    x[j] = extract_solution(T, ld, R, C, j);
 }
 
 // ------------------------------------------------------------------------------------------

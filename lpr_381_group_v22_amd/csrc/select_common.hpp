@@ -1,6 +1,8 @@
 // select_common.hpp -- device helpers shared by the pivot-selection kernels: the primal path
 // (primal_kernels.hip, overlap_kernels.hip, small_kernels.hip) and the strict arg-mins of the two
-// EPS-band side paths (block_cand_min in cut_kernels.hip and sens_engine.hip).  Not part of the ABI.
+// EPS-band side paths (block_cand_min in cut_kernels.hip and sens_engine.hip); and ExtractSolution
+// of one column (primal_kernels.hip, batch_kernels.hip, sens_batch_kernels.hip).  Not part of the
+// ABI.
 #pragma once
 
 #include "engine_common.hpp"
@@ -159,6 +161,29 @@ __device__ __forceinline__ Cand dpp_block_cand_min16(Cand c, double* lds_v, int*
     // (every row of 16 lanes did the same reduction: the result is wave-uniform; say so)
     r.i = __builtin_amdgcn_readfirstlane(r.i);
     return r;
+}
+
+// ------------------------------------------------------------------------------------------
+// ExtractSolution  PrimalSimplexSolver.cs:213-252: x_j of decision column j of an R-row tableau
+// with row stride `stride` and the RHS in column C - 1, by one lane, serial over rows.  The C#'s
+// early `break`s only stop the scan; the verdict "exactly one entry within kExtractEps of 1 and
+// every other entry within kExtractEps of 0" does not depend on where the scan stops, so the full
+// scan gives the same x_j.
+constexpr double kExtractEps = 1e-9;  // the literal of :228 :238
+__device__ __forceinline__ double extract_solution(const double* T, int stride, int R, int C,
+                                                   int j) {
+    int basicRow = -1;
+    bool isBasic = true;
+    for (int i = 1; i < R; ++i) {
+        const double v = T[(size_t)i * stride + j];
+        if (fabs(v - 1.0) < kExtractEps) {
+            if (basicRow == -1) basicRow = i;
+            else isBasic = false;
+        } else if (fabs(v) > kExtractEps) {
+            isBasic = false;
+        }
+    }
+    return (isBasic && basicRow != -1) ? T[(size_t)basicRow * stride + (C - 1)] : 0.0;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 #pragma once
 
 #include "batch_common.hpp"
-#include "fold_common.hpp"
+#include "sens_batch_ranging_common.hpp"
 
 #pragma clang fp contract(off)
 
@@ -36,9 +36,6 @@ constexpr int kSensBatchChunk[kNumForms] = {0, 128, 16};
 static_assert(sizeof(kSensBatchChunk) / sizeof(int) == kNumForms, "one chunk per form");
 constexpr int kSensBatchEditsPerLaunch = 64;
 
-constexpr double kSensBatchEps = kFoldEps;  // SensitivityAnalyzer.cs:20
-constexpr int kSensBatchMaxIter = 10000;    // default argument of ReOptimize / DualSimplexIfNeeded
-constexpr int32_t kSensNoBasic = 0x7f7f7f7f;  // "no column yet" while basicVars is rebuilt
 constexpr int32_t kSensEditNotRun = kRunning;  // outcome of an edit that has not ended yet
 
 // Where a scenario stands inside its current edit.  A launch can stop only in front of a pivot,
@@ -101,5 +98,20 @@ struct SensBatchView {
     int32_t* outcome;    // per edit, packed
     int64_t* edit_piv;   // per edit, packed
 };
+
+// Launchers, for sens_batch_engine.hip.  sens_batch_kernels.hip: the base state into every
+// scenario; the analyzer's constructor per scenario on the LPs `src` names in `slab`; one bounded
+// round of the script kernel in `form` over the scenarios idx_in lists.
+int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, int R, int C,
+                           const double* baseT, int ld, const int32_t* base_basic,
+                           const int32_t* base_bcount, const double* base_sol, int nsol);
+int sens_batch_launch_from_models(hipStream_t s, const SensBatchView& vw, int count,
+                                  const SensModelSrc* src, const double* slab);
+int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& vw,
+                      const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
+                      int chunk);
+// sens_batch_ranging_kernels.hip: the report of every scenario into `out`, laid out by `pl`
+int sens_batch_ranging_launch(hipStream_t s, const SensBatchView& vw, char* out,
+                              const SensBatchRangingPlan& pl);
 
 }  // namespace lpr

@@ -6,32 +6,11 @@
 // every scenario from an LP of a solved LP batch instead: the analyzer's constructor runs per
 // scenario on the device.
 #include "sens_batch_common.hpp"
-#include "sens_batch_ranging_common.hpp"
 
 #include <algorithm>
 #include <cstdio>
 #include <new>
 #include <string>
-
-namespace lpr {
-int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& vw,
-                      const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
-                      int chunk);
-int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, int R, int C,
-                           const double* baseT, int ld, const int32_t* base_basic,
-                           const int32_t* base_bcount, const double* base_sol, int nsol);
-int sens_batch_launch_from_models(hipStream_t s, const SensBatchView& vw, int count,
-                                  const SensModelSrc* src, const double* slab);
-// batch_engine.hip
-lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
-// sens_batch_ranging_kernels.hip: the report of every scenario into `out`, laid out by `pl`
-int sens_batch_ranging_launch(hipStream_t s, const SensBatchView& vw, char* out,
-                              const SensBatchRangingPlan& pl);
-// sens_engine.hip
-lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,
-                      const int32_t** basic, const int32_t** bcount,
-                      const std::vector<double>** sol, double* z);
-}  // namespace lpr
 
 using namespace lpr;
 
@@ -692,19 +671,8 @@ int lpr_sens_batch_ranging(lpr_sens_batch* b, int32_t* kind, int32_t* var_row,
     LPR_HIP(hipMemcpyAsync(b->rng_pin, b->rng_out, pl.total, hipMemcpyDeviceToHost, s));
     LPR_HIP(hipStreamSynchronize(s));
     b->rng_timed = true;
-    const size_t nc = (size_t)pl.count * pl.mc, nr = (size_t)pl.count * pl.mr;
-    auto put = [&](void* dst, size_t off, size_t bytes) {
-        if (dst && bytes) std::memcpy(dst, b->rng_pin + off, bytes);
-    };
-    put(kind, pl.o_kind, nc * sizeof(int32_t));
-    put(var_row, pl.o_row, nc * sizeof(int32_t));
-    put(reduced_cost, pl.o_rc, nc * sizeof(double));
-    put(cost_lo, pl.o_clo, nc * sizeof(double));
-    put(cost_hi, pl.o_chi, nc * sizeof(double));
-    put(shadow, pl.o_shadow, nr * sizeof(double));
-    put(rhs_lo, pl.o_rlo, nr * sizeof(double));
-    put(rhs_hi, pl.o_rhi, nr * sizeof(double));
-    put(rhs_now, pl.o_now, nr * sizeof(double));
+    sens_report_copy(pl.out, b->rng_pin, kind, var_row, reduced_cost, cost_lo, cost_hi, shadow,
+                     rhs_lo, rhs_hi, rhs_now);
     return LPR_OK_OPTIMAL;
 }
 

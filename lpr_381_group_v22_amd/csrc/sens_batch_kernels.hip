@@ -17,52 +17,17 @@
 //                        scenario on the final tableau of an LP of a solved LP batch
 #include "batch_device.hpp"
 #include "sens_batch_common.hpp"
+#include "sens_rules.hpp"
 
 #pragma clang fp contract(off)
 
 namespace lpr {
 
-// GetBasicRow (:69-84) of one column, by the whole workgroup: exactly one row of 1.. holds
-// |v| > EPS, and that row is within EPS of 1.
-__device__ __forceinline__ int block_basic_row(const double* T, int R, int C, int col, int* slot) {
+// GetBasicRow (:69-84) of column j by one lane (the column scans of :706-723 and :160-165)
+__device__ __forceinline__ int column_basic_row(const double* T, int R, int C, int j) {
     int c = 0, rs = 0;
-    for (int i = 1 + (int)threadIdx.x; i < R; i += 256)
-        if (fabs(T[(size_t)i * C + col]) > kSensBatchEps) {
-            c += 1;
-            rs += i;
-        }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        c += __shfl_xor(c, off, kWave);
-        rs += __shfl_xor(rs, off, kWave);
-    }
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) {
-        slot[2 * wave] = c;
-        slot[2 * wave + 1] = rs;
-    }
-    __syncthreads();
-    int tc = 0, tr = 0;
-    for (int w = 0; w < 4; ++w) {
-        tc += slot[2 * w];
-        tr += slot[2 * w + 1];
-    }
-    __syncthreads();
-    int r = -1;
-    if (tc == 1 && fabs(T[(size_t)tr * C + col] - 1.0) < kSensBatchEps) r = tr;
-    return r;
-}
-
-// GetBasicRow of column j by one lane (the column scans of :706-723 and :160-165)
-__device__ __forceinline__ int lane_basic_row(const double* T, int R, int C, int j) {
-    int c = 0, rs = 0;
-    for (int i = 1; i < R; ++i)
-        if (fabs(T[(size_t)i * C + j]) > kSensBatchEps) {
-            c += 1;
-            rs += i;
-        }
-    if (c == 1 && fabs(T[(size_t)rs * C + j] - 1.0) < kSensBatchEps) return rs;
-    return -1;
+    for (int i = 1; i < R; ++i) basic_row_step(above_eps(T[(size_t)i * C + j]), i, c, rs);
+    return basic_row_verdict(c, rs, T + j, C);
 }
 
 // The membership counts that shadow basicVars, counted again from its m entries
@@ -86,7 +51,7 @@ __device__ __forceinline__ void block_rebuild_basics(const double* T, int R, int
     for (int j = tid; j < C; j += 256) bcount[j] = 0;
     __syncthreads();
     for (int j = tid; j < rhs; j += 256) {  // the first such column per row
-        const int r = lane_basic_row(T, R, C, j);
+        const int r = column_basic_row(T, R, C, j);
         if (r >= 1) atomicMin(&basic[r - 1], j);
     }
     __syncthreads();
@@ -221,7 +186,7 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
             } else if (e.op == LPR_SENS_EDIT_BASIC) {  // :368-388
                 valid = e.a >= 0 && e.a < rhs && bcount[e.a] > 0;
                 int r = -1;
-                if (valid) r = block_basic_row(T, R, C, e.a, slot);
+                if (valid) r = block_basic_row<256>(T, R, C, e.a, slot);
                 valid = valid && r >= 1;  // "Could not locate basic row." :379
                 if (valid) {
                     for (int j = tid; j < C; j += 256) {  // j < C - 1, then the RHS entry
@@ -391,16 +356,13 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
                     status = LPR_PIVOT_LIMIT;
                     break;
                 }
-                if (it_d > kSensBatchMaxIter) {  // `if (iter++ > maxIter) throw` (:183)
+                if (it_d > kSensMaxIter) {  // `if (iter++ > maxIter) throw` (:183)
                     outcome = LPR_SENS_ITER_LIMIT;
                 } else {
                     ++it_d;
                     // `a < -EPS: ratio = cbar / (-a); ratio < best - EPS`, columns ascending
                     const double* lrow = T + (size_t)leave * C;
-                    for (int j = tid; j < rhs; j += 256) {
-                        const double a = lrow[j];
-                        prow[j] = (a < -kSensBatchEps) ? ieee_div(T[j], -a) : (double)NAN;
-                    }
+                    for (int j = tid; j < rhs; j += 256) prow[j] = dual_ratio(T[j], lrow[j]);
                     __syncthreads();
                     enter = staged_eps_fold(prow, 0, rhs, INFINITY, slot);
                     if (enter == -1) outcome = LPR_SENS_INFEASIBLE;  // :197
@@ -410,18 +372,8 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
         if (phase == kPhasePrimal) {
             // IsOptimal (:86-96) and the entering column `rc < mostNeg`, first index (:131-141)
             int notopt = 0;
-            Cand best;
-            best.v = 0.0;
-            best.i = -1;
-            for (int j = tid; j < rhs; j += 256) {
-                if (bcount[j] > 0) continue;
-                const double rc = T[j];
-                if (rc < -kSensBatchEps) notopt = 1;
-                if (rc < best.v) {  // ascending j per lane: strict < keeps the first index
-                    best.v = rc;
-                    best.i = j;
-                }
-            }
+            Cand best = entering_start();
+            for (int j = tid; j < rhs; j += 256) entering_step(bcount, T, j, notopt, best);
             notopt = __syncthreads_or(notopt);
             if (!notopt) {
                 phase = kPhaseEpilogue;
@@ -431,7 +383,7 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
                     status = LPR_PIVOT_LIMIT;
                     break;
                 }
-                if (it_p > kSensBatchMaxIter) {  // `if (iter++ > maxIter) throw` (:126)
+                if (it_p > kSensMaxIter) {  // `if (iter++ > maxIter) throw` (:126)
                     outcome = LPR_SENS_ITER_LIMIT;
                 } else {
                     ++it_p;
@@ -442,12 +394,8 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
                     } else {
                         // `a > EPS: ratio = rhs / a; ratio < best - EPS`, rows ascending (:144-150)
                         // (staged in the factor column's buffer, which is idle until the pivot)
-                        for (int i = tid; i < R; i += 256) {
-                            const double a = T[(size_t)i * C + enter];
-                            fcol[i] = (a > kSensBatchEps)
-                                          ? ieee_div(T[(size_t)i * C + rhs], a)
-                                          : (double)NAN;
-                        }
+                        for (int i = tid; i < R; i += 256)
+                            fcol[i] = primal_ratio(T[(size_t)i * C + rhs], T[(size_t)i * C + enter]);
                         __syncthreads();
                         leave = staged_eps_fold(fcol, 1, R, INFINITY, slot);
                         if (leave == -1) outcome = LPR_SENS_UNBOUNDED;  // :151
@@ -459,7 +407,7 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
         if (outcome == kSensEditNotRun && leave >= 1 && enter >= 0) {
             // ---- Pivot :98-119 ----
             const double piv = T[(size_t)leave * C + enter];
-            if (fabs(piv) < kSensBatchEps) {
+            if (zero_pivot(piv)) {
                 outcome = LPR_SENS_ZERO_PIVOT;  // :101
             } else {
                 __syncthreads();  // the staged ratios have been read
@@ -496,7 +444,7 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
                                     T[x] = prow[jj[u]];
                                 } else {
                                     const double f = fcol[ii[u]];
-                                    if (!(fabs(f) < kSensBatchEps)) {
+                                    if (!row_untouched(f)) {
                                         const double prod = f * prow[jj[u]];  // rounded: no FMA
                                         T[x] = v[u] - prod;
                                     }
@@ -506,16 +454,8 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
                     }
                 }
                 if (tid == 0) {
-                    const int old = basic[leave - 1];  // basicVars[leaveRow - 1] = enterCol
-                    if (old >= 0) bcount[old] -= 1;
-                    basic[leave - 1] = enter;
-                    bcount[enter] += 1;
-                    if (log_n < vw.log_cap) {
-                        int32_t* e3 = g_log + 3 * log_n;
-                        e3[0] = phase == kPhaseDual ? 0 : 1;
-                        e3[1] = leave;
-                        e3[2] = enter;
-                    }
+                    basis_enter(basic, bcount, leave, enter, phase == kPhaseDual ? 0 : 1, g_log, log_n,
+                                vw.log_cap);
                 }
                 ++log_n;
                 ++pivots;
@@ -529,7 +469,7 @@ __global__ __launch_bounds__(256) void k_sens_batch(SensBatchView vw,
         if (phase == kPhaseEpilogue) {  // :159-165
             z = T[rhs];
             for (int j = tid; j < rhs; j += 256) {
-                const int r = lane_basic_row(T, R, C, j);
+                const int r = column_basic_row(T, R, C, j);
                 g_sol[j] = (r == -1) ? 0.0 : T[(size_t)r * C + rhs];
             }
             nsol = rhs;
@@ -628,9 +568,8 @@ __global__ __launch_bounds__(256) void k_sens_batch_init(SensBatchView vw, int c
 // batch: one workgroup per scenario, on the LP src[k] names.  In order:
 //   1. the LP's compact rows x cols tableau into the scenario's cur slice (:24), compact by the
 //      scenario's own cols; row 0's last cell already holds finalZ, so :32 stores what is there
-//   2. solutionVector = ExtractSolution() over the LP's n (PrimalSimplexSolver.cs:213-249: the
-//      first entry within 1e-9 of 1 is the basic row, a second one or any other entry above 1e-9
-//      gives 0), one lane per decision column; finalZ = tableau[0, cols - 1]
+//   2. solutionVector = ExtractSolution() over the LP's n (extract_solution, select_common.hpp),
+//      one lane per decision column; finalZ = tableau[0, cols - 1]
 //   3. RebuildBasicsFromTableau (:35), not the LP batch's stored basis
 //   4. the membership counts of basicVars
 //   5. the descriptor fields that depend on the LP: R, C, nsol, z, old_z
@@ -650,20 +589,7 @@ __global__ __launch_bounds__(256) void k_sens_batch_from_models(SensBatchView vw
     double* const T = vw.cur + (size_t)k * vw.R * vw.C;
     for (int x = tid; x < RC; x += 256) T[x] = S[x];
     double* const sol = vw.sol + (size_t)k * vw.sol_cap;
-    for (int j = tid; j < s.n; j += 256) {
-        int basicRow = -1;
-        bool isBasic = true;
-        for (int i = 1; i < R && isBasic; ++i) {
-            const double t = S[(size_t)i * C + j];
-            if (fabs(t - 1.0) < 1e-9) {
-                if (basicRow == -1) basicRow = i;
-                else isBasic = false;
-            } else if (fabs(t) > 1e-9) {
-                isBasic = false;
-            }
-        }
-        sol[j] = (isBasic && basicRow != -1) ? S[(size_t)basicRow * C + rhs] : 0.0;
-    }
+    for (int j = tid; j < s.n; j += 256) sol[j] = extract_solution(S, C, R, C, j);
     block_rebuild_basics(S, R, C, s_basic, s_bcount);
     int32_t* const g_basic = vw.basic + (size_t)k * (vw.R - 1);
     int32_t* const g_bcount = vw.bcount + (size_t)k * vw.C;
@@ -681,7 +607,7 @@ __global__ __launch_bounds__(256) void k_sens_batch_from_models(SensBatchView vw
 }
 
 // ------------------------------------------------------------------------------------------
-// Launchers (sens_batch_engine.hip).
+// Launchers (declared in sens_batch_common.hpp).
 int sens_batch_launch_from_models(hipStream_t s, const SensBatchView& vw, int count,
                                   const SensModelSrc* src, const double* slab) {
     hipLaunchKernelGGL(k_sens_batch_from_models, dim3(count), dim3(256), 0, s, vw, count, src, slab);

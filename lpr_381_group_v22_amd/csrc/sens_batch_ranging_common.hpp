@@ -6,8 +6,7 @@
 // any host compiler.  Not part of the ABI (include/lpr_engine.h is).
 #pragma once
 
-#include <cstddef>
-#include <cstdint>
+#include "sens_ranging_common.hpp"  // the output block: SensReportLayout, SensReportOut
 
 namespace lpr {
 
@@ -46,15 +45,12 @@ inline SensBatchRangingLds sens_batch_ranging_lds(int SR, int SC) {
     return l;
 }
 
-// The output block: nine arrays, scenario k at row k of each.  Offsets in bytes from the start of
-// one device buffer (and of its pinned mirror); the doubles come first, so every array is aligned
-// to its element.
+// The output block is the whole device buffer (and its pinned mirror): scenario k at row k of each
+// array, rows of max_cols - 1 and max_rows - 1.
 struct SensBatchRangingPlan {
     int count;
-    int mc, mr;                            // max_cols - 1, max_rows - 1: the row lengths
-    size_t o_rc, o_clo, o_chi;             // count x mc doubles each
-    size_t o_shadow, o_rlo, o_rhi, o_now;  // count x mr doubles each
-    size_t o_kind, o_row;                  // count x mc int32 each
+    int mc, mr;            // max_cols - 1, max_rows - 1: the row lengths
+    SensReportLayout out;  // at offset 0
     size_t total;
 };
 
@@ -67,19 +63,8 @@ inline bool sens_batch_ranging_plan(int count, int base_R, int base_C, int max_R
     p->count = count;
     p->mc = max_C - 1;
     p->mr = max_R - 1;
-    const size_t D = sizeof(double), I = sizeof(int32_t);
-    const size_t nc = (size_t)count * (size_t)p->mc, nr = (size_t)count * (size_t)p->mr;
-    size_t off = 0;
-    p->o_rc = off;     off += nc * D;
-    p->o_clo = off;    off += nc * D;
-    p->o_chi = off;    off += nc * D;
-    p->o_shadow = off; off += nr * D;
-    p->o_rlo = off;    off += nr * D;
-    p->o_rhi = off;    off += nr * D;
-    p->o_now = off;    off += nr * D;
-    p->o_kind = off;   off += nc * I;
-    p->o_row = off;    off += nc * I;
-    p->total = (off + 15) & ~(size_t)15;
+    p->out = sens_report_layout(count, p->mc, p->mr, 0);
+    p->total = p->out.end;
     return true;
 }
 

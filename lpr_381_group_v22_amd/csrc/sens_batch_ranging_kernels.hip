@@ -18,9 +18,9 @@
 //   3. one lane per column / constraint writes the outputs, the padding past the scenario's own
 //      shape included, with plain vector stores.
 // No atomics, nothing depends on arrival order; the batch is only read.
-#include "dotnet_minmax.hpp"  // dn_max / dn_min, kRngEps
+#include "dotnet_minmax.hpp"  // dn_max / dn_min
 #include "sens_batch_common.hpp"
-#include "sens_batch_ranging_common.hpp"
+#include "sens_rules.hpp"
 
 #include <climits>
 
@@ -28,7 +28,6 @@
 
 namespace lpr {
 
-static_assert(kRngEps == kSensBatchEps, "one EPS: SensitivityAnalyzer.cs:20");
 static_assert(kSbrWaveLanes == kWave, "a wave folds a row");
 constexpr int kSbrLoad = 4;  // entries a lane loads ahead of their use (8 spill SGPRs)
 constexpr int kSbrDiv = 2;   // ... and divides behind one branch (more of them spill SGPRs)
@@ -40,12 +39,6 @@ struct SensBatchRangingIn {
     const double *cur, *alt;
     const int32_t* bcount;
     int SR, SC;  // the maximal shape: the strides of the slabs
-};
-
-struct SensBatchRangingOut {
-    double *rc, *clo, *chi, *shadow, *rlo, *rhi, *now;
-    int32_t *kind, *row;
-    int mc, mr;  // row lengths of the arrays: max_cols - 1, max_rows - 1
 };
 
 namespace {
@@ -81,7 +74,7 @@ __device__ __forceinline__ void combine_min(double& v, int& at, double ov, int o
 
 __global__ __launch_bounds__(kSbrLanes) void k_sens_batch_ranging(SensBatchRangingIn in, int count,
                                                                   SensBatchRangingLds lds,
-                                                                  SensBatchRangingOut o) {
+                                                                  SensReportOut o, int mc, int mr) {
     extern __shared__ double smem[];
     const int k = blockIdx.x;
     if (k >= count) return;
@@ -132,9 +125,10 @@ __global__ __launch_bounds__(kSbrLanes) void k_sens_batch_ranging(SensBatchRangi
                 for (int u = 0; u < kSbrDiv; ++u) {
                     const int i = i0 + g + u;
                     const double v = a[g + u];
-                    const bool cand = v > kRngEps || v < -kRngEps;  // a NaN entry is neither
-                    c += cand ? 1 : 0;
-                    rs += cand ? i : 0;
+                    bool pos, neg;
+                    range_sign(v, pos, neg);
+                    const bool cand = pos || neg;  // above_eps(v)
+                    basic_row_step(cand, i, c, rs);
                     num[u] = (cand && slack) ? -s_b[i] : 0.0;  // -bi / coeff (:415 :417)
                     den[u] = (cand && slack) ? v : 1.0;
                 }
@@ -142,20 +136,20 @@ __global__ __launch_bounds__(kSbrLanes) void k_sens_batch_ranging(SensBatchRangi
                     ieee_div_n<kSbrDiv>(num, den, q);
 #pragma unroll
                     for (int u = 0; u < kSbrDiv; ++u) {
-                        lo = a[g + u] > kRngEps ? dn_max(lo, q[u]) : lo;
-                        hi = a[g + u] < -kRngEps ? dn_min(hi, q[u]) : hi;
+                        bool pos, neg;
+                        range_sign(a[g + u], pos, neg);
+                        lo = pos ? dn_max(lo, q[u]) : lo;
+                        hi = neg ? dn_min(hi, q[u]) : hi;
                     }
                 }
             }
         }
-        // GetBasicRow (:69-84): exactly one row holds |v| > EPS, and that row is within EPS of 1
-        int r = -1;
-        if (c == 1 && fabs(T[(size_t)rs * C + j] - 1.0) < kRngEps) r = rs;
+        const int r = basic_row_verdict(c, rs, T + j, C);  // GetBasicRow (:69-84)
         const bool member = bcount[j] > 0;  // basicVars.Contains(j)
         s_cand[j] = member ? r : -1;
         if (member && r >= 1) s_need[r] = 1;  // every writer stores the same 1
         if (slack) {
-            const size_t t = (size_t)k * o.mr + (j - n);
+            const size_t t = (size_t)k * mr + (j - n);
             o.shadow[t] = T[j];
             o.rlo[t] = lo;
             o.rhi[t] = hi;
@@ -192,7 +186,9 @@ __global__ __launch_bounds__(kSbrLanes) void k_sens_batch_ranging(SensBatchRangi
 #pragma unroll
                     for (int u = 0; u < kSbrDiv; ++u) {
                         const double v = a[g + u];
-                        const bool cand = v > kRngEps || v < -kRngEps;
+                        bool pos, neg;
+                        range_sign(v, pos, neg);
+                        const bool cand = pos || neg;
                         num[u] = cand ? -z[g + u] : 0.0;  // -cbar_j / a_rj (:351 :354)
                         den[u] = cand ? v : 1.0;
                     }
@@ -200,8 +196,10 @@ __global__ __launch_bounds__(kSbrLanes) void k_sens_batch_ranging(SensBatchRangi
 #pragma unroll
                     for (int u = 0; u < kSbrDiv; ++u) {  // the lane's columns ascend
                         const int j = j0 + (g + u) * kSbrWaveLanes;
-                        if (a[g + u] > kRngEps) dn_max_at(lo, lo_at, q[u], j);
-                        if (a[g + u] < -kRngEps) dn_min_at(hi, hi_at, q[u], j);
+                        bool pos, neg;
+                        range_sign(a[g + u], pos, neg);
+                        if (pos) dn_max_at(lo, lo_at, q[u], j);
+                        if (neg) dn_min_at(hi, hi_at, q[u], j);
                     }
                 }
             }
@@ -224,28 +222,17 @@ __global__ __launch_bounds__(kSbrLanes) void k_sens_batch_ranging(SensBatchRangi
 
     // ---- 3. the outputs, padded to the batch's maximal shape ----
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-    for (int j = tid; j < o.mc; j += kSbrLanes) {
-        const size_t t = (size_t)k * o.mc + j;
+    for (int j = tid; j < mc; j += kSbrLanes) {
+        const size_t t = (size_t)k * mc + j;
         if (j < nc) {
             const double cbar = T[j];
             double lo = -INFINITY, hi = INFINITY;
-            int32_t kind, vr = -1;
-            if (bcount[j] > 0) {  // DisplayRangeBasic
-                vr = s_cand[j];
-                if (vr >= 1) {
-                    kind = LPR_SENS_RANGE_BASIC;
-                    lo = s_lo[vr];
-                    hi = s_hi[vr];
-                } else {
-                    kind = LPR_SENS_RANGE_BASIC_ROW_NOT_FOUND;  // :337
-                    vr = -1;
-                }
-            } else if (cbar > kRngEps) {  // DisplayRangeNonBasic :291-296
-                kind = LPR_SENS_RANGE_NONBASIC_RANGE;
-            } else if (fabs(cbar) <= kRngEps) {
-                kind = LPR_SENS_RANGE_NONBASIC_BOUNDARY;
-            } else {  // negative, or NaN
-                kind = LPR_SENS_RANGE_NONBASIC_NOT_OPTIMAL;
+            const bool member = bcount[j] > 0;  // basicVars.Contains(j)
+            int32_t kind, vr;
+            range_classify(member, member ? s_cand[j] : -1, cbar, kind, vr);
+            if (kind == LPR_SENS_RANGE_BASIC) {
+                lo = s_lo[vr];
+                hi = s_hi[vr];
             }
             o.rc[t] = cbar;
             o.clo[t] = lo;
@@ -260,8 +247,8 @@ __global__ __launch_bounds__(kSbrLanes) void k_sens_batch_ranging(SensBatchRangi
             o.row[t] = INT32_MIN;
         }
     }
-    for (int i = m + tid; i < o.mr; i += kSbrLanes) {
-        const size_t t = (size_t)k * o.mr + i;
+    for (int i = m + tid; i < mr; i += kSbrLanes) {
+        const size_t t = (size_t)k * mr + i;
         o.shadow[t] = qnan;
         o.rlo[t] = qnan;
         o.rhi[t] = qnan;
@@ -269,21 +256,10 @@ __global__ __launch_bounds__(kSbrLanes) void k_sens_batch_ranging(SensBatchRangi
     }
 }
 
-// sens_batch_engine.hip: the one launch on `s`; out is the device buffer laid out by `pl`
+// the one launch on `s` (declared in sens_batch_common.hpp)
 int sens_batch_ranging_launch(hipStream_t s, const SensBatchView& vw, char* out,
                               const SensBatchRangingPlan& pl) {
-    SensBatchRangingOut o;
-    o.rc = reinterpret_cast<double*>(out + pl.o_rc);
-    o.clo = reinterpret_cast<double*>(out + pl.o_clo);
-    o.chi = reinterpret_cast<double*>(out + pl.o_chi);
-    o.shadow = reinterpret_cast<double*>(out + pl.o_shadow);
-    o.rlo = reinterpret_cast<double*>(out + pl.o_rlo);
-    o.rhi = reinterpret_cast<double*>(out + pl.o_rhi);
-    o.now = reinterpret_cast<double*>(out + pl.o_now);
-    o.kind = reinterpret_cast<int32_t*>(out + pl.o_kind);
-    o.row = reinterpret_cast<int32_t*>(out + pl.o_row);
-    o.mc = pl.mc;
-    o.mr = pl.mr;
+    const SensReportOut o = sens_report_bind(out, pl.out);
     SensBatchRangingIn in;
     in.desc = vw.desc;
     in.cur = vw.cur;
@@ -293,7 +269,7 @@ int sens_batch_ranging_launch(hipStream_t s, const SensBatchView& vw, char* out,
     in.SC = vw.C;
     const SensBatchRangingLds lds = sens_batch_ranging_lds(vw.R, vw.C);
     hipLaunchKernelGGL(k_sens_batch_ranging, dim3(pl.count), dim3(kSbrLanes), (size_t)lds.total, s,
-                       in, pl.count, lds, o);
+                       in, pl.count, lds, o, pl.mc, pl.mr);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) {
         set_error("k_sens_batch_ranging (%d scenarios) failed to launch: %s", pl.count,

@@ -12,6 +12,7 @@
 #include "fold_common.hpp"
 #include "select_common.hpp"
 #include "sens_ranging_common.hpp"
+#include "sens_rules.hpp"
 
 #include <algorithm>
 #include <new>
@@ -56,10 +57,6 @@ struct lpr_sens {
 
 namespace lpr {
 
-constexpr double kSensEps = 1e-9;     // SensitivityAnalyzer.cs:20
-constexpr int kSensMaxIter = 10000;   // default argument of ReOptimize / DualSimplexIfNeeded
-constexpr int32_t kNoBasic = 0x7f7f7f7f;  // "no column yet" while basicVars is rebuilt (memset 0x7f)
-
 struct SensState {
     int32_t status;      // kRunning or an lpr_sens_outcome
     int32_t phase;       // 0 DualSimplexIfNeeded, 1 ReOptimize
@@ -73,9 +70,8 @@ struct SensState {
 };
 
 // ---- RebuildBasicsFromTableau / GetBasicRow -------------------------------------------------
-// IsPivotColumn(i, j) && |T[i][j] - 1| < EPS  <=>  exactly one row (1..R-1) of column j has
-// |v| > EPS, it is row i, and |v - 1| < EPS (a row within EPS of 1 is itself counted).  So one
-// pass over the tableau yields GetBasicRow for every column.
+// One pass over the tableau yields GetBasicRow (:69-84) for every column: the counts and row sums
+// of basic_row_step, per group of rows.
 __global__ __launch_bounds__(256) void k_sens_colscan(const double* __restrict__ T, int ld, int R,
                                                       int ncols, int rows_per_group,
                                                       int32_t* __restrict__ cnt,
@@ -85,13 +81,7 @@ __global__ __launch_bounds__(256) void k_sens_colscan(const double* __restrict__
     const int i0 = 1 + blockIdx.y * rows_per_group;
     const int i1 = min(R, i0 + rows_per_group);
     int c = 0, rs = 0;
-    for (int i = i0; i < i1; ++i) {
-        const double v = T[(size_t)i * ld + j];
-        if (fabs(v) > kSensEps) {
-            c += 1;
-            rs += i;
-        }
-    }
+    for (int i = i0; i < i1; ++i) basic_row_step(above_eps(T[(size_t)i * ld + j]), i, c, rs);
     if (c) {
         atomicAdd(&cnt[j], c);
         atomicAdd(&rowsum[j], rs);
@@ -108,11 +98,7 @@ __global__ __launch_bounds__(256) void k_sens_cand(const double* __restrict__ T,
                                                    double* __restrict__ sol) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= C - 1) return;
-    int r = -1;
-    if (cnt[j] == 1) {
-        const int i = rowsum[j];
-        if (fabs(T[(size_t)i * ld + j] - 1.0) < kSensEps) r = i;
-    }
+    const int r = basic_row_verdict(cnt[j], rowsum[j], T + j, ld);
     cand[j] = r;
     if (basic && r >= 1) atomicMin(&basic[r - 1], j);
     if (sol) sol[j] = (r == -1) ? 0.0 : T[(size_t)r * ld + (C - 1)];
@@ -123,7 +109,7 @@ __global__ __launch_bounds__(256) void k_sens_basics_finish(int32_t* __restrict_
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const int b = basic[i];
-    if (b == kNoBasic)
+    if (b == kSensNoBasic)
         basic[i] = -1;
     else
         atomicAdd(&bcount[b], 1);
@@ -132,34 +118,9 @@ __global__ __launch_bounds__(256) void k_sens_basics_finish(int32_t* __restrict_
 // GetBasicRow of one column -> out[0]
 __global__ __launch_bounds__(1024) void k_sens_basic_row(const double* __restrict__ T, int ld,
                                                          int R, int col, int32_t* out) {
-    int c = 0, rs = 0;
-    for (int i = 1 + threadIdx.x; i < R; i += blockDim.x)
-        if (fabs(T[(size_t)i * ld + col]) > kSensEps) {
-            c += 1;
-            rs += i;
-        }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        c += __shfl_xor(c, off, kWave);
-        rs += __shfl_xor(rs, off, kWave);
-    }
-    __shared__ int lc[16], lr[16];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) {
-        lc[wave] = c;
-        lr[wave] = rs;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tc = 0, tr = 0;
-        for (int w = 0; w < (int)(blockDim.x / kWave); ++w) {
-            tc += lc[w];
-            tr += lr[w];
-        }
-        int r = -1;
-        if (tc == 1 && fabs(T[(size_t)tr * ld + col] - 1.0) < kSensEps) r = tr;
-        out[0] = r;
-    }
+    __shared__ int slot[2 * 1024 / kWave];
+    const int r = block_basic_row<1024>(T, R, ld, col, slot);
+    if (threadIdx.x == 0) out[0] = r;
 }
 
 // ---- one loop head of DualSimplexIfNeeded (:171-200) or ReOptimize (:124-157) --------------
@@ -205,10 +166,7 @@ __global__ __launch_bounds__(1024) void k_sens_select(double* __restrict__ T, in
             const double* __restrict__ lrow = T + (size_t)leave * ld;
             enter = eps_fold<K>(
                 0, rhs, INFINITY,
-                [&](int j) {
-                    const double a = lrow[j];
-                    return (a < -kSensEps) ? ieee_div(T[j], -a) : NAN;
-                },
+                [&](int j) { return dual_ratio(T[j], lrow[j]); },
                 lds, lds_v);
             if (enter == -1) {
                 if (tid == 0) st->status = LPR_SENS_INFEASIBLE;  // :197
@@ -223,18 +181,8 @@ __global__ __launch_bounds__(1024) void k_sens_select(double* __restrict__ T, in
         kind = 1;
         // IsOptimal (:86-96) and the entering column `rc < mostNeg`, first index (:131-141)
         int notopt = 0;
-        Cand best;  // `rc < mostNeg`, mostNeg = 0.0 at the start
-        best.v = 0.0;
-        best.i = -1;
-        for (int j = tid; j < rhs; j += nt) {
-            if (bcount[j] > 0) continue;
-            const double rc = T[j];
-            if (rc < -kSensEps) notopt = 1;
-            if (rc < best.v) {  // ascending j per thread: strict < keeps the first index
-                best.v = rc;
-                best.i = j;
-            }
-        }
+        Cand best = entering_start();
+        for (int j = tid; j < rhs; j += nt) entering_step(bcount, T, j, notopt, best);
         notopt = __syncthreads_or(notopt);
         if (!notopt) {
             if (tid == 0) st->status = LPR_SENS_OK;
@@ -256,10 +204,7 @@ __global__ __launch_bounds__(1024) void k_sens_select(double* __restrict__ T, in
         // `a > EPS: ratio = rhs / a; ratio < best - EPS`, rows ascending (:144-150)
         leave = eps_fold<K>(
             1, R, INFINITY,
-            [&](int i) {
-                const double a = colbuf[i];
-                return (a > kSensEps) ? ieee_div(rhsd[i], a) : NAN;
-            },
+            [&](int i) { return primal_ratio(rhsd[i], colbuf[i]); },
             lds, lds_v);
         if (leave == -1) {
             if (tid == 0) st->status = LPR_SENS_UNBOUNDED;  // :151
@@ -270,7 +215,7 @@ __global__ __launch_bounds__(1024) void k_sens_select(double* __restrict__ T, in
 
     // Pivot (:98-119): stage the normalised row (the factor column is in colbuf already)
     const double piv = T[(size_t)leave * ld + enter];
-    if (fabs(piv) < kSensEps) {
+    if (zero_pivot(piv)) {
         if (tid == 0) st->status = LPR_SENS_ZERO_PIVOT;  // :101
         return;
     }
@@ -281,16 +226,7 @@ __global__ __launch_bounds__(1024) void k_sens_select(double* __restrict__ T, in
         st->pc = enter;
         st->sweep ^= 1;
         st->done += 1;
-        const int old = basic[leave - 1];  // basicVars[leaveRow - 1] = enterCol (:117-118)
-        if (old >= 0) bcount[old] -= 1;
-        basic[leave - 1] = enter;
-        bcount[enter] += 1;
-        if (st->log_n < st->log_cap) {
-            int32_t* e = log + 3 * st->log_n;
-            e[0] = kind;
-            e[1] = leave;
-            e[2] = enter;
-        }
+        basis_enter(basic, bcount, leave, enter, kind, log, st->log_n, st->log_cap);
         st->log_n += 1;
     }
 }
@@ -331,7 +267,7 @@ __global__ __launch_bounds__(256) void k_sens_update(double* __restrict__ T, int
         if (i < R) {
             const double f = colbuf[i];
             const bool is_r = (i == r);
-            if (is_r || !(fabs(f) < kSensEps)) {
+            if (is_r || !row_untouched(f)) {
                 double2 o;
                 const double px = f * pr2.x;
                 const double py = f * pr2.y;
@@ -677,10 +613,6 @@ lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,
     *z = s->z;
     return s->eng;
 }
-// sens_ranging_kernels.hip: the sweep and the finish of lpr_sens_ranging on `st`
-int sens_ranging_launch(hipStream_t st, const double* T, int ld, int R, int C,
-                        const int32_t* bcount, const int32_t* cand, char* ws,
-                        const SensRangingPlan& pl, hipEvent_t ev_mid);
 }  // namespace lpr
 
 #define LPR_LIVE_S(s)                                                                       \
@@ -878,7 +810,7 @@ int lpr_sens_ranging(lpr_sens* s, int32_t* kind, int32_t* var_row, double* reduc
         }
         s->rng_ws_cap = pl.total;
     }
-    const size_t out_bytes = pl.total - pl.out_off;
+    const size_t out_bytes = pl.out.end - pl.out.base;
     if (s->rng_pin_cap < out_bytes) {
         if (s->rng_pin) hipHostFree(s->rng_pin);
         s->rng_pin = nullptr;
@@ -905,24 +837,12 @@ int lpr_sens_ranging(lpr_sens* s, int32_t* kind, int32_t* var_row, double* reduc
     if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipEventRecord(s->rng_ev[2], st));
     // one copy of the whole output block, then plain host copies to whatever the caller asked for
-    LPR_HIP(hipMemcpyAsync(s->rng_pin, s->rng_ws + pl.out_off, out_bytes, hipMemcpyDeviceToHost,
+    LPR_HIP(hipMemcpyAsync(s->rng_pin, s->rng_ws + pl.out.base, out_bytes, hipMemcpyDeviceToHost,
                            st));
     LPR_HIP(hipStreamSynchronize(st));
     s->rng_timed = true;
-    const size_t nd = (size_t)pl.nc * sizeof(double), md = (size_t)pl.m * sizeof(double);
-    const size_t ni = (size_t)pl.nc * sizeof(int32_t);
-    auto put = [&](void* dst, size_t off, size_t bytes) {  // off: the plan's, from the buffer start
-        if (dst) std::memcpy(dst, s->rng_pin + (off - pl.out_off), bytes);
-    };
-    put(kind, pl.o_kind, ni);
-    put(var_row, pl.o_row, ni);
-    put(reduced_cost, pl.o_rc, nd);
-    put(cost_lo, pl.o_clo, nd);
-    put(cost_hi, pl.o_chi, nd);
-    put(shadow, pl.o_shadow, md);
-    put(rhs_lo, pl.o_rlo, md);
-    put(rhs_hi, pl.o_rhi, md);
-    put(rhs_now, pl.o_now, md);
+    sens_report_copy(pl.out, s->rng_pin, kind, var_row, reduced_cost, cost_lo, cost_hi, shadow,
+                     rhs_lo, rhs_hi, rhs_now);
     return LPR_OK_OPTIMAL;
 }
 

@@ -11,9 +11,10 @@
 // NaN sticks once met, and the combine keeps both properties.  Everything below is that one rule:
 // a lane folds its two adjacent columns, lanes are combined in lane order (= column order), tiles
 // in tile order by the second launch.  No atomics, nothing depends on arrival order.
-#include "dotnet_minmax.hpp"  // dn_max / dn_min, kRngEps
+#include "dotnet_minmax.hpp"  // dn_max / dn_min
 #include "engine_common.hpp"
 #include "sens_ranging_common.hpp"
+#include "sens_rules.hpp"
 
 #pragma clang fp contract(off)
 
@@ -80,7 +81,8 @@ __global__ __launch_bounds__(kRngLanes) void k_sens_ranging_sweep(
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const double a = e ? x[k].y : x[k].x;
-                const bool pos = a > kRngEps, neg = a < -kRngEps;  // a NaN entry is neither
+                bool pos, neg;
+                range_sign(a, pos, neg);
                 if (pos || neg) {
                     if (rowok[e]) {
                         const double q = ieee_div(-z[e], a);  // -cbar_j / a_rj (:351 :354)
@@ -135,42 +137,26 @@ __global__ __launch_bounds__(kRngLanes) void k_sens_ranging_sweep(
 // The launch boundary is the reduce: thread t folds the row slab of column t's basic row, and the
 // column slab of constraint t + 1, in tile order, and writes the report.  cand = GetBasicRow of
 // every column, made by k_sens_colscan + k_sens_cand on zeroed scratch just before the sweep.
-struct SensRangingOut {
-    double *rc, *clo, *chi, *shadow, *rlo, *rhi, *now;
-    int32_t *kind, *row;
-};
-
 __global__ __launch_bounds__(256) void k_sens_ranging_finish(
     const double* __restrict__ T, int ld, int R, int C, int n, const int32_t* __restrict__ bcount,
     const int32_t* __restrict__ cand, const double2* __restrict__ rowpart, int ntc,
-    const double2* __restrict__ colpart, int ntr, SensRangingOut o) {
+    const double2* __restrict__ colpart, int ntr, SensReportOut o) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int m = R - 1, nc = C - 1;
     if (t < nc) {
         const double cbar = T[t];
         double lo = -INFINITY, hi = INFINITY;
-        int32_t kind, vr = -1;
-        if (bcount[t] > 0) {  // basicVars.Contains(t): DisplayRangeBasic
-            vr = cand[t];
-            if (vr >= 1) {
-                kind = LPR_SENS_RANGE_BASIC;
-                const double2* __restrict__ p = rowpart + (size_t)(vr - 1) * ntc;
+        const bool member = bcount[t] > 0;  // basicVars.Contains(t)
+        int32_t kind, vr;
+        range_classify(member, member ? cand[t] : -1, cbar, kind, vr);
+        if (kind == LPR_SENS_RANGE_BASIC) {
+            const double2* __restrict__ p = rowpart + (size_t)(vr - 1) * ntc;
 #pragma unroll 4
-                for (int q = 0; q < ntc; ++q) {
-                    const double2 v = p[q];
-                    lo = dn_max(lo, v.x);
-                    hi = dn_min(hi, v.y);
-                }
-            } else {
-                kind = LPR_SENS_RANGE_BASIC_ROW_NOT_FOUND;  // :337
-                vr = -1;
+            for (int q = 0; q < ntc; ++q) {
+                const double2 v = p[q];
+                lo = dn_max(lo, v.x);
+                hi = dn_min(hi, v.y);
             }
-        } else if (cbar > kRngEps) {  // DisplayRangeNonBasic :291-296
-            kind = LPR_SENS_RANGE_NONBASIC_RANGE;
-        } else if (fabs(cbar) <= kRngEps) {
-            kind = LPR_SENS_RANGE_NONBASIC_BOUNDARY;
-        } else {  // negative, or NaN
-            kind = LPR_SENS_RANGE_NONBASIC_NOT_OPTIMAL;
         }
         o.rc[t] = cbar;
         o.clo[t] = lo;
@@ -193,22 +179,13 @@ __global__ __launch_bounds__(256) void k_sens_ranging_finish(
     }
 }
 
-// sens_engine.hip: both launches on `st`; ws is the buffer laid out by `pl`
+// both launches on `st` (declared in engine_common.hpp)
 int sens_ranging_launch(hipStream_t st, const double* T, int ld, int R, int C,
                         const int32_t* bcount, const int32_t* cand, char* ws,
                         const SensRangingPlan& pl, hipEvent_t ev_mid) {
     double2* rowpart = reinterpret_cast<double2*>(ws + pl.rowpart_off);
     double2* colpart = reinterpret_cast<double2*>(ws + pl.colpart_off);
-    SensRangingOut o;
-    o.rc = reinterpret_cast<double*>(ws + pl.o_rc);
-    o.clo = reinterpret_cast<double*>(ws + pl.o_clo);
-    o.chi = reinterpret_cast<double*>(ws + pl.o_chi);
-    o.shadow = reinterpret_cast<double*>(ws + pl.o_shadow);
-    o.rlo = reinterpret_cast<double*>(ws + pl.o_rlo);
-    o.rhi = reinterpret_cast<double*>(ws + pl.o_rhi);
-    o.now = reinterpret_cast<double*>(ws + pl.o_now);
-    o.kind = reinterpret_cast<int32_t*>(ws + pl.o_kind);
-    o.row = reinterpret_cast<int32_t*>(ws + pl.o_row);
+    const SensReportOut o = sens_report_bind(ws, pl.out);
     hipLaunchKernelGGL(k_sens_ranging_sweep, dim3(pl.ntc, pl.ntr), dim3(kRngLanes), 0, st, T, ld, R,
                        C, pl.n, bcount, rowpart, pl.ntc, colpart);
     LPR_HIP(hipGetLastError());

@@ -28,10 +28,14 @@ static int check_shape(int R, int C) {
     const int ld = (C + 15) / 16 * 16, ld2 = ld / 2;
     const int m = pl.m, nc = pl.nc, n = pl.n;
     if (m != R - 1 || nc != C - 1 || n != C - R || n + m != nc) return fail("m / n / nc", R, C);
-    if (pl.rowpart_off % 16 || pl.colpart_off % 16 || pl.out_off % 16 || pl.o_rc % 8 ||
-        pl.o_now % 8 || pl.o_kind % 4 || pl.o_row % 4 || pl.total % 16)
+    const SensReportLayout& o = pl.out;
+    if (pl.rowpart_off % 16 || pl.colpart_off % 16 || o.base % 16 || o.o_rc % 8 ||
+        o.o_now % 8 || o.o_kind % 4 || o.o_row % 4 || pl.total % 16)
         return fail("alignment", R, C);
-    if (pl.o_row + (size_t)nc * 4 > pl.total) return fail("the output block passes the total", R, C);
+    if (o.count != 1 || o.mc != nc || o.mr != m || o.end != pl.total)
+        return fail("the output block is not one item of nc and m behind the slabs", R, C);
+    if (o.o_row + (size_t)nc * 4 > pl.total)
+        return fail("the output block passes the total", R, C);
 
     std::unique_ptr<double[]> T(new double[(size_t)R * ld]);
     std::unique_ptr<unsigned char[]> ws(new unsigned char[pl.total]);
@@ -81,15 +85,15 @@ static int check_shape(int R, int C) {
             sink += T[t];
             for (int vr = 1; vr <= m; vr += (m > 8 ? m - 1 : 1))  // first and last basic row
                 for (int q = 0; q < pl.ntc; ++q) sink += rowcell((size_t)(vr - 1) * pl.ntc + q);
-            ws[pl.o_rc + (size_t)t * 8] = ws[pl.o_clo + (size_t)t * 8] = 1;
-            ws[pl.o_chi + (size_t)t * 8 + 7] = ws[pl.o_kind + (size_t)t * 4 + 3] = 1;
-            ws[pl.o_row + (size_t)t * 4 + 3] = 1;
+            ws[o.o_rc + (size_t)t * 8] = ws[o.o_clo + (size_t)t * 8] = 1;
+            ws[o.o_chi + (size_t)t * 8 + 7] = ws[o.o_kind + (size_t)t * 4 + 3] = 1;
+            ws[o.o_row + (size_t)t * 4 + 3] = 1;
         }
         if (t < m) {
             for (int q = 0; q < pl.ntr; ++q) sink += colcell((size_t)q * m + t);
             sink += T[n + t] + T[(size_t)(t + 1) * ld + nc];
-            ws[pl.o_shadow + (size_t)t * 8 + 7] = ws[pl.o_rlo + (size_t)t * 8 + 7] = 1;
-            ws[pl.o_rhi + (size_t)t * 8 + 7] = ws[pl.o_now + (size_t)t * 8 + 7] = 1;
+            ws[o.o_shadow + (size_t)t * 8 + 7] = ws[o.o_rlo + (size_t)t * 8 + 7] = 1;
+            ws[o.o_rhi + (size_t)t * 8 + 7] = ws[o.o_now + (size_t)t * 8 + 7] = 1;
         }
     }
     return sink < 0.0;  // never: keeps the reads alive

@@ -42,10 +42,13 @@ static int check_batch(int base_R, int base_C, const std::vector<Shape>& sc) {
         return ok ? fail("a batch without a report was planned", SR, SC, -1) : 0;
     if (!ok) return fail("a valid batch was refused", SR, SC, -1);
     if (pl.mc != SC - 1 || pl.mr != SR - 1) return fail("row lengths", SR, SC, -1);
-    if (pl.o_rc % 8 || pl.o_clo % 8 || pl.o_chi % 8 || pl.o_shadow % 8 || pl.o_rlo % 8 ||
-        pl.o_rhi % 8 || pl.o_now % 8 || pl.o_kind % 4 || pl.o_row % 4 || pl.total % 16)
+    const SensReportLayout& o = pl.out;
+    if (o.count != count || o.mc != pl.mc || o.mr != pl.mr || o.base != 0 || o.end != pl.total)
+        return fail("the output block is not the whole buffer", SR, SC, -1);
+    if (o.o_rc % 8 || o.o_clo % 8 || o.o_chi % 8 || o.o_shadow % 8 || o.o_rlo % 8 ||
+        o.o_rhi % 8 || o.o_now % 8 || o.o_kind % 4 || o.o_row % 4 || pl.total % 16)
         return fail("alignment", SR, SC, -1);
-    if (pl.o_row + (size_t)count * pl.mc * 4 > pl.total)
+    if (o.o_row + (size_t)count * pl.mc * 4 > pl.total)
         return fail("the output block passes the total", SR, SC, -1);
     const SensBatchRangingLds l = sens_batch_ranging_lds(SR, SC);
     if (l.b_off % 8 || l.lo_off % 8 || l.hi_off % 8 || l.cand_off % 4 || l.need_off % 4 ||
@@ -95,10 +98,10 @@ static int check_batch(int base_R, int base_C, const std::vector<Shape>& sc) {
                 if (j >= n) {
                     const size_t t = (size_t)k * pl.mr + (size_t)(j - n);
                     sink += T[j] + s_b[j - n + 1];
-                    d_cell(pl.o_shadow, t) += 1;
-                    d_cell(pl.o_rlo, t) += 1;
-                    d_cell(pl.o_rhi, t) += 1;
-                    d_cell(pl.o_now, t) += 1;
+                    d_cell(o.o_shadow, t) += 1;
+                    d_cell(o.o_rlo, t) += 1;
+                    d_cell(o.o_rhi, t) += 1;
+                    d_cell(o.o_now, t) += 1;
                 }
             }
         for (int j = 0; j < nc; ++j)
@@ -134,29 +137,29 @@ static int check_batch(int base_R, int base_C, const std::vector<Shape>& sc) {
                     const int vr = s_cand[j];
                     sink += T[j] + bc[j] + s_lo[vr] + s_hi[vr];
                 }
-                d_cell(pl.o_rc, t) += 1;
-                d_cell(pl.o_clo, t) += 1;
-                d_cell(pl.o_chi, t) += 1;
-                i_cell(pl.o_kind, t) += 1;
-                i_cell(pl.o_row, t) += 1;
+                d_cell(o.o_rc, t) += 1;
+                d_cell(o.o_clo, t) += 1;
+                d_cell(o.o_chi, t) += 1;
+                i_cell(o.o_kind, t) += 1;
+                i_cell(o.o_row, t) += 1;
             }
             for (int i = m + tid; i < pl.mr; i += kSbrLanes) {
                 const size_t t = (size_t)k * pl.mr + (size_t)i;
-                d_cell(pl.o_shadow, t) += 1;
-                d_cell(pl.o_rlo, t) += 1;
-                d_cell(pl.o_rhi, t) += 1;
-                d_cell(pl.o_now, t) += 1;
+                d_cell(o.o_shadow, t) += 1;
+                d_cell(o.o_rlo, t) += 1;
+                d_cell(o.o_rhi, t) += 1;
+                d_cell(o.o_now, t) += 1;
             }
         }
     }
     const size_t ncell = (size_t)count * pl.mc, nrow = (size_t)count * pl.mr;
     for (size_t t = 0; t < ncell; ++t)
-        if (d_cell(pl.o_rc, t) != 1 || d_cell(pl.o_clo, t) != 1 || d_cell(pl.o_chi, t) != 1 ||
-            i_cell(pl.o_kind, t) != 1 || i_cell(pl.o_row, t) != 1)
+        if (d_cell(o.o_rc, t) != 1 || d_cell(o.o_clo, t) != 1 || d_cell(o.o_chi, t) != 1 ||
+            i_cell(o.o_kind, t) != 1 || i_cell(o.o_row, t) != 1)
             return fail("a per-column output cell is not written exactly once", SR, SC, (int)t);
     for (size_t t = 0; t < nrow; ++t)
-        if (d_cell(pl.o_shadow, t) != 1 || d_cell(pl.o_rlo, t) != 1 ||
-            d_cell(pl.o_rhi, t) != 1 || d_cell(pl.o_now, t) != 1)
+        if (d_cell(o.o_shadow, t) != 1 || d_cell(o.o_rlo, t) != 1 ||
+            d_cell(o.o_rhi, t) != 1 || d_cell(o.o_now, t) != 1)
             return fail("a per-constraint output cell is not written exactly once", SR, SC, (int)t);
     return sink < 0.0;  // never: keeps the reads alive
 }
