@@ -1061,8 +1061,9 @@ int lpr_knap_batch_dp(lpr_knap_batch* b, const uint8_t* which, int64_t* best);
  * exit.  Forms, picked per LP by the bytes it keeps resident (B^-1 and A with odd leading
  * dimensions, six vectors of m, c, the n + m staged candidates, the basis and the non-basic
  * flags): W one wave per LP (four per workgroup), G one workgroup with everything in LDS, H one
- * workgroup with B^-1 and A in a global slab.  IterationSnapshots are not kept: a caller who
- * wants the text uses lpr_revised_step on one model.  The reference has no batch mode. */
+ * workgroup with B^-1 and A in a global slab.  IterationSnapshots are kept, as numbers, by a
+ * batch made traced with lpr_rev_batch_trace_reserve (below); an untraced batch keeps none.  The
+ * reference has no batch mode. */
 typedef struct lpr_rev_batch lpr_rev_batch;
 
 /* new RevisedPrimalSimplexSolver(objective, constraints, isMin) per LP (:41-80): c = -objective
@@ -1121,6 +1122,40 @@ int lpr_rev_batch_binv_read(lpr_rev_batch* b, int32_t k, double* out);
 int lpr_rev_batch_xb_read(lpr_rev_batch* b, int32_t k, double* out);
 /* n (:45) and m (:46) of LP k; either may be NULL. */
 int lpr_rev_batch_shape(lpr_rev_batch* b, int32_t k, int32_t* n, int32_t* m);
+
+/* Traced batches: the solve also records, per LP, every snapshot
+ * CaptureSnapshot (:294-387) would have appended to IterationSnapshots -- one after each pivot
+ * (:232-247) and the "Optimal" one (:124-146) -- as numbers in device memory; the host only
+ * formats.  One record is 6 + 7 m + n + m n + m m doubles, indices stored as doubles:
+ *   [0] enteringIdx  [1] leavingRow  [2] leavingVarIndex_Pre  [3] enteringRC_pre  [4] zWorking
+ *   [5] zOriginal, then y[m], rcX[n], rcS[m], u_pre[m], ratios_pre[m] (+inf where u_i <= EPS),
+ *   basisForRatios_Pre[m], basicVariables after the pivot [m], xB[m], BInvA[m x n]
+ *   (MultiplyMatrices(BInverse, A) in the C#'s order, :360), BInv[m x m].
+ * The "Optimal" record has -1, -1, -1, rc 0.0, u_pre +0.0, ratios_pre +inf and the current basis
+ * twice.  An LP has iterations + (status == LPR_OK_OPTIMAL) records: LPR_UNBOUNDED,
+ * LPR_ENTERING_ALREADY_BASIC and LPR_PIVOT_TOO_SMALL add none for the failing pass, and an LP
+ * that ends LPR_INFEASIBLE_BASIS after k pivots has k complete ones.  PARITY: every record is the
+ * bytes of the single-model path's numbers for that snapshot, and everything else a traced batch
+ * ends with is the bytes of the untraced batch.
+ *
+ * lpr_rev_batch_trace_reserve makes the handle traced and allocates trace_cap records per LP,
+ * zero-filled; a record index >= trace_cap is counted, not written.  Only before the handle's
+ * first solve: LPR_BAD_ARGUMENT with a message afterwards, when called twice, or for
+ * trace_cap < 1.  A failed allocation is LPR_OUT_OF_MEMORY and the message names the buffer and
+ * its size; the handle stays untraced.  opts and result of lpr_rev_batch_solve are unchanged. */
+int lpr_rev_batch_trace_reserve(lpr_rev_batch* b, int32_t trace_cap);
+/* Per LP (count entries each, any may be NULL): snapshots, the exact number of records (may
+ * exceed trace_cap; min(snapshots, trace_cap) are kept); offset, where LP k's records start in
+ * the trace slab, in doubles; stride, the doubles of one record. */
+int lpr_rev_batch_trace_info(lpr_rev_batch* b, int64_t* snapshots, int64_t* offset,
+                             int64_t* stride);
+/* Records [first, first + n) of LP k into out[n * stride]; a range beyond the kept records is
+ * LPR_BAD_ARGUMENT. */
+int lpr_rev_batch_trace_read(lpr_rev_batch* b, int32_t k, int64_t first, int64_t n, double* out);
+/* The whole trace slab (trace_cap * sum of the strides doubles) in one copy; cap_doubles is what
+ * `out` holds, LPR_BAD_ARGUMENT when it is too small.  Every trace read on an untraced or
+ * orphaned handle is LPR_BAD_ARGUMENT with a message. */
+int lpr_rev_batch_trace_read_all(lpr_rev_batch* b, double* out, int64_t cap_doubles);
 
 #ifdef __cplusplus
 }

@@ -178,22 +178,26 @@ namespace LPR_381_Group_V22.Simplex
     }
 
     /// <summary>RevisedPrimalSimplexSolver.Solve() + ExtractSolution (RevisedPrimalSimplexSolver.cs:82-251, :277-287) for many
-    /// LPs in one device call (DESIGN.md section 17); each LP gives the bits of RevisedPrimalSimplexSolver alone.  No
-    /// IterationSnapshots: solve that one model with RevisedPrimalSimplexSolver for the text.</summary>
+    /// LPs in one device call (DESIGN.md section 17); each LP gives the bits of RevisedPrimalSimplexSolver alone.  With
+    /// traceCap > 0 the batch is traced (section 21): the device records every CaptureSnapshot as numbers and
+    /// IterationSnapshots(k) formats LP k's; an untraced batch keeps none.</summary>
     public class RevisedSimplexBatch : IDisposable
     {
         private IntPtr batch;                           // lpr_rev_batch*
         private readonly int[] nvars, ncons;
+        private readonly bool[] isMinModel;
+        private readonly int traceCap;                  // records kept per LP; 0: untraced
         public int Count { get; }
         public List<int> Status { get; } = new List<int>();
         public List<long> Iterations { get; } = new List<long>();
         public List<double> FinalZ { get; } = new List<double>();
         public List<List<double>> SolutionVector { get; } = new List<List<double>>();
 
-        public RevisedSimplexBatch(List<(List<double> objective, List<IOConstraint> constraints, bool isMinimization)> models, int logCap = 0)
+        public RevisedSimplexBatch(List<(List<double> objective, List<IOConstraint> constraints, bool isMinimization)> models, int logCap = 0, int traceCap = 0)
         {
             Count = models.Count;
             nvars = new int[Count]; ncons = new int[Count]; var isMin = new sbyte[Count];
+            isMinModel = models.Select(mdl => mdl.isMinimization).ToArray();
             var obj = new List<double>(); var A = new List<double>(); var b = new List<double>();
             for (int k = 0; k < Count; k++)
             {
@@ -210,6 +214,8 @@ namespace LPR_381_Group_V22.Simplex
             }
             NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_create(Engine.Handle, Count, nvars, ncons, obj.ToArray(), A.ToArray(),
                 b.ToArray(), isMin, logCap, out batch), "lpr_rev_batch_create");
+            if (traceCap > 0) NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_trace_reserve(batch, traceCap), "lpr_rev_batch_trace_reserve");
+            this.traceCap = traceCap;
         }
 
         /// <summary>Solve() of every unfinished LP; an LP stopped by maxPivots resumes on the next call.</summary>
@@ -261,6 +267,57 @@ namespace LPR_381_Group_V22.Simplex
             var xb = new double[ncons[k]];
             NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_xb_read(batch, k, xb), "lpr_rev_batch_xb_read");
             return xb;
+        }
+
+        /// <summary>Snapshots the reference's list of LP k would hold (may exceed traceCap).</summary>
+        public long SnapshotCount(int k)
+        {
+            var snaps = new long[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_trace_info(batch, snaps, null, null), "lpr_rev_batch_trace_info");
+            return snaps[k];
+        }
+
+        /// <summary>Every LP's records in one copy: record i of LP k starts at offset[k] + i * stride[k].</summary>
+        public double[] TracePacked(out long[] snapshots, out long[] offset, out long[] stride)
+        {
+            snapshots = new long[Count]; offset = new long[Count]; stride = new long[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_trace_info(batch, snapshots, offset, stride), "lpr_rev_batch_trace_info");
+            var slab = new double[traceCap * stride.Sum()];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_trace_read_all(batch, slab, slab.LongLength), "lpr_rev_batch_trace_read_all");
+            return slab;
+        }
+
+        /// <summary>IterationSnapshots of LP k (RevisedPrimalSimplexSolver.cs:35): "Iteration i" per pivot and "Optimal",
+        /// formatted from the device's records; past traceCap the list stops after the kept prefix.</summary>
+        public List<string> IterationSnapshots(int k)
+        {
+            int n = nvars[k], m = ncons[k];
+            long stride = 6 + 7L * m + n + (long)m * n + (long)m * m;   // rev_trace_stride
+            long kept = Math.Min(SnapshotCount(k), traceCap);
+            var recs = new double[Math.Max(1, kept * stride)];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_trace_read(batch, k, 0, kept, recs), "lpr_rev_batch_trace_read");
+            var list = new List<string>();
+            for (long q = 0; q < kept; q++)
+            {
+                long at = q * stride;
+                Func<long, int, double[]> take = (off, len) => { var v = new double[len]; Array.Copy(recs, at + off, v, 0, len); return v; };
+                int entering = (int)recs[at], leavingRow = (int)recs[at + 1], leavingVar = (int)recs[at + 2];
+                long o = 6;
+                double[] y = take(o, m); o += m;
+                double[] rcX = take(o, n); o += n;
+                double[] rcS = take(o, m); o += m;
+                double[] u = take(o, m); o += m;
+                double[] ratios = take(o, m); o += m;
+                List<int> basisPre = take(o, m).Select(v => (int)v).ToList(); o += m;
+                List<int> basisPost = take(o, m).Select(v => (int)v).ToList(); o += m;
+                double[] xB = take(o, m); o += m;
+                var binvA = new double[m, n]; var binv = new double[m, m];
+                Buffer.BlockCopy(recs, (int)((at + o) * sizeof(double)), binvA, 0, m * n * sizeof(double)); o += (long)m * n;
+                Buffer.BlockCopy(recs, (int)((at + o) * sizeof(double)), binv, 0, m * m * sizeof(double));
+                list.Add(RevisedPrimalSimplexSolver.FormatSnapshot(n, m, isMinModel[k], basisPost, entering < 0 ? "Optimal" : $"Iteration {q + 1}", xB, y,
+                    rcX, rcS, entering, recs[at + 3], u, ratios, basisPre, leavingRow, leavingVar, recs[at + 4], recs[at + 5], binvA, binv));
+            }
+            return list;
         }
 
         public void Dispose() { if (batch != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_rev_batch_destroy(batch), "lpr_rev_batch_destroy"); batch = IntPtr.Zero; } }
@@ -411,7 +468,7 @@ namespace LPR_381_Group_V22.Simplex
                     NativeMethods.ThrowIfError(NativeMethods.lpr_revised_binv_read(solver, binv), "lpr_revised_binv_read");
                     bool optimal = status == (int)LprStatus.Optimal;
                     if (optimal) { u = new double[m]; for (int i = 0; i < m; i++) ratios[i] = double.PositiveInfinity; basisPre = BasicVariables.ToArray(); }
-                    IterationSnapshots.Add(FormatSnapshot(optimal ? "Optimal" : $"Iteration {++iteration}", xB, y,
+                    IterationSnapshots.Add(FormatSnapshot(n, m, isMin, BasicVariables, optimal ? "Optimal" : $"Iteration {++iteration}", xB, y,
                         rc.Take(n).ToArray(), rc.Skip(n).ToArray(), info.entering, info.entering_rc_pre, u, ratios,
                         basisPre.ToList(), info.leaving_row, info.leaving_var, info.z_working, info.z_original, binvA, binv));
                     if (optimal) break;
@@ -445,7 +502,8 @@ namespace LPR_381_Group_V22.Simplex
         // byte for byte with an independent restatement.  NumFormat.N3 stays the reference's own (:451-466).
         private static string Label(int idx, int nVars) => idx < nVars ? $"x{idx + 1}" : $"S{idx - nVars + 1}";   // VarLabel :289-292
 
-        private string FormatSnapshot(string title, double[] xB, double[] y, double[] rcX_post, double[] rcS_post,
+        // Static: RevisedSimplexBatch formats the records of a traced batch with it (`post` = basicVariables after the pivot).
+        internal static string FormatSnapshot(int n, int m, bool isMin, List<int> post, string title, double[] xB, double[] y, double[] rcX_post, double[] rcS_post,
             int enteringIdx, double enteringRC_pre, double[] u_pre, double[] ratios_pre, List<int> basisForRatios_Pre,
             int leavingRow, int leavingVarIndex_Pre, double zWorking, double zOriginal, double[,] BInvA, double[,] BInv)
         {
@@ -490,7 +548,6 @@ namespace LPR_381_Group_V22.Simplex
             foreach (double v in rcX_post) sb.Append(NumFormat.N3(v) + "\t");
             foreach (double v in rcS_post) sb.Append(NumFormat.N3(v) + "\t");
             sb.AppendLine(NumFormat.N3(zWorking));
-            var post = BasicVariables;
             for (int i = 0; i < m; i++)
             {
                 sb.Append(Label(post[i], n) + "\t");

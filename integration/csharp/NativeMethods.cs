@@ -311,6 +311,10 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_binv_read(IntPtr revBatch, int k, [Out] double[,] rowmajor);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_xb_read(IntPtr revBatch, int k, double[] xB);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_shape(IntPtr revBatch, int k, out int n, out int m);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_trace_reserve(IntPtr revBatch, int trace_cap);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_trace_info(IntPtr revBatch, long[] snapshots, long[] offset, long[] stride);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_trace_read(IntPtr revBatch, int k, long first, long n, double[] records);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_trace_read_all(IntPtr revBatch, double[] slab, long cap_doubles);
 
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 

@@ -474,6 +474,10 @@ SIGNATURES = {
     "lpr_rev_batch_binv_read": (C.c_int, [_P, C.c_int32, _D]),
     "lpr_rev_batch_xb_read": (C.c_int, [_P, C.c_int32, _D]),
     "lpr_rev_batch_shape": (C.c_int, [_P, C.c_int32, _I32, _I32]),
+    "lpr_rev_batch_trace_reserve": (C.c_int, [_P, C.c_int32]),
+    "lpr_rev_batch_trace_info": (C.c_int, [_P, _I64, _I64, _I64]),
+    "lpr_rev_batch_trace_read": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D]),
+    "lpr_rev_batch_trace_read_all": (C.c_int, [_P, _D, C.c_int64]),
 }
 
 

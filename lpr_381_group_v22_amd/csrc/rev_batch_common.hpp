@@ -1,7 +1,8 @@
 // rev_batch_common.hpp -- definitions shared by the batched revised simplex (rev_batch_engine.hip,
-// host) and its kernels (rev_batch_kernels.hip); DESIGN.md section 17.  The forms, the rule that
-// picks one, the running-list driver and the handle plumbing are those of batch_common.hpp.  Not
-// part of the ABI (include/lpr_engine.h is).
+// host) and its kernels (rev_batch_body.hpp, instantiated by rev_batch_kernels.hip and, traced, by
+// rev_batch_trace_kernels.hip); DESIGN.md sections 17 and 21.  The forms, the rule that picks one,
+// the running-list driver and the handle plumbing are those of batch_common.hpp.  Not part of the
+// ABI (include/lpr_engine.h is).
 #pragma once
 
 #include "batch_common.hpp"
@@ -63,6 +64,36 @@ struct RevBatchDesc {
 inline int64_t rev_batch_slice(int m, int n) {  // doubles
     return (int64_t)m * m + (int64_t)m * n + 3 * (int64_t)m + n;
 }
+
+// One CaptureSnapshot (:294-387) of a traced batch as numbers, in doubles,
+// indices stored as doubles:
+//   [0] enteringIdx  [1] leavingRow  [2] leavingVarIndex_Pre  [3] enteringRC_pre  [4] zWorking
+//   [5] zOriginal, then y[m], rcX[n], rcS[m], u_pre[m], ratios_pre[m], basisForRatios_Pre[m],
+//   basicVariables (post)[m], xB[m], BInvA[m x n], BInv[m x m]
+// LP k's records are at trace + trace_off[k], rev_trace_stride apart, the first trace_cap kept.
+enum RevTraceScalar : int {
+    kRevTraceEnter = 0, kRevTraceRow = 1, kRevTraceLeave = 2, kRevTraceRcPre = 3,
+    kRevTraceZWorking = 4, kRevTraceZOriginal = 5, kRevTraceScalars = 6
+};
+constexpr int64_t rev_trace_y(int, int) { return kRevTraceScalars; }
+constexpr int64_t rev_trace_rcx(int m, int n) { return rev_trace_y(m, n) + m; }
+constexpr int64_t rev_trace_rcs(int m, int n) { return rev_trace_rcx(m, n) + n; }
+constexpr int64_t rev_trace_u(int m, int n) { return rev_trace_rcs(m, n) + m; }
+constexpr int64_t rev_trace_ratios(int m, int n) { return rev_trace_u(m, n) + m; }
+constexpr int64_t rev_trace_basis_pre(int m, int n) { return rev_trace_ratios(m, n) + m; }
+constexpr int64_t rev_trace_basis_post(int m, int n) { return rev_trace_basis_pre(m, n) + m; }
+constexpr int64_t rev_trace_xb(int m, int n) { return rev_trace_basis_post(m, n) + m; }
+constexpr int64_t rev_trace_binva(int m, int n) { return rev_trace_xb(m, n) + m; }
+constexpr int64_t rev_trace_binv(int m, int n) { return rev_trace_binva(m, n) + (int64_t)m * n; }
+constexpr int64_t rev_trace_stride(int m, int n) { return rev_trace_binv(m, n) + (int64_t)m * m; }
+static_assert(rev_trace_stride(3, 4) == 6 + 7 * 3 + 4 + 3 * 4 + 3 * 3, "6 + 7m + n + mn + mm");
+
+// Where a traced batch keeps its records; all zero for an untraced one.
+struct RevBatchTrace {
+    double* slab;        // every LP's records
+    const int64_t* off;  // per LP, doubles
+    int32_t cap;         // records kept per LP; a record index >= cap is counted, not written
+};
 
 // Inputs of lpr_rev_batch_create per LP: offsets into the packed arrays.
 struct RevBatchBuild {

@@ -2,7 +2,8 @@
 // lpr_rev_batch_*).  Every LP of a batch is solved on the device with the
 // rules of RevisedPrimalSimplexSolver; the host only picks each LP's form, relaunches the bounded
 // solve kernels while LPs are still running (BatchRunLists: one small counter read per launch
-// round) and copies results out.
+// round) and copies results out.  A handle made traced (lpr_rev_batch_trace_*, section 21) launches
+// the traced kernels, which also write every CaptureSnapshot of every LP as numbers.
 #include "rev_batch_common.hpp"
 
 #include <algorithm>
@@ -12,6 +13,10 @@ namespace lpr {
 int rev_batch_launch(int form, hipStream_t s, RevBatchDesc* desc, double* slab, int32_t* basis,
                      int32_t* logs, double* xs, const int32_t* idx_in, int n_in,
                      int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles);
+int rev_batch_trace_launch(int form, hipStream_t s, RevBatchDesc* desc, double* slab,
+                           int32_t* basis, int32_t* logs, double* xs, const int32_t* idx_in,
+                           int n_in, int32_t* idx_out, int32_t* n_out, int chunk,
+                           int slot_doubles, RevBatchTrace tr);
 void rev_batch_launch_build(hipStream_t s, const RevBatchDesc* desc, const RevBatchBuild* bd,
                             int count, double* slab, int32_t* basis, double* xs,
                             const double* obj, const double* A, const double* rhs);
@@ -30,6 +35,13 @@ struct lpr_rev_batch {
     double* xs = nullptr;              // packed by n
     BatchRunLists run;                 // the running lists and their counters
     int64_t slab_n = 0, basis_n = 0, log_n = 0, x_total = 0;
+    bool solved = false;               // lpr_rev_batch_solve has run: too late to reserve a trace
+    // traced (lpr_rev_batch_trace_reserve): trace_cap records per LP, section 21
+    int32_t trace_cap = 0;             // 0: untraced
+    double* trace = nullptr;           // device, trace_n doubles
+    int64_t* trace_off = nullptr;      // device, per LP
+    std::vector<int64_t> h_trace_off;  // LP k's records start at trace + h_trace_off[k]
+    int64_t trace_n = 0;
 };
 
 namespace {
@@ -45,6 +57,10 @@ void rb_release_device(lpr_rev_batch* b) {
     hipFree(b->basis);
     hipFree(b->logs);
     hipFree(b->xs);
+    hipFree(b->trace);
+    hipFree(b->trace_off);
+    b->trace = nullptr;
+    b->trace_off = nullptr;
     b->run.release();
     b->desc = nullptr;
     b->slab = nullptr;
@@ -233,9 +249,15 @@ int lpr_rev_batch_solve(lpr_rev_batch* b, const lpr_rev_batch_opts* opts,
     LPR_HIP(hipMemcpyAsync(b->desc, b->h_desc.data(), (size_t)count * sizeof(RevBatchDesc),
                            hipMemcpyHostToDevice, s));
     int launches = 0;
+    b->solved = true;
+    const RevBatchTrace tr{b->trace, b->trace_off, b->trace_cap};
     rc = b->run.rounds(s, [&](int f, const int32_t* in, int n_in, int32_t* out, int32_t* n_out) {
+        const int chunk = o.chunk > 0 ? o.chunk : kRevBatchChunk[f];
+        if (b->trace_cap > 0)
+            return rev_batch_trace_launch(f, s, b->desc, b->slab, b->basis, b->logs, b->xs, in,
+                                          n_in, out, n_out, chunk, (int)slot[f], tr);
         return rev_batch_launch(f, s, b->desc, b->slab, b->basis, b->logs, b->xs, in, n_in, out,
-                                n_out, o.chunk > 0 ? o.chunk : kRevBatchChunk[f], (int)slot[f]);
+                                n_out, chunk, (int)slot[f]);
     }, &launches);
     if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(b->h_desc.data(), b->desc, (size_t)count * sizeof(RevBatchDesc),
@@ -355,6 +377,134 @@ int lpr_rev_batch_shape(lpr_rev_batch* b, int32_t k, int32_t* n, int32_t* m) {
     const RevBatchDesc& d = b->h_desc[(size_t)k];
     if (n) *n = d.n;
     if (m) *m = d.m;
+    return LPR_OK_OPTIMAL;
+}
+
+// ---------------------------------------------------------------- traced batches, section 21
+
+// Records LP k has: one per iteration (:232-247) and the "Optimal" one (:124-146); exact, may
+// exceed trace_cap.
+static int64_t rb_snapshots(const RevBatchDesc& d) {
+    return d.iter + (d.status == LPR_OK_OPTIMAL ? 1 : 0);
+}
+
+static bool rb_traced(const char* where, const lpr_rev_batch* b) {
+    if (b->trace_cap > 0) return true;
+    set_error("%s: the batch is not traced (call lpr_rev_batch_trace_reserve before the first "
+              "solve)", where);
+    return false;
+}
+
+// Makes the handle traced: trace_cap records of rev_trace_stride(m, n) doubles per LP
+int lpr_rev_batch_trace_reserve(lpr_rev_batch* b, int32_t trace_cap) {
+    static const char* W = "lpr_rev_batch_trace_reserve";
+    LPR_LIVE_HANDLE(b, "revised batch");
+    if (trace_cap < 1) {
+        set_error("%s: trace_cap %d < 1", W, trace_cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (b->trace_cap > 0) {
+        set_error("%s: the batch is already traced (trace_cap %d)", W, b->trace_cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (b->solved) {
+        set_error("%s: only before the handle's first lpr_rev_batch_solve", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    std::vector<int64_t> off;
+    try {
+        off.resize((size_t)b->count);
+    } catch (...) {
+        return rb_oom("trace offsets", b->count);
+    }
+    int64_t total = 0;  // 64-bit: a stride is below 2^22 doubles, trace_cap and count below 2^31
+    for (int32_t k = 0; k < b->count; ++k) {
+        const RevBatchDesc& d = b->h_desc[(size_t)k];
+        off[(size_t)k] = total;
+        total += (int64_t)trace_cap * rev_trace_stride(d.m, d.n);
+    }
+    int rc = LPR_OK_OPTIMAL;
+    double* slab = nullptr;
+    int64_t* d_off = nullptr;
+    dev_alloc(&slab, total, "trace: trace_cap x (6 + 7 m + n + m x n + m x m) doubles per LP", &rc,
+              rb_oom);
+    dev_alloc(&d_off, b->count, "trace offsets", &rc, rb_oom);
+    hipStream_t s = b->eng->stream;
+    auto upload = [&]() -> int {
+        LPR_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)b->count * sizeof(int64_t),
+                               hipMemcpyHostToDevice, s));
+        // what no record reaches reads as +0.0, the same in every form
+        LPR_HIP(hipMemsetAsync(slab, 0, (size_t)total * sizeof(double), s));
+        LPR_HIP(hipStreamSynchronize(s));
+        return LPR_OK_OPTIMAL;
+    };
+    if (rc == LPR_OK_OPTIMAL) rc = upload();
+    if (rc != LPR_OK_OPTIMAL) {
+        hipFree(slab);
+        hipFree(d_off);
+        return rc;
+    }
+    b->trace = slab;
+    b->trace_off = d_off;
+    b->h_trace_off.swap(off);
+    b->trace_n = total;
+    b->trace_cap = trace_cap;
+    return LPR_OK_OPTIMAL;
+}
+
+// Per LP: records counted, and where the kept ones are in the trace slab; any may be NULL
+int lpr_rev_batch_trace_info(lpr_rev_batch* b, int64_t* snapshots, int64_t* offset,
+                             int64_t* stride) {
+    LPR_LIVE_HANDLE(b, "revised batch");
+    if (!rb_traced("lpr_rev_batch_trace_info", b)) return LPR_BAD_ARGUMENT;
+    for (int32_t k = 0; k < b->count; ++k) {
+        const RevBatchDesc& d = b->h_desc[(size_t)k];
+        if (snapshots) snapshots[k] = rb_snapshots(d);
+        if (offset) offset[k] = b->h_trace_off[(size_t)k];
+        if (stride) stride[k] = rev_trace_stride(d.m, d.n);
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// Records [first, first + n) of LP k
+int lpr_rev_batch_trace_read(lpr_rev_batch* b, int32_t k, int64_t first, int64_t n, double* out) {
+    static const char* W = "lpr_rev_batch_trace_read";
+    LPR_LIVE_HANDLE(b, "revised batch");
+    if (!rb_traced(W, b) || !rb_item_ok(W, b, k)) return LPR_BAD_ARGUMENT;
+    const RevBatchDesc& d = b->h_desc[(size_t)k];
+    const int64_t kept = std::min<int64_t>(rb_snapshots(d), b->trace_cap);
+    if (first < 0 || n < 0 || first > kept || n > kept - first) {
+        set_error("%s: records [%lld, %lld + %lld) of LP %d, which keeps %lld (trace_cap %d)", W,
+                  (long long)first, (long long)first, (long long)n, k, (long long)kept,
+                  b->trace_cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (n == 0) return LPR_OK_OPTIMAL;
+    if (!out) {
+        set_error("%s: null output", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    const int64_t st = rev_trace_stride(d.m, d.n);
+    LPR_HIP(hipMemcpyAsync(out, b->trace + b->h_trace_off[(size_t)k] + first * st,
+                           (size_t)(n * st) * sizeof(double), hipMemcpyDeviceToHost,
+                           b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// The whole trace slab in one copy; cap_doubles is what `out` holds
+int lpr_rev_batch_trace_read_all(lpr_rev_batch* b, double* out, int64_t cap_doubles) {
+    static const char* W = "lpr_rev_batch_trace_read_all";
+    LPR_LIVE_HANDLE(b, "revised batch");
+    if (!rb_traced(W, b)) return LPR_BAD_ARGUMENT;
+    if (!out || cap_doubles < b->trace_n) {
+        set_error("%s: null output, or cap_doubles %lld below the slab's %lld doubles", W,
+                  (long long)cap_doubles, (long long)b->trace_n);
+        return LPR_BAD_ARGUMENT;
+    }
+    LPR_HIP(hipMemcpyAsync(out, b->trace, (size_t)b->trace_n * sizeof(double),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
     return LPR_OK_OPTIMAL;
 }
 

@@ -4,8 +4,10 @@ section 17).
 Every LP of a batch is built and solved on the MI355X with the rules of
 Simplex/RevisedPrimalSimplexSolver.cs, the same bits ``RevisedPrimalSimplexSolver`` gives for that
 LP alone.  The reference has no batch mode: the members below are per-LP lists / accessors named
-after the single-model mirror (revised_primal_simplex_solver.py), and the batch keeps no iteration
-snapshots (a caller who wants the text solves that one model with the single mirror).
+after the single-model mirror (revised_primal_simplex_solver.py).  A batch made with
+``trace_cap > 0`` is traced: its solve also records every snapshot
+``CaptureSnapshot`` would have appended, as numbers on the device, and ``IterationSnapshots(k)``
+formats them with the single mirror's formatter; an untraced batch keeps none.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import numpy as np
 
 from . import _native as N
 from .engine import Engine, default_engine
-from .revised_primal_simplex_solver import MESSAGES, SolverException
+from .revised_primal_simplex_solver import MESSAGES, SolverException, format_snapshot
 
 
 class PackedRevisedModels(NamedTuple):
@@ -91,6 +93,43 @@ def pick_form(m: int, n: int, variant: int = 0) -> int:
     return FORM_W if fit_w else (FORM_G if fit_g else FORM_H)
 
 
+# One record of a traced batch (rev_trace_* of rev_batch_common.hpp), in doubles: six scalars,
+# then the fields below in this order.
+TRACE_SCALARS = ("entering", "leaving_row", "leaving_var", "rc_pre", "z_working", "z_original")
+TRACE_FIELDS = ("y", "rcX", "rcS", "u_pre", "ratios_pre", "basis_pre", "basis_post", "xB",
+                "BInvA", "BInv")
+
+
+def trace_offsets(m: int, n: int) -> dict:
+    """Field name -> (offset, length) in doubles inside one record."""
+    sizes = dict(y=m, rcX=n, rcS=m, u_pre=m, ratios_pre=m, basis_pre=m, basis_post=m, xB=m,
+                 BInvA=m * n, BInv=m * m)
+    out, at = {}, len(TRACE_SCALARS)
+    for name in TRACE_FIELDS:
+        out[name] = (at, sizes[name])
+        at += sizes[name]
+    return out
+
+
+def trace_stride(m: int, n: int) -> int:
+    """rev_trace_stride: doubles of one record, 6 + 7 m + n + m n + m m."""
+    at, ln = trace_offsets(m, n)["BInv"]
+    return at + ln
+
+
+def trace_record(r: np.ndarray, m: int, n: int) -> dict:
+    """One record as the dict ``oracle.revised_trace`` gives for a snapshot."""
+    d = dict(entering=int(r[0]), leaving_row=int(r[1]), leaving_var=int(r[2]), rc_pre=r[3],
+             z_working=r[4], z_original=r[5])
+    for name, (at, ln) in trace_offsets(m, n).items():
+        d[name] = r[at:at + ln].copy()
+    d["BInvA"] = d["BInvA"].reshape(m, n)
+    d["BInv"] = d["BInv"].reshape(m, m)
+    d["basis_pre"] = d["basis_pre"].astype(np.int32)
+    d["basis_post"] = d["basis_post"].astype(np.int32)
+    return d
+
+
 def _ptr(a: np.ndarray, ctype):
     return a.ctypes.data_as(C.POINTER(ctype)) if a.size else None
 
@@ -102,7 +141,9 @@ class RevisedSimplexBatch:
     the vector are set only on the optimal exit (0.0 and [] otherwise).  ``Iterations[k]`` is the
     C#'s ``iteration``.  ``Raise(k)`` raises what the single mirror's Solve() raises."""
 
-    def __init__(self, models, engine: Optional[Engine] = None, log_cap: int = 0):
+    def __init__(self, models, engine: Optional[Engine] = None, log_cap: int = 0,
+                 trace_cap: int = 0):
+        models = list(models)
         p = pack_revised_models(models)
         self._engine = engine or default_engine()
         self._h = None
@@ -125,6 +166,16 @@ class RevisedSimplexBatch:
         self.SolutionVector: List[List[float]] = [[] for _ in range(self.Count)]
         self.Iterations: List[int] = [0] * self.Count
         self.LastResult: Optional[N.RevBatchResult] = None
+        self._is_min = [bool(v) for v in p.is_min]
+        self.TraceCap = 0  # records kept per LP; 0: untraced
+        if trace_cap:
+            self.trace_reserve(trace_cap)
+
+    def trace_reserve(self, trace_cap: int) -> None:
+        """Make the batch traced (lpr_rev_batch_trace_reserve): only before the first Solve."""
+        N.check(N.lib.lpr_rev_batch_trace_reserve(self._h, int(trace_cap)),
+                "lpr_rev_batch_trace_reserve")
+        self.TraceCap = int(trace_cap)
 
     def destroy(self) -> None:
         if self._h:
@@ -219,4 +270,58 @@ class RevisedSimplexBatch:
         out = np.empty(self._shapes[k][1], dtype=np.float64)
         N.check(N.lib.lpr_rev_batch_xb_read(self._h, int(k), _ptr(out, C.c_double)),
                 "lpr_rev_batch_xb_read")
+        return out
+
+    # -- the trace --------------------------------------------------
+    def trace_info(self):
+        """(snapshots, offset, stride), int64[count] each: the exact number of records of every
+        LP (min(snapshots, TraceCap) are kept), where its records start in the trace slab and the
+        doubles of one record."""
+        snaps = np.zeros(self.Count, dtype=np.int64)
+        off = np.zeros(self.Count, dtype=np.int64)
+        stride = np.zeros(self.Count, dtype=np.int64)
+        N.check(N.lib.lpr_rev_batch_trace_info(self._h, _ptr(snaps, C.c_int64),
+                                               _ptr(off, C.c_int64), _ptr(stride, C.c_int64)),
+                "lpr_rev_batch_trace_info")
+        return snaps, off, stride
+
+    def trace_packed(self):
+        """(slab, snapshots, offset, stride): every LP's records in one copy."""
+        snaps, off, stride = self.trace_info()
+        slab = np.zeros(int(self.TraceCap * stride.sum()), dtype=np.float64)
+        N.check(N.lib.lpr_rev_batch_trace_read_all(self._h, _ptr(slab, C.c_double), slab.size),
+                "lpr_rev_batch_trace_read_all")
+        return slab, snaps, off, stride
+
+    def trace_read(self, k: int, first: int, n: int) -> np.ndarray:
+        """Records [first, first + n) of LP k, one per row."""
+        nv, m = self._shapes[k]
+        out = np.zeros((max(int(n), 0), trace_stride(m, nv)), dtype=np.float64)
+        N.check(N.lib.lpr_rev_batch_trace_read(self._h, int(k), int(first), int(n),
+                                               _ptr(out, C.c_double)),
+                "lpr_rev_batch_trace_read")
+        return out
+
+    def SnapshotCount(self, k: int) -> int:
+        """Snapshots the C# list of LP k would hold (may exceed TraceCap)."""
+        return int(self.trace_info()[0][k])
+
+    def Snapshot(self, k: int, i: int) -> dict:
+        """Snapshot i of LP k as numbers, with the keys of one ``CaptureSnapshot`` call: entering,
+        leaving_row, leaving_var, rc_pre, z_working, z_original, y, rcX, rcS, u_pre, ratios_pre,
+        basis_pre, basis_post, xB, BInvA, BInv."""
+        nv, m = self._shapes[k]
+        return trace_record(self.trace_read(k, i, 1)[0], m, nv)
+
+    def IterationSnapshots(self, k: int) -> List[str]:  # :35, filled by CaptureSnapshot :294-387
+        """The C#'s list of text blocks for LP k: "Iteration i" per pivot and "Optimal"; past
+        TraceCap it stops after the kept prefix."""
+        nv, m = self._shapes[k]
+        count = self.SnapshotCount(k)
+        recs = self.trace_read(k, 0, min(count, self.TraceCap))
+        out = []
+        for i, r in enumerate(recs):
+            snap = trace_record(r, m, nv)
+            title = "Optimal" if snap["entering"] < 0 else f"Iteration {i + 1}"
+            out.append(format_snapshot(title, nv, m, self._is_min[k], snap))
         return out

@@ -32,6 +32,54 @@ def VarLabel(idx: int, n: int) -> str:  # :289-292
     return f"x{idx + 1}" if idx < n else f"S{idx - n + 1}"
 
 
+def format_snapshot(title: str, n: int, m: int, is_min: bool, snap) -> str:
+    """The text block of CaptureSnapshot (:294-387) from the numbers of one snapshot: ``snap`` has
+    entering, leaving_row, leaving_var, rc_pre, z_working, z_original, y, rcX, rcS, u_pre,
+    ratios_pre, basis_pre, basis_post, xB, BInvA (m x n, the C#'s own order) and BInv (m x m)."""
+    from .table_iteration_formater import N3, NEWLINE as nl
+    y, rcX, rcS, u_pre = snap["y"], snap["rcX"], snap["rcS"], snap["u_pre"]
+    ratios_pre, basis_pre, basis, xB = (snap["ratios_pre"], snap["basis_pre"],
+                                        snap["basis_post"], snap["xB"])
+    entering, leaving_row, leaving_var = (int(snap["entering"]), int(snap["leaving_row"]),
+                                          int(snap["leaving_var"]))
+    z_working, z_original = snap["z_working"], snap["z_original"]
+    kind = "MIN (solving by MAX of -c)" if is_min else "MAX"
+    sb = [title + nl, "Current Tableau (Revised Simplex)" + nl, f"Problem type: {kind}" + nl, nl]
+    sb += ["Dual prices (y = c_B^T B^{-1}):" + nl, "\t".join(N3(v) for v in y) + nl, nl]
+    sb += ["Reduced costs:" + nl, "  x: ", "\t".join(N3(v) for v in rcX) + nl,
+           "  s: ", "\t".join(N3(v) for v in rcS) + nl, nl]
+    if entering >= 0:
+        elabel = VarLabel(entering, n)
+        sb.append(f"Entering variable (chosen pre-pivot): {elabel}  (reduced cost pre = "
+                  f"{N3(snap['rc_pre'])})" + nl)
+        sb.append("Direction u = B^{-1} a_enter (pre-pivot):" + nl)
+        sb.append("\t".join(N3(v) for v in u_pre) + nl)
+        sb.append(nl)
+        sb.append("Ratio test (xB_i / u_i; \u221e if u_i \u2264 0)  [labels = pre-pivot basis]:" + nl)
+        for i in range(m):
+            rstr = "\u221e" if ratios_pre[i] == np.inf else N3(ratios_pre[i])
+            sb.append(f"{VarLabel(int(basis_pre[i]), n)}: {rstr}" + nl)
+        if leaving_row >= 0 and leaving_var >= 0:
+            sb.append(f"Pivot (pre\u2192post): {VarLabel(leaving_var, n)}  \u2192  {elabel}"
+                      f"    (pivot = {N3(u_pre[leaving_row])})" + nl)
+            sb.append(nl)
+    sb.append(f"Working objective Z_working (maxified): {N3(z_working)}" + nl)
+    sb.append(f"Original objective Z_original ({'MIN' if is_min else 'MAX'}): "
+              f"{N3(z_original)}" + nl)
+    sb.append(nl)
+    BInvA, BInv = snap["BInvA"], snap["BInv"]
+    sb.append("Table\t" + "".join(f"x{j + 1}\t" for j in range(n))
+              + "".join(f"S{j + 1}\t" for j in range(m)) + "RHS" + nl)
+    sb.append("Z~\t" + "".join(N3(v) + "\t" for v in rcX) + "".join(N3(v) + "\t" for v in rcS)
+              + N3(z_working) + nl)
+    for i in range(m):
+        sb.append(VarLabel(int(basis[i]), n) + "\t"
+                  + "".join(N3(v) + "\t" for v in BInvA[i])
+                  + "".join(N3(v) + "\t" for v in BInv[i]) + N3(xB[i]) + nl)
+    sb.append("Basic Variables: " + ", ".join(VarLabel(int(v), n) for v in basis) + nl)
+    return "".join(sb)
+
+
 class RevisedPrimalSimplexSolver:
     #: one snapshot prints the m x (n + m + 1) table B^-1 A | B^-1 | RHS (:359-384); above this
     #: many entries ``snapshots="auto"`` keeps none (the C# would produce megabytes of text per pivot)
@@ -105,52 +153,21 @@ class RevisedPrimalSimplexSolver:
             return
 
     def _capture(self, title: str, info) -> None:  # CaptureSnapshot :294-387
-        from .table_iteration_formater import N3, NEWLINE as nl
         n, m = self.numVariables, self.numConstraints
         y, rc, u_pre, ratios_pre, basis_pre, xB = self._st.snapshot()
         basis = self._st.basis()
-        entering = info.entering
-        if entering < 0:  # the "Optimal" call passes fresh zeros / infinities (:133-134)
+        if info.entering < 0:  # the "Optimal" call passes fresh zeros / infinities (:133-134)
             u_pre = np.zeros(m)
             ratios_pre = np.full(m, np.inf)
             basis_pre = basis
-        rcX, rcS = rc[:n], rc[n:]
-        kind = "MIN (solving by MAX of -c)" if self.isMinimization else "MAX"
-        sb = [title + nl, "Current Tableau (Revised Simplex)" + nl, f"Problem type: {kind}" + nl, nl]
-        sb += ["Dual prices (y = c_B^T B^{-1}):" + nl, "\t".join(N3(v) for v in y) + nl, nl]
-        sb += ["Reduced costs:" + nl, "  x: ", "\t".join(N3(v) for v in rcX) + nl,
-               "  s: ", "\t".join(N3(v) for v in rcS) + nl, nl]
-        if entering >= 0:
-            elabel = VarLabel(entering, n)
-            sb.append(f"Entering variable (chosen pre-pivot): {elabel}  (reduced cost pre = "
-                      f"{N3(info.entering_rc_pre)})" + nl)
-            sb.append("Direction u = B^{-1} a_enter (pre-pivot):" + nl)
-            sb.append("\t".join(N3(v) for v in u_pre) + nl)
-            sb.append(nl)
-            sb.append("Ratio test (xB_i / u_i; \u221e if u_i \u2264 0)  [labels = pre-pivot basis]:" + nl)
-            for i in range(m):
-                rstr = "\u221e" if ratios_pre[i] == np.inf else N3(ratios_pre[i])
-                sb.append(f"{VarLabel(int(basis_pre[i]), n)}: {rstr}" + nl)
-            if info.leaving_row >= 0 and info.leaving_var >= 0:
-                sb.append(f"Pivot (pre\u2192post): {VarLabel(info.leaving_var, n)}  \u2192  {elabel}"
-                          f"    (pivot = {N3(u_pre[info.leaving_row])})" + nl)
-                sb.append(nl)
-        sb.append(f"Working objective Z_working (maxified): {N3(info.z_working)}" + nl)
-        sb.append(f"Original objective Z_original ({'MIN' if self.isMinimization else 'MAX'}): "
-                  f"{N3(info.z_original)}" + nl)
-        sb.append(nl)
-        BInvA = self._st.binv_a_exact()   # MultiplyMatrices(BInverse, A) :360, the C#'s own order
-        BInv = self._st.binv()
-        sb.append("Table\t" + "".join(f"x{j + 1}\t" for j in range(n))
-                  + "".join(f"S{j + 1}\t" for j in range(m)) + "RHS" + nl)
-        sb.append("Z~\t" + "".join(N3(v) + "\t" for v in rcX) + "".join(N3(v) + "\t" for v in rcS)
-                  + N3(info.z_working) + nl)
-        for i in range(m):
-            sb.append(VarLabel(int(basis[i]), n) + "\t"
-                      + "".join(N3(v) + "\t" for v in BInvA[i])
-                      + "".join(N3(v) + "\t" for v in BInv[i]) + N3(xB[i]) + nl)
-        sb.append("Basic Variables: " + ", ".join(VarLabel(int(v), n) for v in basis) + nl)
-        self.IterationSnapshots.append("".join(sb))
+        snap = dict(entering=info.entering, leaving_row=info.leaving_row,
+                    leaving_var=info.leaving_var, rc_pre=info.entering_rc_pre,
+                    z_working=info.z_working, z_original=info.z_original, y=y, rcX=rc[:n],
+                    rcS=rc[n:], u_pre=u_pre, ratios_pre=ratios_pre, basis_pre=basis_pre,
+                    basis_post=basis, xB=xB,
+                    BInvA=self._st.binv_a_exact(),  # MultiplyMatrices(BInverse, A) :360
+                    BInv=self._st.binv())
+        self.IterationSnapshots.append(format_snapshot(title, n, m, self.isMinimization, snap))
 
     @property
     def BasicVariables(self) -> List[int]:  # :39

@@ -18,6 +18,15 @@ are seeded (numpy RandomState(seed + workload)).
 
 Run it under a time limit:
     timeout -k 10 900 python tools/revised_batch_bench.py --out profiles/revised_batch_bench.json
+
+--trace measures the traced batch on the same workloads instead, three
+passes each with all values kept: (a) create + reserve + solve + trace_read_all and the solve
+alone, (b) the same workload untraced in the same process, (c) what the trace replaces, the
+per-model lpr_revised_step loop with the reads of CaptureSnapshot (a time-bounded prefix, scaled),
+and, with --parent-lib, (d) the untraced solve of this library against the parent commit's,
+alternating fresh processes.  trace_cap per workload is TRACE_CAP and is recorded; 256 LPs per
+workload are checked record by record against the oracle's trace.
+    timeout -k 10 900 python tools/revised_batch_bench.py --trace
 """
 from __future__ import annotations
 
@@ -175,8 +184,234 @@ def bit_check(N, orc, w, offs, out) -> int:
     return bad
 
 
+# ------------------------------------------------------------------ --trace
+# Records kept per LP: W keeps every snapshot its LPs make; G and H keep a prefix (a record of H
+# is about 1.6 MB).
+TRACE_CAP = {"W": 0, "G": 16, "H": 2}  # 0: the most snapshots any LP of the workload makes
+
+
+def run_traced(N, eng, w, trace_cap: int):
+    """create + reserve + solve + trace_read_all: (seconds end to end, seconds of the solve,
+    outputs)."""
+    count = len(w["n"])
+    m, n = w["m"].astype(np.int64), w["n"].astype(np.int64)
+    stride = 6 + 7 * m + n + m * n + m * m
+    slab = np.empty(int(trace_cap * stride.sum()))
+    snaps, off, st = (np.zeros(count, dtype=np.int64) for _ in range(3))
+    h = C.c_void_p()
+    opts = N.RevBatchOpts(max_pivots=CAP, chunk=0, variant=0)
+    res = N.RevBatchResult()
+    eng.sync()
+    t0 = time.perf_counter()
+    N.check(N.lib.lpr_rev_batch_create(
+        eng._h, count, ptr(w["n"], C.c_int32), ptr(w["m"], C.c_int32), ptr(w["obj"], C.c_double),
+        ptr(w["A"], C.c_double), ptr(w["b"], C.c_double), ptr(w["is_min"], C.c_int8), 0,
+        C.byref(h)), "lpr_rev_batch_create")
+    N.check(N.lib.lpr_rev_batch_trace_reserve(h, trace_cap), "lpr_rev_batch_trace_reserve")
+    t1 = time.perf_counter()
+    N.check(N.lib.lpr_rev_batch_solve(h, C.byref(opts), C.byref(res)), "lpr_rev_batch_solve")
+    t2 = time.perf_counter()
+    N.check(N.lib.lpr_rev_batch_trace_info(h, ptr(snaps, C.c_int64), ptr(off, C.c_int64),
+                                           ptr(st, C.c_int64)), "lpr_rev_batch_trace_info")
+    N.check(N.lib.lpr_rev_batch_trace_read_all(h, ptr(slab, C.c_double), slab.size),
+            "lpr_rev_batch_trace_read_all")
+    eng.sync()
+    t3 = time.perf_counter()
+    return t3 - t0, t2 - t1, dict(h=h, slab=slab, snaps=snaps, off=off, stride=st, res=res)
+
+
+def step_loop(pkg, eng, w, offs, trace_cap: int, budget_s: float, limit: int):
+    """What the traced batch replaces: one RevisedState per model, lpr_revised_step per iteration
+    with the snapshot, B^-1 A, B^-1 and basis reads of CaptureSnapshot for the first trace_cap
+    snapshots, then lpr_revised_solve for the rest."""
+    done = snaps = 0
+    t0 = time.perf_counter()
+    while done < limit and time.perf_counter() - t0 < budget_s:
+        c, A, b = lp_of(w, offs, done)
+        s = pkg.RevisedState.create(eng, c, A, b, False)
+        kept = 0
+        while kept < trace_cap:
+            info = s.step()
+            if info.status not in (0, 5):
+                break
+            s.snapshot()
+            s.binv_a_exact()
+            s.binv()
+            s.basis()
+            kept += 1
+            if info.status == 0:
+                break
+        else:
+            s.solve(max_pivots=CAP)
+        s.destroy()
+        snaps += kept
+        done += 1
+    dt = time.perf_counter() - t0
+    return dict(lps=done, seconds=dt, lps_per_s=done / dt, snapshots_per_s=snaps / dt)
+
+
+def trace_check(orc, w, offs, out, trace_cap: int) -> int:
+    """LPs among the first CHECK whose count or any kept record differs from the oracle's trace."""
+    from lpr_381_group_v22_amd.revised_batch import trace_record
+    bad = 0
+    for k in range(min(CHECK, len(w["n"]))):
+        c, A, b = lp_of(w, offs, k)
+        n, m = len(c), len(b)
+        tr = orc.revised_trace(c, A, b, False, max_iter=CAP, cap=trace_cap)
+        ok = int(out["snaps"][k]) == tr["count"]
+        for i, want in enumerate(tr["snapshots"]):
+            at = int(out["off"][k] + i * out["stride"][k])
+            got = trace_record(out["slab"][at:at + int(out["stride"][k])], m, n)
+            ok = ok and all(np.asarray(got[key]).tobytes() == np.asarray(want[key]).tobytes()
+                            for key in want)
+        bad += 0 if ok else 1
+    return bad
+
+
+def solve_child(lib_path: str, names, seed: int, repeat: int, trace_caps=None) -> int:
+    """--solve-child: the solve alone on the library at lib_path, `repeat` passes per workload,
+    one JSON line.  Untraced (the library may predate the trace calls) unless --child-trace-caps
+    gives a trace_cap per workload: that is how two builds of the traced kernels are compared."""
+    from lpr_381_group_v22_amd import _native as N
+    lib = C.CDLL(lib_path)
+    calls = ["lpr_engine_open", "lpr_engine_close", "lpr_engine_sync", "lpr_rev_batch_create",
+             "lpr_rev_batch_solve", "lpr_rev_batch_destroy"]
+    if trace_caps:
+        calls.append("lpr_rev_batch_trace_reserve")
+    for name in calls:
+        getattr(lib, name).restype, getattr(lib, name).argtypes = N.SIGNATURES[name]
+    eng = C.c_void_p()
+    if lib.lpr_engine_open(0, C.byref(eng)) != 0:
+        return 1
+    out = {}
+    for i, name in enumerate(names):
+        w = gen_workload(name, seed + i)
+        count = len(w["n"])
+        times = []
+        for _ in range(repeat):
+            h = C.c_void_p()
+            opts = N.RevBatchOpts(max_pivots=CAP, chunk=0, variant=0)
+            res = N.RevBatchResult()
+            if lib.lpr_rev_batch_create(
+                    eng, count, ptr(w["n"], C.c_int32), ptr(w["m"], C.c_int32),
+                    ptr(w["obj"], C.c_double), ptr(w["A"], C.c_double), ptr(w["b"], C.c_double),
+                    ptr(w["is_min"], C.c_int8), 0, C.byref(h)) != 0:
+                return 1
+            if trace_caps and lib.lpr_rev_batch_trace_reserve(h, int(trace_caps[i])) != 0:
+                return 1
+            lib.lpr_engine_sync(eng)
+            t0 = time.perf_counter()
+            if lib.lpr_rev_batch_solve(h, C.byref(opts), C.byref(res)) != 0:
+                return 1
+            times.append(time.perf_counter() - t0)
+            lib.lpr_rev_batch_destroy(h)
+        out[name] = times
+    lib.lpr_engine_close(eng)
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+def against_parent(args, names):
+    """(d): the untraced solve of this library and of --parent-lib, alternating fresh child
+    processes (this, parent, this, parent), all values kept."""
+    import subprocess
+    from lpr_381_group_v22_amd import _native as N
+    runs = {"this": [], "parent": []}
+    for _ in range(2):
+        for tag, path in (("this", N.LIB_PATH), ("parent", args.parent_lib)):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--solve-child", path,
+                                "--workloads", ",".join(names), "--seed", str(args.seed),
+                                "--repeat", str(args.repeat)],
+                               capture_output=True, text=True, timeout=600)
+            if p.returncode != 0:
+                raise RuntimeError(f"solve child on {path} failed: {p.stderr[-400:]}")
+            runs[tag].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    out = {}
+    for name in names:
+        this = [t for r in runs["this"] for t in r[name]]
+        parent = [t for r in runs["parent"] for t in r[name]]
+        margin = max(max(r[name]) - min(r[name]) for r in runs["parent"])
+        out[name] = dict(this_solve_seconds_all=this, parent_solve_seconds_all=parent,
+                         this_best=min(this), parent_best=min(parent),
+                         parent_margin_max_minus_min=margin,
+                         within_margin=min(this) <= min(parent) + margin)
+    return out
+
+
+def main_trace(args) -> int:
+    import lpr_381_group_v22_amd as pkg
+    from lpr_381_group_v22_amd import _native as N
+    from oracle_lib import Oracle
+    orc = Oracle()
+    names = args.workloads.split(",")
+    failures = 0
+    lines = []
+    with pkg.Engine(0) as eng:
+        for i, name in enumerate(names):
+            w = gen_workload(name, args.seed + i)
+            offs = offsets(w)
+            count = len(w["n"])
+            plain = [run_batch(N, eng, w) for _ in range(3)]                      # (b)
+            it, st = plain[-1][3]["it"], plain[-1][3]["st"]
+            most = int((it + (st == 0)).max())
+            trace_cap = TRACE_CAP[name] or most
+            for r in plain:
+                N.lib.lpr_rev_batch_destroy(r[3]["h"])
+            traced = []
+            for _ in range(3):                                                    # (a)
+                traced.append(run_traced(N, eng, w, trace_cap))
+                if len(traced) > 1:
+                    N.lib.lpr_rev_batch_destroy(traced[-2][2]["h"])
+                    traced[-2][2]["slab"] = None
+            out = traced[-1][2]
+            bad = trace_check(orc, w, offs, out, trace_cap)
+            failures += bad
+            kept = int(np.minimum(out["snaps"], trace_cap).sum())
+            base = step_loop(pkg, eng, w, offs, trace_cap, args.single_seconds, count)  # (c)
+            a_best = min(r[0] for r in traced)
+            rec = dict(workload=name, mode="trace", lps=count, trace_cap=trace_cap,
+                       most_snapshots_of_an_lp=most, snapshots=int(out["snaps"].sum()),
+                       snapshots_kept=kept, trace_slab_bytes=int(out["slab"].nbytes),
+                       traced_e2e_seconds_all=[r[0] for r in traced],
+                       traced_solve_seconds_all=[r[1] for r in traced],
+                       untraced_e2e_seconds_all=[r[0] for r in plain],
+                       untraced_solve_seconds_all=[r[1] for r in plain],
+                       traced_e2e_lps_per_s=count / a_best,
+                       trace_price_e2e_seconds=a_best - min(r[0] for r in plain),
+                       trace_price_solve_seconds=min(r[1] for r in traced)
+                       - min(r[1] for r in plain),
+                       step_loop=base, step_loop_seconds_scaled=count / base["lps_per_s"],
+                       speedup_traced_e2e_vs_step_loop=(count / a_best) / base["lps_per_s"],
+                       trace_checked=min(CHECK, count), trace_mismatches=bad)
+            N.lib.lpr_rev_batch_destroy(out["h"])
+            out["slab"] = None
+            lines.append(rec)
+    if args.parent_lib:
+        d = against_parent(args, names)
+        for rec in lines:
+            rec["untraced_solve_vs_parent"] = d[rec["workload"]]
+    text = [json.dumps(rec) for rec in lines]
+    for line in text:
+        print(line, flush=True)
+    with open(args.out or os.path.join(ROOT, "profiles", "revised_batch_trace_bench.json"),
+              "a") as f:
+        f.write("\n".join(text) + "\n")
+    if failures:
+        print(f"trace check: {failures} LP(s) differ from the oracle", file=sys.stderr)
+        return 1
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--trace", action="store_true",
+                    help="measure the traced batch (section 21) instead; appends to --out, by "
+                         "default profiles/revised_batch_trace_bench.json")
+    ap.add_argument("--parent-lib", default=None,
+                    help="--trace: a liblpr_engine.so built from the parent commit, for the "
+                         "untraced solve against it")
+    ap.add_argument("--solve-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child-trace-caps", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--workloads", default="W,G,H")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--seed", type=int, default=20261019)
@@ -185,6 +420,12 @@ def main() -> int:
     ap.add_argument("--no-check", action="store_true", help="skip the bit check and the loops")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
+    if args.solve_child:
+        caps = args.child_trace_caps.split(",") if args.child_trace_caps else None
+        return solve_child(args.solve_child, args.workloads.split(","), args.seed, args.repeat,
+                           caps)
+    if args.trace:
+        return main_trace(args)
 
     import lpr_381_group_v22_amd as pkg
     from lpr_381_group_v22_amd import _native as N
