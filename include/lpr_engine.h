@@ -672,6 +672,38 @@ int lpr_batch_tableau_read(lpr_batch* b, int32_t k, double* rowmajor);
 /* rows, cols and decision variables n of LP k; any may be NULL. */
 int lpr_batch_shape(lpr_batch* b, int32_t k, int32_t* rows, int32_t* cols, int32_t* n);
 
+/* Traced batches: the solve also stores, per LP, the tableau after every
+ * pivot in device memory -- the numbers of PrimalSimplexSolver's IterationSnapshots, "Initial
+ * Tableau" (:86) and "Iteration i - After pivot" (:148); the host only formats.  Record i of an LP
+ * is its state after i pivots, 2 + rows * cols doubles, indices stored as doubles:
+ *   [0] leavingRow of pivot i (1-based, as logged at :138)  [1] enteringCol of pivot i
+ *   T[rows x cols] row-major: the tableau after pivot i
+ * Record 0 is the tableau as built or uploaded, its header -1, -1.  An LP has 1 + pivots records
+ * and keeps the first min(., trace_cap); a record index >= trace_cap is counted, not written.
+ * The C#'s list holds one more entry when the LP is optimal (:118-122) or unbounded (:133): that
+ * one is formatted from lpr_batch_tableau_read, so it survives a small trace_cap.  PARITY: every
+ * record is the bytes of the single-model path's tableau at that point, and everything else a
+ * traced batch ends with is the bytes of the untraced batch.
+ *
+ * lpr_batch_trace_reserve makes the handle traced: it allocates trace_cap records per LP,
+ * zero-filled, and writes record 0 of every LP.  Only before the handle's first solve:
+ * LPR_BAD_ARGUMENT with a message afterwards, when called twice, or for trace_cap < 1.  A failed
+ * allocation, or a slab beyond an int64 count of bytes, is LPR_OUT_OF_MEMORY and the message
+ * names the buffer and its size; the handle stays usable and untraced.  opts and result of
+ * lpr_batch_solve are unchanged. */
+int lpr_batch_trace_reserve(lpr_batch* b, int32_t trace_cap);
+/* Per LP (count entries each, any may be NULL): records, the exact number 1 + pivots (:137; may
+ * exceed trace_cap, min(records, trace_cap) are kept); offset, where LP k's records start in the
+ * trace slab, in doubles; stride, the doubles of one record. */
+int lpr_batch_trace_info(lpr_batch* b, int64_t* records, int64_t* offset, int64_t* stride);
+/* Records [first, first + n) of LP k (:86, :148) into out[n * stride]; a range beyond the kept
+ * records is LPR_BAD_ARGUMENT. */
+int lpr_batch_trace_read(lpr_batch* b, int32_t k, int64_t first, int64_t n, double* out);
+/* The whole trace slab (trace_cap * sum of the strides doubles: every LP's :86 and :148 tableaux)
+ * in one copy; cap_doubles is what `out` holds, LPR_BAD_ARGUMENT when it is too small.  Every
+ * trace read on an untraced or orphaned handle is LPR_BAD_ARGUMENT with a message. */
+int lpr_batch_trace_read_all(lpr_batch* b, double* out, int64_t cap_doubles);
+
 
 /* ------------------------------------------------------- batched branch and bound */
 

@@ -89,20 +89,24 @@ namespace LPR_381_Group_V22.Simplex
     /// <summary>
     /// Many PrimalSimplexSolver models in one call (no reference counterpart: the reference solves one model per
     /// object).  Each LP is built and solved on the device with the rules of PrimalSimplexSolver.cs, the same bits a
-    /// PrimalSimplexSolver gives for it alone; members are per-LP versions of that class's.
+    /// PrimalSimplexSolver gives for it alone; members are per-LP versions of that class's.  With traceCap > 0 the
+    /// batch is traced (DESIGN.md section 22): the device stores the tableau after every pivot and
+    /// IterationSnapshots(k) formats LP k's; an untraced batch keeps none.
     /// </summary>
     public class PrimalSimplexBatch : IDisposable
     {
         private IntPtr batch;                           // lpr_batch*
         internal IntPtr Handle => batch;
         private readonly int[] rows, cols, nvars;
+        private readonly int traceCap;                  // records kept per LP; 0: untraced
+        private long[] traceRecords;                    // lpr_batch_trace_info's counts, read once per Solve
         public int Count { get; }
         public List<int> Status { get; } = new List<int>();
         public List<long> Iterations { get; } = new List<long>();
         public List<double> FinalZ { get; } = new List<double>();
         public List<List<double>> SolutionVector { get; } = new List<List<double>>();
 
-        public PrimalSimplexBatch(List<(List<double> objective, List<IOConstraint> constraints, bool isMaximization)> models, int logCap = 0)
+        public PrimalSimplexBatch(List<(List<double> objective, List<IOConstraint> constraints, bool isMaximization)> models, int logCap = 0, int traceCap = 0)
         {
             Count = models.Count;
             var n = new int[Count]; var m = new int[Count]; var isMax = new sbyte[Count];
@@ -126,6 +130,8 @@ namespace LPR_381_Group_V22.Simplex
             }
             NativeMethods.ThrowIfError(NativeMethods.lpr_batch_from_lps(Engine.Handle, Count, n, m, NonEmpty(obj), NonEmpty(A),
                 NonEmpty(ncoef), NonEmpty(rel), NonEmpty(rhs), isMax, logCap, out batch), "lpr_batch_from_lps");
+            if (traceCap > 0) NativeMethods.ThrowIfError(NativeMethods.lpr_batch_trace_reserve(batch, traceCap), "lpr_batch_trace_reserve");
+            this.traceCap = traceCap;
         }
 
         private static T[] NonEmpty<T>(List<T> l) => l.Count > 0 ? l.ToArray() : new T[1];
@@ -140,6 +146,7 @@ namespace LPR_381_Group_V22.Simplex
             var x = new double[Math.Max(1, nvars.Sum())];
             NativeMethods.ThrowIfError(NativeMethods.lpr_batch_solution_read(batch, x), "lpr_batch_solution_read");
             Status.Clear(); Iterations.Clear(); FinalZ.Clear(); SolutionVector.Clear();
+            traceRecords = null;
             for (int k = 0, at = 0; k < Count; at += nvars[k], k++)
             {
                 Status.Add(st[k]); Iterations.Add(piv[k]);
@@ -172,6 +179,62 @@ namespace LPR_381_Group_V22.Simplex
             var t = new double[r, c];
             NativeMethods.ThrowIfError(NativeMethods.lpr_batch_tableau_read(batch, k, t), "lpr_batch_tableau_read");
             return t;
+        }
+
+        /// <summary>Records LP k has: 1 + pivots (may exceed traceCap).  The reference's list holds one more entry when
+        /// the LP is optimal or unbounded.</summary>
+        public long RecordCount(int k)
+        {
+            if (traceRecords == null)
+            {
+                var recs = new long[Count];
+                NativeMethods.ThrowIfError(NativeMethods.lpr_batch_trace_info(batch, recs, null, null), "lpr_batch_trace_info");
+                traceRecords = recs;
+            }
+            return traceRecords[k];
+        }
+
+        /// <summary>Every LP's records in one copy: record i of LP k starts at offset[k] + i * stride[k].</summary>
+        public double[] TracePacked(out long[] records, out long[] offset, out long[] stride)
+        {
+            records = new long[Count]; offset = new long[Count]; stride = new long[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_trace_info(batch, records, offset, stride), "lpr_batch_trace_info");
+            var slab = new double[checked((long)traceCap * stride.Sum())];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_trace_read_all(batch, slab, slab.LongLength), "lpr_batch_trace_read_all");
+            return slab;
+        }
+
+        /// <summary>IterationSnapshots of LP k (PrimalSimplexSolver.cs:86, :148, :118-122, :133): "Initial Tableau" and
+        /// "Iteration i - After pivot" formatted from the device's records (past traceCap the kept prefix), then the final
+        /// block from the LP's tableau in the batch.  Call after Solve().</summary>
+        public List<string> IterationSnapshots(int k)
+        {
+            int r = rows[k], c = cols[k];
+            long stride = 2 + (long)r * c;                               // batch_trace_stride
+            long kept = Math.Min(RecordCount(k), traceCap);
+            var recs = new double[Math.Max(1L, checked(kept * stride))];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_trace_read(batch, k, 0, kept, recs), "lpr_batch_trace_read");
+            var list = new List<string>();
+            for (long q = 0; q < kept; q++)
+            {
+                var t = new double[r, c];
+                Array.Copy(recs, q * stride + 2, t, 0L, (long)r * c);      // long indices: kept records may pass 2 GB
+                list.Add(TableIterationFormater.Format(t, nvars[k], q == 0 ? "Initial Tableau" : $"Iteration {q} - After pivot"));
+            }
+            if (Status[k] == (int)LprStatus.Optimal)
+            {
+                var sb = new System.Text.StringBuilder();
+                sb.AppendLine(TableIterationFormater.Format(GetFinalTableau(k), nvars[k], "Final Tableau (Optimal)"));
+                var sum = new System.Text.StringBuilder();                  // SolutionSummary :256-267
+                sum.AppendLine("Optimal solution:");
+                sum.AppendLine($"Z = {FinalZ[k]:F6}");
+                for (int i = 0; i < nvars[k]; i++) sum.AppendLine($"x{i + 1} = {SolutionVector[k][i]:F6}");
+                sb.AppendLine(sum.ToString());
+                list.Add(sb.ToString());
+            }
+            else if (Status[k] == (int)LprStatus.Unbounded)
+                list.Add(TableIterationFormater.Format(GetFinalTableau(k), nvars[k], "Unbounded Tableau"));
+            return list;
         }
 
         public void Dispose() { if (batch != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_batch_destroy(batch), "lpr_batch_destroy"); batch = IntPtr.Zero; } }

@@ -250,6 +250,10 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_log_read(IntPtr batch, int k, int[] rows, int[] cols, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_tableau_read(IntPtr batch, int k, [Out] double[,] rowmajor);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_shape(IntPtr batch, int k, out int rows, out int cols, out int n);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_trace_reserve(IntPtr batch, int trace_cap);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_trace_info(IntPtr batch, long[] records, long[] offset, long[] stride);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_trace_read(IntPtr batch, int k, long first, long n, double[] records);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_trace_read_all(IntPtr batch, double[] slab, long cap_doubles);
 
         // ---- Batched branch and bound (DESIGN.md section 13): ExecuteBranchAndBound per IP, many IPs per call ----
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_create(IntPtr engine, int count, int[] rows, int[] cols, double[] tableaux, int[] nvars, int node_cap, int trace_cap, out IntPtr bbBatch);

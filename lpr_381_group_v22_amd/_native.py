@@ -417,6 +417,10 @@ SIGNATURES = {
     "lpr_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, _I32, C.c_int64, _I64]),
     "lpr_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
     "lpr_batch_shape": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32]),
+    "lpr_batch_trace_reserve": (C.c_int, [_P, C.c_int32]),
+    "lpr_batch_trace_info": (C.c_int, [_P, _I64, _I64, _I64]),
+    "lpr_batch_trace_read": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D]),
+    "lpr_batch_trace_read_all": (C.c_int, [_P, _D, C.c_int64]),
     "lpr_bb_batch_create": (C.c_int, [_P, C.c_int32, _I32, _I32, _D, _I32, C.c_int32, C.c_int32,
                                       _PP]),
     "lpr_bb_batch_from_batch": (C.c_int, [_P, C.c_int32, C.c_int32, _PP]),

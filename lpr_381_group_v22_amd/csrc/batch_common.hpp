@@ -1,9 +1,41 @@
 // batch_common.hpp -- definitions shared by the batched primal simplex (batch_engine.hip, host)
-// and its kernels (batch_kernels.hip), and what the four batch engines (LP, B&B: bb_batch_*,
+// and its kernels (batch_body.hpp, instantiated by batch_kernels.hip and, traced, by
+// batch_trace_kernels.hip), and what the four batch engines (LP, B&B: bb_batch_*,
 // scenarios: sens_batch_*, cutting plane: cut_batch_*) have in common on the host: the forms and the rule that picks one, the
 // running-list driver, the dynamic-LDS attribute and the handle plumbing.  The device side of what
 // they share is batch_device.hpp.  Not part of the ABI (include/lpr_engine.h is).
 #pragma once
+
+#include <cstdint>
+
+namespace lpr {
+
+// One record of a traced primal batch (lpr_batch_trace_*), in doubles,
+// indices stored as doubles: record i of an LP is its state after i pivots,
+//   [0] leavingRow of pivot i (1-based, PrimalSimplexSolver.cs:138)  [1] enteringCol of pivot i
+//   T[rows x cols] row-major: the tableau after pivot i
+// Record 0 is the tableau as built or uploaded, its header -1, -1.  LP k's records are at
+// trace + trace_off[k], batch_trace_stride apart, the first trace_cap kept.  This part of the
+// header needs no HIP: with LPR_BATCH_LAYOUT_ONLY defined a plain host compiler takes it
+// (tools/batch_trace_check.cpp).
+constexpr int64_t batch_trace_row() { return 0; }
+constexpr int64_t batch_trace_col() { return 1; }
+constexpr int64_t batch_trace_tab() { return 2; }
+constexpr int64_t batch_trace_stride(int rows, int cols) {
+    return batch_trace_tab() + (int64_t)rows * cols;
+}
+static_assert(batch_trace_stride(3, 4) == 14, "header, then the tableau");
+
+// Where a traced batch keeps its records.
+struct BatchTrace {
+    double* slab;        // every LP's records
+    const int64_t* off;  // per LP, doubles
+    int32_t cap;         // records kept per LP; a record index >= cap is counted, not written
+};
+
+}  // namespace lpr
+
+#ifndef LPR_BATCH_LAYOUT_ONLY
 
 #include "engine_common.hpp"
 
@@ -50,6 +82,9 @@ struct BatchDesc {
     int32_t status;    // kRunning or an lpr_status
     int32_t log_fill;  // pairs kept: min(iter, log_cap)
 };
+// lpr_sens_batch_from_batch and lpr_bb_batch_from_batch read it through batch_view: a traced
+// batch keeps its trace beside the descriptors (BatchTrace), not in them.
+static_assert(sizeof(BatchDesc) == 72, "BatchDesc is 72 bytes");
 
 // Inputs of lpr_batch_from_lps per LP: offsets into the packed arrays.
 struct BatchBuild {
@@ -166,6 +201,40 @@ inline int raise_dynamic_lds(const void* fn, size_t bytes, unsigned long long* m
     return LPR_OK_OPTIMAL;
 }
 
+// The launch of one form's kernel of the LP batch (k_batch_simplex or k_batch_simplex_trace: W, G
+// or H; the three of a file have one signature, whose last parameter is the LDS slot of one LP,
+// appended here: slot_doubles in W and G, 0 in H).  slot_doubles: W and G, the LDS share of one LP; max_rows, max_cols:
+// H, the factor column and pivot row of the largest LP.  g_mask: per device bit, the dynamic-LDS
+// attribute of the G kernel is set.
+template <class K, class... Args>
+int batch_launch_form(const char* name, K kw, K kg, K kh, unsigned long long* g_mask, int form,
+                      hipStream_t s, int n_in, int slot_doubles, int max_rows, int max_cols,
+                      Args... args) {
+    if (n_in <= 0) return LPR_OK_OPTIMAL;
+    if (form == kFormW) {
+        const size_t lds = (size_t)4 * slot_doubles * sizeof(double);
+        hipLaunchKernelGGL(kw, dim3((n_in + 3) / 4), dim3(256), lds, s, args..., slot_doubles);
+    } else if (form == kFormG) {
+        const size_t lds = (size_t)slot_doubles * sizeof(double);
+        if (lds > ((size_t)64 << 10)) {
+            const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kg), kBatchMaxLdsG,
+                                             g_mask);
+            if (rc != LPR_OK_OPTIMAL) return rc;
+        }
+        hipLaunchKernelGGL(kg, dim3(n_in), dim3(256), lds, s, args..., slot_doubles);
+    } else {
+        const size_t lds = (size_t)(max_rows + max_cols) * sizeof(double);
+        hipLaunchKernelGGL(kh, dim3(n_in), dim3(256), lds, s, args..., 0);
+    }
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) {
+        set_error("%s (form %d, %d LPs) failed to launch: %s", name, form, n_in,
+                  hipGetErrorString(err));
+        return LPR_DEVICE_ERROR;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
 // A batch handle leaves its engine's list of live ones (the *_destroy calls).
 template <class H>
 void unlist(std::vector<H*>& live, H* h) {
@@ -191,3 +260,5 @@ lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const 
         }                                                                                   \
         LPR_HIP(hipSetDevice((b)->eng->device));                                            \
     } while (0)
+
+#endif  // LPR_BATCH_LAYOUT_ONLY

@@ -2,7 +2,8 @@
 // DESIGN.md section 12).  Every LP of a batch is solved on the device with the rules of
 // PrimalSimplexSolver; the host only picks each LP's form, relaunches the bounded solve kernels
 // while LPs are still running (BatchRunLists: one small counter read per launch round) and copies
-// results out.
+// results out.  A handle made traced (lpr_batch_trace_*, section 22) launches the traced kernels,
+// which also write the tableau after every pivot of every LP.
 #include "batch_common.hpp"
 
 #include <algorithm>
@@ -12,6 +13,12 @@ namespace lpr {
 int batch_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab, int32_t* basis,
                          int32_t* logs, const int32_t* idx_in, int n_in, int32_t* idx_out,
                          int32_t* n_out, int chunk, int slot_doubles, int max_rows, int max_cols);
+int batch_trace_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab,
+                               int32_t* basis, int32_t* logs, const int32_t* idx_in, int n_in,
+                               int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles,
+                               int max_rows, int max_cols, BatchTrace tr);
+void batch_trace_launch_first(hipStream_t s, const BatchDesc* desc, int count, const double* slab,
+                              BatchTrace tr);
 void batch_launch_build(hipStream_t s, const BatchDesc* desc, const BatchBuild* bd, int count,
                         double* slab, int32_t* basis, const double* obj, const double* A,
                         const int32_t* ncoef, const int8_t* rel, const double* rhs,
@@ -33,6 +40,13 @@ struct lpr_batch {
     BatchRunLists run;              // the running lists and their counters
     double* xz = nullptr;           // extract output: x (x_total) then z (count), lazy
     int64_t slab_n = 0, basis_n = 0, log_n = 0, x_total = 0;
+    bool solved = false;               // lpr_batch_solve has run: too late to reserve a trace
+    // traced (lpr_batch_trace_reserve): trace_cap records per LP, section 22
+    int32_t trace_cap = 0;             // 0: untraced
+    double* trace = nullptr;           // device, trace_n doubles
+    int64_t* trace_off = nullptr;      // device, per LP
+    std::vector<int64_t> h_trace_off;  // LP k's records start at trace + h_trace_off[k]
+    int64_t trace_n = 0;
 };
 
 namespace {
@@ -48,6 +62,10 @@ void batch_release_device(lpr_batch* b) {
     hipFree(b->basis);
     hipFree(b->logs);
     hipFree(b->xz);
+    hipFree(b->trace);
+    hipFree(b->trace_off);
+    b->trace = nullptr;
+    b->trace_off = nullptr;
     b->run.release();
     b->desc = nullptr;
     b->slab = nullptr;
@@ -349,14 +367,15 @@ int lpr_batch_solve(lpr_batch* b, const lpr_batch_opts* opts, lpr_batch_result* 
         if (d.status != kRunning && d.status != LPR_PIVOT_LIMIT) continue;  // finished stays so
         d.status = kRunning;
         d.max_iter = o.max_pivots > 0 ? d.iter + o.max_pivots : 0;
-        const int f = batch_pick_form(batch_footprint(d.rows, d.cols) * sizeof(double), o.variant);
+        // one footprint and one form rule, traced or not: the trace adds nothing to LDS
+        const size_t fp = batch_footprint(d.rows, d.cols);
+        const int f = batch_pick_form(fp * sizeof(double), o.variant);
         lists[f].push_back(k);
         if (f == kFormH) {
             max_rows = std::max(max_rows, d.rows);
             max_cols = std::max(max_cols, d.cols);
         } else {
-            const int fp = (int)batch_footprint(d.rows, d.cols);
-            slot[f] = std::max(slot[f], (fp + 1) & ~1);
+            slot[f] = std::max(slot[f], ((int)fp + 1) & ~1);
         }
     }
     int rc = b->run.upload(s, lists);
@@ -364,10 +383,15 @@ int lpr_batch_solve(lpr_batch* b, const lpr_batch_opts* opts, lpr_batch_result* 
     LPR_HIP(hipMemcpyAsync(b->desc, b->h_desc.data(), (size_t)count * sizeof(BatchDesc),
                            hipMemcpyHostToDevice, s));
     int launches = 0;
+    b->solved = true;
+    const BatchTrace tr{b->trace, b->trace_off, b->trace_cap};
     rc = b->run.rounds(s, [&](int f, const int32_t* in, int n_in, int32_t* out, int32_t* n_out) {
+        const int chunk = o.chunk > 0 ? o.chunk : kBatchChunk[f];
+        if (b->trace_cap > 0)
+            return batch_trace_launch_simplex(f, s, b->desc, b->slab, b->basis, b->logs, in, n_in,
+                                              out, n_out, chunk, slot[f], max_rows, max_cols, tr);
         return batch_launch_simplex(f, s, b->desc, b->slab, b->basis, b->logs, in, n_in, out,
-                                    n_out, o.chunk > 0 ? o.chunk : kBatchChunk[f], slot[f],
-                                    max_rows, max_cols);
+                                    n_out, chunk, slot[f], max_rows, max_cols);
     }, &launches);
     if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(b->h_desc.data(), b->desc, (size_t)count * sizeof(BatchDesc),
@@ -494,6 +518,149 @@ int lpr_batch_shape(lpr_batch* b, int32_t k, int32_t* rows, int32_t* cols, int32
     if (rows) *rows = d.rows;
     if (cols) *cols = d.cols;
     if (n) *n = d.n;
+    return LPR_OK_OPTIMAL;
+}
+
+// ---------------------------------------------------------------- traced batches, section 22
+
+// Records LP k has: the tableau as built (:86) and one per pivot (:148); exact, may exceed
+// trace_cap.  The C#'s list also ends with a block formatted from the final tableau (:118-122,
+// :133), which lpr_batch_tableau_read gives.
+static int64_t batch_records(const BatchDesc& d) { return 1 + d.iter; }
+
+static bool batch_traced(const char* where, const lpr_batch* b) {
+    if (b->trace_cap > 0) return true;
+    set_error("%s: the batch is not traced (call lpr_batch_trace_reserve before the first solve)",
+              where);
+    return false;
+}
+
+// IterationSnapshots of PrimalSimplexSolver (:86, :148) as numbers: makes the handle traced,
+// trace_cap records of batch_trace_stride(rows, cols) doubles per LP, record 0 written here
+int lpr_batch_trace_reserve(lpr_batch* b, int32_t trace_cap) {
+    static const char* W = "lpr_batch_trace_reserve";
+    LPR_LIVE_HANDLE(b, "batch");
+    if (trace_cap < 1) {
+        set_error("%s: trace_cap %d < 1", W, trace_cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (b->trace_cap > 0) {
+        set_error("%s: the batch is already traced (trace_cap %d)", W, b->trace_cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (b->solved) {
+        set_error("%s: only before the handle's first lpr_batch_solve", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    static const char* kSlab = "trace slab: trace_cap records of a header and rows x cols doubles "
+                               "per LP";
+    std::vector<int64_t> off;
+    try {
+        off.resize((size_t)b->count);
+    } catch (...) {
+        return batch_oom("trace offsets", b->count);
+    }
+    // a stride is below 2^22 doubles, trace_cap and count below 2^31: the sum can pass 2^63
+    int64_t total = 0;
+    for (int32_t k = 0; k < b->count; ++k) {
+        const BatchDesc& d = b->h_desc[(size_t)k];
+        const int64_t mine = (int64_t)trace_cap * batch_trace_stride(d.rows, d.cols);  // < 2^53
+        off[(size_t)k] = total;
+        if (total > INT64_MAX / (int64_t)sizeof(double) - mine) {
+            set_error("lpr_batch: cannot allocate %s (trace_cap %d: more than 2^63 bytes at LP %d "
+                      "of %d)", kSlab, trace_cap, k, b->count);
+            return LPR_OUT_OF_MEMORY;
+        }
+        total += mine;
+    }
+    int rc = LPR_OK_OPTIMAL;
+    double* slab = nullptr;
+    int64_t* d_off = nullptr;
+    dev_alloc(&slab, total, kSlab, &rc, batch_oom);
+    dev_alloc(&d_off, b->count, "trace offsets", &rc, batch_oom);
+    hipStream_t s = b->eng->stream;
+    auto fill = [&]() -> int {
+        LPR_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)b->count * sizeof(int64_t),
+                               hipMemcpyHostToDevice, s));
+        // what no record reaches reads as +0.0, the same in every form
+        LPR_HIP(hipMemsetAsync(slab, 0, (size_t)total * sizeof(double), s));
+        batch_trace_launch_first(s, b->desc, b->count, b->slab, BatchTrace{slab, d_off, trace_cap});
+        LPR_HIP(hipGetLastError());
+        LPR_HIP(hipStreamSynchronize(s));
+        return LPR_OK_OPTIMAL;
+    };
+    if (rc == LPR_OK_OPTIMAL) rc = fill();
+    if (rc != LPR_OK_OPTIMAL) {
+        hipFree(slab);
+        hipFree(d_off);
+        return rc;
+    }
+    b->trace = slab;
+    b->trace_off = d_off;
+    b->h_trace_off.swap(off);
+    b->trace_n = total;
+    b->trace_cap = trace_cap;
+    return LPR_OK_OPTIMAL;
+}
+
+// Per LP: records counted (1 + `iteration`, :137), and where the kept ones are in the trace slab;
+// any may be NULL
+int lpr_batch_trace_info(lpr_batch* b, int64_t* records, int64_t* offset, int64_t* stride) {
+    LPR_LIVE_HANDLE(b, "batch");
+    if (!batch_traced("lpr_batch_trace_info", b)) return LPR_BAD_ARGUMENT;
+    for (int32_t k = 0; k < b->count; ++k) {
+        const BatchDesc& d = b->h_desc[(size_t)k];
+        if (records) records[k] = batch_records(d);
+        if (offset) offset[k] = b->h_trace_off[(size_t)k];
+        if (stride) stride[k] = batch_trace_stride(d.rows, d.cols);
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// Records [first, first + n) of LP k: the tableaux of :86 and :148 with their pivots (:138)
+int lpr_batch_trace_read(lpr_batch* b, int32_t k, int64_t first, int64_t n, double* out) {
+    static const char* W = "lpr_batch_trace_read";
+    LPR_LIVE_HANDLE(b, "batch");
+    if (!batch_traced(W, b)) return LPR_BAD_ARGUMENT;
+    if (k < 0 || k >= b->count) {
+        set_error("%s: LP %d out of range (0..%d)", W, k, b->count - 1);
+        return LPR_BAD_ARGUMENT;
+    }
+    const BatchDesc& d = b->h_desc[(size_t)k];
+    const int64_t kept = std::min<int64_t>(batch_records(d), b->trace_cap);
+    if (first < 0 || n < 0 || first > kept || n > kept - first) {
+        set_error("%s: records [%lld, %lld + %lld) of LP %d, which keeps %lld (trace_cap %d)", W,
+                  (long long)first, (long long)first, (long long)n, k, (long long)kept,
+                  b->trace_cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (n == 0) return LPR_OK_OPTIMAL;
+    if (!out) {
+        set_error("%s: null output", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    const int64_t st = batch_trace_stride(d.rows, d.cols);
+    LPR_HIP(hipMemcpyAsync(out, b->trace + b->h_trace_off[(size_t)k] + first * st,
+                           (size_t)(n * st) * sizeof(double), hipMemcpyDeviceToHost,
+                           b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// The whole trace slab in one copy (every LP's :86 and :148 tableaux); cap_doubles is what `out`
+// holds
+int lpr_batch_trace_read_all(lpr_batch* b, double* out, int64_t cap_doubles) {
+    static const char* W = "lpr_batch_trace_read_all";
+    LPR_LIVE_HANDLE(b, "batch");
+    if (!batch_traced(W, b)) return LPR_BAD_ARGUMENT;
+    if (!out || cap_doubles < b->trace_n) {
+        set_error("%s: null output, or cap_doubles %lld below the slab's %lld doubles", W,
+                  (long long)cap_doubles, (long long)b->trace_n);
+        return LPR_BAD_ARGUMENT;
+    }
+    LPR_HIP(hipMemcpyAsync(out, b->trace, (size_t)b->trace_n * sizeof(double),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
     return LPR_OK_OPTIMAL;
 }
 

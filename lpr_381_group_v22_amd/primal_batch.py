@@ -3,7 +3,10 @@
 Every LP of a batch is built and solved on the MI355X with the rules of
 Simplex/PrimalSimplexSolver.cs, the same bits ``PrimalSimplexSolver`` gives for that LP alone.
 The reference has no batch mode: the members below are per-LP lists / accessors named after the
-single-model mirror (primal_simplex_solver.py), and the batch keeps no iteration snapshots.
+single-model mirror (primal_simplex_solver.py).  A batch made with ``trace_cap > 0`` is traced
+(DESIGN.md section 22): its solve also stores the tableau after every pivot of every LP on the
+device, and ``IterationSnapshots(k)`` / ``ConsoleText(k)`` format them with the single mirror's
+formatter; an untraced batch keeps none.
 """
 from __future__ import annotations
 
@@ -15,6 +18,7 @@ import numpy as np
 
 from . import _native as N
 from .engine import Engine, default_engine
+from .primal_simplex_solver import format_console, format_snapshots
 
 
 class PackedModels(NamedTuple):
@@ -104,6 +108,23 @@ def pack_models(models) -> PackedModels:
         np.asarray(rhs, dtype=np.float64), np.asarray(mx, dtype=np.int8))
 
 
+# One record of a traced batch (batch_trace_* of batch_common.hpp), in doubles: the header
+# [0] leavingRow (1-based) [1] enteringCol of the pivot that made it (-1, -1 for record 0), then
+# the tableau after that pivot, rows x cols row-major.
+TRACE_ROW, TRACE_COL, TRACE_TAB = 0, 1, 2
+
+
+def trace_stride(rows: int, cols: int) -> int:
+    """batch_trace_stride: doubles of one record."""
+    return TRACE_TAB + rows * cols
+
+
+def trace_record(r: np.ndarray, rows: int, cols: int):
+    """One record as (leaving_row, entering_col, tableau)."""
+    return (int(r[TRACE_ROW]), int(r[TRACE_COL]),
+            r[TRACE_TAB:TRACE_TAB + rows * cols].reshape(rows, cols).copy())
+
+
 def _ptr(a: np.ndarray, ctype):
     return a.ctypes.data_as(C.POINTER(ctype)) if a.size else None
 
@@ -115,7 +136,8 @@ class PrimalSimplexBatch:
     ``SolutionVector[k]`` (None unless optimal) and ``Iterations[k]`` are set by ``Solve``;
     ``BasicVariables(k)``, ``PivotLog(k)`` and ``GetFinalTableau(k)`` read LP k."""
 
-    def __init__(self, models, engine: Optional[Engine] = None, log_cap: int = 0):
+    def __init__(self, models, engine: Optional[Engine] = None, log_cap: int = 0,
+                 trace_cap: int = 0):
         p = pack_models(models)
         self._init(engine)
         h = C.c_void_p()
@@ -126,18 +148,21 @@ class PrimalSimplexBatch:
             int(log_cap), C.byref(h)), "lpr_batch_from_lps")
         self._attach(h, [(int(m) + 1, int(n) + int(m) + 1, int(n)) for n, m in zip(p.n, p.m)],
                      log_cap)
+        if trace_cap:
+            self.trace_reserve(trace_cap)
 
     @classmethod
-    def from_parsers(cls, parsers, engine: Optional[Engine] = None,
-                     log_cap: int = 0) -> "PrimalSimplexBatch":
+    def from_parsers(cls, parsers, engine: Optional[Engine] = None, log_cap: int = 0,
+                     trace_cap: int = 0) -> "PrimalSimplexBatch":
         """One LP per InputFileParser, maximising unless ProblemType is "min" (program.py)."""
         models = [(p.ObjectiveCoefficients, p.Constraints,
                    (p.ProblemType or "").lower() != "min") for p in parsers]
-        return cls(models, engine=engine, log_cap=log_cap)
+        return cls(models, engine=engine, log_cap=log_cap, trace_cap=trace_cap)
 
     @classmethod
     def from_tableaux(cls, tableaux: Sequence[np.ndarray], bases=None,
-                      engine: Optional[Engine] = None, log_cap: int = 0) -> "PrimalSimplexBatch":
+                      engine: Optional[Engine] = None, log_cap: int = 0,
+                      trace_cap: int = 0) -> "PrimalSimplexBatch":
         """Ready (rows x cols) tableaux, with their bases (rows - 1 entries each) or None."""
         self = cls.__new__(cls)
         self._init(engine)
@@ -160,6 +185,8 @@ class PrimalSimplexBatch:
                                        C.byref(h)), "lpr_batch_create")
         self._attach(h, [(int(r), int(c), max(0, int(c) - int(r))) for r, c in zip(rows, cols)],
                      log_cap)
+        if trace_cap:
+            self.trace_reserve(trace_cap)
         return self
 
     def _init(self, engine: Optional[Engine]) -> None:
@@ -180,6 +207,14 @@ class PrimalSimplexBatch:
         self.SolutionVector: List[Optional[List[float]]] = [None] * self.Count
         self.Iterations: List[int] = [0] * self.Count
         self.LastResult: Optional[N.BatchResult] = None
+        self.TraceCap = 0  # records kept per LP; 0: untraced
+        self._trace_info = None  # (records, offset, stride), read once per solve
+
+    def trace_reserve(self, trace_cap: int) -> None:
+        """Make the batch traced (lpr_batch_trace_reserve): only before the first Solve."""
+        N.check(N.lib.lpr_batch_trace_reserve(self._h, int(trace_cap)), "lpr_batch_trace_reserve")
+        self.TraceCap = int(trace_cap)
+        self._trace_info = None
 
     def destroy(self) -> None:
         if self._h:
@@ -199,6 +234,7 @@ class PrimalSimplexBatch:
         N.check(N.lib.lpr_batch_solve(self._h, C.byref(opts), C.byref(res)), "lpr_batch_solve")
         self.LastResult = res
         self._basis = None
+        self._trace_info = None
         st, piv, z = self.status_arrays()
         x = self.solution_packed()
         at = 0
@@ -267,3 +303,76 @@ class PrimalSimplexBatch:
         N.check(N.lib.lpr_batch_tableau_read(self._h, int(k), _ptr(out, C.c_double)),
                 "lpr_batch_tableau_read")
         return out
+
+    # -- the trace --------------------------------------------------
+    def trace_info(self):
+        """(records, offset, stride), int64[count] each: the exact number of records of every LP
+        (1 + pivots; min(records, TraceCap) are kept), where its records start in the trace slab
+        and the doubles of one record.  Read once per solve: the per-LP accessors below share
+        the arrays, so a loop over every LP of a large batch stays linear."""
+        if self._trace_info is not None:
+            return self._trace_info
+        recs = np.zeros(self.Count, dtype=np.int64)
+        off = np.zeros(self.Count, dtype=np.int64)
+        stride = np.zeros(self.Count, dtype=np.int64)
+        N.check(N.lib.lpr_batch_trace_info(self._h, _ptr(recs, C.c_int64), _ptr(off, C.c_int64),
+                                           _ptr(stride, C.c_int64)), "lpr_batch_trace_info")
+        for a in (recs, off, stride):
+            a.setflags(write=False)
+        self._trace_info = (recs, off, stride)
+        return self._trace_info
+
+    def trace_packed(self):
+        """(slab, records, offset, stride): every LP's records in one copy."""
+        recs, off, stride = self.trace_info()
+        slab = np.zeros(int(self.TraceCap * stride.sum()), dtype=np.float64)
+        N.check(N.lib.lpr_batch_trace_read_all(self._h, _ptr(slab, C.c_double), slab.size),
+                "lpr_batch_trace_read_all")
+        return slab, recs, off, stride
+
+    def trace_read(self, k: int, first: int, n: int) -> np.ndarray:
+        """Records [first, first + n) of LP k, one per row."""
+        r, c, _ = self._shapes[k]
+        out = np.zeros((max(int(n), 0), trace_stride(r, c)), dtype=np.float64)
+        N.check(N.lib.lpr_batch_trace_read(self._h, int(k), int(first), int(n),
+                                           _ptr(out, C.c_double)), "lpr_batch_trace_read")
+        return out
+
+    def _kept(self, k: int):
+        """The kept records of LP k as (leaving_row, entering_col, tableau)."""
+        r, c, _ = self._shapes[k]
+        count = int(self.trace_info()[0][k])
+        return [trace_record(rec, r, c) for rec in self.trace_read(k, 0, min(count, self.TraceCap))]
+
+    def _ended(self, k: int) -> bool:
+        return self.Status[k] in (N.LPR_OK_OPTIMAL, N.LPR_UNBOUNDED)
+
+    def SnapshotCount(self, k: int) -> int:
+        """Entries the C# list of LP k holds: one per record (may exceed TraceCap) and the final
+        block of the optimal (:118-122) or unbounded (:133) exit."""
+        return int(self.trace_info()[0][k]) + (1 if self._ended(k) else 0)
+
+    def Snapshot(self, k: int, i: int):
+        """Record i of LP k: (leaving_row, entering_col, tableau after i pivots)."""
+        r, c, _ = self._shapes[k]
+        return trace_record(self.trace_read(k, i, 1)[0], r, c)
+
+    def IterationSnapshots(self, k: int) -> List[str]:  # :86, :148, :118-122, :133
+        """The C#'s list of text blocks for LP k: "Initial Tableau", "Iteration i - After pivot"
+        per kept record, then the final block from the LP's tableau in the batch (an LP stopped
+        at the pivot limit has none)."""
+        final = self.GetFinalTableau(k) if self._ended(k) else None
+        return format_snapshots([T for _, _, T in self._kept(k)], self._shapes[k][2],
+                                self.Status[k], final, self.FinalZ[k], self.SolutionVector[k])
+
+    def ConsoleText(self, k: int) -> str:  # :117-148
+        """What Solve() of LP k alone writes to the console, from the records' headers and
+        tableaux (independent of log_cap).  The text of a solve has no gaps: an LP that made more
+        records than TraceCap keeps raises ValueError instead of returning its first pivots
+        followed by the exit lines."""
+        count = int(self.trace_info()[0][k])
+        if count > self.TraceCap:
+            raise ValueError(f"LP {k} made {count} records and TraceCap keeps {self.TraceCap}: "
+                             "its console text would miss pivots")
+        return format_console(self._kept(k), self._shapes[k][2], self.Status[k], self.FinalZ[k],
+                              self.SolutionVector[k])

@@ -17,6 +17,65 @@ from .engine import Engine, Tableau, default_engine
 from .input_file_parser import Constraint
 
 
+def col_label(col: int, numVariables: int) -> str:  # :253-254
+    return f"x{col + 1}" if col < numVariables else f"t{col - numVariables + 1}"
+
+
+def solution_summary(final_z: float, solution, numVariables: int,
+                     title: str = "Optimal solution") -> str:  # :256-267
+    nl = fmt.NEWLINE
+    s = title + ":" + nl + f"Z = {fmt.F6(final_z)}" + nl
+    if solution is not None:
+        for i in range(numVariables):
+            s += f"x{i + 1} = {fmt.F6(solution[i])}" + nl
+    return s
+
+
+def format_snapshots(tableaux, numVariables: int, status: Optional[int] = None,
+                     final_tableau=None, final_z: float = 0.0, solution=None,
+                     first: int = 0) -> List[str]:
+    """The text blocks Solve() appends to IterationSnapshots, from numbers: ``tableaux[q]`` is the
+    tableau after ``first + q`` pivots ("Initial Tableau" :86 for 0 pivots, "Iteration i - After
+    pivot" :148), then, for ``status`` optimal (:118-122) or unbounded (:133), the final block from
+    ``final_tableau``.  The single mirror and ``PrimalSimplexBatch`` both format with it."""
+    out = []
+    for q, T in enumerate(tableaux):
+        i = first + q
+        title = "Initial Tableau" if i == 0 else f"Iteration {i} - After pivot"
+        out.append(fmt.Format(T, numVariables, title))
+    if status == N.LPR_OK_OPTIMAL:
+        block = fmt.Format(final_tableau, numVariables, "Final Tableau (Optimal)") + fmt.NEWLINE
+        block += solution_summary(final_z, solution, numVariables) + fmt.NEWLINE
+        out.append(block)
+    elif status == N.LPR_UNBOUNDED:
+        out.append(fmt.Format(final_tableau, numVariables, "Unbounded Tableau"))
+    return out
+
+
+def format_console(records, numVariables: int, status: Optional[int] = None,
+                   final_z: float = 0.0, solution=None) -> str:
+    """What Solve() writes to the console (:117-148), from numbers: ``records[i]`` is
+    ``(leaving_row, entering_col, tableau)`` after i pivots (record 0: the start tableau).  Per
+    pivot the line of :138, "Before pivot" from record i - 1 and "After pivot" from record i;
+    then the lines of the optimal (:117, :123-124) or unbounded (:131) exit."""
+    nl = fmt.NEWLINE
+    out = []
+    for i in range(1, len(records)):
+        r, e, T = records[i]
+        label = col_label(int(e), numVariables)
+        out.append(f"\nIteration {i}: pivot @ constraint {int(r)}, column {label}" + nl)
+        out.append(fmt.Format(records[i - 1][2], numVariables, "Before pivot") + nl)
+        out.append(f"After pivot (constraint {int(r)}, column {label}):" + nl)
+        out.append(fmt.Format(T, numVariables, "After pivot") + nl)
+    if status == N.LPR_OK_OPTIMAL:
+        out.append("Optimal Solution Found!" + nl)
+        out.append(solution_summary(final_z, solution, numVariables) + nl)
+        out.append("-" * 100 + nl)
+    elif status == N.LPR_UNBOUNDED:
+        out.append("Unbounded Solution!" + nl)
+    return "".join(out)
+
+
 class PrimalSimplexSolver:
     #: snapshots are O(R*C) text each (three per pivot in the C#, :139,146,148); above this many
     #: tableau elements the default policy keeps only the initial and final ones.
@@ -56,26 +115,27 @@ class PrimalSimplexSolver:
             snapshots = "all" if elems <= self.SNAPSHOT_ALL_LIMIT else "none"
         self._snapshots = snapshots
         if snapshots != "none":
-            self._capture("Initial Tableau")  # :86
+            self._capture()  # :86
 
     # -- helpers ---------------------------------------------------------------------------
     def _col_label(self, col: int) -> str:  # :253-254
-        return f"x{col + 1}" if col < self.numVariables else f"t{col - self.numVariables + 1}"
+        return col_label(col, self.numVariables)
 
-    def _capture(self, title: str) -> None:  # :89-92
-        self.IterationSnapshots.append(fmt.Format(self._tab.read(), self.numVariables, title))
+    def _capture(self) -> None:  # :89-92, the tableau after self.iteration pivots
+        self.IterationSnapshots += format_snapshots([self._tab.read()], self.numVariables,
+                                                    first=self.iteration)
 
     def _say(self, text: str) -> None:
         if self._verbose:
             print(text)
 
     def _solution_summary(self, title: str = "Optimal solution") -> str:  # :256-267
-        nl = fmt.NEWLINE
-        s = title + ":" + nl + f"Z = {fmt.F6(self.FinalZ)}" + nl
-        if self.SolutionVector is not None:
-            for i in range(self.numVariables):
-                s += f"x{i + 1} = {fmt.F6(self.SolutionVector[i])}" + nl
-        return s
+        return solution_summary(self.FinalZ, self.SolutionVector, self.numVariables, title)
+
+    def _capture_final(self, status: int) -> None:  # :118-122, :133
+        self.IterationSnapshots += format_snapshots([], self.numVariables, status,
+                                                    self.FinalTableau, self.FinalZ,
+                                                    self.SolutionVector)
 
     # -- Solve :102-150 --------------------------------------------------------------------
     def Solve(self, max_pivots: int = 0) -> None:
@@ -93,18 +153,14 @@ class PrimalSimplexSolver:
             self.FinalTableau = self._tab.read()
             self._say("Optimal Solution Found!")
             if self._snapshots != "none":
-                block = fmt.Format(self.FinalTableau, self.numVariables,
-                                   "Final Tableau (Optimal)") + fmt.NEWLINE
-                block += self._solution_summary() + fmt.NEWLINE
-                self.IterationSnapshots.append(block)
+                self._capture_final(status)
             self._say(self._solution_summary())
             self._say("-" * 100)
         elif status == N.LPR_UNBOUNDED:  # :129-135: prints, keeps FinalZ = 0, SolutionVector null
             self._say("Unbounded Solution!")
             self.FinalTableau = self._tab.read()
             if self._snapshots != "none":
-                self.IterationSnapshots.append(
-                    fmt.Format(self.FinalTableau, self.numVariables, "Unbounded Tableau"))
+                self._capture_final(status)
         # LPR_PIVOT_LIMIT has no C# counterpart (the reference loop is uncapped)
 
     def _solve_stepwise(self, max_pivots: int) -> int:
@@ -128,7 +184,7 @@ class PrimalSimplexSolver:
             if self._verbose:
                 print(f"After pivot (constraint {r}, column {self._col_label(e)}):")
                 print(fmt.Format(t.read(), self.numVariables, "After pivot"))
-            self._capture(f"Iteration {self.iteration} - After pivot")  # :148
+            self._capture()  # :148
 
     # -- result accessors :18-24, 269-278 -----------------------------------------------------
     def GetFinalTableau(self) -> np.ndarray:
