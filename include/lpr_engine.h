@@ -776,6 +776,49 @@ int lpr_bb_batch_pop_order_read(lpr_bb_batch* b, int32_t k, int32_t* ids, int64_
 int lpr_bb_batch_trace_read(lpr_bb_batch* b, int32_t k, int32_t* quads, int64_t cap,
                             int64_t* count);
 
+/* A NARRATED batch also keeps, per IP, the numbers behind everything
+ * ExecuteBranchAndBound writes to the console (:1006-1233), written by the search kernel itself:
+ *   - per child record, the list DoDualSimplex returns (:292, :341, :388): the tableau
+ *     AddConstraint hands it, then one per pivot, each (rows + depth) x (cols + depth) doubles,
+ *     row-major, unrounded, back to back and compact in the IP's slice of one slab; a last tableau
+ *     dropped by :392-400 (trace phase 2) is dropped here too;
+ *   - per pop, objVal (:892-897), the nvars decision values (:899-921) and a flag word: bit 0
+ *     scored (not pruned, :985-1004), bit 1 every value integer, bit 2 became the incumbent;
+ *   - the incumbent's tableau (bestTableau of UpdateOptimalSolution :935-983, printed at :1221).
+ * Results, records, pop order, trace and solution are those of an un-narrated batch.
+ *
+ * lpr_bb_batch_narrate_reserve makes the handle narrated: cap_doubles[k] >= 0 is the doubles of
+ * child tableaux IP k may keep.  A tableau that does not fit whole is counted and not written, and
+ * so is every later one of that IP: what is kept is a prefix, and the totals stay exact.  It may
+ * be called again between runs (read the exact needs with lpr_bb_batch_narrate_info, reserve
+ * them, run again: a run is deterministic); the old slab is freed first.  LPR_BAD_ARGUMENT: NULL,
+ * an entry below 0, an orphaned handle.  LPR_OUT_OF_MEMORY names the buffer and its size and
+ * leaves the handle usable and un-narrated. */
+int lpr_bb_batch_narrate_reserve(lpr_bb_batch* b, const int64_t* cap_doubles);
+/* Per IP, count entries each, any pointer may be NULL: tableaux and doubles the child LPs of the
+ * last run made (exact), doubles kept, and the start of the IP's slice in the slab. */
+int lpr_bb_batch_narrate_info(lpr_bb_batch* b, int64_t* tableaux, int64_t* doubles_made,
+                              int64_t* doubles_kept, int64_t* offset);
+/* The pops of IP k in pop order (:1045-1076): *count = min(processed, cap); flags and z one per
+ * pop, vals nvars per pop (undefined for a pruned pop); any of the three may be NULL. */
+int lpr_bb_batch_narrate_pops_read(lpr_bb_batch* b, int32_t k, int32_t* flags, double* z,
+                                   double* vals, int64_t cap, int64_t* count);
+/* One entry per record of IP k: tab_off (doubles from the IP's slice start) and ntab, the
+ * tableaux of its DoDualSimplex list (made; the kept ones are those below doubles_kept).  The
+ * root has ntab 0. */
+int lpr_bb_batch_narrate_children_read(lpr_bb_batch* b, int32_t k, int64_t* tab_off,
+                                       int32_t* ntab, int64_t cap, int64_t* count);
+/* Doubles [first_double, first_double + n) of IP k's slice, what DisplayTableau (:623-640) is
+ * given; a range beyond what is kept is refused. */
+int lpr_bb_batch_narrate_tableaux_read(lpr_bb_batch* b, int32_t k, int64_t first_double,
+                                       int64_t n, double* out);
+/* The whole slab (the sum of cap_doubles) in one copy; cap_doubles is what `out` holds. */
+int lpr_bb_batch_narrate_read_all(lpr_bb_batch* b, double* out, int64_t cap_doubles);
+/* The incumbent's tableau of IP k (:935-983, :1221), rows x cols; out may be NULL to ask for the
+ * shape.  LPR_BAD_ARGUMENT if IP k has no incumbent. */
+int lpr_bb_batch_narrate_best_read(lpr_bb_batch* b, int32_t k, double* out, int32_t* rows,
+                                   int32_t* cols);
+
 
 /* ------------------------------------------------------- sensitivity scenario batch */
 

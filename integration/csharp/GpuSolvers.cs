@@ -392,6 +392,7 @@ namespace LPR_381_Group_V22.Simplex
     {
         private IntPtr bb;                              // lpr_bb_batch*
         private readonly int[] nvars;
+        private readonly int[] rootRows, rootCols;      // the roots' shapes: a child at depth d is d larger each way
         private readonly int nodeCap;
         public int Count { get; }
         public List<int> Status { get; } = new List<int>();
@@ -409,6 +410,7 @@ namespace LPR_381_Group_V22.Simplex
                 r[k] = roots[k].GetLength(0); c[k] = roots[k].GetLength(1);
                 foreach (var v in roots[k]) flat.Add(v);                       // row-major
             }
+            rootRows = r; rootCols = c;
             this.nodeCap = nodeCap > 0 ? nodeCap : 20;
             NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_create(Engine.Handle, Count, r, c, flat.ToArray(), nvars,
                 nodeCap, traceCap, out bb), "lpr_bb_batch_create");
@@ -418,10 +420,13 @@ namespace LPR_381_Group_V22.Simplex
         public BranchAndBoundBatch(PrimalSimplexBatch primal, int nodeCap = 0, int traceCap = 0)
         {
             Count = primal.Count;
-            nvars = new int[Count];
+            nvars = new int[Count]; rootRows = new int[Count]; rootCols = new int[Count];
             for (int k = 0; k < Count; k++)                                     // :20
-                nvars[k] = primal.SolutionVector[k] != null ? primal.SolutionVector[k].Count
-                                                            : Math.Max(1, primal.GetFinalTableau(k).GetLength(1) - 1);
+            {
+                var root = primal.GetFinalTableau(k);
+                rootRows[k] = root.GetLength(0); rootCols[k] = root.GetLength(1);
+                nvars[k] = primal.SolutionVector[k] != null ? primal.SolutionVector[k].Count : Math.Max(1, rootCols[k] - 1);
+            }
             this.nodeCap = nodeCap > 0 ? nodeCap : 20;
             NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_from_batch(primal.Handle, nodeCap, traceCap, out bb),
                 "lpr_bb_batch_from_batch");
@@ -473,6 +478,148 @@ namespace LPR_381_Group_V22.Simplex
             var tr = new List<(int, int, int, int)>();
             for (long q = 0; q < count; q++) tr.Add((q4[4 * q], q4[4 * q + 1], q4[4 * q + 2], q4[4 * q + 3]));
             return tr;
+        }
+
+        // ---- narration (DESIGN.md section 23): what ExecuteBranchAndBound writes to the console, from the device's numbers ----
+        private bool pruning;                          // of the last Narrate
+
+        /// <summary>The two-pass flow: reserve nothing, run, read the exact needs, reserve them, run again (a run is
+        /// deterministic and starts from the roots).</summary>
+        public void Narrate(bool enablePruning = false)
+        {
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_reserve(bb, new long[Count]), "lpr_bb_batch_narrate_reserve");
+            Run(enablePruning);
+            var need = new long[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_info(bb, null, need, null, null), "lpr_bb_batch_narrate_info");
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_reserve(bb, need), "lpr_bb_batch_narrate_reserve");
+            Run(enablePruning);
+            pruning = enablePruning;
+        }
+
+        /// <summary>The whole slab of child tableaux in one copy; `total` is the sum of the reserved doubles.</summary>
+        public double[] NarrationSlab(long total)
+        {
+            var slab = new double[Math.Max(1, total)];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_read_all(bb, slab, slab.LongLength), "lpr_bb_batch_narrate_read_all");
+            return slab;
+        }
+
+        private static double[,] Block(double[] flat, long at, int rows, int cols)
+        {
+            var t = new double[rows, cols];
+            Buffer.BlockCopy(flat, (int)(at * sizeof(double)), t, 0, rows * cols * sizeof(double));
+            return t;
+        }
+
+        private static double[,] Rounded(double[,] t)   // RoundTableau :552-567
+        {
+            var r = (double[,])t.Clone();
+            for (int i = 0; i < r.GetLength(0); i++) for (int j = 0; j < r.GetLength(1); j++) r[i, j] = Math.Round(r[i, j], 4);
+            return r;
+        }
+
+        private static string G(double v) => v.ToString();
+
+        /// <summary>The console text of ExecuteBranchAndBound (:1006-1233) for IP k alone, from the records a narrated
+        /// run kept.  Throws where the IP kept fewer tableaux or trace quads than it made, or hit a child pivot limit:
+        /// the text of a search has no gaps.  (`failed: {e}` (:1147 / :1207) carries the exception's message, no stack trace.)</summary>
+        public string Narration(int k)
+        {
+            var made = new long[Count]; var kept = new long[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_info(bb, null, made, kept, null), "lpr_bb_batch_narrate_info");
+            if (kept[k] < made[k]) throw new InvalidOperationException($"IP {k} made {made[k]} doubles of child tableaux and keeps {kept[k]}");
+            if (Status[k] == (int)LprStatus.PivotLimit) throw new InvalidOperationException($"IP {k} ended with LPR_PIVOT_LIMIT");
+            var piv = new long[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_result_read(bb, null, null, null, null, null, piv, null), "lpr_bb_batch_result_read");
+            var trace = Trace(k, (int)Math.Max(1, piv[k]));
+            if (trace.Count < piv[k]) throw new InvalidOperationException($"IP {k} made {piv[k]} trace quads and keeps {trace.Count}");
+            var recs = Records(k);
+            int n = nvars[k], cap = 1 + 2 * nodeCap;
+            var off = new long[cap]; var nt = new int[cap];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_children_read(bb, k, off, nt, cap, out _), "lpr_bb_batch_narrate_children_read");
+            var fl = new int[nodeCap]; var zs = new double[nodeCap]; var vals = new double[Math.Max(1, nodeCap * n)];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_pops_read(bb, k, fl, zs, vals, nodeCap, out long pops), "lpr_bb_batch_narrate_pops_read");
+            var ids = PopOrder(k);
+            var flat = new double[Math.Max(1, kept[k])];
+            if (kept[k] > 0) NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_tableaux_read(bb, k, 0, kept[k], flat), "lpr_bb_batch_narrate_tableaux_read");
+            int rootRows = this.rootRows[k], rootCols = this.rootCols[k];
+            var sb = new System.Text.StringBuilder();
+            Action<string> wl = s => sb.Append(s).Append(Environment.NewLine);
+            Action<double[,], string> display = (t, caption) =>                 // DisplayTableau :623-640
+            {
+                if (t == null || t.Length == 0) wl($"{caption} (empty)");
+                else wl(TableIterationFormater.Format(Rounded(t), n, caption));
+            };
+            wl("Initiating Branch and Bound Algorithm");
+            wl(pruning ? "Pruning: Enabled" : "Pruning: Disabled");
+            wl(new string('-', 50));
+            var label = new Dictionary<int, string> { [0] = "0" };
+            var path = new Dictionary<int, List<string>> { [0] = new List<string>() };
+            var counters = new Dictionary<string, int>();
+            string optimalLabel = null; double optimalValue = double.NegativeInfinity; List<double> optimalX = null;
+            for (int i = 0; i < pops; i++)
+            {
+                int id = ids[i]; var rec = recs[id]; string lab = label[id];
+                wl($"\n--- Processing branch {lab} (Depth {rec.depth}) ---");
+                if (rec.parent >= 0) wl($"Parent branch: {label[rec.parent]}");
+                wl($"Constraint Path: [{string.Join(", ", path[id])}]");
+                if ((fl[i] & 1) == 0) { wl($"branch {lab} pruned"); continue; }
+                var sol = vals.Skip(i * n).Take(n).ToList();
+                string joined = string.Join(", ", sol.Select(G));
+                if ((fl[i] & 4) != 0)
+                {
+                    optimalValue = zs[i]; optimalX = sol; optimalLabel = lab;
+                    wl($"New optimal integer solution found: [{joined}] with value {G(zs[i])}");
+                }
+                else if ((fl[i] & 2) != 0) wl($"Integer solution found: [{joined}] with value {G(zs[i])} (not better than current optimal)");
+                var kids = Enumerable.Range(0, recs.Count).Where(q => recs[q].parent == id).ToList();
+                if (kids.Count == 0) { wl($"branch {lab}: Integer solution [{joined}] with value {G(zs[i])}"); continue; }
+                int var = recs[kids[0]].var;
+                wl($"Branching on x{var + 1} = {G(Math.Round(sol[var], 4))}");
+                if (!counters.ContainsKey(lab)) counters[lab] = 0;
+                foreach (int q in kids)
+                {
+                    bool lower = recs[q].kind == 1; string name = lower ? "Lower" : "Upper";
+                    counters[lab]++;
+                    string child = lab == "0" ? (lower ? "1" : "2") : $"{lab}.{counters[lab]}";
+                    var bnd = Enumerable.Range(0, n).Select(j => j == var ? 1.0 : 0.0).Concat(new[] { recs[q].bound, lower ? 0.0 : 1.0 }).ToList();
+                    sb.Append($"\n{name} Branch (branch {child}): {string.Join(", ", bnd.Select(G))} ");
+                    sb.Append($"x{var + 1} ").Append(lower ? "<= " : ">= ").Append($"{G(recs[q].bound)} ");
+                    foreach (var t in trace.Where(t => t.node == q && t.phase < 2)) wl($"pivot @ constraint {t.row}, column {t.col + 1}");
+                    if (recs[q].status == 2)
+                    {
+                        wl($"{name} branch (branch {counters[lab]}) failed: System.ArgumentOutOfRangeException: Index was out of range. Must be non-negative and less than the size of the collection.");
+                        continue;
+                    }
+                    int rows = rootRows + recs[q].depth, cols = rootCols + recs[q].depth;
+                    var shown = Enumerable.Range(0, nt[q]).Select(j => Block(flat, off[q] + (long)j * rows * cols, rows, cols)).ToList();
+                    if (recs[q].status == 1)
+                    {
+                        display(shown.Count > 0 ? shown[0] : null, $"branch {child}: Infeasible tableau");
+                        continue;
+                    }
+                    label[q] = child;
+                    path[q] = path[id].Concat(new[] { $"x{var + 1} {(lower ? "<=" : ">=")} {G(recs[q].bound)}" }).ToList();
+                    wl($"{name} branch (branch {child}) infeasible");            // (sic) :1130 / :1193
+                    for (int j = 0; j + 1 < shown.Count; j++) display(shown[j], $"branch {child} {name} branch Tableau {j + 1}");
+                    if (shown.Count > 0) display(shown[shown.Count - 1], $"branch {child} {name} branch final tableau");
+                }
+            }
+            if (Status[k] == (int)LprStatus.BbNodeCap) wl("Potential infinite loop detected");
+            wl("\n" + new string('-', 50)); wl("BRANCH AND BOUND COMPLETED"); wl(new string('-', 50));
+            if (optimalX != null)
+            {
+                NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_best_read(bb, k, null, out int br, out int bc), "lpr_bb_batch_narrate_best_read");
+                var best = new double[br * bc];
+                NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_best_read(bb, k, best, out br, out bc), "lpr_bb_batch_narrate_best_read");
+                display(Block(best, 0, br, bc), $"Optimal solution tableau at branch {optimalLabel}");
+                wl($"Optimal branch: {optimalLabel}");
+                wl($"Optimal integer solution: [{string.Join(", ", optimalX.Select(G))}]");
+                wl($"Optimal value: {G(optimalValue)}");
+            }
+            else wl("No integer solution found");
+            wl($"Total branchs processed: {pops}");
+            return sb.ToString();
         }
 
         public void Dispose() { if (bb != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_destroy(bb), "lpr_bb_batch_destroy"); bb = IntPtr.Zero; } }

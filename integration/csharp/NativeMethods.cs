@@ -265,6 +265,14 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_records_read(IntPtr bbBatch, int k, int[] parent, int[] kind, int[] depth, int[] var, double[] bound, int[] status, double[] z, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_pop_order_read(IntPtr bbBatch, int k, int[] ids, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_trace_read(IntPtr bbBatch, int k, int[] quads, long cap, out long count);
+        // narrated B&B batch (DESIGN.md section 23): the numbers behind ExecuteBranchAndBound's console text (:1006-1233)
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_narrate_reserve(IntPtr bbBatch, long[] cap_doubles);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_narrate_info(IntPtr bbBatch, long[] tableaux, long[] doubles_made, long[] doubles_kept, long[] offset);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_narrate_pops_read(IntPtr bbBatch, int k, int[] flags, double[] z, double[] vals, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_narrate_children_read(IntPtr bbBatch, int k, long[] tab_off, int[] ntab, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_narrate_tableaux_read(IntPtr bbBatch, int k, long first_double, long n, double[] rowmajor);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_narrate_read_all(IntPtr bbBatch, double[] rowmajor, long cap_doubles);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_narrate_best_read(IntPtr bbBatch, int k, double[] rowmajor, out int rows, out int cols);
 
         // ---- Sensitivity scenario batch (DESIGN.md section 14): one solved model, many what-if scripts per call ----
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_sens_batch_create(IntPtr sens, int count, int[] nedits, LprSensEdit[] edits, int log_cap, out IntPtr sensBatch);

@@ -5,7 +5,8 @@ Importing this package loads ``_lib/liblpr_engine.so`` (hand-written HIP for gfx
 """
 from . import _native
 from .engine import Engine, RevisedState, Tableau, default_engine
-from .bb_batch import BranchAndBoundBatch, solve_integer_programs
+from .bb_batch import (BranchAndBoundBatch, option3_texts, solve_integer_programs,
+                       write_option3_files)
 from .branch_and_bound import (BranchAndBoundAdapter, BranchBoundTree, Comm,
                                solve_level_sync_native, solve_level_synchronous,
                                torch_collectives)
@@ -26,6 +27,7 @@ __all__ = [
     "BranchAndBoundAdapter", "BranchBoundTree", "solve_level_synchronous", "torch_collectives",
     "Comm", "solve_level_sync_native", "KnapsackBranchBoundSimplex", "KnapsackBranchBoundSolver",
     "PrimalSimplexBatch", "pack_models", "BranchAndBoundBatch", "solve_integer_programs",
+    "option3_texts", "write_option3_files",
     "SensitivityBatch", "SensitivityGrowBatch", "pack_scripts", "pack_grow_scripts",
     "SensitivityModelBatch", "optimal_items",
     "CuttingPlaneBatch", "pack_tableaux", "KnapsackBatch", "pack_knapsacks", "solve_knapsacks",

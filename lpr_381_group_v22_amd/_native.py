@@ -432,6 +432,13 @@ SIGNATURES = {
                                             C.c_int64, _I64]),
     "lpr_bb_batch_pop_order_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
     "lpr_bb_batch_trace_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
+    "lpr_bb_batch_narrate_reserve": (C.c_int, [_P, _I64]),
+    "lpr_bb_batch_narrate_info": (C.c_int, [_P, _I64, _I64, _I64, _I64]),
+    "lpr_bb_batch_narrate_pops_read": (C.c_int, [_P, C.c_int32, _I32, _D, _D, C.c_int64, _I64]),
+    "lpr_bb_batch_narrate_children_read": (C.c_int, [_P, C.c_int32, _I64, _I32, C.c_int64, _I64]),
+    "lpr_bb_batch_narrate_tableaux_read": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D]),
+    "lpr_bb_batch_narrate_read_all": (C.c_int, [_P, _D, C.c_int64]),
+    "lpr_bb_batch_narrate_best_read": (C.c_int, [_P, C.c_int32, _D, _I32, _I32]),
     "lpr_sens_batch_create": (C.c_int, [_P, C.c_int32, _I32, C.POINTER(SensEdit), C.c_int32, _PP]),
     "lpr_sens_batch_create_grow": (C.c_int, [_P, C.c_int32, _I32, C.POINTER(SensEdit), _D,
                                              C.c_int64, C.c_int32, _PP]),

@@ -6,16 +6,35 @@ the bits ``BranchBoundTree.run`` (lpr_bb_run) gives for that root alone.  The re
 batch mode: the per-IP accessors below are named after the single-tree surface
 (branch_and_bound.py), and ``solve_integer_programs`` is menu option 3 (Program.cs:356-416) for
 many models at once.
+
+A batch made NARRATED (``narrate_reserve`` / ``Narrate``) also keeps what the
+console text of ExecuteBranchAndBound is made of, written by the search kernel; ``NarrationText(k)``
+formats it with branch_and_bound.format_branch_and_bound, the formatter of the single-tree path.
+The record layout (csrc/bb_narr_layout.hpp), per IP:
+
+* child tableaux: for record ``rid`` the list DoDualSimplex returns (:292, :341, :388) -- the
+  tableau AddConstraint hands it, then one per pivot -- each (R0 + depth) x (C0 + depth) doubles,
+  row-major, unrounded, back to back in the IP's slice of one slab; ``tab_off[rid]`` (doubles from
+  the slice start) and ``ntab[rid]`` (tableaux made, after the drop of :392-400) go with the
+  record; the root has ntab 0;
+* per pop: objVal, nvars decision values, flags (1 scored, 2 all integer, 4 became the incumbent);
+* the incumbent's tableau at its node's own shape.
+
+A tableau that does not fit whole in the IP's reserved doubles is counted and not written, nor is
+any later one: what is kept is a prefix and the totals are exact.
 """
 from __future__ import annotations
 
 import ctypes as C
+import io
 import math
+from contextlib import redirect_stdout
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _native as N
+from . import branch_and_bound as bnb
 from .engine import Engine, default_engine
 from .input_file_parser import Constraint
 from .primal_batch import PrimalSimplexBatch
@@ -25,6 +44,15 @@ MAX_NODE_CAP = 64       # kBBBatchMaxNodeCap
 MAX_ROWS_H = 1024       # at full depth: rows + node_cap
 MAX_COLS_H = 2048       # ... and cols + node_cap
 DEFAULT_TRACE_CAP = 256
+NARR_SCORED, NARR_INTEGER, NARR_INCUMBENT = 1, 2, 4  # pop flags (bb_narr_layout.hpp)
+
+
+class NarrationInfo(NamedTuple):
+    """lpr_bb_batch_narrate_info, one entry per IP."""
+    tableaux: np.ndarray      # child tableaux made (exact)
+    doubles_made: np.ndarray  # ... and their doubles
+    doubles_kept: np.ndarray  # doubles kept: a prefix of those made
+    offset: np.ndarray        # start of the IP's slice in the slab
 
 
 class PackedRoots(NamedTuple):
@@ -109,6 +137,9 @@ class BranchAndBoundBatch:
         self.trace_cap = trace_cap
         self.Count = len(self._shapes)
         self.LastResult: Optional[N.BBBatchResult] = None
+        self.Narrated = False
+        self._pruning = False      # of the last Run
+        self._narr_info = None     # read once per run
 
     @classmethod
     def from_tableaux(cls, tableaux: Sequence[np.ndarray], nvars: Sequence[int], node_cap: int = 0,
@@ -161,7 +192,150 @@ class BranchAndBoundBatch:
         res = N.BBBatchResult()
         N.check(N.lib.lpr_bb_batch_run(self._h, C.byref(opts), C.byref(res)), "lpr_bb_batch_run")
         self.LastResult = res
+        self._pruning = bool(enable_pruning)
+        self._narr_info = None
         return res
+
+    # -- narration (section 23) ------------------------------------------------------------------
+    def narrate_reserve(self, cap) -> None:
+        """Make the batch narrated (lpr_bb_batch_narrate_reserve): ``cap`` doubles of child
+        tableaux per IP (one int for all, or one per IP).  May be called again between runs."""
+        caps = np.full(self.Count, int(cap), dtype=np.int64) if np.isscalar(cap) else \
+            np.ascontiguousarray([int(c) for c in cap], dtype=np.int64)
+        if caps.shape != (self.Count,):
+            raise ValueError(f"{caps.size} caps for {self.Count} IPs")
+        self.Narrated = False
+        self._narr_info = None
+        self._caps = caps
+        N.check(N.lib.lpr_bb_batch_narrate_reserve(self._h, caps.ctypes.data_as(
+            C.POINTER(C.c_int64))), "lpr_bb_batch_narrate_reserve")
+        self.Narrated = True
+
+    def narration_info(self) -> NarrationInfo:
+        if self._narr_info is None:
+            a = [np.zeros(self.Count, dtype=np.int64) for _ in range(4)]
+            N.check(N.lib.lpr_bb_batch_narrate_info(self._h, *[_ptr(x, C.c_int64) for x in a]),
+                    "lpr_bb_batch_narrate_info")
+            self._narr_info = NarrationInfo(*a)
+        return self._narr_info
+
+    def Narrate(self, enable_pruning: bool = False, **run_opts) -> N.BBBatchResult:
+        """The two-pass flow: reserve nothing, run, read the exact needs, reserve them, run
+        again.  A run is deterministic and starts from the roots, so the second keeps all."""
+        self.narrate_reserve(0)
+        self.Run(enable_pruning=enable_pruning, **run_opts)
+        self.narrate_reserve(self.narration_info().doubles_made)
+        return self.Run(enable_pruning=enable_pruning, **run_opts)
+
+    def narration_packed(self) -> np.ndarray:
+        """The whole slab in one copy (lpr_bb_batch_narrate_read_all)."""
+        total = int(self._caps.sum())
+        out = np.zeros(max(total, 1), dtype=np.float64)
+        N.check(N.lib.lpr_bb_batch_narrate_read_all(self._h, _ptr(out, C.c_double), out.size),
+                "lpr_bb_batch_narrate_read_all")
+        return out[:total]
+
+    def PopInfo(self, k: int) -> List[dict]:
+        """The pops of IP k in order: dict(id, z, vals (None for a pruned pop), flags)."""
+        cap, nv = self.node_cap, self.nvars[k]
+        fl, z = np.zeros(cap, dtype=np.int32), np.zeros(cap)
+        vals = np.zeros(max(cap * nv, 1))
+        n = C.c_int64()
+        N.check(N.lib.lpr_bb_batch_narrate_pops_read(
+            self._h, int(k), _ptr(fl, C.c_int32), _ptr(z, C.c_double), _ptr(vals, C.c_double), cap,
+            C.byref(n)), "lpr_bb_batch_narrate_pops_read")
+        ids = self.PopOrder(k)
+        return [dict(id=ids[i], z=float(z[i]), flags=int(fl[i]),
+                     vals=[float(v) for v in vals[i * nv:(i + 1) * nv]]
+                     if fl[i] & NARR_SCORED else None) for i in range(n.value)]
+
+    def Children(self, k: int):
+        """(tab_off, ntab) per record of IP k (lpr_bb_batch_narrate_children_read)."""
+        cap = 1 + 2 * self.node_cap
+        off, nt = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int32)
+        n = C.c_int64()
+        N.check(N.lib.lpr_bb_batch_narrate_children_read(
+            self._h, int(k), _ptr(off, C.c_int64), _ptr(nt, C.c_int32), cap, C.byref(n)),
+            "lpr_bb_batch_narrate_children_read")
+        return off[:n.value], nt[:n.value]
+
+    def _child_tableaux(self, k: int, rid: int, depth: int, off, nt, kept: int):
+        """The kept tableaux of record rid, and how many its list holds."""
+        r, c = self._shapes[k][0] + depth, self._shapes[k][1] + depth
+        have = max(0, min(int(nt[rid]), (kept - int(off[rid])) // (r * c)))
+        out = np.zeros((max(have, 1), r, c))
+        if have:
+            N.check(N.lib.lpr_bb_batch_narrate_tableaux_read(
+                self._h, int(k), int(off[rid]), have * r * c, _ptr(out, C.c_double)),
+                "lpr_bb_batch_narrate_tableaux_read")
+        return [out[i] for i in range(have)], int(nt[rid])
+
+    def ChildTableaux(self, k: int, rid: int) -> List[np.ndarray]:
+        """The kept tableaux of the child LP of record ``rid`` of IP k: DoDualSimplex's list
+        (:292, :341, :388), unrounded.  Fewer than the record's ntab where the IP's cap cut it."""
+        off, nt = self.Children(k)
+        if not 0 <= rid < len(nt):
+            raise IndexError(f"IP {k} has {len(nt)} records")
+        depth = self.Records(k)[rid]["depth"]
+        return self._child_tableaux(k, rid, depth, off, nt,
+                                    int(self.narration_info().doubles_kept[k]))[0]
+
+    def IncumbentTableau(self, k: int) -> Optional[np.ndarray]:
+        """bestTableau of IP k (:935-983), or None where no integer solution was found."""
+        if not self.Result(k)["found"]:
+            return None
+        r, c = C.c_int32(), C.c_int32()
+        N.check(N.lib.lpr_bb_batch_narrate_best_read(self._h, int(k), None, C.byref(r),
+                                                     C.byref(c)), "lpr_bb_batch_narrate_best_read")
+        out = np.zeros((r.value, c.value))
+        N.check(N.lib.lpr_bb_batch_narrate_best_read(self._h, int(k), _ptr(out, C.c_double),
+                                                     C.byref(r), C.byref(c)),
+                "lpr_bb_batch_narrate_best_read")
+        return out
+
+    def NarrationNumbers(self, k: int):
+        """(pops, incumbent tableau, capped) of IP k for format_branch_and_bound.  The text of a
+        search has no gaps: raises ValueError where IP k kept fewer tableaux or trace quads than
+        it made, or ended with LPR_PIVOT_LIMIT."""
+        res = self.Result(k)
+        if res["status"] == N.LPR_PIVOT_LIMIT:
+            raise ValueError(f"IP {k} ended with LPR_PIVOT_LIMIT: its search is incomplete")
+        info = self.narration_info()
+        if info.doubles_kept[k] < info.doubles_made[k]:
+            raise ValueError(f"IP {k} made {int(info.doubles_made[k])} doubles of child tableaux "
+                             f"and keeps {int(info.doubles_kept[k])}: its text would miss tableaux")
+        if res["pivots"] > self.trace_cap:
+            raise ValueError(f"IP {k} made {res['pivots']} trace quads and trace_cap keeps "
+                             f"{self.trace_cap}: its text would miss pivots")
+        recs = self.Records(k)
+        off, nt = self.Children(k)
+        kept = int(info.doubles_kept[k])
+        pivots = {}
+        for rid, ph, r, c in self.Trace(k):
+            pivots.setdefault(rid, []).append((ph, r, c))
+        kids = {}
+        for rid, rec in enumerate(recs):
+            if rec["parent"] >= 0:
+                kids.setdefault(rec["parent"], []).append(rid)
+        status = {0: bnb.BB_SOLVED, 1: bnb.BB_INFEASIBLE, 2: bnb.BB_FAILED}
+        pops = []
+        for pop in self.PopInfo(k):
+            children = None
+            if pop["id"] in kids:
+                children = [bnb.ChildNumbers(
+                    status[recs[rid]["status"]], pivots.get(rid, []),
+                    self._child_tableaux(k, rid, recs[rid]["depth"], off, nt, kept)[0])
+                    for rid in kids[pop["id"]]]
+            pops.append(bnb.PopNumbers(pop["z"], pop["vals"], children))
+        return pops, self.IncumbentTableau(k), res["status"] == N.LPR_BB_NODE_CAP
+
+    def NarrationText(self, k: int, newline: str = "\n") -> str:
+        """What ExecuteBranchAndBound of IP k alone writes to the console (:1006-1233), with
+        "Potential infinite loop detected" (:1040) for LPR_BB_NODE_CAP.  ``newline`` ends every
+        Console.WriteLine (format_branch_and_bound)."""
+        pops, tab, capped = self.NarrationNumbers(k)
+        return bnb.format_branch_and_bound(self.nvars[k], pops, tab, capped, self._pruning,
+                                           newline)[0]
 
     # -- bulk reads -----------------------------------------------------------------------------
     def result_arrays(self) -> dict:
@@ -252,4 +426,70 @@ def solve_integer_programs(parsers, node_cap: int = 0, enable_pruning: bool = Fa
         else:
             out.append(([], -math.inf))
         at += n
+    return out
+
+
+def option3_texts(parsers, node_cap: int = 0, enable_pruning: bool = False,
+                  engine: Optional[Engine] = None, primal_trace_cap: int = 256,
+                  trace_cap: int = 1 << 14) -> List[Tuple[str, List[float], float]]:
+    """Menu option 3 (Program.cs:356-415) for many models at once, with its text: one traced
+    PrimalSimplexBatch and one narrated BranchAndBoundBatch.  Per model ``(text, x, z)``: the
+    console text Program.cs captures into the result file -- the banner (:358), the canonical
+    form (:360-361), the primal solve's tables (``ConsoleText(k)``), everything
+    ExecuteBranchAndBound writes (``NarrationText(k)``) and the result block (:401-407) -- and
+    SolveFromPrimal's ``(x, z)``.  The caller's parsers are left as they are."""
+    from . import program as prog
+    from . import table_iteration_formater as fmt
+    nl = fmt.NEWLINE
+    primal = PrimalSimplexBatch(option3_models(parsers), engine=engine,
+                                trace_cap=primal_trace_cap)
+    try:
+        primal.Solve()
+        consoles = [primal.ConsoleText(k) for k in range(primal.Count)]
+        bb = BranchAndBoundBatch.from_primal_batch(primal, node_cap=node_cap, trace_cap=trace_cap)
+    finally:
+        primal.destroy()
+    try:
+        bb.Narrate(enable_pruning=enable_pruning)
+        res = bb.result_arrays()
+        xs = bb.solution_packed()
+        out, at = [], 0
+        for k, p in enumerate(parsers):
+            n = bb.nvars[k]
+            found = bool(res["found"][k])
+            x = [float(v) for v in xs[at:at + n]] if found else []
+            z = float(res["z"][k]) if found else -math.inf
+            at += n
+            buf = io.StringIO()
+
+            class _Console(io.TextIOBase):  # print()'s own terminator is Console.WriteLine's
+                def write(self, t):
+                    buf.write(nl if t == "\n" else t)
+                    return len(t)
+
+            with redirect_stdout(_Console()):
+                print("Solving with Branch and Bound Simplex Algorithm...")
+                prog.display_canonical_form(p.ProblemType, p.ObjectiveCoefficients, p.Constraints,
+                                            p.SignRestrictions)
+            tail = ["\n=== Branch & Bound Result ===" + nl,
+                    f"Z* = {fmt._custom_0_hashes(z) if math.isfinite(z) else z}" + nl]
+            tail += [f"x{i + 1} = {fmt._custom_0_hashes(v)}" + nl for i, v in enumerate(x)]
+            out.append((buf.getvalue() + consoles[k] + bb.NarrationText(k, newline=nl) +
+                        "".join(tail), x, z))
+    finally:
+        bb.destroy()
+    return out
+
+
+def write_option3_files(parsers, paths: Sequence[str], **kw) -> List[Tuple[List[float], float]]:
+    """option3_texts, each text written as Program.cs:409-410 writes it (WriteSnapshotsOnly,
+    OutputFileWrite.cs:83-119) to its own path.  Returns ``(x, z)`` per model."""
+    from . import program as prog
+    if len(paths) != len(parsers):
+        raise ValueError(f"{len(paths)} paths for {len(parsers)} models")
+    out = []
+    for path, (text, x, z) in zip(paths, option3_texts(parsers, **kw)):
+        prog.write_snapshots_only(path, "Branch and Bound Simplex Algorithm", [text], z, x,
+                                  append=False)
+        out.append((x, z))
     return out

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -184,126 +184,197 @@ def _join(vals) -> str:  # string.Join(", ", List<double>)
     return ", ".join(_g(v) for v in vals)
 
 
-def execute_branch_and_bound_narrated(tree: "BranchBoundTree", root_shape: Tuple[int, int],
-                                      enable_pruning: bool = False, node_cap: int = 0):
+class ChildNumbers(NamedTuple):
+    """One child LP of a pop (:1083-1148 lower, :1150-1208 upper), as numbers."""
+    status: int                          # BB_SOLVED / BB_INFEASIBLE / BB_FAILED
+    pivots: List[Tuple[int, int, int]]   # (phase, row, col) in order; phase 2 = the drop of :392-400
+    tableaux: List[np.ndarray]           # DoDualSimplex's list (:292, :341, :388), unrounded
+
+
+class PopNumbers(NamedTuple):
+    """One pop of the DFS stack (:1045-1076), as numbers."""
+    z: float                                  # GetObjective :892-897
+    vals: Optional[List[float]]               # ExtractSolution :899-921; None for a pruned pop
+    children: Optional[List[ChildNumbers]]    # [lower, upper]; None where the node did not branch
+
+
+def gather_branch_and_bound_numbers(tree: "BranchBoundTree", root_shape: Tuple[int, int],
+                                    enable_pruning: bool = False, node_cap: int = 0):
     """ExecuteBranchAndBound (BranchBoundSimplexSolver.cs:1006-1233) driven from the host over the
-    engine's building blocks, WRITING WHAT THE C# WRITES to the console (captured by Program.cs
-    option 3 into the result file): every node header, the branching lines, "pivot @ constraint r,
-    column c" of every pivot (:198 / :276) and every tableau of every child through DisplayTableau
-    (:623-640).  The numbers -- scores, tableaux, pivots -- come from the device
-    (lpr_bb_node_info, lpr_bb_expand_traced); this function only orders and formats them, and only
-    for textbook-sized models (the adapter's narrate="auto": <= 4 096 tableau entries).  Same search,
-    same answer as lpr_bb_run.  One thing cannot be reproduced: `failed: {e}` (:1147 / :1207) prints
-    a .NET exception with its stack trace; the exception's type and message are printed here, the
-    trace is not.  Returns (x or None, z, processed)."""
-    n = tree.nvars
+    engine's building blocks (lpr_bb_node_info, lpr_bb_expand_traced): the numbers the console
+    text is made of, and nothing formatted.  Returns (pops, incumbent tableau or None, capped) for
+    format_branch_and_bound."""
     cap = node_cap if node_cap > 0 else 20  # :1038
-    print("Initiating Branch and Bound Algorithm")                       # :1010
-    print("Pruning: Enabled" if enable_pruning else "Pruning: Disabled")  # :1013 / :1017
-    print("-" * 50)                                                       # :1019
-
-    def display(tab: np.ndarray, caption: str) -> None:  # DisplayTableau :623-640
-        if tab is None or tab.size == 0:
-            print(f"{caption} (empty)")
-            return
-        print(fmt.Format(_round4_np(np.asarray(tab, dtype=np.float64)), n, caption))
-
-    optimal_x, optimal_z, optimal_label, optimal_tab = None, -math.inf, None, None
-    branch_count = 0
-    counters = {}
-    # (node id, its rows, cols, depth, label, constraint path, parent label)
-    stack = [(0, root_shape[0], root_shape[1], 0, "0", [], None)]
-    iteration = 0
+    pops: List[PopNumbers] = []
+    have, optimal_z, optimal_tab = False, -math.inf, None
+    stack = [(0, root_shape[0], root_shape[1])]  # (node id, its rows, cols)
+    iteration, capped = 0, False
     while stack:
         iteration += 1
         if iteration > cap:
-            print("Potential infinite loop detected")  # :1040
+            capped = True
             break
-        nid, rows, cols, depth, label, path, parent = stack.pop()
-        branch_count += 1
-        print(f"\n--- Processing branch {label} (Depth {depth}) ---")  # :1049
-        if parent is not None:
-            print(f"Parent branch: {parent}")
-        print(f"Constraint Path: [{', '.join(path)}]")
+        nid, rows, cols = stack.pop()
         zs, vals = tree.node_info([nid])  # RoundAllTableaux :1047 + GetObjective + ExtractSolution
         z, sol = float(zs[0]), [float(v) for v in vals[0]]
-        if enable_pruning and optimal_x is not None and z <= optimal_z:  # :1060, :985-1004
-            print(f"branch {label} pruned")
+        if enable_pruning and have and z <= optimal_z:  # :1060, :985-1004
+            pops.append(PopNumbers(z, None, None))
             tree.release([nid])
+            continue
+        if all(_is_integer(v) for v in sol) and z > optimal_z:  # UpdateOptimalSolution :935-983
+            have, optimal_z = True, z
+            optimal_tab = tree.node_read(nid)
+        k, val = choose_branch(sol)  # CreateBranches :859-890
+        if k < 0:
+            pops.append(PopNumbers(z, sol, None))
+            tree.release([nid])
+            continue
+        lo, up = float(dotnet_int32(math.floor(val))), float(dotnet_int32(math.ceil(val)))
+        child, st, _piv, traces, tabs = tree.expand_traced(
+            [nid, nid], [k, k], [lo, up], [0, 1], (rows, cols))
+        pops.append(PopNumbers(z, sol, [ChildNumbers(int(st[side]), traces[side],
+                                                     [np.array(t) for t in tabs[side]])
+                                        for side in range(2)]))
+        for side in (1, 0):  # :1210-1213
+            if st[side] not in (BB_FAILED, BB_INFEASIBLE):
+                stack.append((int(child[side]), rows + 1, cols + 1))
+        tree.release([nid])
+    for item in stack:
+        tree.release([item[0]])
+    return pops, optimal_tab, capped
+
+
+def format_branch_and_bound(n: int, pops: Sequence[PopNumbers], incumbent_tab, capped: bool,
+                            enable_pruning: bool = False, newline: str = "\n", write=None):
+    """WHAT THE C# WRITES to the console in ExecuteBranchAndBound (:1006-1233; Program.cs option 3
+    captures it into the result file), from numbers alone: every node header, the branching
+    lines, "pivot @ constraint r, column c" of every pivot (:198 / :276) and every tableau of every
+    child through DisplayTableau (:623-640).  ``pops`` are the pops in order; the labels, the
+    constraint paths and the incumbent rule are replayed here, which is all the bookkeeping the C#
+    keeps in its Stack<...>.  The single-handle path (gather_branch_and_bound_numbers) and the
+    narrated batch (bb_batch.py) both end here.  One thing cannot be reproduced: `failed: {e}`
+    (:1147 / :1207) prints a .NET exception with its stack trace; the exception's type and message
+    are written, the trace is not.  ``newline`` ends every Console.WriteLine: "\\n" is what print()
+    writes, Environment.NewLine what the C#'s captured text holds (a "\\n" inside a literal stays).
+    ``write(s, end)``, if given, receives every Console.Write / WriteLine as it is made instead
+    of the text being collected (the single path prints them one by one, so that a stream which
+    tells print()'s terminator from a "\\n" inside a string still can).
+    Returns (text, x or None, z, processed)."""
+    out: List[str] = []
+
+    def emit(s: str = "", end: Optional[str] = None) -> None:
+        end = newline if end is None else end
+        if write is not None:
+            write(s, end)
+        else:
+            out.append(s + end)
+
+    emit("Initiating Branch and Bound Algorithm")                        # :1010
+    emit("Pruning: Enabled" if enable_pruning else "Pruning: Disabled")  # :1013 / :1017
+    emit("-" * 50)                                                       # :1019
+
+    def display(tab, caption: str) -> None:  # DisplayTableau :623-640
+        if tab is None or tab.size == 0:
+            emit(f"{caption} (empty)")
+            return
+        emit(fmt.Format(_round4_np(np.asarray(tab, dtype=np.float64)), n, caption))
+
+    optimal_x, optimal_z, optimal_label = None, -math.inf, None
+    branch_count = 0
+    counters = {}
+    stack = [(0, "0", [], None)]  # (depth, label, constraint path, parent label)
+    for pop in pops:
+        depth, label, path, parent = stack.pop()
+        branch_count += 1
+        emit(f"\n--- Processing branch {label} (Depth {depth}) ---")  # :1049
+        if parent is not None:
+            emit(f"Parent branch: {parent}")
+        emit(f"Constraint Path: [{', '.join(path)}]")
+        z, sol = float(pop.z), pop.vals
+        if sol is None:  # :1060, :985-1004
+            emit(f"branch {label} pruned")
             continue
         if all(_is_integer(v) for v in sol):  # UpdateOptimalSolution :935-983
             if z > optimal_z:
                 optimal_z, optimal_x, optimal_label = z, list(sol), label
-                optimal_tab = tree.node_read(nid)
-                print(f"New optimal integer solution found: [{_join(sol)}] with value {_g(z)}")
+                emit(f"New optimal integer solution found: [{_join(sol)}] with value {_g(z)}")
             else:
-                print(f"Integer solution found: [{_join(sol)}] with value {_g(z)} (not better "
-                      f"than current optimal)")
+                emit(f"Integer solution found: [{_join(sol)}] with value {_g(z)} (not better "
+                     f"than current optimal)")
         k, val = choose_branch(sol)  # CreateBranches :859-890
         if k < 0:
-            print(f"branch {label}: Integer solution [{_join(sol)}] with value {_g(z)}")  # :1074
-            tree.release([nid])
+            emit(f"branch {label}: Integer solution [{_join(sol)}] with value {_g(z)}")  # :1074
             continue
-        print(f"Branching on x{k + 1} = {_g(_round4(val))}")  # :868
+        emit(f"Branching on x{k + 1} = {_g(_round4(val))}")  # :868
         lower = [1.0 if i == k else 0.0 for i in range(n)] + [float(dotnet_int32(math.floor(val))), 0.0]
         upper = [1.0 if i == k else 0.0 for i in range(n)] + [float(dotnet_int32(math.ceil(val))), 1.0]
         counters.setdefault(label, 0)
-        child, st, _piv, traces, tabs = tree.expand_traced(
-            [nid, nid], [k, k], [lower[n], upper[n]], [0, 1], (rows, cols))
         kids = []
         for side, (name, bnd, star) in enumerate((("Lower", lower, "t"), ("Upper", upper, "x"))):
+            ch = pop.children[side]
             counters[label] += 1
             if label == "0":
                 child_label = "1" if side == 0 else "2"
             else:
                 child_label = f"{label}.{counters[label]}"
-            print(f"\n{name} Branch (branch {child_label}): {_join(bnd)} ", end="")  # :1088 / :1155
+            emit(f"\n{name} Branch (branch {child_label}): {_join(bnd)} ", end="")  # :1088 / :1155
             for i in range(n):
                 if bnd[i] == 0:
                     continue
-                print(f"x{i + 1} " if bnd[i] == 1 else f"{_g(bnd[i])}*{star}{i + 1} ", end="")
-            print("<= " if bnd[-1] == 0 else ">= ", end="")
-            print(f"{_g(bnd[-2])} ", end="")
-            for ph, r, c in traces[side]:  # PerformDualPivot :198 / PerformPrimalPivot :276
+                emit(f"x{i + 1} " if bnd[i] == 1 else f"{_g(bnd[i])}*{star}{i + 1} ", end="")
+            emit("<= " if bnd[-1] == 0 else ">= ", end="")
+            emit(f"{_g(bnd[-2])} ", end="")
+            for ph, r, c in ch.pivots:  # PerformDualPivot :198 / PerformPrimalPivot :276
                 if ph < 2:
-                    print(f"pivot @ constraint {r}, column {c + 1}")
-            shown = [np.array(t) for t in tabs[side]]
-            if st[side] == BB_FAILED:  # an exception escaped DoDualSimplex (:396-399)
-                print(f"{name} branch (branch {counters[label]}) failed: "
-                      f"System.ArgumentOutOfRangeException: Index was out of range. Must be "
-                      f"non-negative and less than the size of the collection.")
+                    emit(f"pivot @ constraint {r}, column {c + 1}")
+            shown = [np.asarray(t) for t in ch.tableaux]
+            if ch.status == BB_FAILED:  # an exception escaped DoDualSimplex (:396-399)
+                emit(f"{name} branch (branch {counters[label]}) failed: "
+                     f"System.ArgumentOutOfRangeException: Index was out of range. Must be "
+                     f"non-negative and less than the size of the collection.")
                 continue
-            if st[side] == BB_INFEASIBLE:  # optimalSolution == null :1110 / :1177
+            if ch.status == BB_INFEASIBLE:  # optimalSolution == null :1110 / :1177
                 display(shown[0] if shown else None, f"branch {child_label}: Infeasible tableau")
                 shown = []
             else:
                 shown = [_round4_np(t) for t in shown]  # RoundAllTableaux :1124 / :1187
                 op = "<=" if side == 0 else ">="
                 desc = f"x{k + 1} {op} {_g(bnd[-2])}"
-                kids.append((int(child[side]), rows + 1, cols + 1, depth + 1, child_label,
-                             path + [desc], label))
-                print(f"{name} branch (branch {child_label}) infeasible")  # (sic) :1130 / :1193
+                kids.append((depth + 1, child_label, path + [desc], label))
+                emit(f"{name} branch (branch {child_label}) infeasible")  # (sic) :1130 / :1193
             for i, t in enumerate(shown[:-1]):
                 display(t, f"branch {child_label} {name} branch Tableau {i + 1}")
             if shown:
                 display(shown[-1], f"branch {child_label} {name} branch final tableau")
         for kid in reversed(kids):  # :1210-1213
             stack.append(kid)
-        tree.release([nid])
-    for item in stack:
-        tree.release([item[0]])
-    print("\n" + "-" * 50)
-    print("BRANCH AND BOUND COMPLETED")
-    print("-" * 50)
+    if capped:
+        emit("Potential infinite loop detected")  # :1040
+    emit("\n" + "-" * 50)
+    emit("BRANCH AND BOUND COMPLETED")
+    emit("-" * 50)
     if optimal_x is not None:
-        display(optimal_tab, f"Optimal solution tableau at branch {optimal_label}")
-        print(f"Optimal branch: {optimal_label}")
-        print(f"Optimal integer solution: [{_join(optimal_x)}]")
-        print(f"Optimal value: {_g(optimal_z)}")
+        display(incumbent_tab, f"Optimal solution tableau at branch {optimal_label}")
+        emit(f"Optimal branch: {optimal_label}")
+        emit(f"Optimal integer solution: [{_join(optimal_x)}]")
+        emit(f"Optimal value: {_g(optimal_z)}")
     else:
-        print("No integer solution found")
-    print(f"Total branchs processed: {branch_count}")
-    return optimal_x, optimal_z, branch_count
+        emit("No integer solution found")
+    emit(f"Total branchs processed: {branch_count}")
+    return "".join(out), optimal_x, optimal_z, branch_count
+
+
+def execute_branch_and_bound_narrated(tree: "BranchBoundTree", root_shape: Tuple[int, int],
+                                      enable_pruning: bool = False, node_cap: int = 0):
+    """ExecuteBranchAndBound (:1006-1233) on one tree, WRITING WHAT THE C# WRITES to the console:
+    gather_branch_and_bound_numbers drives the search on the device and
+    format_branch_and_bound orders and formats its numbers, only for textbook-sized models (the
+    adapter's narrate="auto": <= 4 096 tableau entries).  Same search, same answer as lpr_bb_run.
+    Returns (x or None, z, processed)."""
+    pops, tab, capped = gather_branch_and_bound_numbers(tree, root_shape, enable_pruning, node_cap)
+    _, x, z, processed = format_branch_and_bound(tree.nvars, pops, tab, capped, enable_pruning,
+                                                 write=lambda s, end: print(s, end=end))
+    return x, z, processed
 
 
 class BranchAndBoundAdapter:

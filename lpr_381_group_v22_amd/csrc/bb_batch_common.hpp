@@ -3,6 +3,7 @@
 #pragma once
 
 #include "batch_common.hpp"
+#include "bb_narr_layout.hpp"
 
 namespace lpr {
 
@@ -70,6 +71,20 @@ struct BBBatchBufs {
     int32_t* trace;  // 4 per quad
     int32_t* ints;
     int32_t* stk;
+};
+
+// What a narrated batch adds (the layout is stated in bb_narr_layout.hpp),
+// passed by value to k_bb_batch_narr.  Records and pops are addressed with the IP's rec_off /
+// pop_off; its pop values start at node_cap * x_off.
+struct BBNarr {
+    BBNarrDesc* desc;
+    double* slab;        // child tableaux, compact per IP
+    double* best;        // incumbent tableaux: slot_n doubles per IP
+    int64_t* tab_off;    // per record
+    int32_t* ntab;       // per record
+    double* pop_z;       // per pop
+    int32_t* pop_flags;  // per pop
+    double* pop_vals;    // nvars per pop
 };
 
 // Doubles of LDS (or of the work slab) one IP needs: the working pair at full depth and the factor

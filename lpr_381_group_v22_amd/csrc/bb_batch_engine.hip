@@ -15,6 +15,11 @@ int bb_batch_launch(int form, hipStream_t s, const BBBatchBufs& B, const int32_t
 void bb_batch_launch_load(hipStream_t s, const BBBatchDesc* desc, int count, const double* src,
                           const int64_t* src_off, double* stack);
 void bb_batch_launch_reset(hipStream_t s, const BBBatchBufs& B, int count);
+int bb_batch_narr_launch(int form, hipStream_t s, const BBBatchBufs& B, const BBNarr& narr,
+                         const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
+                         int chunk, int slot_doubles, int max_rows);
+void bb_batch_narr_launch_reset(hipStream_t s, const BBBatchBufs& B, const BBNarr& narr,
+                                int count);
 lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
 }  // namespace lpr
 
@@ -30,6 +35,11 @@ struct lpr_bb_batch {
     BatchRunLists run;                // the running lists and their counters
     int64_t x_total = 0, rec_total = 0, trace_total = 0;
     bool ran = false;
+    // narrated (lpr_bb_batch_narrate_reserve, section 23): narr.desc != nullptr
+    BBNarr narr{};
+    std::vector<BBNarrDesc> h_narr;  // host mirror, current after every reserve / run
+    int64_t narr_n = 0;              // doubles of narr.slab
+    bool narr_ran = false;           // a run since the last reserve
 };
 
 namespace {
@@ -40,7 +50,22 @@ int bbb_oom(const char* what, int64_t n, size_t elem) {
     return LPR_OUT_OF_MEMORY;
 }
 
+void bbb_release_narr(lpr_bb_batch* b) {
+    hipFree(b->narr.desc);
+    hipFree(b->narr.slab);
+    hipFree(b->narr.best);
+    hipFree(b->narr.tab_off);
+    hipFree(b->narr.ntab);
+    hipFree(b->narr.pop_z);
+    hipFree(b->narr.pop_flags);
+    hipFree(b->narr.pop_vals);
+    b->narr = BBNarr{};
+    b->narr_n = 0;
+    b->narr_ran = false;
+}
+
 void bbb_release_device(lpr_bb_batch* b) {
+    bbb_release_narr(b);
     hipFree(b->d.desc);
     hipFree(b->d.stack);
     hipFree(b->d.work);
@@ -367,12 +392,25 @@ int lpr_bb_batch_run(lpr_bb_batch* b, const lpr_bb_batch_opts* opts, lpr_bb_batc
                            hipMemcpyHostToDevice, s));
     bb_batch_launch_reset(s, b->d, count);
     LPR_HIP(hipGetLastError());
+    const bool narrated = b->narr.desc != nullptr;
+    if (narrated) {
+        bb_batch_narr_launch_reset(s, b->d, b->narr, count);
+        LPR_HIP(hipGetLastError());
+    }
     int launches = 0;
     rc = b->run.rounds(s, [&](int f, const int32_t* in, int n_in, int32_t* out, int32_t* n_out) {
-        return bb_batch_launch(f, s, b->d, in, n_in, out, n_out,
-                               o.chunk > 0 ? o.chunk : kBBBatchChunk[f], slot[f], max_rows);
+        const int chunk = o.chunk > 0 ? o.chunk : kBBBatchChunk[f];
+        if (narrated)
+            return bb_batch_narr_launch(f, s, b->d, b->narr, in, n_in, out, n_out, chunk, slot[f],
+                                        max_rows);
+        return bb_batch_launch(f, s, b->d, in, n_in, out, n_out, chunk, slot[f], max_rows);
     }, &launches);
     if (rc != LPR_OK_OPTIMAL) return rc;
+    if (narrated) {
+        LPR_HIP(hipMemcpyAsync(b->h_narr.data(), b->narr.desc, (size_t)count * sizeof(BBNarrDesc),
+                               hipMemcpyDeviceToHost, s));
+        b->narr_ran = true;
+    }
     LPR_HIP(hipMemcpyAsync(b->h_desc.data(), b->d.desc, (size_t)count * sizeof(BBBatchDesc),
                            hipMemcpyDeviceToHost, s));
     LPR_HIP(hipStreamSynchronize(s));
@@ -492,6 +530,233 @@ int lpr_bb_batch_trace_read(lpr_bb_batch* b, int32_t k, int32_t* quads, int64_t 
     *count = n;
     if (n == 0 || !quads) return LPR_OK_OPTIMAL;
     LPR_HIP(hipMemcpyAsync(quads, b->d.trace + 4 * d.trace_off, (size_t)n * 4 * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// ------------------------------------------------------------------------------------------
+// Narration: what ExecuteBranchAndBound writes to the console, as numbers.
+
+static bool bbb_narrated(const char* where, const lpr_bb_batch* b) {
+    if (b->narr.desc) return true;
+    set_error("%s: the batch is not narrated (call lpr_bb_batch_narrate_reserve first)", where);
+    return false;
+}
+
+static bool bbb_narr_ip(const char* where, const lpr_bb_batch* b, int32_t k) {
+    if (k >= 0 && k < b->count) return true;
+    set_error("%s: IP %d out of range (0..%d)", where, k, b->count - 1);
+    return false;
+}
+
+// Makes the handle narrated: room for cap_doubles[k] doubles of child tableaux (the lists
+// DoDualSimplex returns, :292 / :341 / :388) per IP, and the per-pop and incumbent buffers
+int lpr_bb_batch_narrate_reserve(lpr_bb_batch* b, const int64_t* cap_doubles) {
+    static const char* W = "lpr_bb_batch_narrate_reserve";
+    LPR_LIVE_HANDLE(b, "B&B batch");
+    if (!cap_doubles) {
+        set_error("%s: null cap_doubles", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    const int32_t count = b->count;
+    for (int32_t k = 0; k < count; ++k)
+        if (cap_doubles[k] < 0) {
+            set_error("%s: cap_doubles[%d] = %lld < 0", W, k, (long long)cap_doubles[k]);
+            return LPR_BAD_ARGUMENT;
+        }
+    std::vector<BBNarrDesc> nd;
+    try {
+        nd.resize((size_t)count);
+    } catch (...) {
+        return bbb_oom("narration descriptors", count, sizeof(BBNarrDesc));
+    }
+    static const char* kSlab = "narration slab: the reserved doubles of child tableaux per IP";
+    int64_t total = 0, best = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        BBNarrDesc& c = nd[(size_t)k];
+        std::memset(&c, 0, sizeof c);
+        c.slab_off = total;
+        c.cap = cap_doubles[k];
+        c.best_off = best;
+        c.best_depth = -1;
+        if (total > INT64_MAX / (int64_t)sizeof(double) - c.cap) {
+            set_error("lpr_bb_batch: cannot allocate %s (more than 2^63 bytes at IP %d of %d)",
+                      kSlab, k, count);
+            return LPR_OUT_OF_MEMORY;
+        }
+        total += c.cap;
+        best += b->h_desc[(size_t)k].slot_n();
+    }
+    hipStream_t s = b->eng->stream;
+    LPR_HIP(hipStreamSynchronize(s));
+    bbb_release_narr(b);  // the old slab goes first: the two need not fit side by side
+    auto one = [](int64_t n) { return std::max<int64_t>(n, 1); };
+    auto gb = [](int64_t n, size_t elem) {
+        return [=](const char* what, int64_t) { return bbb_oom(what, n, elem); };
+    };
+    const int64_t pop = (int64_t)count * b->node_cap;
+    const int64_t pv = (int64_t)b->node_cap * b->x_total;
+    int rc = LPR_OK_OPTIMAL;
+    BBNarr& D = b->narr;
+    dev_alloc(&D.slab, one(total), kSlab, &rc, gb(total, sizeof(double)));
+    dev_alloc(&D.best, one(best), "incumbent tableaux", &rc, gb(best, sizeof(double)));
+    dev_alloc(&D.tab_off, one(b->rec_total), "child tableau offsets", &rc,
+              gb(b->rec_total, sizeof(int64_t) + sizeof(int32_t)));
+    dev_alloc(&D.ntab, one(b->rec_total), "child tableau offsets", &rc,
+              gb(b->rec_total, sizeof(int64_t) + sizeof(int32_t)));
+    dev_alloc(&D.pop_z, one(pop), "pop scores", &rc, gb(pop, sizeof(double) + sizeof(int32_t)));
+    dev_alloc(&D.pop_flags, one(pop), "pop scores", &rc,
+              gb(pop, sizeof(double) + sizeof(int32_t)));
+    dev_alloc(&D.pop_vals, one(pv), "pop decision values", &rc, gb(pv, sizeof(double)));
+    dev_alloc(&D.desc, count, "narration descriptors", &rc, gb(count, sizeof(BBNarrDesc)));
+    auto fill = [&]() -> int {
+        LPR_HIP(hipMemcpyAsync(D.desc, nd.data(), (size_t)count * sizeof(BBNarrDesc),
+                               hipMemcpyHostToDevice, s));
+        // what no record reaches reads as +0.0
+        LPR_HIP(hipMemsetAsync(D.slab, 0, (size_t)one(total) * sizeof(double), s));
+        LPR_HIP(hipMemsetAsync(D.pop_vals, 0, (size_t)one(pv) * sizeof(double), s));
+        LPR_HIP(hipStreamSynchronize(s));
+        return LPR_OK_OPTIMAL;
+    };
+    if (rc == LPR_OK_OPTIMAL) rc = fill();
+    if (rc != LPR_OK_OPTIMAL) {
+        bbb_release_narr(b);  // usable, and un-narrated
+        return rc;
+    }
+    b->h_narr.swap(nd);
+    b->narr_n = total;
+    return LPR_OK_OPTIMAL;
+}
+
+// Per IP: tableaux and doubles the child LPs of the last run made (exact), doubles kept (a
+// prefix of those made), and where the IP's slice starts in the slab; any may be NULL
+int lpr_bb_batch_narrate_info(lpr_bb_batch* b, int64_t* tableaux, int64_t* doubles_made,
+                              int64_t* doubles_kept, int64_t* offset) {
+    LPR_LIVE_HANDLE(b, "B&B batch");
+    if (!bbb_narrated("lpr_bb_batch_narrate_info", b)) return LPR_BAD_ARGUMENT;
+    for (int32_t k = 0; k < b->count; ++k) {
+        const BBNarrDesc& c = b->h_narr[(size_t)k];
+        if (tableaux) tableaux[k] = c.made_t;
+        if (doubles_made) doubles_made[k] = c.made_d;
+        if (doubles_kept) doubles_kept[k] = c.cur;
+        if (offset) offset[k] = c.slab_off;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+// The pops of IP k in pop order (:1045-1076): flags (bit 0 scored, bit 1 every decision value
+// integer, bit 2 became the incumbent), objVal, and nvars decision values per pop
+int lpr_bb_batch_narrate_pops_read(lpr_bb_batch* b, int32_t k, int32_t* flags, double* z,
+                                   double* vals, int64_t cap, int64_t* count) {
+    static const char* W = "lpr_bb_batch_narrate_pops_read";
+    LPR_LIVE_HANDLE(b, "B&B batch");
+    if (!bbb_narrated(W, b)) return LPR_BAD_ARGUMENT;
+    int rc = bbb_ip(b, W, k, cap, count);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    const BBBatchDesc& d = b->h_desc[(size_t)k];
+    const int64_t n = b->narr_ran ? std::min<int64_t>(d.processed, cap) : 0;
+    *count = n;
+    if (n == 0) return LPR_OK_OPTIMAL;
+    hipStream_t s = b->eng->stream;
+    if (flags)
+        LPR_HIP(hipMemcpyAsync(flags, b->narr.pop_flags + d.pop_off, (size_t)n * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+    if (z)
+        LPR_HIP(hipMemcpyAsync(z, b->narr.pop_z + d.pop_off, (size_t)n * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+    if (vals && d.nvars > 0)
+        LPR_HIP(hipMemcpyAsync(vals, b->narr.pop_vals + (int64_t)d.node_cap * d.x_off,
+                               (size_t)(n * d.nvars) * sizeof(double), hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    return LPR_OK_OPTIMAL;
+}
+
+// Per record of IP k: where its child LP's tableaux start (doubles from the IP's slice start) and
+// how many DoDualSimplex's list holds (:292, :341, :388, after the drop of :392-400)
+int lpr_bb_batch_narrate_children_read(lpr_bb_batch* b, int32_t k, int64_t* tab_off,
+                                       int32_t* ntab, int64_t cap, int64_t* count) {
+    static const char* W = "lpr_bb_batch_narrate_children_read";
+    LPR_LIVE_HANDLE(b, "B&B batch");
+    if (!bbb_narrated(W, b)) return LPR_BAD_ARGUMENT;
+    int rc = bbb_ip(b, W, k, cap, count);
+    if (rc != LPR_OK_OPTIMAL) return rc;
+    const BBBatchDesc& d = b->h_desc[(size_t)k];
+    const int64_t n = b->narr_ran ? std::min<int64_t>(d.nrec, cap) : 0;
+    *count = n;
+    if (n == 0) return LPR_OK_OPTIMAL;
+    hipStream_t s = b->eng->stream;
+    if (tab_off)
+        LPR_HIP(hipMemcpyAsync(tab_off, b->narr.tab_off + d.rec_off, (size_t)n * sizeof(int64_t),
+                               hipMemcpyDeviceToHost, s));
+    if (ntab)
+        LPR_HIP(hipMemcpyAsync(ntab, b->narr.ntab + d.rec_off, (size_t)n * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    return LPR_OK_OPTIMAL;
+}
+
+// Doubles [first_double, first_double + n) of IP k's slice: the tableaux DisplayTableau prints
+// (:623-640), unrounded
+int lpr_bb_batch_narrate_tableaux_read(lpr_bb_batch* b, int32_t k, int64_t first_double,
+                                       int64_t n, double* out) {
+    static const char* W = "lpr_bb_batch_narrate_tableaux_read";
+    LPR_LIVE_HANDLE(b, "B&B batch");
+    if (!bbb_narrated(W, b) || !bbb_narr_ip(W, b, k)) return LPR_BAD_ARGUMENT;
+    const BBNarrDesc& c = b->h_narr[(size_t)k];
+    const int64_t kept = b->narr_ran ? c.cur : 0;
+    if (first_double < 0 || n < 0 || first_double > kept || n > kept - first_double) {
+        set_error("%s: doubles [%lld, %lld + %lld) of IP %d, which keeps %lld of %lld made", W,
+                  (long long)first_double, (long long)first_double, (long long)n, k,
+                  (long long)kept, (long long)c.made_d);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (n == 0) return LPR_OK_OPTIMAL;
+    if (!out) {
+        set_error("%s: null output", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    LPR_HIP(hipMemcpyAsync(out, b->narr.slab + c.slab_off + first_double,
+                           (size_t)n * sizeof(double), hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// The whole slab in one copy (every IP's child tableaux); cap_doubles is what `out` holds
+int lpr_bb_batch_narrate_read_all(lpr_bb_batch* b, double* out, int64_t cap_doubles) {
+    static const char* W = "lpr_bb_batch_narrate_read_all";
+    LPR_LIVE_HANDLE(b, "B&B batch");
+    if (!bbb_narrated(W, b)) return LPR_BAD_ARGUMENT;
+    if (cap_doubles < b->narr_n || (!out && b->narr_n > 0)) {
+        set_error("%s: null output, or cap_doubles %lld below the slab's %lld doubles", W,
+                  (long long)cap_doubles, (long long)b->narr_n);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (b->narr_n == 0) return LPR_OK_OPTIMAL;
+    LPR_HIP(hipMemcpyAsync(out, b->narr.slab, (size_t)b->narr_n * sizeof(double),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// bestTableau of IP k (:935-983, printed at :1221): the incumbent's node as popped, rows x cols;
+// out may be NULL to ask for the shape
+int lpr_bb_batch_narrate_best_read(lpr_bb_batch* b, int32_t k, double* out, int32_t* rows,
+                                   int32_t* cols) {
+    static const char* W = "lpr_bb_batch_narrate_best_read";
+    LPR_LIVE_HANDLE(b, "B&B batch");
+    if (!bbb_narrated(W, b) || !bbb_narr_ip(W, b, k)) return LPR_BAD_ARGUMENT;
+    const BBNarrDesc& c = b->h_narr[(size_t)k];
+    const BBBatchDesc& d = b->h_desc[(size_t)k];
+    if (!b->narr_ran || c.best_depth < 0) {
+        set_error("%s: IP %d has no incumbent (\"No integer solution found\", :1229)", W, k);
+        return LPR_BAD_ARGUMENT;
+    }
+    const int32_t r = d.rows + c.best_depth, cc = d.cols + c.best_depth;
+    if (rows) *rows = r;
+    if (cols) *cols = cc;
+    if (!out) return LPR_OK_OPTIMAL;
+    LPR_HIP(hipMemcpyAsync(out, b->narr.best + c.best_off, (size_t)r * cc * sizeof(double),
                            hipMemcpyDeviceToHost, b->eng->stream));
     LPR_HIP(hipStreamSynchronize(b->eng->stream));
     return LPR_OK_OPTIMAL;

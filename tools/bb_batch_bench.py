@@ -16,6 +16,16 @@ bit for bit (status, found, processed, best_node, z, x, every record, pop order,
 kept trace); any mismatch makes the exit status non-zero.  Inputs are seeded (numpy
 RandomState(seed + workload)).
 
+--narrate measures the narrated batch instead, per workload (--ips N keeps
+the first N IPs of each): (a) narrated end to end -- create, the two-pass reserve (reserve 0, run,
+read the needs, reserve them), run, lpr_bb_batch_narrate_read_all; (a') that narrated run alone;
+(b) the un-narrated end to end and run in the same process; (c) the per-model number-gathering
+loop of the single-handle path (gather_branch_and_bound_numbers, no formatting) on a timed prefix,
+marked "extrapolated" where scaled to the whole workload.  The only speed-up stated is (c)/(a).
+256 IPs per workload are compared record by record with that loop's numbers (pop scores, child
+status, pivots and every child tableau, the incumbent's tableau); mismatches make the exit status
+non-zero.
+
 Run it under a time limit:  timeout -k 10 1200 python tools/bb_batch_bench.py [--out FILE]
 Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python
 tools/bb_batch_bench.py --no-check --repeat 1
@@ -127,6 +137,129 @@ def run_batch(N, eng, packed):
     return t3 - t0, t2 - t1, res, out
 
 
+def run_narrated(N, eng, packed):
+    """One narrated end-to-end pass: (seconds end to end, seconds of the second run, result,
+    info arrays, the slab, the handle)."""
+    rows, cols, flat, nv = packed
+    count = len(rows)
+    h = C.c_void_p()
+    opts = N.BBBatchOpts(enable_pruning=0, chunk=0, variant=0, max_child_pivots=0)
+    res = N.BBBatchResult()
+    need, kept, off = (np.zeros(count, dtype=np.int64) for _ in range(3))
+    eng.sync()
+    t0 = time.perf_counter()
+    N.check(N.lib.lpr_bb_batch_create(eng._h, count, ptr(rows, C.c_int32), ptr(cols, C.c_int32),
+                                      ptr(flat, C.c_double), ptr(nv, C.c_int32), NODE_CAP,
+                                      TRACE_CAP, C.byref(h)), "lpr_bb_batch_create")
+    N.check(N.lib.lpr_bb_batch_narrate_reserve(h, ptr(need, C.c_int64)), "narrate_reserve")
+    N.check(N.lib.lpr_bb_batch_run(h, C.byref(opts), C.byref(res)), "lpr_bb_batch_run")
+    N.check(N.lib.lpr_bb_batch_narrate_info(h, None, ptr(need, C.c_int64), None, None),
+            "narrate_info")
+    N.check(N.lib.lpr_bb_batch_narrate_reserve(h, ptr(need, C.c_int64)), "narrate_reserve")
+    t1 = time.perf_counter()
+    N.check(N.lib.lpr_bb_batch_run(h, C.byref(opts), C.byref(res)), "lpr_bb_batch_run")
+    t2 = time.perf_counter()
+    N.check(N.lib.lpr_bb_batch_narrate_info(h, None, None, ptr(kept, C.c_int64),
+                                            ptr(off, C.c_int64)), "narrate_info")
+    slab = np.empty(max(int(need.sum()), 1))
+    N.check(N.lib.lpr_bb_batch_narrate_read_all(h, ptr(slab, C.c_double), slab.size),
+            "narrate_read_all")
+    eng.sync()
+    t3 = time.perf_counter()
+    return t3 - t0, t2 - t1, res, dict(need=need, kept=kept, off=off), slab, h
+
+
+def gather_loop(pkg, eng, roots, nvars, budget_s: float, skip):
+    """The single-handle number gathering (no formatting) on a timed prefix; the numbers of the
+    first CHECK IPs are kept for the record check."""
+    from lpr_381_group_v22_amd.branch_and_bound import gather_branch_and_bound_numbers
+    done, kept = 0, {}
+    t0 = time.perf_counter()
+    while done < len(roots) and (time.perf_counter() - t0 < budget_s or done < CHECK):
+        if not skip[done]:
+            tree = pkg.BranchBoundTree.from_array(eng, roots[done], nvars[done],
+                                                  max_depth=NODE_CAP)
+            got = gather_branch_and_bound_numbers(tree, roots[done].shape, False, NODE_CAP)
+            tree.destroy()
+            if done < CHECK:
+                kept[done] = got
+        done += 1
+    dt = time.perf_counter() - t0
+    return dict(ips=done, seconds=dt, ips_per_s=done / dt), kept
+
+
+def narr_check(bb, want) -> int:
+    """IPs whose narrated records differ from the single-handle loop's numbers in any bit."""
+    def same(a, b):
+        return np.asarray(a, dtype=np.float64).tobytes() == np.asarray(b, dtype=np.float64).tobytes()
+    bad = 0
+    for k, (pops, tab, capped) in want.items():
+        got, gtab, gcapped = bb.NarrationNumbers(k)
+        ok = gcapped == capped and len(got) == len(pops) and (gtab is None) == (tab is None)
+        ok = ok and (tab is None or same(gtab, tab))
+        for g, w in zip(got, pops) if ok else ():
+            ok = ok and same(g.z, w.z) and same(g.vals, w.vals)
+            ok = ok and (g.children is None) == (w.children is None)
+            for cg, cw in zip(g.children or [], w.children or []):
+                ok = ok and cg.status == cw.status and cg.pivots == cw.pivots
+                ok = ok and len(cg.tableaux) == len(cw.tableaux)
+                ok = ok and all(same(a, b) for a, b in zip(cg.tableaux, cw.tableaux))
+        bad += 0 if ok else 1
+    return bad
+
+
+def narrate_workload(pkg, N, eng, name, roots, nvars, packed, args):
+    from lpr_381_group_v22_amd.bb_batch import BranchAndBoundBatch, node_cap_of
+    count = len(roots)
+    plain, narr = [], []
+    for _ in range(max(1, args.repeat)):  # alternated, in one process
+        e2e, run, res, out = run_batch(N, eng, packed)
+        N.lib.lpr_bb_batch_destroy(out.pop("h"))
+        plain.append((e2e, run))
+        if narr:
+            N.lib.lpr_bb_batch_destroy(narr[-1][5])
+        narr.append(run_narrated(N, eng, packed))
+        progress(f"{name}: plain e2e {e2e:.4f}s run {run:.4f}s; narrated e2e {narr[-1][0]:.4f}s "
+                 f"run {narr[-1][1]:.4f}s")
+    e2e, run, res, info, slab, h = narr[-1]
+    a = min(r[0] for r in narr)
+    skip = np.zeros(count, dtype=bool)
+    st = np.zeros(count, dtype=np.int32)
+    N.check(N.lib.lpr_bb_batch_result_read(h, ptr(st, C.c_int32), None, None, None, None, None,
+                                           None), "lpr_bb_batch_result_read")
+    skip = st == N.LPR_PIVOT_LIMIT
+    rec = dict(workload=name, mode="narrate", ips=count, node_cap=NODE_CAP,
+               pops=int(res.pops), pivots=int(res.pivots), launches=res.launches,
+               slab_doubles=int(info["need"].sum()), slab_gb=8e-9 * float(info["need"].sum()),
+               kept_all=bool((info["kept"] == info["need"]).all()),
+               a_narrated_e2e_seconds=a, a_narrated_e2e_all=[r[0] for r in narr],
+               a1_narrated_run_seconds=min(r[1] for r in narr),
+               a1_narrated_run_all=[r[1] for r in narr],
+               b_plain_e2e_seconds=min(r[0] for r in plain), b_plain_e2e_all=[r[0] for r in plain],
+               b_plain_run_seconds=min(r[1] for r in plain), b_plain_run_all=[r[1] for r in plain],
+               pivot_limit_ips_skipped=int(skip.sum()))
+    if not args.no_check:
+        loop, want = gather_loop(pkg, eng, roots, nvars, args.single_seconds, skip)
+        c = loop["seconds"] * count / loop["ips"]
+        rec["c_single_gather"] = dict(loop, whole_workload_seconds=c,
+                                      extrapolated=loop["ips"] < count)
+        rec["speedup_c_over_a"] = c / a
+        bb = BranchAndBoundBatch(h, eng, zip(packed.rows.tolist(), packed.cols.tolist()),
+                                 packed.nvars, node_cap_of(NODE_CAP), TRACE_CAP)
+        bb._caps = info["need"]
+        checked = {k: v for k, v in want.items() if _whole(bb, k)}
+        rec["records_checked"] = len(checked)
+        rec["record_mismatches"] = narr_check(bb, checked)
+        bb._h = None  # the handle is destroyed below
+    N.lib.lpr_bb_batch_destroy(h)
+    return rec
+
+
+def _whole(bb, k) -> bool:
+    """IP k keeps its whole trace (TRACE_CAP quads): its numbers can be rebuilt."""
+    return bb.Result(k)["pivots"] <= bb.trace_cap
+
+
 def single_loop(pkg, eng, roots, nvars, budget_s: float, skip):
     done = pops = pivots = 0
     t0 = time.perf_counter()
@@ -216,6 +349,8 @@ def main() -> int:
     ap.add_argument("--single-seconds", type=float, default=5.0)
     ap.add_argument("--oracle-seconds", type=float, default=5.0)
     ap.add_argument("--no-check", action="store_true", help="skip the bit check and the loops")
+    ap.add_argument("--narrate", action="store_true", help="measure the narrated batch")
+    ap.add_argument("--ips", type=int, default=0, help="keep the first N IPs of each workload")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
 
@@ -233,8 +368,17 @@ def main() -> int:
             progress(f"{name}: generating")
             models = gen_models(name, args.seed + i)
             progress(f"{name}: primal batch")
+            if args.ips > 0:
+                models = models[:args.ips]
             roots, nvars = roots_of(pkg, N, eng, models)
             packed = pack_roots(roots, nvars, NODE_CAP)
+            if args.narrate:
+                rec = narrate_workload(pkg, N, eng, name, roots, nvars, packed, args)
+                failures += rec.get("record_mismatches", 0)
+                line = json.dumps(rec)
+                print(line, flush=True)
+                lines.append(line)
+                continue
             count = len(roots)
             forms = {f: 0 for f in "WGH"}
             for T in roots:
