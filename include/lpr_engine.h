@@ -1056,6 +1056,49 @@ int lpr_cut_batch_log_read(lpr_cut_batch* b, int32_t k, int32_t* triples, int64_
 /* T[0, cols - 1] of every item (what lpr_solve_result.z is in lpr_dual_solve). */
 int lpr_cut_batch_z_read(lpr_cut_batch* b, double* z);
 
+/* Narration: the numbers behind the console text of
+ * CuttingPlaneSolver.CuttingPlaneSolution (IntegerProgramming/CuttingPlaneSolver.cs:47-54, 64-229)
+ * -- "Initial tableau:", "Before / After pivot on cut: row r, col c", every tableau both clean-up
+ * solvers print under printSteps: true (Simplex/DualSimplex.cs:14-114, 193-207, 228-239;
+ * Simplex/PrimalSimplexSolver2.cs:46-97, 184-189) and the closing lines -- kept on the device by
+ * the kernel that makes them; the host only formats (cut_batch.py: format_cutting_plane).
+ *
+ * lpr_cut_batch_narrate_reserve makes the handle narrated: per item an event list of ev_cap
+ * events of four int32 (kind, a, b, rows_now) and cap_doubles[k] >= 0 doubles of tableau data,
+ * both appended over the handle's life as the log is.  Event kinds: 0 CALL (a mode, b
+ * print_steps; start of every lpr_cut_batch_run), 1 LEVEL (one CuttingPlaneSolution call :64;
+ * "Initial tableau:" :74 is the state at this point), 2 CUT (a the source row, 0-based among the
+ * constraint rows :96; the row of :110 is the next data block), 3 SOLVE_BEGIN (a 0 dual :188-190,
+ * 1 primal2 :198-200), 4 SOLVE_END (a the lpr_status of the inner solve -- DualSimplex.cs:42, :74,
+ * :110; PrimalSimplexSolver2.cs:58, :65, :92; LPR_PIVOT_TOO_SMALL for :156 / :149 -- b 1 where
+ * LPR_PIVOT_LIMIT came from opts.hard_cap and not from maxIters), 5 EXIT (a the code of
+ * lpr_cut_batch_result_read), 8 + q PIVOT (q the log kind 0 dual / 1 primal2 / 2 cut; a, b the
+ * row and column of the log triple; the whole rows_now x cols tableau after it is the next data
+ * block).  Data: block 0 is the rows x cols tableau at reserve time, then one block per CUT
+ * (cols doubles) and per PIVOT (rows_now x cols), back to back in event order.  A block that does
+ * not fit whole is counted and not written, and so is every later one; the made counts are exact.
+ * Allowed once and only before the first run: called twice, after a run, with NULL, with an entry
+ * < 0 or with ev_cap < 1 it is LPR_BAD_ARGUMENT.  A failed allocation is LPR_OUT_OF_MEMORY naming
+ * the buffer and its size, and leaves the handle usable and un-narrated.  Code, cuts, log and
+ * tableau of a narrated handle are those of an un-narrated one. */
+int lpr_cut_batch_narrate_reserve(lpr_cut_batch* b, const int64_t* cap_doubles, int32_t ev_cap);
+/* Per item: events made, doubles made, doubles kept (a whole number of blocks) and the offset of
+ * its slice in the data lpr_cut_batch_narrate_read_all copies; any may be NULL.  The reads below
+ * are LPR_BAD_ARGUMENT on an un-narrated handle. */
+int lpr_cut_batch_narrate_info(lpr_cut_batch* b, int64_t* events_made, int64_t* doubles_made,
+                               int64_t* doubles_kept, int64_t* data_off);
+/* Item k's events as quads: *count = all of them, the first min(*count, ev_cap, cap) copied. */
+int lpr_cut_batch_narrate_events_read(lpr_cut_batch* b, int32_t k, int32_t* quads, int64_t cap,
+                                      int64_t* count);
+/* n doubles of item k's data from first_double; a range beyond what is kept is refused. */
+int lpr_cut_batch_narrate_data_read(lpr_cut_batch* b, int32_t k, int64_t first_double, int64_t n,
+                                    double* out);
+/* Every item at once: the event buffer (count x ev_cap quads, item k at quad k * ev_cap) and the
+ * data slab (the sum of cap_doubles, item k at its data_off); either pointer may be NULL, a
+ * capacity below the size is LPR_BAD_ARGUMENT. */
+int lpr_cut_batch_narrate_read_all(lpr_cut_batch* b, int32_t* quads, int64_t cap_quads,
+                                   double* data, int64_t cap_doubles);
+
 
 /* ------------------------------------------------------------------ knapsack batch */
 

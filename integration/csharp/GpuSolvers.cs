@@ -625,6 +625,178 @@ namespace LPR_381_Group_V22.Simplex
         public void Dispose() { if (bb != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_destroy(bb), "lpr_bb_batch_destroy"); bb = IntPtr.Zero; } }
     }
 
+    /// <summary>
+    /// Many CuttingPlaneSolver.CuttingPlaneSolution runs in one device call (lpr_cut_batch_*).  Narrate() runs the
+    /// batch twice on two handles -- the first counts what every item makes, the second keeps it -- and Narration(k)
+    /// is what CuttingPlaneSolution writes to the console for item k (CuttingPlaneSolver.cs:47-54, 64-229 with the
+    /// printSteps text of DualSimplex.cs:14-114 and PrimalSimplexSolver2.cs:46-97), formatted from the events and
+    /// tableaux the kernel stored.  The single-tableau path (lpr_cutting_plane) pivots on the cut in the call that
+    /// appends it and cannot show the cut row: a one-item batch serves that caller.
+    /// </summary>
+    public class CuttingPlaneBatch : IDisposable
+    {
+        private IntPtr cb;                               // lpr_cut_batch*, the keeping handle after Narrate()
+        private readonly int[] rows0, cols;
+        private readonly double[] flat;
+        private readonly int maxCuts;
+        private long[] evMade, dMade, dKept, dataOff;
+        private int evCap;
+        private int[] quads;
+        private double[] data;
+        public int Count { get; }
+        public int[] ExitCode { get; private set; }
+
+        /// <summary>objectiveRow + constraintRows per item (:64-70), as row 0 and rows 1.. of each tableau.</summary>
+        public CuttingPlaneBatch(List<double[,]> tableaux, int maxCuts = 0)
+        {
+            Count = tableaux.Count; this.maxCuts = maxCuts;
+            rows0 = new int[Count]; cols = new int[Count];
+            var f = new List<double>();
+            for (int k = 0; k < Count; k++)
+            {
+                rows0[k] = tableaux[k].GetLength(0); cols[k] = tableaux[k].GetLength(1);
+                foreach (var v in tableaux[k]) f.Add(v);                        // row-major
+            }
+            flat = f.ToArray();
+        }
+
+        private IntPtr Create()
+        {
+            NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_create(Engine.Handle, Count, rows0, cols, flat, maxCuts, 0, out IntPtr h),
+                "lpr_cut_batch_create");
+            return h;
+        }
+
+        private static void RunOnce(IntPtr h)
+        {
+            var opts = new LprCutBatchOpts();
+            NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_run(h, ref opts, out _), "lpr_cut_batch_run");
+        }
+
+        /// <summary>CuttingPlaneSolution for every item, keeping what its console text needs.</summary>
+        public void Narrate()
+        {
+            Dispose();
+            evMade = new long[Count]; dMade = new long[Count]; dKept = new long[Count]; dataOff = new long[Count];
+            IntPtr counting = Create();
+            try
+            {
+                NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_narrate_reserve(counting, new long[Count], 1), "lpr_cut_batch_narrate_reserve");
+                RunOnce(counting);
+                NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_narrate_info(counting, evMade, dMade, null, null), "lpr_cut_batch_narrate_info");
+            }
+            finally { NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_destroy(counting), "lpr_cut_batch_destroy"); }
+            cb = Create();
+            evCap = (int)Math.Max(1, evMade.Max());
+            NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_narrate_reserve(cb, dMade, evCap), "lpr_cut_batch_narrate_reserve");
+            RunOnce(cb);
+            NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_narrate_info(cb, evMade, dMade, dKept, dataOff), "lpr_cut_batch_narrate_info");
+            quads = new int[4L * Count * evCap]; data = new double[Math.Max(1, dMade.Sum())];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_narrate_read_all(cb, quads, (long)Count * evCap, data, dMade.Sum()), "lpr_cut_batch_narrate_read_all");
+            ExitCode = new int[Count];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_result_read(cb, ExitCode, null, null, null), "lpr_cut_batch_result_read");
+        }
+
+        /// <summary>Item k's events (kind, a, b, rows_now), read on their own (Narrate() reads all of them at once).</summary>
+        public int[] Events(int k)
+        {
+            var q = new int[4 * evCap];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_narrate_events_read(cb, k, q, evCap, out long n), "lpr_cut_batch_narrate_events_read");
+            return q.Take(4 * (int)Math.Min(n, evCap)).ToArray();
+        }
+
+        /// <summary>n doubles of item k's data blocks from `first`, read on their own.</summary>
+        public double[] Data(int k, long first, long n)
+        {
+            var d = new double[Math.Max(1, n)];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_narrate_data_read(cb, k, first, n, d), "lpr_cut_batch_narrate_data_read");
+            return d;
+        }
+
+        private static string H4(double v) => v.ToString("0.####", System.Globalization.CultureInfo.InvariantCulture);
+
+        /// <summary>The console text of CuttingPlaneSolution for item k.  Throws where the item stopped at the cut
+        /// limit, on an escaped exception or kept less than it made: the reference has no text for those.</summary>
+        public string Narration(int k)
+        {
+            if (evMade[k] > evCap || dKept[k] < dMade[k]) throw new InvalidOperationException($"item {k} kept less than it made");
+            int C = cols[k], R = rows0[k];
+            long at = dataOff[k];
+            var T = new List<double[]>();
+            Func<int, double[]> take = n => { var r = new double[n]; Array.Copy(data, at, r, 0, n); at += n; return r; };
+            Action<int> load = rows => { T.Clear(); for (int i = 0; i < rows; i++) T.Add(take(C)); };
+            load(R);
+            var sb = new StringBuilder();
+            Action<string> wl = s => sb.Append(s).Append(Environment.NewLine);
+            Action<string> print = title =>                                     // CuttingPlaneSolver.PrintTableau :47-54
+            {
+                wl(title);
+                wl("z:  " + string.Join("\t", T[0].Select(H4)));
+                for (int i = 1; i < T.Count; i++) wl($"r{i}: " + string.Join("\t", T[i].Select(H4)));
+                wl("");
+            };
+            Func<double[,]> table = () => { var t = new double[T.Count, C]; for (int i = 0; i < T.Count; i++) for (int j = 0; j < C; j++) t[i, j] = T[i][j]; return t; };
+            Action dualTab = () => wl(TableIterationFormater.Format(table(), C - 1 - (T.Count - 1), "Dual Simplex Tableau"));   // DualSimplex.cs:193-207, 228-234
+            Action primalTab = () =>                                            // PrimalSimplexSolver2.cs:184-189
+            {
+                wl("OBJ: " + string.Join("\t", T[0].Select(H4)));
+                for (int i = 1; i < T.Count; i++) wl($"r{i}: " + string.Join("\t", T[i].Select(H4)));
+            };
+            bool fresh = true; int solver = 0, iter = 0;
+            for (long e = 0; e < evMade[k]; e++)
+            {
+                long q = 4 * ((long)k * evCap + e);
+                int kind = quads[q], a = quads[q + 1], b = quads[q + 2], rowsNow = quads[q + 3];
+                switch (kind)
+                {
+                    case 0: fresh = true; break;                                // CALL
+                    case 1:                                                     // LEVEL
+                        if (!fresh) wl("Objective optimal but RHS has fractional values → adding another Gomory cut...");   // :219
+                        fresh = false; print("Initial tableau:"); break;        // :74
+                    case 2: T.Add(take(C)); break;                              // CUT :110
+                    case 3:                                                     // SOLVE_BEGIN :188 / :198
+                        solver = a; iter = 0;
+                        wl(a == 0 ? "Negative RHS detected → running Dual Simplex..." : "Negative reduced cost detected → running Primal Simplex...");
+                        break;
+                    case 10:                                                    // the pivot on the cut :141-180
+                        print($"Before pivot on cut: row {a + 1}, col {b + 1}"); load(rowsNow); print($"After pivot on cut: row {a + 1}, col {b + 1}"); break;
+                    case 8:                                                     // DualSimplex.cs:91-105
+                    {
+                        int n = C - 1 - (T.Count - 1);
+                        wl($"\nIteration {++iter}: pivot @ constraint {a + 1}, column {(b < n ? $"x{b + 1}" : $"t{b - n + 1}")}");
+                        dualTab(); load(rowsNow); wl("After pivot:"); dualTab(); break;
+                    }
+                    case 9:                                                     // PrimalSimplexSolver2.cs:73-88
+                        wl($"\nIter {++iter}: pivot @ row {a}, col {b}"); primalTab(); load(rowsNow); wl("After pivot:"); primalTab(); break;
+                    case 4:                                                     // SOLVE_END
+                        if (b != 0 || a == 3) throw new InvalidOperationException($"item {k}: an inner solve stopped where the reference cannot");
+                        if (solver == 0)
+                        {
+                            wl(a == 0 ? "Dual phase complete: all RHS >= 0." : a == 2 ? "Infeasible: pivot row has no negative coefficients with non-zero ratios." : "Max iterations reached.");
+                            if (a == 0) print("After Dual Simplex:"); else wl("Dual Simplex failed (infeasible or max iters).");   // :191-192
+                        }
+                        else
+                        {
+                            wl(a == 0 ? "Optimal reached." : a == 1 ? "Unbounded: no valid leaving row." : "Max iterations reached.");
+                            print("After Primal Simplex:");                     // :211
+                        }
+                        break;
+                    case 5:                                                     // EXIT
+                        if (a == 0) wl("Displayed the Optimal Tableau.");        // :224
+                        else if (a == 1) wl("All RHS are integers. No Gomory cut needed.");   // :89
+                        else if (a == 2) wl("No valid pivot column on the cut (need a negative cut coeff with non-zero obj coeff).");   // :136
+                        else if (a == 3) { print($"Before pivot on cut: row {rowsNow - 1}, col {b + 1}"); wl("Pivot too small/zero."); }   // :148
+                        else if (a == 5) wl("Cutting-plane step finished (further steps may be required).");   // :228
+                        else if (a != 4) throw new InvalidOperationException($"item {k} ended at exit {a}: the reference has no text for it");
+                        break;
+                }
+            }
+            return sb.ToString();
+        }
+
+        public void Dispose() { if (cb != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_cut_batch_destroy(cb), "lpr_cut_batch_destroy"); cb = IntPtr.Zero; } }
+    }
+
     public class RevisedPrimalSimplexSolver : IDisposable
     {
         private readonly int n, m;

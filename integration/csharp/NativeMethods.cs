@@ -303,6 +303,11 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_tableau_read(IntPtr cutBatch, int k, [Out] double[,] rowmajor);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_log_read(IntPtr cutBatch, int k, int[] triples, long cap, out long count);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_z_read(IntPtr cutBatch, double[] z);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_narrate_reserve(IntPtr cutBatch, long[] cap_doubles, int ev_cap);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_narrate_info(IntPtr cutBatch, long[] events_made, long[] doubles_made, long[] doubles_kept, long[] data_off);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_narrate_events_read(IntPtr cutBatch, int k, [Out] int[] quads, long cap, out long count);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_narrate_data_read(IntPtr cutBatch, int k, long first_double, long n, [Out] double[] data);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_cut_batch_narrate_read_all(IntPtr cutBatch, [Out] int[] quads, long cap_quads, [Out] double[] data, long cap_doubles);
 
         // ---- Knapsack batch (DESIGN.md section 16): many option-5 instances per call ----
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_knap_batch_create(IntPtr engine, int count, long[] capacity, int[] n, double[] weights, double[] values, long[] node_cap, int narrate, out IntPtr knapBatch);

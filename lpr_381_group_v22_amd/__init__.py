@@ -10,7 +10,8 @@ from .bb_batch import (BranchAndBoundBatch, option3_texts, solve_integer_program
 from .branch_and_bound import (BranchAndBoundAdapter, BranchBoundTree, Comm,
                                solve_level_sync_native, solve_level_synchronous,
                                torch_collectives)
-from .cut_batch import CuttingPlaneBatch, pack_tableaux
+from .cut_batch import (CuttingPlaneBatch, cutting_plane_texts, format_cutting_plane,
+                        pack_tableaux)
 from .input_file_parser import Constraint, InputFileParser
 from .knapsack import KnapsackBranchBoundSimplex, KnapsackBranchBoundSolver
 from .knapsack_batch import KnapsackBatch, pack_knapsacks, solve_knapsacks
@@ -30,7 +31,8 @@ __all__ = [
     "option3_texts", "write_option3_files",
     "SensitivityBatch", "SensitivityGrowBatch", "pack_scripts", "pack_grow_scripts",
     "SensitivityModelBatch", "optimal_items",
-    "CuttingPlaneBatch", "pack_tableaux", "KnapsackBatch", "pack_knapsacks", "solve_knapsacks",
+    "CuttingPlaneBatch", "pack_tableaux", "cutting_plane_texts", "format_cutting_plane",
+    "KnapsackBatch", "pack_knapsacks", "solve_knapsacks",
     "RevisedSimplexBatch", "pack_revised_models",
     "_native",
 ]

@@ -465,6 +465,11 @@ SIGNATURES = {
     "lpr_cut_batch_tableau_read": (C.c_int, [_P, C.c_int32, _D]),
     "lpr_cut_batch_log_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
     "lpr_cut_batch_z_read": (C.c_int, [_P, _D]),
+    "lpr_cut_batch_narrate_reserve": (C.c_int, [_P, _I64, C.c_int32]),
+    "lpr_cut_batch_narrate_info": (C.c_int, [_P, _I64, _I64, _I64, _I64]),
+    "lpr_cut_batch_narrate_events_read": (C.c_int, [_P, C.c_int32, _I32, C.c_int64, _I64]),
+    "lpr_cut_batch_narrate_data_read": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D]),
+    "lpr_cut_batch_narrate_read_all": (C.c_int, [_P, _I32, C.c_int64, _D, C.c_int64]),
     "lpr_knap_batch_create": (C.c_int, [_P, C.c_int32, _I64, _I32, _D, _D, _I64, C.c_int32, _PP]),
     "lpr_knap_batch_destroy": (C.c_int, [_P]),
     "lpr_knap_batch_solve": (C.c_int, [_P, C.POINTER(KnapBatchOpts), C.POINTER(KnapBatchResult)]),

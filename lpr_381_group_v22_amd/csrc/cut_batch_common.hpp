@@ -1,10 +1,13 @@
-// cut_batch_common.hpp -- definitions shared by the batched cutting plane:
-// cut_batch_engine.hip (host) and cut_batch_kernels.hip.  Not part of the ABI
+// cut_batch_common.hpp -- definitions shared by the batched cutting plane (DESIGN.md sections 15
+// and 24): cut_batch_engine.hip (host), cut_batch_body.hpp (the one text of the state machine) and
+// its two instantiations, cut_batch_kernels.hip and cut_batch_narr_kernels.hip (the narrated
+// twins, which also keep what cut_narr_layout.hpp lays out).  Not part of the ABI
 // (include/lpr_engine.h is).
 #pragma once
 
 #include "batch_common.hpp"
 #include "cut_common.hpp"
+#include "cut_narr_layout.hpp"
 
 namespace lpr {
 
@@ -68,6 +71,13 @@ struct CutBatchCall {
     int64_t max_iters;    // modes 1, 2 (mode 0: kCutBatchInnerIters)
     int64_t hard_cap;     // per inner solve, <= 0: none
     int32_t chunk;
+};
+
+// The narration buffers of a narrated handle (cut_narr_layout.hpp); all null otherwise.
+struct CutNarr {
+    CutNarrDesc* desc = nullptr;  // count cursors
+    int32_t* ev = nullptr;        // events: four int32 each, packed by ev_cap
+    double* data = nullptr;       // the data slab: cap doubles per item
 };
 
 }  // namespace lpr

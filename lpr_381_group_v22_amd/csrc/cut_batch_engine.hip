@@ -14,6 +14,14 @@ int cut_batch_launch(int form, hipStream_t s, CutBatchDesc* desc, double* slab, 
                      int32_t* idx_out, int32_t* n_out);
 int cut_batch_launch_load(hipStream_t s, CutBatchDesc* desc, int count, const double* src,
                           const int64_t* src_off, double* slab);
+// cut_batch_narr_kernels.hip
+int cut_batch_narr_launch(int form, hipStream_t s, CutBatchDesc* desc, double* slab,
+                          int32_t* logs, const CutBatchCall& call, const CutNarr& narr, size_t lds,
+                          const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out);
+int cut_batch_narr_launch_first(hipStream_t s, const CutBatchDesc* desc, const double* slab,
+                                const CutNarr& narr, int count);
+int cut_batch_narr_launch_call(hipStream_t s, const CutBatchDesc* desc, const CutNarr& narr,
+                               int count, int mode, int print_steps);
 // batch_engine.hip
 lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
 }  // namespace lpr
@@ -29,6 +37,13 @@ struct lpr_cut_batch {
     double* slab = nullptr;            // every tableau at capacity: rcap x cols per item
     int32_t* logs = nullptr;           // packed by log_cap triples
     BatchRunLists run;
+    // narration: set by lpr_cut_batch_narrate_reserve, before the first run
+    bool ran = false;                 // lpr_cut_batch_run has been called
+    bool narrated = false;
+    CutNarr narr;                     // device
+    std::vector<CutNarrDesc> h_narr;  // host mirror, current after reserve and every run
+    int64_t narr_doubles = 0;         // the data slab: the sum of the caps
+    int64_t narr_events = 0;          // the event buffer: count * ev_cap quads
 };
 
 namespace {
@@ -38,7 +53,16 @@ int cb_oom(const char* what, int64_t n) {
     return LPR_OUT_OF_MEMORY;
 }
 
+void cb_release_narr(lpr_cut_batch* b) {
+    hipFree(b->narr.desc);
+    hipFree(b->narr.ev);
+    hipFree(b->narr.data);
+    b->narr = CutNarr();
+    b->narrated = false;
+}
+
 void cb_release_device(lpr_cut_batch* b) {
+    cb_release_narr(b);
     hipFree(b->desc);
     hipFree(b->slab);
     hipFree(b->logs);
@@ -277,6 +301,7 @@ int lpr_cut_batch_run(lpr_cut_batch* b, const lpr_cut_batch_opts* opts, lpr_cut_
         return LPR_BAD_ARGUMENT;
     }
     std::memset(res, 0, sizeof *res);
+    b->ran = true;
     hipStream_t s = b->eng->stream;
     const int32_t count = b->count;
     CutBatchCall call;
@@ -316,13 +341,23 @@ int lpr_cut_batch_run(lpr_cut_batch* b, const lpr_cut_batch_opts* opts, lpr_cut_
     if (rc != LPR_OK_OPTIMAL) return rc;
     LPR_HIP(hipMemcpyAsync(b->desc, b->h_desc.data(), (size_t)count * sizeof(CutBatchDesc),
                            hipMemcpyHostToDevice, s));
+    if (b->narrated) {
+        rc = cut_batch_narr_launch_call(s, b->desc, b->narr, count, call.mode, call.print_steps);
+        if (rc != LPR_OK_OPTIMAL) return rc;
+    }
     int launches = 0;
     rc = b->run.rounds(s, [&](int f, const int32_t* in, int n_in, int32_t* out, int32_t* n_out) {
         CutBatchCall c = call;
         c.chunk = o.chunk > 0 ? o.chunk : kCutBatchChunk[f];
+        if (b->narrated)
+            return cut_batch_narr_launch(f, s, b->desc, b->slab, b->logs, c, b->narr, lds[f], in,
+                                         n_in, out, n_out);
         return cut_batch_launch(f, s, b->desc, b->slab, b->logs, c, lds[f], in, n_in, out, n_out);
     }, &launches);
     if (rc != LPR_OK_OPTIMAL) return rc;
+    if (b->narrated)
+        LPR_HIP(hipMemcpyAsync(b->h_narr.data(), b->narr.desc,
+                               (size_t)count * sizeof(CutNarrDesc), hipMemcpyDeviceToHost, s));
     LPR_HIP(hipMemcpyAsync(b->h_desc.data(), b->desc, (size_t)count * sizeof(CutBatchDesc),
                            hipMemcpyDeviceToHost, s));
     LPR_HIP(hipStreamSynchronize(s));
@@ -403,6 +438,173 @@ int lpr_cut_batch_z_read(lpr_cut_batch* b, double* z) {
         return LPR_BAD_ARGUMENT;
     }
     for (int32_t k = 0; k < b->count; ++k) z[k] = b->h_desc[(size_t)k].z;
+    return LPR_OK_OPTIMAL;
+}
+
+// ---- narration ---------------------------------------------------------
+
+// What the console text of CuttingPlaneSolution (CuttingPlaneSolver.cs:47-54, 64-229) and of the
+// two clean-up solvers under printSteps (DualSimplex.cs:14-114, 193-207; PrimalSimplexSolver2.cs:
+// 46-97, 184-189) needs: from now on the handle launches the narrated kernels.
+int lpr_cut_batch_narrate_reserve(lpr_cut_batch* b, const int64_t* cap_doubles, int32_t ev_cap) {
+    static const char* W = "lpr_cut_batch_narrate_reserve";
+    LPR_LIVE_HANDLE(b, "cutting-plane batch");
+    if (b->narrated || b->ran || !cap_doubles || ev_cap < 1) {
+        set_error("%s: %s", W,
+                  b->narrated ? "the handle is narrated already"
+                  : b->ran    ? "the handle has run; reserve before the first lpr_cut_batch_run"
+                  : !cap_doubles ? "null cap_doubles" : "ev_cap < 1");
+        return LPR_BAD_ARGUMENT;
+    }
+    const int32_t count = b->count;
+    int64_t total = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        if (cap_doubles[k] < 0 || cap_doubles[k] > (INT64_MAX >> 4) - total) {
+            set_error("%s: cap_doubles[%d] = %lld", W, k, (long long)cap_doubles[k]);
+            return LPR_BAD_ARGUMENT;
+        }
+        total += cap_doubles[k];
+    }
+    try {
+        b->h_narr.assign((size_t)count, CutNarrDesc());
+    } catch (...) {
+        return cb_oom("narration cursors", count);
+    }
+    int64_t off = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        CutNarrDesc& c = b->h_narr[(size_t)k];
+        std::memset(&c, 0, sizeof c);
+        c.ev_off = (int64_t)k * ev_cap;
+        c.ev_cap = ev_cap;
+        c.data_off = off;
+        c.cap = cap_doubles[k];
+        off += c.cap;
+    }
+    b->narr_doubles = total;
+    b->narr_events = (int64_t)count * ev_cap;
+    hipStream_t s = b->eng->stream;
+    int rc = LPR_OK_OPTIMAL;
+    dev_alloc(&b->narr.desc, count, "narration cursors", &rc, cb_oom);
+    dev_alloc(&b->narr.ev, 4 * b->narr_events, "narration events: 4 x ev_cap int32 per item", &rc,
+              cb_oom);
+    dev_alloc(&b->narr.data, std::max<int64_t>(total, 1),
+              "narration data slab: the sum of cap_doubles", &rc, cb_oom);
+    if (rc == LPR_OK_OPTIMAL) {
+        // The data slab starts as 0xFF bytes (a quiet NaN in every double): what no kept block
+        // covers stays that, so a read of it cannot be mistaken for a stored value.
+        hipError_t err = hipMemsetAsync(b->narr.data, 0xFF,
+                                        (size_t)std::max<int64_t>(total, 1) * sizeof(double), s);
+        if (err == hipSuccess)
+            err = hipMemcpyAsync(b->narr.desc, b->h_narr.data(),
+                                 (size_t)count * sizeof(CutNarrDesc), hipMemcpyHostToDevice, s);
+        if (err == hipSuccess)
+            rc = cut_batch_narr_launch_first(s, b->desc, b->slab, b->narr, count);
+        if (err == hipSuccess && rc == LPR_OK_OPTIMAL)
+            err = hipMemcpyAsync(b->h_narr.data(), b->narr.desc,
+                                 (size_t)count * sizeof(CutNarrDesc), hipMemcpyDeviceToHost, s);
+        if (err == hipSuccess && rc == LPR_OK_OPTIMAL) err = hipStreamSynchronize(s);
+        if (err != hipSuccess) {
+            set_error("%s: writing block 0 failed: %s", W, hipGetErrorString(err));
+            rc = LPR_DEVICE_ERROR;
+        }
+    }
+    if (rc != LPR_OK_OPTIMAL) {  // the handle stays usable and un-narrated
+        cb_release_narr(b);
+        b->h_narr.clear();
+        return rc;
+    }
+    b->narrated = true;
+    return LPR_OK_OPTIMAL;
+}
+
+}  // extern "C"
+
+namespace {
+bool cb_narrated(const char* where, const lpr_cut_batch* b) {
+    if (b->narrated) return true;
+    set_error("%s: the handle is not narrated (lpr_cut_batch_narrate_reserve)", where);
+    return false;
+}
+}  // namespace
+
+extern "C" {
+
+// Per item: events made, doubles made, doubles kept, and where its slice starts in what
+// lpr_cut_batch_narrate_read_all copies.  Events kept = min(made, ev_cap), at quad k * ev_cap.
+int lpr_cut_batch_narrate_info(lpr_cut_batch* b, int64_t* events_made, int64_t* doubles_made,
+                               int64_t* doubles_kept, int64_t* data_off) {
+    LPR_LIVE_HANDLE(b, "cutting-plane batch");
+    if (!cb_narrated("lpr_cut_batch_narrate_info", b)) return LPR_BAD_ARGUMENT;
+    for (int32_t k = 0; k < b->count; ++k) {
+        const CutNarrDesc& c = b->h_narr[(size_t)k];
+        if (events_made) events_made[k] = c.ev_n;
+        if (doubles_made) doubles_made[k] = c.made_d;
+        if (doubles_kept) doubles_kept[k] = c.cur;
+        if (data_off) data_off[k] = c.data_off;
+    }
+    return LPR_OK_OPTIMAL;
+}
+
+int lpr_cut_batch_narrate_events_read(lpr_cut_batch* b, int32_t k, int32_t* quads, int64_t cap,
+                                      int64_t* count) {
+    static const char* W = "lpr_cut_batch_narrate_events_read";
+    LPR_LIVE_HANDLE(b, "cutting-plane batch");
+    if (!cb_narrated(W, b) || !cb_item_ok(W, b, k)) return LPR_BAD_ARGUMENT;
+    if (cap < 0 || !count) {
+        set_error("%s: cap %lld or null count", W, (long long)cap);
+        return LPR_BAD_ARGUMENT;
+    }
+    const CutNarrDesc& c = b->h_narr[(size_t)k];
+    *count = c.ev_n;
+    const int64_t n = std::min(std::min<int64_t>(c.ev_n, c.ev_cap), cap);
+    if (n == 0 || !quads) return LPR_OK_OPTIMAL;
+    LPR_HIP(hipMemcpyAsync(quads, b->narr.ev + 4 * c.ev_off, (size_t)n * 4 * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+int lpr_cut_batch_narrate_data_read(lpr_cut_batch* b, int32_t k, int64_t first_double, int64_t n,
+                                    double* out) {
+    static const char* W = "lpr_cut_batch_narrate_data_read";
+    LPR_LIVE_HANDLE(b, "cutting-plane batch");
+    if (!cb_narrated(W, b) || !cb_item_ok(W, b, k)) return LPR_BAD_ARGUMENT;
+    const CutNarrDesc& c = b->h_narr[(size_t)k];
+    if (first_double < 0 || n < 0 || first_double > c.cur || n > c.cur - first_double ||
+        (n > 0 && !out)) {
+        set_error("%s: item %d keeps %lld doubles; [%lld, %lld + %lld) is beyond them (or a null "
+                  "output)", W, k, (long long)c.cur, (long long)first_double,
+                  (long long)first_double, (long long)n);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (n == 0) return LPR_OK_OPTIMAL;
+    LPR_HIP(hipMemcpyAsync(out, b->narr.data + c.data_off + first_double,
+                           (size_t)n * sizeof(double), hipMemcpyDeviceToHost, b->eng->stream));
+    LPR_HIP(hipStreamSynchronize(b->eng->stream));
+    return LPR_OK_OPTIMAL;
+}
+
+// The whole event buffer (count x ev_cap quads) and the whole data slab (the sum of the caps) in
+// two copies; either may be NULL.
+int lpr_cut_batch_narrate_read_all(lpr_cut_batch* b, int32_t* quads, int64_t cap_quads,
+                                   double* data, int64_t cap_doubles) {
+    static const char* W = "lpr_cut_batch_narrate_read_all";
+    LPR_LIVE_HANDLE(b, "cutting-plane batch");
+    if (!cb_narrated(W, b)) return LPR_BAD_ARGUMENT;
+    if ((quads && cap_quads < b->narr_events) || (data && cap_doubles < b->narr_doubles)) {
+        set_error("%s: the events take %lld quads and the data %lld doubles; %lld / %lld given",
+                  W, (long long)b->narr_events, (long long)b->narr_doubles, (long long)cap_quads,
+                  (long long)cap_doubles);
+        return LPR_BAD_ARGUMENT;
+    }
+    hipStream_t s = b->eng->stream;
+    if (quads)
+        LPR_HIP(hipMemcpyAsync(quads, b->narr.ev, (size_t)b->narr_events * 4 * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+    if (data && b->narr_doubles > 0)
+        LPR_HIP(hipMemcpyAsync(data, b->narr.data, (size_t)b->narr_doubles * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
     return LPR_OK_OPTIMAL;
 }
 

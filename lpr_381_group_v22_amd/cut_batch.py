@@ -16,6 +16,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
+from . import table_iteration_formater as fmt
 from .engine import Engine, default_engine
 from .primal_batch import PrimalSimplexBatch
 
@@ -28,6 +29,264 @@ MAX_COLS_H = 2048
 MAX_LDS_G = 160 * 1024 - 1024    # kBatchMaxLdsG
 LOG_DEFAULT_MAX = 4096           # kBatchLogDefaultMax
 CHUNK = {FORM_G: 128, FORM_H: 16}  # kCutBatchChunk: pivots per item per launch
+
+# ---- narration; csrc/cut_narr_layout.hpp restated --------------------------
+# Per item: events of four int32 (kind, a, b, rows_now) -- the count exact, the first ev_cap kept --
+# and blocks of doubles back to back in event order: block 0 the rows x cols tableau at reserve
+# time, one block per EV_CUT (the appended row, cols doubles) and per pivot event (the whole
+# rows_now x cols tableau after it).  A block that does not fit whole is counted and not written,
+# and so is every later one.
+EV_CALL, EV_LEVEL, EV_CUT, EV_SOLVE_BEGIN, EV_SOLVE_END, EV_EXIT = 0, 1, 2, 3, 4, 5
+EV_PIVOT = 8                     # + the log kind: 8 dual, 9 primal2, 10 cut
+KIND_DUAL, KIND_PRIMAL2, KIND_CUT = 0, 1, 2
+ST_OK, ST_UNBOUNDED, ST_INFEASIBLE, ST_PIVOT_TOO_SMALL, ST_PIVOT_LIMIT = 0, 1, 2, 3, 5
+
+
+def event_doubles(kind: int, rows_now: int, cols: int) -> int:
+    """cut_narr_event_doubles: the doubles of the block an event adds."""
+    if kind == EV_CUT:
+        return cols
+    return rows_now * cols if kind >= EV_PIVOT else 0
+
+
+def block_offsets(events, rows0: int, cols: int) -> List[Tuple[int, int]]:
+    """(offset, doubles) of every block the events make, block 0 first: the prefix sum of
+    event_doubles."""
+    out = [(0, rows0 * cols)]
+    at = rows0 * cols
+    for kind, _a, _b, rows_now in events:
+        n = event_doubles(kind, rows_now, cols)
+        if n:
+            out.append((at, n))
+            at += n
+    return out
+
+
+def narr_push(c: dict, n: int) -> int:
+    """cut_narr_push on a dict of cursors (cap, cur, made_d, made_b, kept_b): where the block
+    goes, or -1 where it is only counted."""
+    keep = c["kept_b"] == c["made_b"] and n <= c["cap"] - c["cur"]
+    at = c["cur"] if keep else -1
+    c["made_b"] += 1
+    c["made_d"] += n
+    if keep:
+        c["kept_b"] += 1
+        c["cur"] += n
+    return at
+
+
+class NarrationInfo(NamedTuple):
+    """lpr_cut_batch_narrate_info, per item."""
+    events_made: np.ndarray
+    doubles_made: np.ndarray
+    doubles_kept: np.ndarray
+    data_off: np.ndarray
+
+
+class NarrationStopped(ValueError):
+    """The item has no complete C# text: it kept less than it made, or it ended where the
+    reference cannot (the cut limit, an escaped exception, a hard_cap stop)."""
+
+
+_DUAL_END = {ST_OK: "Dual phase complete: all RHS >= 0.",                          # :42
+             ST_INFEASIBLE: "Infeasible: pivot row has no negative coefficients with non-zero "
+                            "ratios.",                                             # :74
+             ST_PIVOT_LIMIT: "Max iterations reached."}                            # :110
+_PRIMAL2_END = {ST_OK: "Optimal reached.",                                         # :58
+                ST_UNBOUNDED: "Unbounded: no valid leaving row.",                  # :65
+                ST_PIVOT_LIMIT: "Max iterations reached."}                         # :92
+
+
+def _h4_row(row) -> str:
+    return "\t".join(fmt.H4(float(v)) for v in row)
+
+
+def format_cutting_plane(events, record0, blocks, newline: str = "\n",
+                         partial: bool = False) -> str:
+    """WHAT THE C# WRITES to the console in CuttingPlaneSolver.CuttingPlaneSolution
+    (IntegerProgramming/CuttingPlaneSolver.cs:47-54, 64-229, the recursion unrolled) and in the
+    two clean-up solvers under printSteps (Simplex/DualSimplex.cs:14-114, 193-207, 228-239;
+    Simplex/PrimalSimplexSolver2.cs:46-97, 184-189), from numbers alone: ``events`` are the
+    (kind, a, b, rows_now) quads of one item, ``record0`` its tableau at reserve time and
+    ``blocks`` the data blocks after it in event order (a 1-D row per EV_CUT, a 2-D tableau per
+    pivot).  Pure: no device, and no control flow beyond walking the events -- which branch was
+    taken is what the events say.  In modes 1 and 2 (EV_CALL's a) the text is that of
+    Solve(printSteps) alone.  Raises NarrationStopped where the text cannot go on: a block is
+    missing, or the item ended at exit 6, exit 7 or a hard_cap stop, which the reference cannot
+    reach; with ``partial`` the text up to there is returned.  ``newline`` ends every
+    Console.WriteLine (TableIterationFormater.Format keeps its own Environment.NewLine)."""
+    out: List[str] = []
+    T = np.array(record0, dtype=np.float64, copy=True)
+    nxt = iter(blocks)
+    mode, steps, fresh, solver, it = MODE_CUTTING_PLANE, True, True, None, 0
+
+    def emit(s: str = "") -> None:
+        out.append(s + newline)
+
+    def print_tableau(title: str) -> None:  # CuttingPlaneSolver.PrintTableau :47-54
+        emit(title)
+        emit("z:  " + _h4_row(T[0]))
+        for i in range(1, T.shape[0]):
+            emit(f"r{i}: " + _h4_row(T[i]))
+        emit()
+
+    def num_vars() -> int:  # DualSimplex.cs:228-234
+        return T.shape[1] - 1 - (T.shape[0] - 1)
+
+    def dual_tableau() -> None:  # DualSimplex.cs:193-207
+        emit(fmt.Format(T, num_vars(), "Dual Simplex Tableau"))
+
+    def primal2_tableau() -> None:  # PrimalSimplexSolver2.cs:184-189
+        emit("OBJ: " + _h4_row(T[0]))
+        for i in range(1, T.shape[0]):
+            emit(f"r{i}: " + _h4_row(T[i]))
+
+    class _Stop(Exception):
+        pass
+
+    if not partial:  # an ending without C# text is refused before anything is formatted
+        m = MODE_CUTTING_PLANE
+        for kind, a, b, _r in events:
+            if kind == EV_CALL:
+                m = a
+            elif (kind == EV_SOLVE_END and (b or a == ST_PIVOT_TOO_SMALL)) or \
+                    (kind == EV_EXIT and m == MODE_CUTTING_PLANE and a in (6, 7)):
+                raise NarrationStopped("the item ended at exit 6, exit 7 or a hard_cap stop: the "
+                                       "reference has no text for that (partial=True gives the "
+                                       "text up to there)")
+
+    def block(shape):
+        b = next(nxt, None)
+        if b is None:
+            raise _Stop("a data block was not kept")
+        return np.asarray(b, dtype=np.float64).reshape(shape)
+
+    try:
+        for kind, a, b, rows_now in events:
+            if kind == EV_CALL:
+                mode, steps, fresh = a, (bool(b) if a != MODE_CUTTING_PLANE else True), True
+            elif kind == EV_LEVEL:
+                if not fresh:                                                       # :219
+                    emit("Objective optimal but RHS has fractional values \u2192 adding another "
+                         "Gomory cut...")
+                fresh = False
+                print_tableau("Initial tableau:")                                   # :74
+            elif kind == EV_CUT:
+                T = np.vstack([T, block((1, T.shape[1]))])                          # :110
+            elif kind == EV_SOLVE_BEGIN:
+                solver, it = a, 0
+                if mode == MODE_CUTTING_PLANE:
+                    emit("Negative RHS detected \u2192 running Dual Simplex..." if a == KIND_DUAL
+                         else "Negative reduced cost detected \u2192 running Primal "
+                              "Simplex...")                                         # :188 / :198
+            elif kind == EV_PIVOT + KIND_CUT:
+                where = f"row {a + 1}, col {b + 1}"
+                print_tableau("Before pivot on cut: " + where)                      # :141-143
+                T = block((rows_now, T.shape[1]))
+                print_tableau("After pivot on cut: " + where)                       # :178-180
+            elif kind == EV_PIVOT + KIND_DUAL:
+                if steps:                                                           # :91-96
+                    it += 1
+                    n = num_vars()
+                    label = f"x{b + 1}" if b < n else f"t{b - n + 1}"               # :236-239
+                    emit(f"\nIteration {it}: pivot @ constraint {a + 1}, column {label}")
+                    dual_tableau()
+                T = block((rows_now, T.shape[1]))
+                if steps:                                                           # :100-105
+                    emit("After pivot:")
+                    dual_tableau()
+            elif kind == EV_PIVOT + KIND_PRIMAL2:
+                if steps:                                                           # :73-77
+                    it += 1
+                    emit(f"\nIter {it}: pivot @ row {a}, col {b}")
+                    primal2_tableau()
+                T = block((rows_now, T.shape[1]))
+                if steps:                                                           # :84-88
+                    emit("After pivot:")
+                    primal2_tableau()
+            elif kind == EV_SOLVE_END:
+                if b or a == ST_PIVOT_TOO_SMALL:
+                    raise _Stop("a hard_cap stop" if b else
+                                "InvalidOperationException: Pivot too small/zero")
+                if steps:
+                    emit((_DUAL_END if solver == KIND_DUAL else _PRIMAL2_END)[a])
+                if mode == MODE_CUTTING_PLANE:
+                    if solver == KIND_PRIMAL2:
+                        print_tableau("After Primal Simplex:")                      # :211
+                    elif a == ST_OK:
+                        print_tableau("After Dual Simplex:")                        # :192
+                    else:
+                        emit("Dual Simplex failed (infeasible or max iters).")      # :191
+            elif kind == EV_EXIT:
+                if mode != MODE_CUTTING_PLANE:
+                    continue
+                if a == 0:
+                    emit("Displayed the Optimal Tableau.")                          # :224
+                elif a == 1:
+                    emit("All RHS are integers. No Gomory cut needed.")             # :89
+                elif a == 2:
+                    emit("No valid pivot column on the cut (need a negative cut coeff with "
+                         "non-zero obj coeff).")                                    # :136
+                elif a == 3:
+                    print_tableau(f"Before pivot on cut: row {rows_now - 1}, col {b + 1}")
+                    emit("Pivot too small/zero.")                                   # :148
+                elif a == 5:
+                    emit("Cutting-plane step finished (further steps may be required).")  # :228
+                elif a != 4:
+                    raise _Stop(f"exit {a}")
+            else:
+                raise ValueError(f"unknown event kind {kind}")
+    except _Stop as e:
+        if not partial:
+            raise NarrationStopped(f"no C# text beyond this point: {e}") from None
+    return "".join(out)
+
+
+def format_primal2_snapshots(events, record0, blocks) -> List[str]:
+    """PrimalSimplexSolver2.IterationSnapshots (PrimalSimplexSolver2.cs:51, :71, :82, :168-182)
+    of the LAST mode-2 call among ``events``: "Start of iter {iter}" at the head of every pass,
+    "Before pivot (iter {iter + 1}) ..." and "After pivot (iter {iter}) ..." around every pivot,
+    each with "Current Tableau:" in 0.###.  `iter` moves only under printSteps (:75), as in the
+    C#.  A hard_cap stop has no C# counterpart: the list ends with the pass that met it."""
+    T = np.array(record0, dtype=np.float64, copy=True)
+    nxt = iter(blocks)
+    nl = fmt.NEWLINE
+    snaps: List[str] = []
+    mode, steps, it, pending = MODE_CUTTING_PLANE, True, 0, False
+
+    def capture(title: str) -> None:
+        rows = [title, "Current Tableau:",
+                "OBJ\t" + "\t".join(fmt.H3(float(v)) for v in T[0])]
+        rows += [f"r{i}\t" + "\t".join(fmt.H3(float(v)) for v in T[i])
+                 for i in range(1, T.shape[0])]
+        snaps.append("".join(r + nl for r in rows))
+
+    for kind, a, b, rows_now in events:
+        if kind == EV_CALL:
+            mode, steps = a, (bool(b) if a != MODE_CUTTING_PLANE else True)
+            if mode == MODE_PRIMAL2:
+                snaps, it, pending = [], 0, True
+        live = mode == MODE_PRIMAL2
+        if kind == EV_CUT or kind >= EV_PIVOT:
+            blk = next(nxt, None)
+            if blk is None:
+                raise NarrationStopped("a data block was not kept")
+            if live and pending:
+                capture(f"Start of iter {it}")                                      # :51
+            if live:
+                capture(f"Before pivot (iter {it + 1}) at row {a}, col {b}")        # :71
+                if steps:
+                    it += 1
+            T = (np.vstack([T, np.asarray(blk).reshape(1, -1)]) if kind == EV_CUT
+                 else np.asarray(blk, dtype=np.float64).reshape(rows_now, T.shape[1]))
+            if live:
+                capture(f"After pivot (iter {it}) at row {a}, col {b}")             # :82
+                pending = True
+        elif kind == EV_SOLVE_END and live:
+            if pending and not (a == ST_PIVOT_LIMIT and not b):  # :90 returns behind the pivot
+                capture(f"Start of iter {it}")
+            pending = False
+    return snaps
 
 
 def max_cuts_of(max_cuts: int) -> int:
@@ -108,6 +367,9 @@ class CuttingPlaneBatch:
         self.Count = int(count)
         self.max_cuts = max_cuts_of(max_cuts)
         self.LastResult: Optional[N.CutBatchResult] = None
+        self._narr_shape: Optional[List[Tuple[int, int]]] = None  # (rows, cols) at reserve time
+        self._ev_cap = 0
+        self._caps_total = 0
 
     @classmethod
     def from_arrays(cls, engine: Optional[Engine], tableaux: Sequence[np.ndarray],
@@ -211,3 +473,135 @@ class CuttingPlaneBatch:
         N.check(N.lib.lpr_cut_batch_log_read(self._h, int(k), None, 0, C.byref(cnt)),
                 "lpr_cut_batch_log_read")
         return cnt.value
+
+    # -- narration -------------------------------------------------------
+    def narrate_reserve(self, cap, ev_cap: int) -> None:
+        """Makes the handle narrated, before its first Run: ``cap`` doubles of tableau data per
+        item (one number for all, or one per item) and ``ev_cap`` events per item.  Caps of 0
+        keep nothing and count everything (narration_info)."""
+        caps = np.ascontiguousarray(np.broadcast_to(np.asarray(cap, dtype=np.int64),
+                                                    (self.Count,)))
+        shapes = [self.Shape(k) for k in range(self.Count)]
+        N.check(N.lib.lpr_cut_batch_narrate_reserve(self._h, caps.ctypes.data_as(
+            C.POINTER(C.c_int64)), int(ev_cap)), "lpr_cut_batch_narrate_reserve")
+        self._narr_shape, self._ev_cap, self._caps_total = shapes, int(ev_cap), int(caps.sum())
+
+    def narration_info(self) -> NarrationInfo:
+        a = [np.zeros(self.Count, dtype=np.int64) for _ in range(4)]
+        N.check(N.lib.lpr_cut_batch_narrate_info(self._h, *(_ptr(x, C.c_int64) for x in a)),
+                "lpr_cut_batch_narrate_info")
+        return NarrationInfo(*a)
+
+    def Events(self, k: int) -> List[Tuple[int, int, int, int]]:
+        """The (kind, a, b, rows_now) events kept for item k; narration_info gives the total."""
+        cnt = C.c_int64()
+        N.check(N.lib.lpr_cut_batch_narrate_events_read(self._h, int(k), None, 0, C.byref(cnt)),
+                "lpr_cut_batch_narrate_events_read")
+        n = min(cnt.value, self._ev_cap)
+        buf = np.zeros(max(4 * n, 4), dtype=np.int32)
+        N.check(N.lib.lpr_cut_batch_narrate_events_read(self._h, int(k), _ptr(buf, C.c_int32), n,
+                                                        C.byref(cnt)),
+                "lpr_cut_batch_narrate_events_read")
+        return [tuple(t) for t in buf[:4 * n].reshape(-1, 4).tolist()]
+
+    def NarrationData(self, k: int, first: int, n: int) -> np.ndarray:
+        out = np.zeros(max(int(n), 1), dtype=np.float64)
+        N.check(N.lib.lpr_cut_batch_narrate_data_read(self._h, int(k), int(first), int(n),
+                                                      _ptr(out, C.c_double)),
+                "lpr_cut_batch_narrate_data_read")
+        return out[:int(n)]
+
+    @staticmethod
+    def _split(events, shape, data: np.ndarray):
+        """Block 0 and the kept blocks after it, out of the kept doubles of one item."""
+        rows0, cols = shape
+        blocks = []
+        for (at, n), ev in zip(block_offsets(events, rows0, cols),
+                               [None] + [e for e in events if event_doubles(e[0], e[3], cols)]):
+            if at + n > data.size:
+                break
+            blk = data[at:at + n]
+            blocks.append(blk.reshape(rows0, cols) if ev is None else
+                          (blk.copy() if ev[0] == EV_CUT else blk.reshape(ev[3], cols)))
+        return (blocks[0] if blocks else None), blocks[1:]
+
+    def NarrationBlocks(self, k: int):
+        """(block 0, [the kept blocks after it]) of item k: a 1-D row per cut, a 2-D tableau per
+        pivot."""
+        kept = int(self.narration_info().doubles_kept[k])
+        return self._split(self.Events(k), self._narr_shape[k], self.NarrationData(k, 0, kept))
+
+    def narration_packed(self) -> Tuple[np.ndarray, np.ndarray]:
+        """Everything in two copies (lpr_cut_batch_narrate_read_all): the events as a count x
+        ev_cap x 4 array and the data slab, item k at narration_info().data_off[k]."""
+        ev = np.zeros((self.Count, self._ev_cap, 4), dtype=np.int32)
+        total = self._caps_total
+        data = np.zeros(max(total, 1), dtype=np.float64)
+        N.check(N.lib.lpr_cut_batch_narrate_read_all(self._h, _ptr(ev, C.c_int32),
+                                                     ev.size // 4, _ptr(data, C.c_double), total),
+                "lpr_cut_batch_narrate_read_all")
+        return ev, data[:total]
+
+    def _item_numbers(self, k: int, info: NarrationInfo, packed=None):
+        made_e, made_d, kept_d = (int(info.events_made[k]), int(info.doubles_made[k]),
+                                  int(info.doubles_kept[k]))
+        if packed is None:
+            events = self.Events(k)
+            data = self.NarrationData(k, 0, kept_d)
+        else:
+            ev, slab = packed
+            events = [tuple(t) for t in ev[k, :min(made_e, self._ev_cap)].tolist()]
+            at = int(info.data_off[k])
+            data = slab[at:at + kept_d]
+        rec0, blocks = self._split(events, self._narr_shape[k], data)
+        return events, rec0, blocks, (len(events) < made_e or kept_d < made_d)
+
+    def NarrationText(self, k: int, newline: str = "\n", partial: bool = False,
+                      _info=None, _packed=None) -> str:
+        """The console text of CuttingPlaneSolution (or, in modes 1 / 2, of Solve(printSteps)) for
+        item k over the handle's life (format_cutting_plane).  Raises NarrationStopped where the
+        item kept fewer events or doubles than it made, or ended at exit 6, exit 7 or a hard_cap
+        stop; ``partial`` returns the text up to there."""
+        info = _info or self.narration_info()
+        events, rec0, blocks, short = self._item_numbers(k, info, _packed)
+        if rec0 is None or (short and not partial):
+            if partial:
+                return ""
+            raise NarrationStopped(f"item {k} kept fewer events or doubles than it made "
+                                   f"(narration_info)")
+        text = format_cutting_plane(events, rec0, blocks, newline, partial=partial)
+        return text
+
+    def Snapshots(self, k: int) -> List[str]:
+        """PrimalSimplexSolver2.IterationSnapshots of item k's last mode-2 Run
+        (format_primal2_snapshots)."""
+        info = self.narration_info()
+        events, rec0, blocks, short = self._item_numbers(k, info)
+        if rec0 is None or short:
+            raise NarrationStopped(f"item {k} kept fewer events or doubles than it made")
+        return format_primal2_snapshots(events, rec0, blocks)
+
+
+def cutting_plane_texts(tableaux: Sequence[np.ndarray], max_cuts: int = 0, hard_cap: int = 0,
+                        engine: Optional[Engine] = None, newline: str = "\n",
+                        partial: bool = False) -> List[str]:
+    """The console text of CuttingPlaneSolution for every tableau.  Two handles: the first runs
+    with caps of 0 and counts what each item makes, the second reserves exactly that and keeps it
+    (a run is deterministic, and a batch continues from its state, so the two passes cannot
+    share a handle)."""
+    count = CuttingPlaneBatch.from_arrays(engine, tableaux, max_cuts)
+    try:
+        count.narrate_reserve(0, 1)
+        count.Run(hard_cap=hard_cap)
+        need = count.narration_info()
+    finally:
+        count.destroy()
+    keep = CuttingPlaneBatch.from_arrays(engine, tableaux, max_cuts)
+    try:
+        keep.narrate_reserve(need.doubles_made, max(1, int(need.events_made.max())))
+        keep.Run(hard_cap=hard_cap)
+        info, packed = keep.narration_info(), keep.narration_packed()
+        return [keep.NarrationText(k, newline, partial, _info=info, _packed=packed)
+                for k in range(keep.Count)]
+    finally:
+        keep.destroy()

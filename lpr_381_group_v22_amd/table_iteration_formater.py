@@ -91,9 +91,16 @@ def dotnet_round_digits(x: float, digits: int, away_from_zero: bool = False) -> 
     return x
 
 
-def _custom_0_hashes(r: float) -> str:
-    """double.ToString("0.###", InvariantCulture): up to 3 decimals, trailing zeros dropped."""
-    d = _dec15(r).quantize(Decimal("0.001"), rounding=ROUND_HALF_UP)
+def _custom_0_hashes(r: float, digits: int = 3) -> str:
+    """double.ToString("0.###", InvariantCulture), or "0.####" with ``digits`` = 4: the
+    15-significant-digit decimal image first, rounded half away from zero to ``digits``
+    decimals, trailing zeros dropped, no "-0"; NaN and the infinities as words."""
+    if math.isnan(r):
+        return "NaN"
+    if math.isinf(r):
+        return "Infinity" if r > 0 else "-Infinity"
+    d = _dec15(r).quantize(Decimal(1).scaleb(-digits), rounding=ROUND_HALF_UP,
+                           context=Context(prec=700))
     neg = d < 0
     s = format(abs(d), "f")
     if "." in s:
@@ -103,6 +110,16 @@ def _custom_0_hashes(r: float) -> str:
     if s == "0":
         neg = False
     return ("-" if neg else "") + s
+
+
+def H3(v: float) -> str:
+    """v.ToString("0.###")"""
+    return _custom_0_hashes(v, 3)
+
+
+def H4(v: float) -> str:
+    """v.ToString("0.####") (CuttingPlaneSolver.cs:50-52, PrimalSimplexSolver2.cs:186-188)"""
+    return _custom_0_hashes(v, 4)
 
 
 def N3(x: float) -> str:

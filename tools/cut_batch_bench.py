@@ -19,6 +19,22 @@ fastest pass, per item: the comparison holds by more than the spread of the repe
 
 Run it under a time limit:  timeout -k 10 900 python tools/cut_batch_bench.py --out
 profiles/cut_batch_bench.json
+
+--narrate measures the narrated batch instead, on the same workloads cut to
+NARR_COUNTS items so that the data slab stays within a few GB, all values kept:
+  (a) narrated end to end: a counting handle (caps 0) and a keeping handle, two runs,
+      lpr_cut_batch_narrate_read_all; also the keeping handle's run alone
+  (b) the un-narrated batch in the same process (create, run, bulk reads)
+  (c) CPU: the restatement loop tests/ref_py_cut_text.py producing the same numbers, one core of
+      the same host, a time-bounded prefix.  The only ratio given is (c) / (a), per item.
+256 evenly spaced items per workload (every item where the cut workload has fewer: H has 64) are
+compared block by block with the restatement.
+
+--parent-lib PATH measures what moving the kernel body into a shared text cost the un-narrated
+batch: lpr_cut_batch_run of this library and of the parent commit's library (PATH) on the full
+workloads, fresh child processes alternated (parent, this) --parent-rounds times, a pass = the
+median of --repeat runs in its process; margin = the parent's own max - min over its passes.  One
+JSON line per workload with both sets of passes is appended to --out.
 """
 from __future__ import annotations
 
@@ -39,6 +55,8 @@ HARD_CAP = 2000
 COUNTS = {"S": 65536, "G": 4096, "H": 256}
 MAX_CUTS = {"S": 6, "G": 8, "H": 12}
 S_DISTINCT = 512
+NARR_COUNTS = {"S": 16384, "G": 1024, "H": 64}
+NARR_CHECK = 256   # evenly spaced items per workload (H is cut to 64 items: every one of them)
 
 
 def gen_workload(orc, name: str, seed: int):
@@ -124,6 +142,177 @@ def bit_check(orc, tabs, max_cuts, batch) -> int:
     return bad
 
 
+def narrated_pass(pkg, eng, tabs, max_cuts):
+    """(seconds end to end, seconds of the keeping run, the keeping batch, info, events, data)"""
+    eng.sync()
+    t0 = time.perf_counter()
+    count = pkg.CuttingPlaneBatch.from_arrays(eng, tabs, max_cuts=max_cuts, log_cap=64)
+    count.narrate_reserve(0, 1)
+    count.Run(hard_cap=HARD_CAP)
+    need = count.narration_info()
+    count.destroy()
+    keep = pkg.CuttingPlaneBatch.from_arrays(eng, tabs, max_cuts=max_cuts, log_cap=64)
+    keep.narrate_reserve(need.doubles_made, int(need.events_made.max()))
+    t1 = time.perf_counter()
+    keep.Run(hard_cap=HARD_CAP)
+    eng.sync()
+    t2 = time.perf_counter()
+    info = keep.narration_info()
+    ev, data = keep.narration_packed()
+    keep.result_arrays()
+    eng.sync()
+    t3 = time.perf_counter()
+    return t3 - t0, t2 - t1, keep, info, ev, data
+
+
+def narrate_main(args, pkg, orc, eng) -> int:
+    import ref_py_cut_text as rt
+    failures = 0
+    lines = []
+    repeat = max(1, args.repeat)
+    for i, name in enumerate(args.workloads.split(",")):
+        tabs = gen_workload(orc, name, args.seed + 1000 * i)[:NARR_COUNTS[name]]
+        mc, count = MAX_CUTS[name], len(tabs)
+        narrated_pass(pkg, eng, tabs, mc)[2].destroy()  # warm-up
+        a_e2e, a_run = [], []
+        for p in range(repeat):
+            e2e, run, keep, info, ev, data = narrated_pass(pkg, eng, tabs, mc)
+            a_e2e.append(e2e)
+            a_run.append(run)
+            if p < repeat - 1:
+                keep.destroy()
+        plain = []
+        for _ in range(repeat):
+            r = run_batch(pkg, eng, tabs, mc)
+            plain.append((r[0], r[1]))
+            r[3].destroy()
+        # (c) the CPU restatement, one core, a time-bounded prefix
+        done, t0 = 0, time.perf_counter()
+        while done < count and time.perf_counter() - t0 < args.oracle_seconds:
+            rt.narrate_cutting_plane(tabs[done], mc, hard_cap=HARD_CAP, text=False)
+            done += 1
+        cpu_s = time.perf_counter() - t0
+        # block by block against the restatement
+        bad, checked = 0, 0
+        step = max(1, count // NARR_CHECK)
+        for k in list(range(0, count, step))[:NARR_CHECK]:
+            n = rt.narrate_cutting_plane(tabs[k], mc, hard_cap=HARD_CAP, text=False)[0]
+            want = np.concatenate([np.asarray(n.record0).reshape(-1)] +
+                                  [np.asarray(b, dtype=np.float64).reshape(-1) for b in n.blocks])
+            at = int(info.data_off[k])
+            ok = int(info.doubles_made[k]) == int(info.doubles_kept[k]) == want.size and \
+                data[at:at + want.size].tobytes() == want.tobytes() and \
+                [tuple(t) for t in ev[k, :int(info.events_made[k])].tolist()] == n.events
+            bad += not ok
+            checked += 1
+        keep.destroy()
+        failures += bad
+        rec = dict(workload=name, narrate=True, items=count, of_section_15_items=COUNTS[name],
+                   rows=int(tabs[0].shape[0]), cols=int(tabs[0].shape[1]), max_cuts=mc,
+                   hard_cap=HARD_CAP, data_doubles=int(info.doubles_made.sum()),
+                   data_bytes=int(info.doubles_made.sum()) * 8,
+                   events=int(info.events_made.sum()),
+                   a_narrated_e2e_seconds_all=a_e2e, a_narrated_run_seconds_all=a_run,
+                   a_narrated_e2e_items_per_s=count / min(a_e2e),
+                   a_narrated_run_items_per_s=count / min(a_run),
+                   b_unnarrated_e2e_seconds_all=[p[0] for p in plain],
+                   b_unnarrated_run_seconds_all=[p[1] for p in plain],
+                   c_cpu_restatement_1core=dict(items=done, seconds=cpu_s,
+                                                items_per_s=done / cpu_s),
+                   c_over_a_per_item=(cpu_s / done) / (min(a_e2e) / count),
+                   blocks_checked_items=checked, block_mismatches=bad)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        lines.append(line)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    if failures:
+        print(f"narration check: {failures} item(s) differ from the restatement", file=sys.stderr)
+        return 1
+    return 0
+
+
+def run_child(path: str, names, seed: int, repeat: int) -> int:
+    """--run-child: lpr_cut_batch_run alone through the library at `path` (raw ctypes: the
+    parent's library has no narrate calls), `repeat` runs per workload, one JSON line."""
+    import ctypes as C
+    from lpr_381_group_v22_amd import _native as N
+    from lpr_381_group_v22_amd.cut_batch import pack_tableaux
+    from oracle_lib import Oracle
+    lib = C.CDLL(path)
+    P = C.c_void_p
+    lib.lpr_engine_open.argtypes = [C.c_int, C.POINTER(P)]
+    lib.lpr_engine_sync.argtypes = [P]
+    lib.lpr_engine_close.argtypes = [P]
+    lib.lpr_cut_batch_create.argtypes = [P, C.c_int32, P, P, P, C.c_int32, C.c_int32, C.POINTER(P)]
+    lib.lpr_cut_batch_run.argtypes = [P, C.POINTER(N.CutBatchOpts), C.POINTER(N.CutBatchResult)]
+    lib.lpr_cut_batch_destroy.argtypes = [P]
+    orc = Oracle()
+    eng = P()
+    if lib.lpr_engine_open(0, C.byref(eng)) != 0:
+        return 1
+    out = {}
+    for name in names:
+        tabs = gen_workload(orc, name, seed + 1000 * "SGH".index(name))
+        p = pack_tableaux(tabs, MAX_CUTS[name])
+        times = []
+        for _ in range(repeat + 1):   # the first run is the warm-up
+            h = P()
+            if lib.lpr_cut_batch_create(eng, len(p.rows), p.rows.ctypes.data, p.cols.ctypes.data,
+                                        p.tableaux.ctypes.data, MAX_CUTS[name], 64,
+                                        C.byref(h)) != 0:
+                return 1
+            opts = N.CutBatchOpts(hard_cap=HARD_CAP)
+            res = N.CutBatchResult()
+            lib.lpr_engine_sync(eng)
+            t0 = time.perf_counter()
+            if lib.lpr_cut_batch_run(h, C.byref(opts), C.byref(res)) != 0:
+                return 1
+            times.append(time.perf_counter() - t0)
+            lib.lpr_cut_batch_destroy(h)
+        out[name] = times[1:]
+    lib.lpr_engine_close(eng)
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+def against_parent(args) -> int:
+    import statistics
+    import subprocess
+    from lpr_381_group_v22_amd import _native as N
+    names = args.workloads.split(",")
+    runs = {"parent": [], "this": []}
+    for _ in range(max(1, args.parent_rounds)):
+        for tag, path in (("parent", args.parent_lib), ("this", N.LIB_PATH)):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--run-child",
+                                os.path.abspath(path), "--workloads", ",".join(names),
+                                "--seed", str(args.seed), "--repeat", str(args.repeat)],
+                               capture_output=True, text=True, timeout=600)
+            if p.returncode != 0:
+                raise RuntimeError(f"run child on {path} failed: {p.stderr[-400:]}")
+            runs[tag].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    lines = []
+    for name in names:
+        par = [statistics.median(r[name]) for r in runs["parent"]]
+        this = [statistics.median(r[name]) for r in runs["this"]]
+        margin = max(par) - min(par)
+        diff = statistics.mean(this) - statistics.mean(par)
+        lines.append(json.dumps(dict(
+            workload=name, unnarrated_ab=True, items=COUNTS[name], rounds=len(par),
+            runs_per_pass=args.repeat, parent_run_seconds_passes=par,
+            this_run_seconds_passes=this,
+            parent_run_seconds_all=[r[name] for r in runs["parent"]],
+            this_run_seconds_all=[r[name] for r in runs["this"]],
+            margin_seconds=margin, this_mean_minus_parent_mean_seconds=diff,
+            within_parent_margin=bool(diff <= margin))))
+        print(lines[-1], flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="S,G,H")
@@ -132,10 +321,23 @@ def main() -> int:
     ap.add_argument("--single-seconds", type=float, default=4.0)
     ap.add_argument("--oracle-seconds", type=float, default=4.0)
     ap.add_argument("--no-check", action="store_true", help="skip the bit check and the loops")
+    ap.add_argument("--narrate", action="store_true",
+                    help="measure the narrated batch (DESIGN.md section 24); the committed record "
+                         "is profiles/cut_batch_narr_bench.json")
     ap.add_argument("--out", default=None,
                     help="also append the JSON lines to this file (the committed record is "
                          "profiles/cut_batch_bench.json; never pass it to a profiled run)")
+    ap.add_argument("--parent-lib", default=None,
+                    help="the parent commit's liblpr_engine.so: the un-narrated run of this "
+                         "library against it, fresh processes alternated")
+    ap.add_argument("--parent-rounds", type=int, default=3)
+    ap.add_argument("--run-child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.run_child:
+        return run_child(args.run_child, args.workloads.split(","), args.seed,
+                         max(1, args.repeat))
+    if args.parent_lib:
+        return against_parent(args)
 
     import lpr_381_group_v22_amd as pkg
     from oracle_lib import Oracle
@@ -143,6 +345,9 @@ def main() -> int:
     failures = 0
     lines = []
     repeat = max(1, args.repeat)
+    if args.narrate:
+        with pkg.Engine(0) as eng:
+            return narrate_main(args, pkg, orc, eng)
     with pkg.Engine(0) as eng:
         for i, name in enumerate(args.workloads.split(",")):
             tabs = gen_workload(orc, name, args.seed + 1000 * i)
