@@ -530,3 +530,9 @@ def check(status: int, where: str) -> int:
     if status < 0:
         raise EngineError(status, where)
     return status
+
+
+def _ptr(a, ctype):
+    """A numpy array as the POINTER(ctype) argument of a call; None (null) for no array or an
+    empty one."""
+    return None if a is None or not a.size else a.ctypes.data_as(C.POINTER(ctype))

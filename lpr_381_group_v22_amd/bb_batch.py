@@ -21,7 +21,7 @@ The record layout (csrc/bb_narr_layout.hpp), per IP:
 * the incumbent's tableau at its node's own shape.
 
 A tableau that does not fit whole in the IP's reserved doubles is counted and not written, nor is
-any later one: what is kept is a prefix and the totals are exact.
+any later one: what is kept is a prefix and the totals are exact (csrc/kept_prefix.hpp).
 """
 from __future__ import annotations
 
@@ -34,6 +34,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
+from ._native import _ptr
 from . import branch_and_bound as bnb
 from .engine import Engine, default_engine
 from .input_file_parser import Constraint
@@ -118,10 +119,6 @@ def option3_models(parsers) -> List[tuple]:
             cons.append(Constraint(co, "<=", 1.0))
         models.append((obj, cons, True))
     return models
-
-
-def _ptr(a: Optional[np.ndarray], ctype):
-    return None if a is None or not a.size else a.ctypes.data_as(C.POINTER(ctype))
 
 
 class BranchAndBoundBatch:

@@ -2,7 +2,8 @@
 // and its kernels (batch_body.hpp, instantiated by batch_kernels.hip and, traced, by
 // batch_trace_kernels.hip), and what the four batch engines (LP, B&B: bb_batch_*,
 // scenarios: sens_batch_*, cutting plane: cut_batch_*) have in common on the host: the forms and the rule that picks one, the
-// running-list driver, the dynamic-LDS attribute and the handle plumbing.  The device side of what
+// running-list driver, the one form launcher (batch_launch, which owns the dynamic-LDS attribute
+// of every kernel instantiation) and the handle plumbing.  The device side of what
 // they share is batch_device.hpp.  Not part of the ABI (include/lpr_engine.h is).
 #pragma once
 
@@ -201,38 +202,41 @@ inline int raise_dynamic_lds(const void* fn, size_t bytes, unsigned long long* m
     return LPR_OK_OPTIMAL;
 }
 
-// The launch of one form's kernel of the LP batch (k_batch_simplex or k_batch_simplex_trace: W, G
-// or H; the three of a file have one signature, whose last parameter is the LDS slot of one LP,
-// appended here: slot_doubles in W and G, 0 in H).  slot_doubles: W and G, the LDS share of one LP; max_rows, max_cols:
-// H, the factor column and pivot row of the largest LP.  g_mask: per device bit, the dynamic-LDS
-// attribute of the G kernel is set.
-template <class K, class... Args>
-int batch_launch_form(const char* name, K kw, K kg, K kh, unsigned long long* g_mask, int form,
-                      hipStream_t s, int n_in, int slot_doubles, int max_rows, int max_cols,
-                      Args... args) {
-    if (n_in <= 0) return LPR_OK_OPTIMAL;
-    if (form == kFormW) {
-        const size_t lds = (size_t)4 * slot_doubles * sizeof(double);
-        hipLaunchKernelGGL(kw, dim3((n_in + 3) / 4), dim3(256), lds, s, args..., slot_doubles);
-    } else if (form == kFormG) {
-        const size_t lds = (size_t)slot_doubles * sizeof(double);
-        if (lds > ((size_t)64 << 10)) {
-            const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kg), kBatchMaxLdsG,
-                                             g_mask);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        hipLaunchKernelGGL(kg, dim3(n_in), dim3(256), lds, s, args..., slot_doubles);
-    } else {
-        const size_t lds = (size_t)(max_rows + max_cols) * sizeof(double);
-        hipLaunchKernelGGL(kh, dim3(n_in), dim3(256), lds, s, args..., 0);
-    }
+// hipGetLastError after a launch, as a return code and a message.
+inline int launch_checked(const char* name) {
     const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("%s (form %d, %d LPs) failed to launch: %s", name, form, n_in,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
+    if (err == hipSuccess) return LPR_OK_OPTIMAL;
+    set_error("%s failed to launch: %s", name, hipGetErrorString(err));
+    return LPR_DEVICE_ERROR;
+}
+
+// The launch of one form's kernel of any batch engine: n_in items (`noun`: "LPs", "IPs", ...) in
+// 256-lane workgroups, four per workgroup in form W, one in forms G and H, with `lds` bytes of
+// dynamic LDS; above 64 KiB the kernel first gets the attribute, attr_bytes, once per device.  The
+// kernel is a template argument, so every instantiation has a mask of its own: one bit per device
+// on which its attribute is set.  An empty list launches nothing.  noun = nullptr: `name` is the
+// ABI call, and the message gives the LDS bytes in place of the count (the knapsack batch).
+template <auto kKernel, class... Args>
+int batch_launch(const char* name, const char* noun, int form, hipStream_t s, int n_in,
+                 size_t lds, size_t attr_bytes, Args... args) {
+    static unsigned long long mask = 0;
+    if (n_in <= 0) return LPR_OK_OPTIMAL;
+    if (lds > ((size_t)64 << 10)) {
+        const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kKernel), attr_bytes,
+                                         &mask);
+        if (rc != LPR_OK_OPTIMAL) return rc;
     }
-    return LPR_OK_OPTIMAL;
+    hipLaunchKernelGGL(kKernel, dim3(form == kFormW ? (n_in + 3) / 4 : n_in), dim3(256), lds, s,
+                       args...);
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return LPR_OK_OPTIMAL;
+    if (noun)
+        set_error("%s (form %d, %d %s) failed to launch: %s", name, form, n_in, noun,
+                  hipGetErrorString(err));
+    else
+        set_error("%s: launch of form %d failed (%zu bytes of LDS): %s", name, form, lds,
+                  hipGetErrorString(err));
+    return LPR_DEVICE_ERROR;
 }
 
 // A batch handle leaves its engine's list of live ones (the *_destroy calls).

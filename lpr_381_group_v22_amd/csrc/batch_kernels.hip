@@ -107,16 +107,25 @@ __global__ __launch_bounds__(256) void k_batch_extract(const BatchDesc* __restri
 }
 
 // ------------------------------------------------------------------------------------------
-// Launchers (batch_engine.hip).
+// Launchers (batch_engine.hip).  slot_doubles: W and G, the LDS share of one LP, which is also the
+// kernel's last argument; max_rows, max_cols: H, the factor column and pivot row of the largest LP.
 int batch_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab, int32_t* basis,
                          int32_t* logs, const int32_t* idx_in, int n_in, int32_t* idx_out,
                          int32_t* n_out, int chunk, int slot_doubles, int max_rows,
                          int max_cols) {
-    static unsigned long long g_mask = 0;  // per device bit: the G attribute is set
-    return batch_launch_form("k_batch_simplex", &k_batch_simplex<kWave, true>,
-                             &k_batch_simplex<256, true>, &k_batch_simplex<256, false>, &g_mask,
-                             form, s, n_in, slot_doubles, max_rows, max_cols, desc, slab, basis,
-                             logs, idx_in, n_in, idx_out, n_out, chunk);
+    const char* const name = "k_batch_simplex";
+    const size_t slot = (size_t)slot_doubles * sizeof(double);
+    if (form == kFormW)
+        return batch_launch<&k_batch_simplex<kWave, true>>(
+            name, "LPs", form, s, n_in, 4 * slot, kBatchMaxLdsG, desc, slab, basis, logs, idx_in,
+            n_in, idx_out, n_out, chunk, slot_doubles);
+    if (form == kFormG)
+        return batch_launch<&k_batch_simplex<256, true>>(
+            name, "LPs", form, s, n_in, slot, kBatchMaxLdsG, desc, slab, basis, logs, idx_in, n_in,
+            idx_out, n_out, chunk, slot_doubles);
+    return batch_launch<&k_batch_simplex<256, false>>(
+        name, "LPs", form, s, n_in, (size_t)(max_rows + max_cols) * sizeof(double), kBatchMaxLdsG,
+        desc, slab, basis, logs, idx_in, n_in, idx_out, n_out, chunk, 0);
 }
 
 void batch_launch_build(hipStream_t s, const BatchDesc* desc, const BatchBuild* bd, int count,

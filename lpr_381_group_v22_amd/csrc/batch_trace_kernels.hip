@@ -70,12 +70,19 @@ int batch_trace_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double*
                                int32_t* basis, int32_t* logs, const int32_t* idx_in, int n_in,
                                int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles,
                                int max_rows, int max_cols, BatchTrace tr) {
-    static unsigned long long g_mask = 0;  // per device bit: the G attribute is set
-    return batch_launch_form("k_batch_simplex_trace", &k_batch_simplex_trace<kWave, true>,
-                             &k_batch_simplex_trace<256, true>,
-                             &k_batch_simplex_trace<256, false>, &g_mask, form, s, n_in,
-                             slot_doubles, max_rows, max_cols, desc, slab, basis, logs, idx_in,
-                             n_in, idx_out, n_out, chunk, tr.slab, tr.off, tr.cap);
+    const char* const name = "k_batch_simplex_trace";
+    const size_t slot = (size_t)slot_doubles * sizeof(double);
+    if (form == kFormW)
+        return batch_launch<&k_batch_simplex_trace<kWave, true>>(
+            name, "LPs", form, s, n_in, 4 * slot, kBatchMaxLdsG, desc, slab, basis, logs, idx_in,
+            n_in, idx_out, n_out, chunk, tr.slab, tr.off, tr.cap, slot_doubles);
+    if (form == kFormG)
+        return batch_launch<&k_batch_simplex_trace<256, true>>(
+            name, "LPs", form, s, n_in, slot, kBatchMaxLdsG, desc, slab, basis, logs, idx_in, n_in,
+            idx_out, n_out, chunk, tr.slab, tr.off, tr.cap, slot_doubles);
+    return batch_launch<&k_batch_simplex_trace<256, false>>(
+        name, "LPs", form, s, n_in, (size_t)(max_rows + max_cols) * sizeof(double), kBatchMaxLdsG,
+        desc, slab, basis, logs, idx_in, n_in, idx_out, n_out, chunk, tr.slab, tr.off, tr.cap, 0);
 }
 
 void batch_trace_launch_first(hipStream_t s, const BatchDesc* desc, int count, const double* slab,

@@ -56,7 +56,7 @@ struct NarrCursor {
     double* slice;
     // One more tableau of n doubles: where its record goes, or nullptr where it is only counted.
     __device__ __forceinline__ double* push(int64_t n) {
-        const int64_t at = narr_push(c, n);
+        const int64_t at = kept_push(c.kp, n);
         return at < 0 ? nullptr : slice + at;
     }
 };
@@ -341,7 +341,7 @@ __device__ int child_lp(double*& cur, double*& oth, double* fcol, int Rc, int Cc
     for (int i = lane; i < Rc; i += NT)
         if (!(cur[(size_t)i * Cc + (Cc - 1)] >= 0)) neg = true;
     if (ip_any<NT>(neg, red_i)) {
-        if constexpr (kNarr) narr_drop(nc.c, tab_n);  // tableaux.RemoveAt(Count - 1) :394
+        if constexpr (kNarr) kept_drop(nc.c.kp, tab_n);  // tableaux.RemoveAt(Count - 1) :394
         if (npiv == 0) return kChildFailed;  // pivotColumns.RemoveAt(-1) throws
         double* t = cur;
         cur = oth;
@@ -498,8 +498,8 @@ __device__ __forceinline__ void bb_batch_body(const BBBatchBufs& B, const BBNarr
             int64_t first_off = 0, made0 = 0;
             double* rec = nullptr;
             if constexpr (kNarr) {
-                first_off = nc.c.cur;
-                made0 = nc.c.made_t;
+                first_off = nc.c.kp.cur;
+                made0 = nc.c.kp.made_n;
                 rec = nc.push((int64_t)Rc * Cc);
             }
             add_constraint<NT, kNarr>(P, Rn, Cn, nv, var, bound, side == 1, cur, keys, list, lane,
@@ -524,7 +524,7 @@ __device__ __forceinline__ void bb_batch_body(const BBBatchBufs& B, const BBNarr
                 rd[2 * rid + 1] = z;
                 if constexpr (kNarr) {
                     n_tab_off[rid] = first_off;
-                    n_ntab[rid] = (int32_t)(nc.c.made_t - made0);
+                    n_ntab[rid] = (int32_t)(nc.c.kp.made_n - made0);
                 }
             }
             group_sync<NT, kFenceWorkgroup>();

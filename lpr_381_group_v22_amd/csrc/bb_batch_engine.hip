@@ -577,15 +577,15 @@ int lpr_bb_batch_narrate_reserve(lpr_bb_batch* b, const int64_t* cap_doubles) {
         BBNarrDesc& c = nd[(size_t)k];
         std::memset(&c, 0, sizeof c);
         c.slab_off = total;
-        c.cap = cap_doubles[k];
+        c.kp.cap = cap_doubles[k];
         c.best_off = best;
         c.best_depth = -1;
-        if (total > INT64_MAX / (int64_t)sizeof(double) - c.cap) {
+        if (total > INT64_MAX / (int64_t)sizeof(double) - c.kp.cap) {
             set_error("lpr_bb_batch: cannot allocate %s (more than 2^63 bytes at IP %d of %d)",
                       kSlab, k, count);
             return LPR_OUT_OF_MEMORY;
         }
-        total += c.cap;
+        total += c.kp.cap;
         best += b->h_desc[(size_t)k].slot_n();
     }
     hipStream_t s = b->eng->stream;
@@ -637,9 +637,9 @@ int lpr_bb_batch_narrate_info(lpr_bb_batch* b, int64_t* tableaux, int64_t* doubl
     if (!bbb_narrated("lpr_bb_batch_narrate_info", b)) return LPR_BAD_ARGUMENT;
     for (int32_t k = 0; k < b->count; ++k) {
         const BBNarrDesc& c = b->h_narr[(size_t)k];
-        if (tableaux) tableaux[k] = c.made_t;
-        if (doubles_made) doubles_made[k] = c.made_d;
-        if (doubles_kept) doubles_kept[k] = c.cur;
+        if (tableaux) tableaux[k] = c.kp.made_n;
+        if (doubles_made) doubles_made[k] = c.kp.made_d;
+        if (doubles_kept) doubles_kept[k] = c.kp.cur;
         if (offset) offset[k] = c.slab_off;
     }
     return LPR_OK_OPTIMAL;
@@ -704,11 +704,11 @@ int lpr_bb_batch_narrate_tableaux_read(lpr_bb_batch* b, int32_t k, int64_t first
     LPR_LIVE_HANDLE(b, "B&B batch");
     if (!bbb_narrated(W, b) || !bbb_narr_ip(W, b, k)) return LPR_BAD_ARGUMENT;
     const BBNarrDesc& c = b->h_narr[(size_t)k];
-    const int64_t kept = b->narr_ran ? c.cur : 0;
+    const int64_t kept = b->narr_ran ? c.kp.cur : 0;
     if (first_double < 0 || n < 0 || first_double > kept || n > kept - first_double) {
         set_error("%s: doubles [%lld, %lld + %lld) of IP %d, which keeps %lld of %lld made", W,
                   (long long)first_double, (long long)first_double, (long long)n, k,
-                  (long long)kept, (long long)c.made_d);
+                  (long long)kept, (long long)c.kp.made_d);
         return LPR_BAD_ARGUMENT;
     }
     if (n == 0) return LPR_OK_OPTIMAL;

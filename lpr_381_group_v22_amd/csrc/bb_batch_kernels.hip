@@ -100,33 +100,19 @@ __global__ __launch_bounds__(256) void k_bb_batch_reset(BBBatchBufs B, int count
 int bb_batch_launch(int form, hipStream_t s, const BBBatchBufs& B, const int32_t* idx_in,
                     int n_in, int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles,
                     int max_rows) {
-    static unsigned long long g_mask = 0;  // per device bit: the G attribute is set
-    if (n_in <= 0) return LPR_OK_OPTIMAL;
-    if (form == kFormW) {
-        const size_t lds = (size_t)4 * slot_doubles * sizeof(double);
-        hipLaunchKernelGGL((k_bb_batch<kWave, true>), dim3((n_in + 3) / 4), dim3(256), lds, s, B,
-                           idx_in, n_in, idx_out, n_out, chunk, slot_doubles);
-    } else if (form == kFormG) {
-        const size_t lds = (size_t)slot_doubles * sizeof(double);
-        if (lds > ((size_t)64 << 10)) {
-            const int rc = raise_dynamic_lds(
-                reinterpret_cast<const void*>(&k_bb_batch<256, true>), kBatchMaxLdsG, &g_mask);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        hipLaunchKernelGGL((k_bb_batch<256, true>), dim3(n_in), dim3(256), lds, s, B, idx_in,
-                           n_in, idx_out, n_out, chunk, slot_doubles);
-    } else {
-        const size_t lds = (size_t)max_rows * sizeof(double);
-        hipLaunchKernelGGL((k_bb_batch<256, false>), dim3(n_in), dim3(256), lds, s, B, idx_in,
-                           n_in, idx_out, n_out, chunk, 0);
-    }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_bb_batch (form %d, %d IPs) failed to launch: %s", form, n_in,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    const char* const name = "k_bb_batch";
+    const size_t slot = (size_t)slot_doubles * sizeof(double);
+    if (form == kFormW)
+        return batch_launch<&k_bb_batch<kWave, true>>(name, "IPs", form, s, n_in, 4 * slot,
+                                                      kBatchMaxLdsG, B, idx_in, n_in, idx_out,
+                                                      n_out, chunk, slot_doubles);
+    if (form == kFormG)
+        return batch_launch<&k_bb_batch<256, true>>(name, "IPs", form, s, n_in, slot,
+                                                    kBatchMaxLdsG, B, idx_in, n_in, idx_out, n_out,
+                                                    chunk, slot_doubles);
+    return batch_launch<&k_bb_batch<256, false>>(name, "IPs", form, s, n_in,
+                                                 (size_t)max_rows * sizeof(double), kBatchMaxLdsG,
+                                                 B, idx_in, n_in, idx_out, n_out, chunk, 0);
 }
 
 void bb_batch_launch_load(hipStream_t s, const BBBatchDesc* desc, int count, const double* src,

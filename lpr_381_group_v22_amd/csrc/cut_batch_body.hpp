@@ -77,28 +77,28 @@ __device__ __forceinline__ CutNarrDesc cut_narr_load(const CutNarrDesc* __restri
     c.ev_off = p->ev_off;
     c.ev_n = p->ev_n;
     c.data_off = p->data_off;
-    c.cap = p->cap;
-    c.cur = p->cur;
-    c.made_d = p->made_d;
-    c.made_b = p->made_b;
-    c.kept_b = p->kept_b;
+    c.kp.cap = p->kp.cap;
+    c.kp.cur = p->kp.cur;
+    c.kp.made_d = p->kp.made_d;
+    c.kp.made_n = p->kp.made_n;
+    c.kp.kept_n = p->kp.kept_n;
     c.ev_cap = p->ev_cap;
     c.pad = 0;
     return c;
 }
 __device__ __forceinline__ void cut_narr_store(CutNarrDesc* __restrict__ p, const CutNarrDesc& c) {
     p->ev_n = c.ev_n;
-    p->cur = c.cur;
-    p->made_d = c.made_d;
-    p->made_b = c.made_b;
-    p->kept_b = c.kept_b;
+    p->kp.cur = c.kp.cur;
+    p->kp.made_d = c.kp.made_d;
+    p->kp.made_n = c.kp.made_n;
+    p->kp.kept_n = c.kp.kept_n;
 }
 
 // One more block of n doubles of item `c`: where the lanes store it, or nullptr where it is only
 // counted.
 __device__ __forceinline__ double* cut_narr_block(CutNarrDesc& c, double* __restrict__ data,
                                                   int64_t n) {
-    const int64_t at = cut_narr_push(c, n);
+    const int64_t at = kept_push(c.kp, n);
     return at >= 0 ? data + c.data_off + at : nullptr;
 }
 

@@ -477,8 +477,8 @@ int lpr_cut_batch_narrate_reserve(lpr_cut_batch* b, const int64_t* cap_doubles, 
         c.ev_off = (int64_t)k * ev_cap;
         c.ev_cap = ev_cap;
         c.data_off = off;
-        c.cap = cap_doubles[k];
-        off += c.cap;
+        c.kp.cap = cap_doubles[k];
+        off += c.kp.cap;
     }
     b->narr_doubles = total;
     b->narr_events = (int64_t)count * ev_cap;
@@ -538,8 +538,8 @@ int lpr_cut_batch_narrate_info(lpr_cut_batch* b, int64_t* events_made, int64_t* 
     for (int32_t k = 0; k < b->count; ++k) {
         const CutNarrDesc& c = b->h_narr[(size_t)k];
         if (events_made) events_made[k] = c.ev_n;
-        if (doubles_made) doubles_made[k] = c.made_d;
-        if (doubles_kept) doubles_kept[k] = c.cur;
+        if (doubles_made) doubles_made[k] = c.kp.made_d;
+        if (doubles_kept) doubles_kept[k] = c.kp.cur;
         if (data_off) data_off[k] = c.data_off;
     }
     return LPR_OK_OPTIMAL;
@@ -570,10 +570,10 @@ int lpr_cut_batch_narrate_data_read(lpr_cut_batch* b, int32_t k, int64_t first_d
     LPR_LIVE_HANDLE(b, "cutting-plane batch");
     if (!cb_narrated(W, b) || !cb_item_ok(W, b, k)) return LPR_BAD_ARGUMENT;
     const CutNarrDesc& c = b->h_narr[(size_t)k];
-    if (first_double < 0 || n < 0 || first_double > c.cur || n > c.cur - first_double ||
+    if (first_double < 0 || n < 0 || first_double > c.kp.cur || n > c.kp.cur - first_double ||
         (n > 0 && !out)) {
         set_error("%s: item %d keeps %lld doubles; [%lld, %lld + %lld) is beyond them (or a null "
-                  "output)", W, k, (long long)c.cur, (long long)first_double,
+                  "output)", W, k, (long long)c.kp.cur, (long long)first_double,
                   (long long)first_double, (long long)n);
         return LPR_BAD_ARGUMENT;
     }

@@ -57,43 +57,24 @@ __global__ __launch_bounds__(256) void k_cut_batch_load(CutBatchDesc* __restrict
 int cut_batch_launch(int form, hipStream_t s, CutBatchDesc* desc, double* slab, int32_t* logs,
                      const CutBatchCall& call, size_t lds, const int32_t* idx_in, int n_in,
                      int32_t* idx_out, int32_t* n_out) {
-    static unsigned long long g_mask = 0;  // per device bit: the G attribute is set
-    if (n_in <= 0) return LPR_OK_OPTIMAL;
-    if (form == kFormG) {
-        if (lds > kBatchMaxLdsG) {
-            set_error("k_cut_batch: %zu bytes of LDS asked for in form G", lds);
-            return LPR_BAD_ARGUMENT;
-        }
-        if (lds > ((size_t)64 << 10)) {
-            const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&k_cut_batch<true>),
-                                             kBatchMaxLdsG, &g_mask);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        hipLaunchKernelGGL(k_cut_batch<true>, dim3(n_in), dim3(256), lds, s, desc, slab, logs,
-                           call, idx_in, n_in, idx_out, n_out);
-    } else {
-        hipLaunchKernelGGL(k_cut_batch<false>, dim3(n_in), dim3(256), lds, s, desc, slab, logs,
-                           call, idx_in, n_in, idx_out, n_out);
+    const char* const name = "k_cut_batch";
+    if (form != kFormG)
+        return batch_launch<&k_cut_batch<false>>(name, "items", form, s, n_in, lds, kBatchMaxLdsG,
+                                                 desc, slab, logs, call, idx_in, n_in, idx_out,
+                                                 n_out);
+    if (n_in > 0 && lds > kBatchMaxLdsG) {
+        set_error("k_cut_batch: %zu bytes of LDS asked for in form G", lds);
+        return LPR_BAD_ARGUMENT;
     }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_cut_batch (form %d, %d items) failed to launch: %s", form, n_in,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    return batch_launch<&k_cut_batch<true>>(name, "items", form, s, n_in, lds, kBatchMaxLdsG, desc,
+                                            slab, logs, call, idx_in, n_in, idx_out, n_out);
 }
 
 int cut_batch_launch_load(hipStream_t s, CutBatchDesc* desc, int count, const double* src,
                           const int64_t* src_off, double* slab) {
     hipLaunchKernelGGL(k_cut_batch_load, dim3(count), dim3(256), 0, s, desc, count, src, src_off,
                        slab);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_cut_batch_load failed to launch: %s", hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    return launch_checked("k_cut_batch_load");
 }
 
 }  // namespace lpr

@@ -88,55 +88,32 @@ __global__ __launch_bounds__(256) void k_cut_batch_narr_call(const CutBatchDesc*
 int cut_batch_narr_launch(int form, hipStream_t s, CutBatchDesc* desc, double* slab,
                           int32_t* logs, const CutBatchCall& call, const CutNarr& narr, size_t lds,
                           const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out) {
-    static unsigned long long g_mask = 0;  // per device bit: the G attribute is set
-    if (n_in <= 0) return LPR_OK_OPTIMAL;
-    if (form == kFormG) {
-        if (lds > kBatchMaxLdsG) {
-            set_error("k_cut_batch_narr: %zu bytes of LDS asked for in form G", lds);
-            return LPR_BAD_ARGUMENT;
-        }
-        if (lds > ((size_t)64 << 10)) {
-            const int rc = raise_dynamic_lds(
-                reinterpret_cast<const void*>(&k_cut_batch_narr<true>), kBatchMaxLdsG, &g_mask);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        hipLaunchKernelGGL(k_cut_batch_narr<true>, dim3(n_in), dim3(256), lds, s, desc, slab, logs,
-                           call, narr, idx_in, n_in, idx_out, n_out);
-    } else {
-        hipLaunchKernelGGL(k_cut_batch_narr<false>, dim3(n_in), dim3(256), lds, s, desc, slab,
-                           logs, call, narr, idx_in, n_in, idx_out, n_out);
+    const char* const name = "k_cut_batch_narr";
+    if (form != kFormG)
+        return batch_launch<&k_cut_batch_narr<false>>(name, "items", form, s, n_in, lds,
+                                                      kBatchMaxLdsG, desc, slab, logs, call, narr,
+                                                      idx_in, n_in, idx_out, n_out);
+    if (n_in > 0 && lds > kBatchMaxLdsG) {
+        set_error("k_cut_batch_narr: %zu bytes of LDS asked for in form G", lds);
+        return LPR_BAD_ARGUMENT;
     }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_cut_batch_narr (form %d, %d items) failed to launch: %s", form, n_in,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    return batch_launch<&k_cut_batch_narr<true>>(name, "items", form, s, n_in, lds, kBatchMaxLdsG,
+                                                 desc, slab, logs, call, narr, idx_in, n_in,
+                                                 idx_out, n_out);
 }
 
 int cut_batch_narr_launch_first(hipStream_t s, const CutBatchDesc* desc, const double* slab,
                                 const CutNarr& narr, int count) {
     hipLaunchKernelGGL(k_cut_batch_narr_first, dim3(count), dim3(256), 0, s, desc, slab, narr,
                        count);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_cut_batch_narr_first failed to launch: %s", hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    return launch_checked("k_cut_batch_narr_first");
 }
 
 int cut_batch_narr_launch_call(hipStream_t s, const CutBatchDesc* desc, const CutNarr& narr,
                                int count, int mode, int print_steps) {
     hipLaunchKernelGGL(k_cut_batch_narr_call, dim3((count + 255) / 256), dim3(256), 0, s, desc,
                        narr, count, mode, print_steps);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_cut_batch_narr_call failed to launch: %s", hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    return launch_checked("k_cut_batch_narr_call");
 }
 
 }  // namespace lpr

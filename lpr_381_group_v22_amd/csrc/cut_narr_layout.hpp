@@ -1,7 +1,8 @@
 // cut_narr_layout.hpp -- what a narrated cutting-plane batch keeps per
-// item, and the cursor rules that place it.  Needs no HIP: the kernels (cut_batch_body.hpp), the
-// engine (cut_batch_engine.hip) and the host-only walker tools/cut_narr_check.cpp include this one
-// text.  Restated for the host mirror at the head of cut_batch.py.
+// item; the cursor rule that places the data blocks is kept_prefix.hpp's.  Needs no HIP: the
+// kernels (cut_batch_body.hpp), the engine (cut_batch_engine.hip) and the host-only walker
+// tools/cut_narr_check.cpp include this one text.  Restated for the host mirror at the head of
+// cut_batch.py.
 //
 // Per item k, all addressed through CutNarrDesc k, appended over the handle's life as the log is:
 //   events   ev[4 * (ev_off + i) ...]: event i as four int32 (kind, a, b, rows_now).  ev_n is
@@ -21,17 +22,10 @@
 //            Block 0 is the rows x cols tableau at reserve time; every kCutEvCut adds the appended
 //            row (cols doubles), every pivot event the whole tableau after it (rows_now x cols).
 //            cut_narr_event_doubles is that rule; offsets are its prefix sum.
-// Capacity: `cap` doubles.  A block that does not fit whole is counted and not written, and so is
-// every later one: what is kept is a prefix, and made_b / made_d stay exact.
+// Capacity: `cap` doubles of data, kept by the rule of kept_prefix.hpp.
 #pragma once
 
-#include <cstdint>
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define LPR_CUT_NARR_HD __host__ __device__ inline
-#else
-#define LPR_CUT_NARR_HD inline
-#endif
+#include "kept_prefix.hpp"
 
 namespace lpr {
 
@@ -50,14 +44,11 @@ struct CutNarrDesc {
     int64_t ev_off;    // quads: this item's ev_cap events start at ev + 4 * ev_off
     int64_t ev_n;      // events made (exact); the first ev_cap kept
     int64_t data_off;  // doubles: this item's slice of the data slab
-    int64_t cap;       // doubles reserved for it
-    int64_t cur;       // doubles kept so far: the next kept block starts here
-    int64_t made_d;    // doubles made (exact)
-    int64_t made_b;    // blocks made (exact)
-    int64_t kept_b;    // blocks kept: the first kept_b of the made ones
+    KeptPrefix kp;     // the blocks in the slice
     int32_t ev_cap;
     int32_t pad;
 };
+static_assert(sizeof(CutNarrDesc) == 72, "CutNarrDesc is 72 bytes");
 
 // Doubles of the block an event adds to the data.
 constexpr int64_t cut_narr_event_doubles(int32_t kind, int32_t rows_now, int32_t cols) {
@@ -65,22 +56,8 @@ constexpr int64_t cut_narr_event_doubles(int32_t kind, int32_t rows_now, int32_t
                              : (kind >= kCutEvPivot ? (int64_t)rows_now * cols : (int64_t)0);
 }
 
-// One more block of n doubles.  Returns where it goes in the slice, or -1 where it is only
-// counted: it does not fit, or an earlier one was not kept.
-LPR_CUT_NARR_HD int64_t cut_narr_push(CutNarrDesc& c, int64_t n) {
-    const bool keep = c.kept_b == c.made_b && n <= c.cap - c.cur;
-    const int64_t at = keep ? c.cur : -1;
-    ++c.made_b;
-    c.made_d += n;
-    if (keep) {
-        ++c.kept_b;
-        c.cur += n;
-    }
-    return at;
-}
-
 // One more event.  Returns its index among the kept ones, or -1 where it is only counted.
-LPR_CUT_NARR_HD int64_t cut_narr_event(CutNarrDesc& c) {
+LPR_HD int64_t cut_narr_event(CutNarrDesc& c) {
     const int64_t at = c.ev_n < (int64_t)c.ev_cap ? c.ev_n : -1;
     ++c.ev_n;
     return at;

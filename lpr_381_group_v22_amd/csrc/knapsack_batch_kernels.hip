@@ -386,74 +386,47 @@ __global__ __launch_bounds__(256) void k_knap_batch_dp(KnapBatchBufs B,
     }
 }
 
-namespace {
-
-int launch_error(const char* what, int form, size_t lds) {
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return LPR_OK_OPTIMAL;
-    set_error("%s: launch of form %d failed (%zu bytes of LDS): %s", what, form, lds,
-              hipGetErrorString(err));
-    return LPR_DEVICE_ERROR;
-}
-
-template <class K>
-int raise_if_large(K kernel, size_t lds, unsigned long long* mask) {
-    if (lds <= ((size_t)64 << 10)) return LPR_OK_OPTIMAL;
-    return raise_dynamic_lds(reinterpret_cast<const void*>(kernel),
-                             kBatchMaxLdsG + kBatchWgScratch, mask);
-}
-
-}  // namespace
+// The launchers name their ABI call and pass no noun: batch_launch's message then gives the LDS
+// bytes.  The workgroup's scratch is dynamic LDS here, so the attribute covers it too.
+constexpr size_t kKnapBatchAttr = kBatchMaxLdsG + kBatchWgScratch;
 
 // slot_bytes: the LDS of one instance of this form in this call (a multiple of 8): the largest
 // footprint (W, G) or the largest items block (H).
 int knap_batch_launch(int form, hipStream_t s, const KnapBatchBufs& B, size_t slot_bytes,
                       const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
                       int chunk) {
-    static unsigned long long g_mask = 0, h_mask = 0;  // per device bit: the attribute is set
-    if (n_in <= 0) return LPR_OK_OPTIMAL;
+    const char* const name = "lpr_knap_batch_solve";
     const int slot_words = (int)(slot_bytes / sizeof(uint64_t));
-    size_t lds = kBatchWgScratch + slot_bytes;
-    if (form == kFormW) {
-        lds = kBatchWgScratch + 4 * slot_bytes;
-        hipLaunchKernelGGL((k_knap_batch<kWave, true>), dim3((n_in + 3) / 4), dim3(256), lds, s, B,
-                           idx_in, n_in, idx_out, n_out, chunk, slot_words);
-    } else if (form == kFormG) {
-        const int rc = raise_if_large(&k_knap_batch<256, true>, lds, &g_mask);
-        if (rc != LPR_OK_OPTIMAL) return rc;
-        hipLaunchKernelGGL((k_knap_batch<256, true>), dim3(n_in), dim3(256), lds, s, B, idx_in,
-                           n_in, idx_out, n_out, chunk, slot_words);
-    } else {
-        const int rc = raise_if_large(&k_knap_batch<256, false>, lds, &h_mask);
-        if (rc != LPR_OK_OPTIMAL) return rc;
-        hipLaunchKernelGGL((k_knap_batch<256, false>), dim3(n_in), dim3(256), lds, s, B, idx_in,
-                           n_in, idx_out, n_out, chunk, slot_words);
-    }
-    return launch_error("lpr_knap_batch_solve", form, lds);
+    const size_t lds = kBatchWgScratch + slot_bytes;
+    if (form == kFormW)
+        return batch_launch<&k_knap_batch<kWave, true>>(
+            name, nullptr, form, s, n_in, kBatchWgScratch + 4 * slot_bytes, kKnapBatchAttr, B,
+            idx_in, n_in, idx_out, n_out, chunk, slot_words);
+    if (form == kFormG)
+        return batch_launch<&k_knap_batch<256, true>>(name, nullptr, form, s, n_in, lds,
+                                                      kKnapBatchAttr, B, idx_in, n_in, idx_out,
+                                                      n_out, chunk, slot_words);
+    return batch_launch<&k_knap_batch<256, false>>(name, nullptr, form, s, n_in, lds,
+                                                   kKnapBatchAttr, B, idx_in, n_in, idx_out, n_out,
+                                                   chunk, slot_words);
 }
 
 // slot_bytes: the largest row of this form in this call (W, G); unused in form H.
 int knap_batch_launch_dp(int form, hipStream_t s, const KnapBatchBufs& B, size_t slot_bytes,
                          const int32_t* idx, int n_in, int64_t* rows, int64_t* best) {
-    static unsigned long long g_mask = 0;
-    if (n_in <= 0) return LPR_OK_OPTIMAL;
+    const char* const name = "lpr_knap_batch_dp";
     const int slot_words = (int)(slot_bytes / sizeof(uint64_t));
-    size_t lds = kBatchWgScratch + slot_bytes;
-    if (form == kFormW) {
-        lds = kBatchWgScratch + 4 * slot_bytes;
-        hipLaunchKernelGGL((k_knap_batch_dp<kWave, true>), dim3((n_in + 3) / 4), dim3(256), lds, s,
-                           B, idx, n_in, rows, best, slot_words);
-    } else if (form == kFormG) {
-        const int rc = raise_if_large(&k_knap_batch_dp<256, true>, lds, &g_mask);
-        if (rc != LPR_OK_OPTIMAL) return rc;
-        hipLaunchKernelGGL((k_knap_batch_dp<256, true>), dim3(n_in), dim3(256), lds, s, B, idx,
-                           n_in, rows, best, slot_words);
-    } else {
-        lds = kBatchWgScratch;
-        hipLaunchKernelGGL((k_knap_batch_dp<256, false>), dim3(n_in), dim3(256), lds, s, B, idx,
-                           n_in, rows, best, 0);
-    }
-    return launch_error("lpr_knap_batch_dp", form, lds);
+    if (form == kFormW)
+        return batch_launch<&k_knap_batch_dp<kWave, true>>(
+            name, nullptr, form, s, n_in, kBatchWgScratch + 4 * slot_bytes, kKnapBatchAttr, B, idx,
+            n_in, rows, best, slot_words);
+    if (form == kFormG)
+        return batch_launch<&k_knap_batch_dp<256, true>>(
+            name, nullptr, form, s, n_in, kBatchWgScratch + slot_bytes, kKnapBatchAttr, B, idx,
+            n_in, rows, best, slot_words);
+    return batch_launch<&k_knap_batch_dp<256, false>>(name, nullptr, form, s, n_in,
+                                                      kBatchWgScratch, kKnapBatchAttr, B, idx,
+                                                      n_in, rows, best, 0);
 }
 
 }  // namespace lpr

@@ -500,41 +500,12 @@ __device__ __forceinline__ void rev_batch_run(RevBatchDesc* __restrict__ desc,
     }
 }
 
-// The launch of one form's kernel (W, G or H; the three of a file have one signature).
-// slot_doubles: W and G, the LDS share of one LP; H, the vectors of the largest LP (the tile
-// follows them).  g_mask / h_mask: per device bit, the dynamic-LDS attribute is set.
-template <class K, class... Args>
-int rev_batch_launch_form(const char* name, K kw, K kg, K kh, unsigned long long* g_mask,
-                          unsigned long long* h_mask, int form, hipStream_t s, int n_in,
-                          int slot_doubles, Args... args) {
-    if (n_in <= 0) return LPR_OK_OPTIMAL;
-    if (form == kFormW) {
-        const size_t lds = (size_t)4 * slot_doubles * sizeof(double);
-        hipLaunchKernelGGL(kw, dim3((n_in + 3) / 4), dim3(256), lds, s, args..., slot_doubles);
-    } else if (form == kFormG) {
-        const size_t lds = (size_t)slot_doubles * sizeof(double);
-        if (lds > ((size_t)64 << 10)) {
-            const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kg), kBatchMaxLdsG,
-                                             g_mask);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        hipLaunchKernelGGL(kg, dim3(n_in), dim3(256), lds, s, args..., slot_doubles);
-    } else {
-        const size_t lds = ((size_t)slot_doubles + kRevBatchTile) * sizeof(double);
-        if (lds > ((size_t)64 << 10)) {
-            const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kh), kBatchMaxLdsG,
-                                             h_mask);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        hipLaunchKernelGGL(kh, dim3(n_in), dim3(256), lds, s, args..., 0);
-    }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("%s (form %d, %d LPs) failed to launch: %s", name, form, n_in,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+// The dynamic LDS of one form's launch of either kernel of this text.  slot_doubles: W and G, the
+// LDS share of one LP; H, the vectors of the largest LP (the tile follows them).
+inline size_t rev_batch_lds(int form, int slot_doubles) {
+    const size_t slot = (size_t)slot_doubles * sizeof(double);
+    return form == kFormW ? 4 * slot
+                          : (form == kFormG ? slot : slot + kRevBatchTile * sizeof(double));
 }
 
 }  // namespace lpr

@@ -87,11 +87,19 @@ __global__ __launch_bounds__(256) void k_rev_batch_build(const RevBatchDesc* __r
 int rev_batch_launch(int form, hipStream_t s, RevBatchDesc* desc, double* slab, int32_t* basis,
                      int32_t* logs, double* xs, const int32_t* idx_in, int n_in,
                      int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles) {
-    static unsigned long long g_mask = 0, h_mask = 0;  // per device bit: the attribute is set
-    return rev_batch_launch_form("k_rev_batch", &k_rev_batch<kWave, true>,
-                                 &k_rev_batch<256, true>, &k_rev_batch<256, false>, &g_mask,
-                                 &h_mask, form, s, n_in, slot_doubles, desc, slab, basis, logs,
-                                 xs, idx_in, n_in, idx_out, n_out, chunk);
+    const char* const name = "k_rev_batch";
+    const size_t lds = rev_batch_lds(form, slot_doubles);
+    if (form == kFormW)
+        return batch_launch<&k_rev_batch<kWave, true>>(
+            name, "LPs", form, s, n_in, lds, kBatchMaxLdsG, desc, slab, basis, logs, xs, idx_in,
+            n_in, idx_out, n_out, chunk, slot_doubles);
+    if (form == kFormG)
+        return batch_launch<&k_rev_batch<256, true>>(
+            name, "LPs", form, s, n_in, lds, kBatchMaxLdsG, desc, slab, basis, logs, xs, idx_in,
+            n_in, idx_out, n_out, chunk, slot_doubles);
+    return batch_launch<&k_rev_batch<256, false>>(
+        name, "LPs", form, s, n_in, lds, kBatchMaxLdsG, desc, slab, basis, logs, xs, idx_in, n_in,
+        idx_out, n_out, chunk, 0);
 }
 
 void rev_batch_launch_build(hipStream_t s, const RevBatchDesc* desc, const RevBatchBuild* bd,

@@ -44,11 +44,19 @@ int rev_batch_trace_launch(int form, hipStream_t s, RevBatchDesc* desc, double* 
                            int32_t* basis, int32_t* logs, double* xs, const int32_t* idx_in,
                            int n_in, int32_t* idx_out, int32_t* n_out, int chunk,
                            int slot_doubles, RevBatchTrace tr) {
-    static unsigned long long g_mask = 0, h_mask = 0;  // per device bit: the attribute is set
-    return rev_batch_launch_form("k_rev_batch_trace", &k_rev_batch_trace<kWave, true>,
-                                 &k_rev_batch_trace<256, true>, &k_rev_batch_trace<256, false>,
-                                 &g_mask, &h_mask, form, s, n_in, slot_doubles, desc, slab, basis,
-                                 logs, xs, idx_in, n_in, idx_out, n_out, chunk, tr);
+    const char* const name = "k_rev_batch_trace";
+    const size_t lds = rev_batch_lds(form, slot_doubles);
+    if (form == kFormW)
+        return batch_launch<&k_rev_batch_trace<kWave, true>>(
+            name, "LPs", form, s, n_in, lds, kBatchMaxLdsG, desc, slab, basis, logs, xs, idx_in,
+            n_in, idx_out, n_out, chunk, tr, slot_doubles);
+    if (form == kFormG)
+        return batch_launch<&k_rev_batch_trace<256, true>>(
+            name, "LPs", form, s, n_in, lds, kBatchMaxLdsG, desc, slab, basis, logs, xs, idx_in,
+            n_in, idx_out, n_out, chunk, tr, slot_doubles);
+    return batch_launch<&k_rev_batch_trace<256, false>>(
+        name, "LPs", form, s, n_in, lds, kBatchMaxLdsG, desc, slab, basis, logs, xs, idx_in, n_in,
+        idx_out, n_out, chunk, tr, 0);
 }
 
 }  // namespace lpr

@@ -611,43 +611,39 @@ __global__ __launch_bounds__(256) void k_sens_batch_from_models(SensBatchView vw
 int sens_batch_launch_from_models(hipStream_t s, const SensBatchView& vw, int count,
                                   const SensModelSrc* src, const double* slab) {
     hipLaunchKernelGGL(k_sens_batch_from_models, dim3(count), dim3(256), 0, s, vw, count, src, slab);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_sens_batch_from_models (%d scenarios) failed to launch: %s", count,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    char name[64];
+    snprintf(name, sizeof(name), "k_sens_batch_from_models (%d scenarios)", count);
+    return launch_checked(name);
 }
+
+namespace {
+
+template <bool kLds, bool kGrow>
+int sens_batch_launch_one(int form, hipStream_t s, const SensBatchView& vw, size_t lds,
+                          const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
+                          int chunk) {
+    return batch_launch<&k_sens_batch<kLds, kGrow>>("k_sens_batch", "scenarios", form, s, n_in,
+                                                    lds, kBatchMaxLdsG, vw, idx_in, n_in, idx_out,
+                                                    n_out, chunk);
+}
+
+}  // namespace
 
 int sens_batch_launch(int form, bool grow, hipStream_t s, const SensBatchView& vw,
                       const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
                       int chunk) {
-    static unsigned long long g_masks[2] = {0, 0};  // per device bit: the G attribute is set
-    if (n_in <= 0) return LPR_OK_OPTIMAL;
-    const auto kern_g = grow ? &k_sens_batch<true, true> : &k_sens_batch<true, false>;
-    const auto kern_h = grow ? &k_sens_batch<false, true> : &k_sens_batch<false, false>;
     if (form == kFormG) {
         const size_t lds = sens_batch_footprint_g(vw.R, vw.C);
-        if (lds > ((size_t)64 << 10)) {
-            const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kern_g), kBatchMaxLdsG,
-                                             &g_masks[grow ? 1 : 0]);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-        }
-        hipLaunchKernelGGL(kern_g, dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in, idx_out, n_out,
-                           chunk);
-    } else {
-        const size_t lds = sens_batch_aux_bytes(vw.R, vw.C);
-        hipLaunchKernelGGL(kern_h, dim3(n_in), dim3(256), lds, s, vw, idx_in, n_in, idx_out, n_out,
-                           chunk);
+        return grow ? sens_batch_launch_one<true, true>(form, s, vw, lds, idx_in, n_in, idx_out,
+                                                        n_out, chunk)
+                    : sens_batch_launch_one<true, false>(form, s, vw, lds, idx_in, n_in, idx_out,
+                                                         n_out, chunk);
     }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_sens_batch (form %d, %d scenarios) failed to launch: %s", form, n_in,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    const size_t lds = sens_batch_aux_bytes(vw.R, vw.C);
+    return grow ? sens_batch_launch_one<false, true>(form, s, vw, lds, idx_in, n_in, idx_out,
+                                                     n_out, chunk)
+                : sens_batch_launch_one<false, false>(form, s, vw, lds, idx_in, n_in, idx_out,
+                                                      n_out, chunk);
 }
 
 int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, int R, int C,
@@ -655,12 +651,7 @@ int sens_batch_launch_init(hipStream_t s, const SensBatchView& vw, int count, in
                            const int32_t* base_bcount, const double* base_sol, int nsol) {
     hipLaunchKernelGGL(k_sens_batch_init, dim3(count), dim3(256), 0, s, vw, count, R, C, baseT, ld,
                        base_basic, base_bcount, base_sol, nsol);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_sens_batch_init failed to launch: %s", hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    return LPR_OK_OPTIMAL;
+    return launch_checked("k_sens_batch_init");
 }
 
 }  // namespace lpr

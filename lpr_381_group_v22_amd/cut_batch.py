@@ -16,6 +16,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
+from ._native import _ptr
 from . import table_iteration_formater as fmt
 from .engine import Engine, default_engine
 from .primal_batch import PrimalSimplexBatch
@@ -35,7 +36,7 @@ CHUNK = {FORM_G: 128, FORM_H: 16}  # kCutBatchChunk: pivots per item per launch
 # and blocks of doubles back to back in event order: block 0 the rows x cols tableau at reserve
 # time, one block per EV_CUT (the appended row, cols doubles) and per pivot event (the whole
 # rows_now x cols tableau after it).  A block that does not fit whole is counted and not written,
-# and so is every later one.
+# and so is every later one (the rule of csrc/kept_prefix.hpp).
 EV_CALL, EV_LEVEL, EV_CUT, EV_SOLVE_BEGIN, EV_SOLVE_END, EV_EXIT = 0, 1, 2, 3, 4, 5
 EV_PIVOT = 8                     # + the log kind: 8 dual, 9 primal2, 10 cut
 KIND_DUAL, KIND_PRIMAL2, KIND_CUT = 0, 1, 2
@@ -63,8 +64,9 @@ def block_offsets(events, rows0: int, cols: int) -> List[Tuple[int, int]]:
 
 
 def narr_push(c: dict, n: int) -> int:
-    """cut_narr_push on a dict of cursors (cap, cur, made_d, made_b, kept_b): where the block
-    goes, or -1 where it is only counted."""
+    """kept_push (csrc/kept_prefix.hpp) on a dict of cursors (cap, cur, made_d, and made_b /
+    kept_b for KeptPrefix's made_n / kept_n): where the block goes, or -1 where it is only
+    counted."""
     keep = c["kept_b"] == c["made_b"] and n <= c["cap"] - c["cur"]
     at = c["cur"] if keep else -1
     c["made_b"] += 1
@@ -352,10 +354,6 @@ def pack_tableaux(tableaux: Sequence[np.ndarray], max_cuts: int = 0) -> PackedTa
     return PackedTableaux(np.asarray([t.shape[0] for t in T], dtype=np.int32),
                           np.asarray([t.shape[1] for t in T], dtype=np.int32),
                           np.concatenate([t.reshape(-1) for t in T]))
-
-
-def _ptr(a: Optional[np.ndarray], ctype):
-    return None if a is None or not a.size else a.ctypes.data_as(C.POINTER(ctype))
 
 
 class CuttingPlaneBatch:

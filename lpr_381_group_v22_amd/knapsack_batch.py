@@ -12,6 +12,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
+from ._native import _ptr
 from .engine import Engine, default_engine
 from .knapsack import KnapsackNode, narration_lines
 
@@ -90,10 +91,6 @@ def pack_knapsacks(capacities: Sequence[int], weights: Sequence[Sequence[float]]
     return PackedKnapsacks(np.asarray([int(c) for c in capacities], dtype=np.int64),
                            np.asarray(ns, dtype=np.int32), np.ascontiguousarray(w),
                            np.ascontiguousarray(v), np.asarray(caps, dtype=np.int64), off)
-
-
-def _ptr(a: Optional[np.ndarray], ctype):
-    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
 
 
 class KnapsackBatch:

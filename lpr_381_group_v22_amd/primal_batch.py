@@ -17,6 +17,7 @@ from typing import List, NamedTuple, Optional, Sequence
 import numpy as np
 
 from . import _native as N
+from ._native import _ptr
 from .engine import Engine, default_engine
 from .primal_simplex_solver import format_console, format_snapshots
 
@@ -123,10 +124,6 @@ def trace_record(r: np.ndarray, rows: int, cols: int):
     """One record as (leaving_row, entering_col, tableau)."""
     return (int(r[TRACE_ROW]), int(r[TRACE_COL]),
             r[TRACE_TAB:TRACE_TAB + rows * cols].reshape(rows, cols).copy())
-
-
-def _ptr(a: np.ndarray, ctype):
-    return a.ctypes.data_as(C.POINTER(ctype)) if a.size else None
 
 
 class PrimalSimplexBatch:

@@ -17,6 +17,7 @@ from typing import List, NamedTuple, Optional
 import numpy as np
 
 from . import _native as N
+from ._native import _ptr
 from .engine import Engine, default_engine
 from .revised_primal_simplex_solver import MESSAGES, SolverException, format_snapshot
 
@@ -128,10 +129,6 @@ def trace_record(r: np.ndarray, m: int, n: int) -> dict:
     d["basis_pre"] = d["basis_pre"].astype(np.int32)
     d["basis_post"] = d["basis_post"].astype(np.int32)
     return d
-
-
-def _ptr(a: np.ndarray, ctype):
-    return a.ctypes.data_as(C.POINTER(ctype)) if a.size else None
 
 
 class RevisedSimplexBatch:

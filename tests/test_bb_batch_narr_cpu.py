@@ -55,9 +55,11 @@ def test_header_and_bindings_declare_and_use_the_calls():
         assert len(re.findall(r"__device__ [\w ]*\b%s\(" % fn,
                               _read(CSRC, "bb_batch_body.hpp"))) == 1, fn
         assert fn + "(" not in _read(CSRC, "bb_batch_kernels.hip"), fn
-    # the layout header needs no HIP, and the cursor rules are stated there alone
-    layout = _read(CSRC, "bb_narr_layout.hpp")
-    assert "hip/" not in layout and "narr_push(" in layout and "narr_drop(" in layout
+    # the layout headers need no HIP, and the cursor rules are stated in kept_prefix.hpp alone
+    layout, rule = _read(CSRC, "bb_narr_layout.hpp"), _read(CSRC, "kept_prefix.hpp")
+    assert "hip/" not in layout and "hip/" not in rule
+    assert "kept_push(" in rule and "kept_drop(" in rule
+    assert "_push(" not in layout and "_drop(" not in layout
 
 
 def _kernels(hipcc, src, out):

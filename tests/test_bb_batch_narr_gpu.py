@@ -379,6 +379,28 @@ def test_a_narrated_batch_gives_the_bytes_of_an_unnarrated_one(batch, engine):
     u.destroy()
 
 
+def test_form_g_above_64_kib_unnarrated_then_narrated(engine, oracle):
+    """One IP whose node cap of 64 puts its form-G footprint (85 768 bytes) above the 64 KiB a
+    kernel gets without the dynamic-LDS attribute, first on an un-narrated handle, then on a
+    narrated one: k_bb_batch<256, true> and k_bb_batch_narr<256, true> each need the attribute
+    set for themselves.  Same bytes from both, and the restatement's text."""
+    cap = 64
+    roots = [r for r in bb_roots(oracle) if r[0] == "frac_4v2c_s10"]
+    name, T, nv = roots[0]
+    assert 64 * 1024 < footprint_bytes(T, cap) <= G_MAX
+    u = make(engine, roots, cap)
+    u.Run()
+    n = narrated(engine, roots, cap=cap)
+    a, b = u.result_arrays(), n.result_arrays()
+    for key in a:
+        assert a[key].tobytes() == b[key].tobytes(), key
+    assert u.solution_packed().tobytes() == n.solution_packed().tobytes()
+    assert u.PopOrder(0) == n.PopOrder(0) and u.Trace(0) == n.Trace(0)
+    assert lf(n.NarrationText(0)) == ref_text(ref_walk(name, T, nv, cap)[0])
+    u.destroy()
+    n.destroy()
+
+
 # ------------------------------------------------------------------------------- 8. option 3
 def test_option3_texts_equal_the_files_option3_writes(engine, tmp_path):
     """option3_texts / write_option3_files on the sample model file and on the B&B cases as

@@ -64,8 +64,9 @@ def test_header_and_bindings_declare_and_use_the_calls():
         assert src.count("#define LPR_CUT_BATCH_BODY_TEXT") == 1
     assert body.count("f * prow[jj[u]]") == 1 and body.count("staged_eps_fold(") == 5
     assert "staged_eps_fold(" not in _read(CSRC, "cut_batch_kernels.hip")
-    layout = _read(CSRC, "cut_narr_layout.hpp")
-    assert "hip/" not in layout and "cut_narr_push(" in layout
+    layout, rule = _read(CSRC, "cut_narr_layout.hpp"), _read(CSRC, "kept_prefix.hpp")
+    assert "hip/" not in layout and "hip/" not in rule
+    assert "kept_push(" in rule and "_push(" not in layout
     assert "constexpr int64_t cut_narr_event_doubles(" in layout
 
 

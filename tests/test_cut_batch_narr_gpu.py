@@ -318,6 +318,39 @@ def test_g_and_h_items_in_one_batch(engine, oracle, textbook):
     batch.destroy()
 
 
+def test_form_g_above_64_kib_unnarrated_then_narrated(engine, oracle):
+    """One 41 x 186 item at two cuts: 65 816 bytes of dynamic LDS in form G, the smallest width at
+    this height above the 64 KiB a kernel gets without the dynamic-LDS attribute.  First on an
+    un-narrated handle, then on narrated ones: k_cut_batch<true> and k_cut_batch_narr<true> each
+    need the attribute set for themselves.  The oracle's bytes from both, the restatement's
+    events and blocks from the narrated one."""
+    from lpr_381_group_v22_amd import CuttingPlaneBatch
+    from lpr_381_group_v22_amd import cut_batch as pycb
+    mc = 2
+    T = cut_cases.side_base(40, 145, 11)
+    assert T.shape == (41, 186)
+    assert pycb.footprint_g(41, 185, mc) <= 64 * 1024 < pycb.footprint_g(41, 186, mc)
+    assert pycb.form_of(41, 186, mc) == pycb.FORM_G
+    ref = cb.reference(oracle, cb.MODE_CUT, T, max_cuts=mc)
+    n, code, cuts = rt.narrate_cutting_plane(T, mc, text=False)
+    assert (code, cuts, n.log) == (ref["code"], ref["cuts"], ref["log"])
+    assert (code, cuts, len(n.log)) == (6, 2, 4)
+    assert np.array(n.table()).tobytes() == ref["T"].tobytes()
+    plain = CuttingPlaneBatch.from_arrays(engine, [T], max_cuts=mc)
+    res = plain.Run()
+    assert (res.items_g, res.items_h) == (1, 0)
+    batch, need, res = two_pass(engine, [T], mc)
+    assert (res.items_g, res.items_h) == (1, 0)
+    check_numbers(batch, 0, n, "G above 64 KiB")
+    a, p = batch.result_arrays(), plain.result_arrays()
+    assert (int(a["code"][0]), int(a["cuts"][0])) == (int(p["code"][0]), int(p["cuts"][0])) \
+        == (code, cuts)
+    assert batch.Log(0) == plain.Log(0) == [tuple(t) for t in ref["log"]]
+    assert batch.Tableau(0).tobytes() == plain.Tableau(0).tobytes() == ref["T"].tobytes()
+    batch.destroy()
+    plain.destroy()
+
+
 # ------------------------------------------------------------------ 6. modes 1 and 2
 @pytest.mark.parametrize("steps", [True, False])
 @pytest.mark.parametrize("mode", [cb.MODE_DUAL, cb.MODE_PRIMAL2])

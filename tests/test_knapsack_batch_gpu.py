@@ -170,6 +170,20 @@ def test_footprint_at_and_beside_the_form_limits(engine):
     b.destroy()
 
 
+def test_form_h_above_64_kib_of_items(engine):
+    """n = 8065 at node cap 64 is form H by its footprint, and its ranked items (8 bytes each)
+    with the workgroup's 1 KiB are 65 544 bytes of dynamic LDS: the fewest items that take form
+    H's launch above the 64 KiB a kernel gets without the dynamic-LDS attribute."""
+    c = kb.strongly_correlated(5, 8065, 64)
+    assert kb.form_of(8065, 64) == 2
+    assert 1024 + 8 * 8064 <= 64 * 1024 < 1024 + 8 * 8065
+    b = make(engine, [c])
+    res = b.Solve()
+    assert (res.items_w, res.items_g, res.items_h) == (0, 0, 1)
+    check_instance(outputs(b), 0, kb.reference(c), name=c["name"])
+    b.destroy()
+
+
 @pytest.mark.parametrize("which", [0, 1])
 def test_node_cap(engine, which):
     """Test 4: caps of E, E - 1, E + 1 and one that stops the search after the root, all in one

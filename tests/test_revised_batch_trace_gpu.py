@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lp_cases
 import revised_batch_cases as rc
 import special_values as sv
 from test_oracle_revised import flat
@@ -238,6 +239,31 @@ def test_mixed_forms_shuffled_neighbours(engine, oracle):
     assert any(int(s) > 4 for s in snaps)
     check_traces(b, traces, "mixed")
     b.destroy()
+
+
+def test_forms_g_and_h_above_64_kib(engine, oracle):
+    """One LP each at the smallest shapes that take more than the 64 KiB of dynamic LDS a kernel
+    gets without the attribute: 61 x 64 in form G (66 304 bytes; 61 x 63 takes 65 312) and
+    64 x 1578 in form H (vectors and tile: 65 552 bytes; 64 x 1577 takes 65 536).  Three passes,
+    every record against the oracle's; the untraced batch gives the same reads."""
+    from lpr_381_group_v22_amd import RevisedSimplexBatch, revised_batch as rb
+    def h_bytes(m, n):
+        return 8 * (rb.footprint(m, n) - m * (m | 1) - m * (n | 1) + 256 * 17)
+    assert 8 * rb.footprint(61, 63) <= 64 * 1024 < 8 * rb.footprint(61, 64) <= rb.MAX_LDS_G
+    assert h_bytes(64, 1577) <= 64 * 1024 < h_bytes(64, 1578)
+    for (m, n), form in (((61, 64), rb.FORM_G), ((64, 1578), rb.FORM_H)):
+        assert rb.pick_form(m, n) == form
+        models = [lp_cases.random_dense(m, n, 17)[:2] + (False,)]
+        traces = traces_of(oracle, ("above 64 KiB", form), models, max_iter=3, cap=5)
+        assert (traces[0]["status"], traces[0]["iterations"], traces[0]["count"]) == (5, 3, 3)
+        b, res = traced(engine, models, cap=3, trace_cap=5)
+        assert res.limit == 1
+        check_traces(b, traces, ("above 64 KiB", form))
+        u = RevisedSimplexBatch(models, engine=engine, log_cap=rc.CAP)
+        u.Solve(max_pivots=3)
+        assert reads(u) == reads(b), form
+        b.destroy()
+        u.destroy()
 
 
 # --------------------------------------------------------------------- 9. special values, division

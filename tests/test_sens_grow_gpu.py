@@ -181,6 +181,33 @@ def test_form_boundary(engine, oracle):
     h.destroy()
 
 
+def test_form_g_above_64_kib_plain_then_grow(engine, oracle):
+    """A 64 x 129 base (68 360 bytes of dynamic LDS in form G, above the 64 KiB a kernel gets
+    without the dynamic-LDS attribute) first under a batch that cannot grow, then under a grow
+    batch that adds a column (64 x 130, 68 888 bytes): k_sens_batch<true, false> and
+    k_sens_batch<true, true> each need the attribute set for themselves."""
+    from lpr_381_group_v22_amd import SensitivityBatch
+    from lpr_381_group_v22_amd.sens_batch import footprint_g
+    base, scripts = cases.threshold_case(63, 2, 43)
+    script = scripts[0][:3]
+    assert base[0].shape == (64, 129)
+    assert 64 * 1024 < footprint_g(64, 129) < footprint_g(64, 130) <= 159 * 1024
+    ref = cases.oracle_run(oracle, base, script)
+    assert sum(ref[2]) == 3
+    d = _handle(engine, base)
+    b = SensitivityBatch(d, [script])
+    d.destroy()
+    res = b.Run(variant=VARIANT_G)
+    assert res.form == FORM_G and res.finished == 1 and res.pivots == 3
+    cases.same_scenario(b, 0, ref, "plain, G above 64 KiB")
+    b.destroy()
+    ops = [("add_activity", grow.activity(99, 1.0)), script[0], script[1]]
+    g, _, refs = _run_and_check(engine, oracle, "grow, G above 64 KiB", base, [ops], form=FORM_G,
+                                variant=VARIANT_G)
+    assert g.Shape(0) == (64, 130) and sum(refs[0][2]) == 3
+    g.destroy()
+
+
 @pytest.mark.parametrize("variant", [VARIANT_G, VARIANT_H])
 def test_resumption_one_pivot_per_call(engine, edit_cases, variant):
     """max_pivots = 1 per call until nothing is running: the bytes of one call.  A scenario that

@@ -1,8 +1,9 @@
 // bb_narr_check.cpp -- host-only walker over the record layout of a narrated B&B batch
 // (lpr_381_group_v22_amd/csrc/bb_narr_layout.hpp).  It replays the cursor
-// rules the search kernel uses (narr_push / narr_drop / narr_rewind, the very text the kernel
-// compiles) over a slab allocated at exactly the reserved size, writes every cell of every kept
-// tableau as the kernel's lanes would, and checks against a model that keeps plain lists:
+// rules the search kernel uses (kept_push / kept_drop of kept_prefix.hpp and narr_rewind, the very
+// text the kernel compiles) over a slab allocated at exactly the reserved size, writes every cell
+// of every kept tableau as the kernel's lanes would, and checks against a model that keeps plain
+// lists:
 //   - kept tableaux are compact and in order, from the slice start;
 //   - the drop of :392-400 steps back by exactly the last tableau, kept or not;
 //   - once a tableau does not fit, no later one is written (a prefix), and the totals stay exact;
@@ -12,6 +13,7 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -I lpr_381_group_v22_amd/csrc \
 //       tools/bb_narr_check.cpp -o bb_narr_check && ./bb_narr_check
 #include "bb_narr_layout.hpp"
+#include "kept_prefix.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -90,9 +92,9 @@ void walk(const char* what, const std::vector<Ip>& ips) {
     for (size_t k = 0; k < ips.size(); ++k) {
         desc[k] = BBNarrDesc{};
         desc[k].slab_off = total;
-        desc[k].cap = ips[k].cap;
-        desc[k].cur = 77;  // stale state of an earlier run: the rewind clears it
-        desc[k].made_t = 5;
+        desc[k].kp.cap = ips[k].cap;
+        desc[k].kp.cur = 77;  // stale state of an earlier run: the rewind clears it
+        desc[k].kp.made_n = 5;
         total += ips[k].cap;
     }
     // exactly sized: one write past the end is an AddressSanitizer report
@@ -108,8 +110,8 @@ void walk(const char* what, const std::vector<Ip>& ips) {
         int64_t last_n = 0;
         for (const Event& e : ips[k].ev) {
             if (e.n) {
-                const int64_t at = lpr::narr_push(c, e.n);
-                const bool keep = !model_full && model_kept + e.n <= c.cap;
+                const int64_t at = lpr::kept_push(c.kp, e.n);
+                const bool keep = !model_full && model_kept + e.n <= c.kp.cap;
                 CHECK((at >= 0) == keep, "%s IP %zu: push of %lld kept=%d, model %d", what, k,
                       (long long)e.n, at >= 0, keep);
                 if (keep) {
@@ -121,7 +123,7 @@ void walk(const char* what, const std::vector<Ip>& ips) {
                 }
                 model.push_back({e.n, at});
                 if (at >= 0) {
-                    CHECK(at + e.n <= c.cap, "%s IP %zu: past the slice", what, k);
+                    CHECK(at + e.n <= c.kp.cap, "%s IP %zu: past the slice", what, k);
                     double* rec = slab + c.slab_off + at;
                     for (int64_t x = 0; x < e.n; ++x) {  // the lanes' second stores
                         rec[x] = (double)x;
@@ -133,7 +135,7 @@ void walk(const char* what, const std::vector<Ip>& ips) {
                 const Made m = model.back();
                 model.pop_back();
                 CHECK(m.n == last_n, "%s: the walker drops only the tableau just made", what);
-                lpr::narr_drop(c, m.n);
+                lpr::kept_drop(c.kp, m.n);
                 if (m.at >= 0) {
                     model_kept -= m.n;
                     for (int64_t x = 0; x < m.n; ++x) --hits[c.slab_off + m.at + x];
@@ -143,10 +145,11 @@ void walk(const char* what, const std::vector<Ip>& ips) {
             }
             int64_t md = 0;
             for (const Made& q : model) md += q.n;
-            CHECK(c.made_t == (int64_t)model.size() && c.made_d == md && c.cur == model_kept,
+            CHECK(c.kp.made_n == (int64_t)model.size() && c.kp.made_d == md &&
+                      c.kp.cur == model_kept,
                   "%s IP %zu: totals (%lld %lld %lld), model (%zu %lld %lld)", what, k,
-                  (long long)c.made_t, (long long)c.made_d, (long long)c.cur, model.size(),
-                  (long long)md, (long long)model_kept);
+                  (long long)c.kp.made_n, (long long)c.kp.made_d, (long long)c.kp.cur,
+                  model.size(), (long long)md, (long long)model_kept);
         }
         // what is kept is a prefix of what was made
         bool gap = false;
@@ -156,13 +159,13 @@ void walk(const char* what, const std::vector<Ip>& ips) {
             gap = gap || q.at < 0;
             kept_t += q.at >= 0;
         }
-        CHECK(c.kept_t == kept_t, "%s IP %zu: kept_t", what, k);
-        if (c.cap >= need_of(ips[k].ev))
-            CHECK(!gap && c.cur == c.made_d, "%s IP %zu: the exact need keeps all", what, k);
-        for (int64_t x = 0; x < c.cap; ++x)
-            if (hits[c.slab_off + x] != (x < c.cur ? 1 : 0)) {
+        CHECK(c.kp.kept_n == kept_t, "%s IP %zu: kept_t", what, k);
+        if (c.kp.cap >= need_of(ips[k].ev))
+            CHECK(!gap && c.kp.cur == c.kp.made_d, "%s IP %zu: the exact need keeps all", what, k);
+        for (int64_t x = 0; x < c.kp.cap; ++x)
+            if (hits[c.slab_off + x] != (x < c.kp.cur ? 1 : 0)) {
                 CHECK(false, "%s IP %zu: cell %lld written %d times (kept %lld)", what, k,
-                      (long long)x, hits[c.slab_off + x], (long long)c.cur);
+                      (long long)x, hits[c.slab_off + x], (long long)c.kp.cur);
                 break;
             }
     }

@@ -1,5 +1,6 @@
 // cut_narr_check.cpp -- host-only walker over the record layout of a narrated cutting-plane batch
-// (DESIGN.md section 24).  It includes csrc/cut_narr_layout.hpp, replays the push rule and the
+// (DESIGN.md section 24).  It includes csrc/cut_narr_layout.hpp and the cursor it embeds
+// (csrc/kept_prefix.hpp), replays the push rule (kept_push, the text the kernels compile) and the
 // lane walk of cut_batch_body.hpp for 256 lanes -- the cut row by its `j += 256` loop, the
 // tableau after a pivot by the four-in-flight update walk, lane `tid` of pass u at element
 // base + u * 256 + tid with its (i, j) advanced by (256 / C, 256 % C) -- over a data buffer of
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "cut_narr_layout.hpp"
+#include "kept_prefix.hpp"
 
 using namespace lpr;
 
@@ -49,7 +51,7 @@ void event(Item& it, int kind, int a, int b, int rows_now) {
 
 void store(Item& it, int64_t at, int64_t x, double v) {
     const int64_t p = at + x;
-    if (p < 0 || p >= it.c.cap) fail("store past the slice", p, it.c.cap);
+    if (p < 0 || p >= it.c.kp.cap) fail("store past the slice", p, it.c.kp.cap);
     if (it.written[(size_t)p]) fail("cell written twice", p, x);
     it.written[(size_t)p] = 1;
     it.data[(size_t)p] = v;
@@ -60,8 +62,8 @@ double cell(int64_t blk, int i, int j) { return (double)blk * 1e7 + (double)i * 
 
 // block 0 (k_cut_batch_narr_first) and the cut row: lane tid stores x = tid, tid + 256, ...
 void strided_block(Item& it, int64_t n, int row, int C) {
-    const int64_t blk = it.c.made_b;
-    const int64_t at = cut_narr_push(it.c, n);
+    const int64_t blk = it.c.kp.made_n;
+    const int64_t at = kept_push(it.c.kp, n);
     it.starts.push_back(it.need);
     it.need += n;
     if (at < 0) return;
@@ -72,9 +74,9 @@ void strided_block(Item& it, int64_t n, int row, int C) {
 
 // the tableau after a pivot: the update walk of cut_batch_body.hpp, four elements in flight
 void pivot_block(Item& it, int R, int C) {
-    const int64_t blk = it.c.made_b;
+    const int64_t blk = it.c.kp.made_n;
     const int64_t n = (int64_t)R * C;
-    const int64_t at = cut_narr_push(it.c, n);
+    const int64_t at = kept_push(it.c.kp, n);
     it.starts.push_back(it.need);
     it.need += n;
     if (at < 0) return;
@@ -111,7 +113,7 @@ void pivot_block(Item& it, int R, int C) {
 int64_t run(int R0, int C, int cuts, int solver_pivots, int64_t cap, int ev_cap) {
     Item it;
     it.c = CutNarrDesc();
-    it.c.cap = cap;
+    it.c.kp.cap = cap;
     it.c.ev_cap = ev_cap;
     it.ev.assign((size_t)4 * ev_cap, -1);
     it.data.assign((size_t)cap, -1.0);
@@ -158,8 +160,8 @@ int64_t run(int R0, int C, int cuts, int solver_pivots, int64_t cap, int ev_cap)
         ++blk;
     }
     if (blk != it.starts.size() || off != it.need) fail("block count / need", (long long)blk, off);
-    if (it.c.made_d != it.need || it.c.made_b != (int64_t)it.starts.size())
-        fail("made counts are not exact", it.c.made_d, it.c.made_b);
+    if (it.c.kp.made_d != it.need || it.c.kp.made_n != (int64_t)it.starts.size())
+        fail("made counts are not exact", it.c.kp.made_d, it.c.kp.made_n);
     // what is kept is the longest prefix of whole blocks that fits
     int64_t kept_b = 0, kept_d = 0;
     for (size_t q = 0; q < it.starts.size(); ++q) {
@@ -168,7 +170,7 @@ int64_t run(int R0, int C, int cuts, int solver_pivots, int64_t cap, int ev_cap)
         kept_b = (int64_t)q + 1;
         kept_d = end;
     }
-    if (it.c.kept_b != kept_b || it.c.cur != kept_d) fail("kept is not the whole-block prefix", it.c.kept_b, kept_b);
+    if (it.c.kp.kept_n != kept_b || it.c.kp.cur != kept_d) fail("kept is not the whole-block prefix", it.c.kp.kept_n, kept_b);
     // every cell of every kept block written exactly once with its own value; nothing behind
     for (int64_t p = 0; p < cap; ++p) {
         const bool want = p < kept_d;
