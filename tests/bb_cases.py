@@ -1,6 +1,12 @@
 """Branch & Bound instances for the parity tests (TEST ONLY).  Every instance goes through the
 reference's own route (Program.cs option 3): model -> x_i <= 1 rows appended -> PrimalSimplexSolver
--> FinalTableau -> BranchAndBoundAdapter.SolveFromPrimal."""
+-> FinalTableau -> BranchAndBoundAdapter.SolveFromPrimal.
+
+Provides: the product-route cases (all_bb_cases, primal_final_tableau), and the edge instances the
+cases never reach (flag_room_cases, tall_cases, widest_lds_case, big_value_cases; edge_cases /
+edge_case by name).  Constructed roots that tie a selection of the batched search exactly across a
+lane, wave, stride or last-round seam are not here but in seam_cases.py (bb_items), built with the
+same widening and heightening that leaves a root's basic columns alone."""
 from __future__ import annotations
 
 import numpy as np

@@ -1,7 +1,9 @@
 """Shared inputs of the revised-simplex batch tests: the models of
 test_oracle_revised.revised_cases(), the shapes on both sides of the form thresholds (derived
 from the footprint formula the Python mirror repeats from rev_batch_common.hpp), the tie-heavy
-set that exercises the ratio fold's tie clause, and an instrumented copy of that fold."""
+set that exercises the ratio fold's tie clause, and an instrumented copy of both folds
+(tie_stats; with a probe list it also reports what the entering and the ratio fold saw and chose
+at every iteration, which seam_cases.py uses to find and assert where its plants are live)."""
 import math
 
 import numpy as np
@@ -70,11 +72,13 @@ def tie_models():
             for (m, n) in TIE_SHAPES for seed in TIE_SEEDS]
 
 
-def tie_stats(model, max_iter=CAP):
+def tie_stats(model, max_iter=CAP, probe=None):
     """The loop of Solve() (:82-251) on ref_py's helpers with an instrumented ratio fold.
     Returns (status, iterations, fired, changed): the iterations at which the tie clause replaces
     an already-taken row, and those at which the chosen row differs from the pure
-    "ratio < best - EPS" fold."""
+    "ratio < best - EPS" fold.  probe: a list that receives, per iteration that reaches a pivot,
+    what the two folds saw and chose: dict(it, rc (per index of n + m, None: not a candidate),
+    entering, ratios (per row, None: u_i <= EPS), basic (before the pivot), leaving)."""
     obj, cons, is_min = model
     n, m = len(obj), len(cons)
     c = [-v for v in obj] if is_min else list(obj)
@@ -93,8 +97,11 @@ def tie_stats(model, max_iter=CAP):
         rcX = [c[j] - _dot(y, [A[i][j] for i in range(m)]) for j in range(n)]
         rcS = [-y[k] for k in range(m)]
         entering, best = -1, -math.inf
+        seen = [None] * (n + m)
         for v in sorted(nonbasic):
             rc = rcX[v] if v < n else rcS[v - n]
+            if rc > REV_EPS:
+                seen[v] = rc
             if rc > REV_EPS and (entering == -1 or rc > best + REV_EPS):
                 best, entering = rc, v
         if entering == -1:
@@ -108,9 +115,11 @@ def tie_stats(model, max_iter=CAP):
         leaving, best_ratio = -1, DBL_MAX
         pure, pure_best = -1, DBL_MAX
         tie_here = False
+        ratios = [None] * m
         for i in range(m):
             if u[i] > REV_EPS:
                 ratio = xB[i] / u[i]
+                ratios[i] = ratio
                 if ratio < pure_best - REV_EPS:
                     pure, pure_best = i, ratio
                 if ratio < best_ratio - REV_EPS:
@@ -123,6 +132,9 @@ def tie_stats(model, max_iter=CAP):
             return "unbounded", it, fired, changed
         fired += tie_here
         changed += leaving != pure
+        if probe is not None:
+            probe.append(dict(it=it, rc=seen, entering=entering, ratios=ratios,
+                              basic=list(basic), leaving=leaving))
         leaving_var = basic[leaving]
         if leaving_var == entering:
             return "entering_already_basic", it, fired, changed
