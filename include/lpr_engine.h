@@ -120,7 +120,9 @@ typedef struct lpr_solve_opts {
                               n-th step only (the events sit on the sweep's stream: two per step
                               cost the two-stream pipeline ~3 %). */
     int32_t batch;         /* pivots queued between host polls of the device status word (0: auto) */
-    int32_t variant;       /* kernel variant (0: auto); for tuning and tests only, same bits.  Low 16
+    int32_t variant;       /* kernel variant (0: auto); for tuning and tests only, same bits.  Decoded
+                              in one place, primal_plan() of csrc/primal_plan.hpp (DESIGN 4b
+                              "Control"), which names every value below.  Low 16
                               bits: path + sweep tile (0x30tr two-stream overlap, 0x40tr heads then
                               in-place sweep; tr = 0x04/0x08/0x10 rows per chunk, 0x24/0x28 two
                               chunks in flight).  0x50tr and 0x60tr named forms since retired and

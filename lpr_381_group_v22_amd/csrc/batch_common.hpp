@@ -2,8 +2,8 @@
 // and its kernels (batch_body.hpp, instantiated by batch_kernels.hip and, traced, by
 // batch_trace_kernels.hip), and what the four batch engines (LP, B&B: bb_batch_*,
 // scenarios: sens_batch_*, cutting plane: cut_batch_*) have in common on the host: the forms and the rule that picks one, the
-// running-list driver, the one form launcher (batch_launch, which owns the dynamic-LDS attribute
-// of every kernel instantiation) and the handle plumbing.  The device side of what
+// running-list driver, the one form launcher (batch_launch, which asks raise_dynamic_lds of engine_common.hpp
+// once per kernel instantiation) and the handle plumbing.  The device side of what
 // they share is batch_device.hpp.  Not part of the ABI (include/lpr_engine.h is).
 #pragma once
 
@@ -184,24 +184,6 @@ struct BatchRunLists {
     }
 };
 
-// Dynamic LDS above 64 KiB needs the attribute once per kernel and device; *mask keeps one bit
-// per device for one kernel instantiation.
-inline int raise_dynamic_lds(const void* fn, size_t bytes, unsigned long long* mask) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LPR_DEVICE_ERROR;
-    const unsigned long long bit = 1ull << dev;
-    if (__atomic_load_n(mask, __ATOMIC_ACQUIRE) & bit) return LPR_OK_OPTIMAL;
-    const hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)bytes);
-    if (err != hipSuccess) {
-        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed: %s", bytes,
-                  hipGetErrorString(err));
-        return LPR_DEVICE_ERROR;
-    }
-    __atomic_fetch_or(mask, bit, __ATOMIC_ACQ_REL);
-    return LPR_OK_OPTIMAL;
-}
-
 // hipGetLastError after a launch, as a return code and a message.
 inline int launch_checked(const char* name) {
     const hipError_t err = hipGetLastError();
@@ -252,6 +234,23 @@ void unlist(std::vector<H*>& live, H* h) {
 // batch_engine.hip: what an engine that starts from a solved LP batch reads of it: its engine (null
 // once orphaned, or with no handle), the descriptors' host mirror and the tableau slab
 lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
+
+// batch_kernels.hip and, traced, batch_trace_kernels.hip: the launchers batch_engine.hip calls
+int batch_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab, int32_t* basis,
+                         int32_t* logs, const int32_t* idx_in, int n_in, int32_t* idx_out,
+                         int32_t* n_out, int chunk, int slot_doubles, int max_rows, int max_cols);
+int batch_trace_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab,
+                               int32_t* basis, int32_t* logs, const int32_t* idx_in, int n_in,
+                               int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles,
+                               int max_rows, int max_cols, BatchTrace tr);
+void batch_trace_launch_first(hipStream_t s, const BatchDesc* desc, int count, const double* slab,
+                              BatchTrace tr);
+void batch_launch_build(hipStream_t s, const BatchDesc* desc, const BatchBuild* bd, int count,
+                        double* slab, int32_t* basis, const double* obj, const double* A,
+                        const int32_t* ncoef, const int8_t* rel, const double* rhs,
+                        const int8_t* is_max);
+void batch_launch_extract(hipStream_t s, const BatchDesc* desc, int count, const double* slab,
+                          double* x, double* z);
 
 }  // namespace lpr
 

@@ -9,24 +9,6 @@
 #include <algorithm>
 #include <climits>
 
-namespace lpr {
-int batch_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab, int32_t* basis,
-                         int32_t* logs, const int32_t* idx_in, int n_in, int32_t* idx_out,
-                         int32_t* n_out, int chunk, int slot_doubles, int max_rows, int max_cols);
-int batch_trace_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab,
-                               int32_t* basis, int32_t* logs, const int32_t* idx_in, int n_in,
-                               int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles,
-                               int max_rows, int max_cols, BatchTrace tr);
-void batch_trace_launch_first(hipStream_t s, const BatchDesc* desc, int count, const double* slab,
-                              BatchTrace tr);
-void batch_launch_build(hipStream_t s, const BatchDesc* desc, const BatchBuild* bd, int count,
-                        double* slab, int32_t* basis, const double* obj, const double* A,
-                        const int32_t* ncoef, const int8_t* rel, const double* rhs,
-                        const int8_t* is_max);
-void batch_launch_extract(hipStream_t s, const BatchDesc* desc, int count, const double* slab,
-                          double* x, double* z);
-}  // namespace lpr
-
 using namespace lpr;
 
 struct lpr_batch {

@@ -8,21 +8,6 @@
 #include <climits>
 #include <cmath>
 
-namespace lpr {
-int bb_batch_launch(int form, hipStream_t s, const BBBatchBufs& B, const int32_t* idx_in,
-                    int n_in, int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles,
-                    int max_rows);
-void bb_batch_launch_load(hipStream_t s, const BBBatchDesc* desc, int count, const double* src,
-                          const int64_t* src_off, double* stack);
-void bb_batch_launch_reset(hipStream_t s, const BBBatchBufs& B, int count);
-int bb_batch_narr_launch(int form, hipStream_t s, const BBBatchBufs& B, const BBNarr& narr,
-                         const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out,
-                         int chunk, int slot_doubles, int max_rows);
-void bb_batch_narr_launch_reset(hipStream_t s, const BBBatchBufs& B, const BBNarr& narr,
-                                int count);
-lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
-}  // namespace lpr
-
 using namespace lpr;
 
 struct lpr_bb_batch {

@@ -50,6 +50,16 @@ struct BBSlot {
     int32_t rep;       // slots[u].rep: a child slot of the u-th distinct parent of the batch
 };
 
+// bb_kernels.hip: the launchers bb_engine.hip calls
+void bb_launch_copy_in(lpr_bb* b, const double* src, int src_ld, int rows, int cols, double* dst);
+void bb_launch_round(lpr_bb* b, int nslots, int rows_max, int clean);
+void bb_launch_node_info(lpr_bb* b, int count);
+void bb_launch_add_constraint(lpr_bb* b, int nslots, int nparents, int rows_max, int cols_max,
+                              bool side, bool inplace);
+void bb_launch_pivot_step(lpr_bb* b, int nslots, int rows_max, int cols_max, int step_no);
+void bb_launch_finish(lpr_bb* b, int nslots, int cols_max);
+void bb_launch_gather_info(lpr_bb* b, int count);
+
 }  // namespace lpr
 
 struct lpr_bb {

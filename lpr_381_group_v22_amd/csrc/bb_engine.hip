@@ -6,6 +6,7 @@
 // primal pivots of DoDualSimplex, the decision-value scans) runs on the device, batched over the
 // children that are evaluated together.  Node tableaux never leave HBM.  No CPU fallback.
 #include "bb_common.hpp"
+#include "comm_engine.hpp"
 
 #include <chrono>
 #include <cstdio>
@@ -17,23 +18,7 @@
 
 #pragma clang fp contract(off)
 
-struct lpr_comm;
 namespace lpr {
-// comm_engine.hip
-int comm_rank(const lpr_comm* c);
-int comm_world(const lpr_comm* c);
-int comm_all_reduce_max(lpr_comm* c, double* v, int n);
-int comm_all_gather(lpr_comm* c, const void* send, void* recv, int bytes);
-
-// bb_kernels.hip
-void bb_launch_copy_in(lpr_bb* b, const double* src, int src_ld, int rows, int cols, double* dst);
-void bb_launch_round(lpr_bb* b, int nslots, int rows_max, int clean);
-void bb_launch_node_info(lpr_bb* b, int count);
-void bb_launch_add_constraint(lpr_bb* b, int nslots, int nparents, int rows_max, int cols_max,
-                              bool side, bool inplace);
-void bb_launch_pivot_step(lpr_bb* b, int nslots, int rows_max, int cols_max, int step_no);
-void bb_launch_finish(lpr_bb* b, int nslots, int cols_max);
-void bb_launch_gather_info(lpr_bb* b, int count);
 
 // ---- .NET Framework rounding on the host (IsInteger :595-599 works on n values per node) ----
 static double dn_round_int(double x) {  // Math.Round(double), COMDouble::Round

@@ -19,50 +19,14 @@
 //   k_bb_node_info     GetObjective (:892-897) + decision values (:807-827 / :899-921)
 #include "bb_common.hpp"
 #include "bb_device_round.hpp"
+#include "select_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace lpr {
 
 // ------------------------------------------------------------------ reductions
-struct Cand {
-    double v;
-    int i;
-};
-__device__ __forceinline__ Cand cand_min(Cand a, Cand b) {
-    if (b.i < 0) return a;
-    if (a.i < 0) return b;
-    if (b.v < a.v || (b.v == a.v && b.i < a.i)) return b;
-    return a;
-}
-__device__ __forceinline__ Cand block_cand_min(Cand c, double* lds_v, int* lds_i) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x / kWave;
-    const int nwaves = blockDim.x / kWave;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Cand o;
-        o.v = __shfl_xor(c.v, off, kWave);
-        o.i = __shfl_xor(c.i, off, kWave);
-        c = cand_min(c, o);
-    }
-    __syncthreads();
-    if (lane == 0) {
-        lds_v[wave] = c.v;
-        lds_i[wave] = c.i;
-    }
-    __syncthreads();
-    Cand r;
-    r.v = lds_v[0];
-    r.i = lds_i[0];
-    for (int w = 1; w < nwaves; ++w) {
-        Cand o;
-        o.v = lds_v[w];
-        o.i = lds_i[w];
-        r = cand_min(r, o);
-    }
-    return r;
-}
+// (Cand, cand_min, block_cand_min: select_common.hpp)
 __device__ __forceinline__ int block_min_int(int v, int* lds) {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x / kWave;
@@ -878,13 +842,9 @@ void bb_launch_add_constraint(lpr_bb* b, int nslots, int nparents, int rows_max,
     // write: no separate pass over the children)
     const size_t elim_lds = (size_t)b->ld * sizeof(int);  // <= kBBEliminateLdsMax (lpr_bb_create)
     if (elim_lds > (48u << 10)) {
-        static bool raised = false;  // one process = one GPU
-        if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bb_eliminate),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kBBEliminateLdsMax);
-            raised = true;
-        }
+        static unsigned long long raised = 0;  // per device
+        (void)raise_dynamic_lds(reinterpret_cast<const void*>(&k_bb_eliminate),
+                                kBBEliminateLdsMax, &raised);
     }
     hipLaunchKernelGGL(k_bb_eliminate, dim3(nslots), dim3(1024), elim_lds, st,
                        b->d_slots, b->ld, b->bflag, b->bkey, b->blist, side ? b->rows_cap : -1);

@@ -5,7 +5,7 @@
 // (reference loop being sharded: BranchBoundSimplexSolver.cs:1006-1233).
 // A caller that brings its own transport (tests over gloo, a host with its own fabric) passes two
 // callbacks instead; they are invoked on the calling thread only.
-#include "engine_common.hpp"
+#include "comm_engine.hpp"
 
 #include <rccl/rccl.h>
 

@@ -8,24 +8,6 @@
 #include <algorithm>
 #include <new>
 
-namespace lpr {
-int cut_batch_launch(int form, hipStream_t s, CutBatchDesc* desc, double* slab, int32_t* logs,
-                     const CutBatchCall& call, size_t lds, const int32_t* idx_in, int n_in,
-                     int32_t* idx_out, int32_t* n_out);
-int cut_batch_launch_load(hipStream_t s, CutBatchDesc* desc, int count, const double* src,
-                          const int64_t* src_off, double* slab);
-// cut_batch_narr_kernels.hip
-int cut_batch_narr_launch(int form, hipStream_t s, CutBatchDesc* desc, double* slab,
-                          int32_t* logs, const CutBatchCall& call, const CutNarr& narr, size_t lds,
-                          const int32_t* idx_in, int n_in, int32_t* idx_out, int32_t* n_out);
-int cut_batch_narr_launch_first(hipStream_t s, const CutBatchDesc* desc, const double* slab,
-                                const CutNarr& narr, int count);
-int cut_batch_narr_launch_call(hipStream_t s, const CutBatchDesc* desc, const CutNarr& narr,
-                               int count, int mode, int print_steps);
-// batch_engine.hip
-lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
-}  // namespace lpr
-
 using namespace lpr;
 
 struct lpr_cut_batch {

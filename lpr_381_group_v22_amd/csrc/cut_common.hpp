@@ -40,3 +40,6 @@ __device__ __forceinline__ double cut_frac(double a) {  // CuttingPlaneSolver.cs
 #endif
 
 }  // namespace lpr
+
+// cut_kernels.hip: frees the cut context of a tableau handle (release_device of lpr_engine.hip)
+void lpr_cut_release(lpr_tableau* t);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/lpr_engine.h"
+#include "primal_plan.hpp"  // kLdAlign, align_up; the limits and thresholds of the primal paths
 
 // The C# rounds every product before it is added/subtracted (e.g. PrimalSimplexSolver.cs:208).
 // hipcc contracts a*b+c into v_fma_f64 by default; that is one rounding fewer and changes bits,
@@ -22,7 +23,6 @@
 namespace lpr {
 
 constexpr int kWave = 64;
-constexpr int kLdAlign = 16;          // tableau rows padded to 16 doubles = 128 B
 constexpr int32_t kRunning = -100;    // device status word while the pivot loop is live
 // K-pivot path, condensed layout: `pending` codes that never leave the driver.  The block ends
 // before the pivot that cannot be staged in that layout; the driver writes the full tableau back
@@ -43,8 +43,6 @@ const char* get_error();
             return LPR_DEVICE_ERROR;                                                      \
         }                                                                                 \
     } while (0)
-
-inline int align_up(int x, int a) { return (x + a - 1) / a * a; }
 
 // a / b, correctly rounded.  The device's own fp64 division (v_div_scale / v_rcp / Newton steps /
 // v_div_fmas / v_div_fixup) ends in ONE fused multiply-add of the residual with an APPROXIMATE
@@ -209,8 +207,45 @@ struct lpr_tableau {
 };
 
 namespace lpr {
+// Dynamic LDS above 64 KiB needs the attribute once per kernel and device; *mask keeps one bit
+// per device for one kernel instantiation.  Every kernel of the engine gets the attribute here.
+inline int raise_dynamic_lds(const void* fn, size_t bytes, unsigned long long* mask) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LPR_DEVICE_ERROR;
+    const unsigned long long bit = 1ull << dev;
+    if (__atomic_load_n(mask, __ATOMIC_ACQUIRE) & bit) return LPR_OK_OPTIMAL;
+    const hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)bytes);
+    if (err != hipSuccess) {
+        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed: %s", bytes,
+                  hipGetErrorString(err));
+        return LPR_DEVICE_ERROR;
+    }
+    __atomic_fetch_or(mask, bit, __ATOMIC_ACQ_REL);
+    return LPR_OK_OPTIMAL;
+}
+
 // lpr_engine.hip: make room for `rows_needed` tableau rows on a live handle
 int tableau_reserve_rows(lpr_tableau* t, int rows_needed);
+// lpr_engine.hip: grow the pivot log so that `need` pairs fit (keeps the old entries)
+int ensure_log(lpr_tableau* t, int64_t need);
+// lpr_engine.hip: the end of every primal solve call -- the handle's pivot count, the five result
+// fields, and z: *z_known, or (null) T[0, cols-1] read back.  Returns status.
+int finish_call(lpr_tableau* t, lpr_solve_result* res, int status, int64_t iter,
+                int64_t start_iter, int K, const double* z_known);
+// lpr_engine_close hands every handle still alive to its engine file: device memory released, the
+// handle detached so that a late *_destroy stays safe
+void rev_orphan(lpr_revised* s);
+void bb_orphan(lpr_bb* b);
+void sens_orphan(lpr_sens* s);
+void comm_orphan(lpr_comm* c);
+void knap_orphan(lpr_knap* k);
+void batch_orphan(lpr_batch* b);
+void bb_batch_orphan(lpr_bb_batch* b);
+void sens_batch_orphan(lpr_sens_batch* b);
+void cut_batch_orphan(lpr_cut_batch* b);
+void knap_batch_orphan(lpr_knap_batch* b);
+void rev_batch_orphan(lpr_rev_batch* b);
 // sens_engine.hip: what lpr_sens_batch_create reads of an analyzer (null: no handle); the engine is
 // null once the handle is orphaned
 lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,

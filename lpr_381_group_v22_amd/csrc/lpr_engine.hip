@@ -2,7 +2,10 @@
 // The pivot loop of PrimalSimplexSolver.Solve() (Simplex/PrimalSimplexSolver.cs:102-150) runs on
 // the device: the host only queues batches of (k_select, k_update) pairs and polls one status
 // word per batch.  There is no CPU fallback: without a gfx950 device lpr_engine_open fails.
-#include "engine_common.hpp"
+#include "cut_common.hpp"
+#include "overlap.hpp"
+#include "primal_kernels.hpp"
+#include "small_kernels.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -26,83 +29,6 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err.c_str(); }
 
-// primal_kernels.hip
-void launch_select(lpr_tableau* t, int mode, int e_in, int r_in, int32_t* out_i);
-void launch_bootstrap(lpr_tableau* t);
-void launch_pivot_head(lpr_tableau* t);
-void launch_update(lpr_tableau* t, int variant, int check_status, int dump_next);
-int num_update_variants();
-void launch_extract(lpr_tableau* t, int n, double* x);
-void launch_pivot_fused(lpr_tableau* t, const double* in, double* out);
-void launch_build(lpr_tableau* t, int n, int m, const double* d_obj, const double* d_A, int lda,
-                  const int32_t* d_ncoef, const int8_t* d_rel, const double* d_rhs, int is_max);
-void launch_synthetic(lpr_tableau* t, int m, int n, uint64_t seed);
-
-// overlap_kernels.hip
-int ov_max_pivots();
-void ov_release(lpr_tableau* t);
-// small_kernels.hip
-bool small_fits(const lpr_tableau* t);
-int small_pivots_per_block();
-void small_release(lpr_tableau* t);
-int small_ensure(lpr_tableau* t);
-int small_upload_state(lpr_tableau* t, int64_t iter, int64_t max_iter);
-int small_set_log_cap(lpr_tableau* t);
-void small_launch_block(lpr_tableau* t);
-int small_poll(lpr_tableau* t, int32_t* status, int64_t* iter);
-int ov_ensure(lpr_tableau* t, bool second_buffer);
-int ov_begin(lpr_tableau* t, int64_t iter, int64_t max_iter);
-int ov_set_log(lpr_tableau* t, int parity);
-void ov_launch_heads(lpr_tableau* t, int K, int flags);
-int ov2_begin(lpr_tableau* t);
-int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t ev_start,
-                    hipEvent_t ev_stop, int snap_slot);
-int ov_read_stamps(lpr_tableau* t, uint64_t* out, int64_t cap, int64_t* count);
-int ov2_join(lpr_tableau* t);
-void ov_launch_sweep(lpr_tableau* t, int tr);
-struct OvPoll {
-    int32_t status, pending, kdone, cur, error;
-    int64_t applied;
-    double z[2];  // RHS column entry 0 (= T[0, cols-1]) after an even / odd number of pivots
-};
-int ov_poll(lpr_tableau* t, int parity, bool with_flags, OvPoll* out);
-int ov_snapshot(lpr_tableau* t, int slot);
-int ov_snapshot_wait(lpr_tableau* t, int slot, OvPoll* out);
-void ov_adopt_buffer(lpr_tableau* t, int cur);
-void ovc_release(lpr_tableau* t);
-bool ovc_fits(const lpr_tableau* t, int spares);
-int ovc_width(const lpr_tableau* t, int spares);
-int ovc_ensure(lpr_tableau* t, int spares);
-int ovc_condense(lpr_tableau* t, bool* ok);
-void ovc_enter(lpr_tableau* t);
-void ovc_leave(lpr_tableau* t);
-int ovc_expand(lpr_tableau* t);
-// revised_engine.hip
-void rev_orphan(lpr_revised* s);
-// bb_engine.hip
-void bb_orphan(lpr_bb* b);
-// sens_engine.hip
-void sens_orphan(lpr_sens* s);
-void comm_orphan(lpr_comm* c);
-// knapsack_engine.hip
-void knap_orphan(lpr_knap* k);
-// batch_engine.hip
-void batch_orphan(lpr_batch* b);
-// bb_batch_engine.hip
-void bb_batch_orphan(lpr_bb_batch* b);
-// sens_batch_engine.hip
-void sens_batch_orphan(lpr_sens_batch* b);
-// cut_batch_engine.hip
-void cut_batch_orphan(lpr_cut_batch* b);
-// knapsack_batch_engine.hip
-void knap_batch_orphan(lpr_knap_batch* b);
-void rev_batch_orphan(lpr_rev_batch* b);
-}  // namespace lpr
-// cut_kernels.hip
-void lpr_cut_release(lpr_tableau* t);
-namespace lpr {
-
-enum : int { kSelEnter = 1, kSelLeave = 2, kSelCommit = 4, kSelFull = 7 };
 constexpr int kTimeStride = 4;  // opts.time_kernels samples one update launch in four (one-pivot
                                 // path; the K-pivot paths time every sweep)
 
@@ -295,7 +221,7 @@ static void release_device(lpr_tableau* t) {
 }
 
 // Grow the pivot log so that `need` pairs fit (keeps the old entries).
-static int ensure_log(lpr_tableau* t, int64_t need) {
+int ensure_log(lpr_tableau* t, int64_t need) {
     if (need <= t->log_cap) return LPR_OK_OPTIMAL;
     int64_t cap = t->log_cap;
     while (cap < need) cap *= 2;
@@ -311,20 +237,6 @@ static int ensure_log(lpr_tableau* t, int64_t need) {
     return LPR_OK_OPTIMAL;
 }
 
-// Tile shape: the tallest row tile (more loads in flight per lane, pivot-row slice reused over
-// more rows) that still gives the 256 CUs >= 8 workgroups each; measured on the 4097 x 12289
-// tableau TR=32 is the fastest (profiles/).  The serpentine sweep (bit 8) reverses the tile order
-// on alternate pivots so the tail of one sweep is re-read from the 256 MiB Infinity Cache.
-static int default_variant(const lpr_tableau* t) {
-    const long ctiles = (t->ld / 2 + 255) / 256;
-    struct { int tr; int idx; } opts[] = {{32, 5}, {16, 0}, {8, 1}, {4, 8}, {2, 9}, {1, 10}};
-    for (auto& o : opts) {
-        const long blocks = ctiles * ((t->rows + o.tr - 1) / o.tr);
-        if (blocks >= 2048 || o.tr == 1) return o.idx | 0x100;
-    }
-    return 0x100;
-}
-
 static int default_batch(const lpr_tableau* t) {
     // aim at a few milliseconds of device work between host polls
     const double bytes = 16.0 * t->rows * (double)t->ld;
@@ -335,23 +247,63 @@ static int default_batch(const lpr_tableau* t) {
     return b;
 }
 
-// Small tableaux (<= kFusedBytes): one k_pivot_fused launch per pivot, ping-pong between T and
-// T2.  opts.variant == 0x7fff forces the two-kernel path (tests), 0x7ffe forces the fused one.
-// (round 2, after the wave-granular hand-offs of the loop heads and the 8-row tiles of the small
-// in-place sweep, pivots/s K-pivot path vs this one: m = 256 (1.6 MB) 143.6 k vs 137.9 k, m = 320
-// 141.9 k vs 121.0 k, m = 512 137.7 k vs 99.7 k.  Below ~1 MB a solve is a few dozen pivots and the
-// start-up of the K-pivot path -- prologue, a fill and a drain step -- is what counts.)
-static constexpr size_t kFusedBytes = (size_t)1 << 20;
-
-static bool use_fused(const lpr_tableau* t, const lpr_solve_opts& o) {
-    if (o.time_kernels) return false;
-    if (o.block >= 2) return false;  // the K-pivots-per-sweep path was asked for explicitly
-    if (o.variant == 0x7fff) return false;
-    if (o.variant == 0x7ffe) return true;
-    if (o.variant != 0) return false;
-    return (size_t)t->rows * t->ld * sizeof(double) <= kFusedBytes;
+// Replays the captured batch of `nb` launches that `key` names, capturing it first (emit() queues
+// the launches on the engine stream) unless the handle holds a valid one.  When a capture pays is
+// the caller's policy.
+template <class Emit>
+static int replay_or_capture(lpr_tableau* t, int nb, int key, Emit emit) {
+    hipStream_t s = t->eng->stream;
+    if (!graph_valid(t, nb, key)) {
+        drop_graph(t);
+        hipGraph_t g = nullptr;
+        LPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        emit();
+        LPR_HIP(hipStreamEndCapture(s, &g));
+        hipError_t ierr = hipGraphInstantiate(&t->graph, g, nullptr, nullptr, 0);
+        hipGraphDestroy(g);
+        if (ierr != hipSuccess) {
+            t->graph = nullptr;
+            set_error("hipGraphInstantiate failed: %s", hipGetErrorString(ierr));
+            return LPR_DEVICE_ERROR;
+        }
+        graph_stamp(t, nb, key);
+    }
+    LPR_HIP(hipGraphLaunch(t->graph, s));
+    return LPR_OK_OPTIMAL;
 }
 
+int finish_call(lpr_tableau* t, lpr_solve_result* res, int status, int64_t iter,
+                int64_t start_iter, int K, const double* z_known) {
+    t->total_pivots = iter;
+    res->status = status;
+    res->block = K;
+    res->pivots = iter - start_iter;
+    res->total_pivots = iter;
+    if (z_known) {
+        res->z = *z_known;
+        return status;
+    }
+    hipStream_t s = t->eng->stream;
+    double z = 0.0;
+    LPR_HIP(hipMemcpyAsync(&z, t->T + (t->cols - 1), sizeof(double), hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    res->z = z;
+    return status;
+}
+
+// scratch_i[idx] after the launch just queued
+static int read_scratch(lpr_tableau* t, int idx, int32_t* out) {
+    hipStream_t s = t->eng->stream;
+    LPR_HIP(hipGetLastError());
+    LPR_HIP(hipMemcpyAsync(t->h_scratch_i, t->scratch_i, 4 * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, s));
+    LPR_HIP(hipStreamSynchronize(s));
+    *out = t->h_scratch_i[idx];
+    return LPR_OK_OPTIMAL;
+}
+
+// Tableaux up to kFusedBytes that the cache-resident path does not take (PrimalPath::Fused): one
+// k_pivot_fused launch per pivot, ping-pong between T and T2.
 static int solve_fused(lpr_tableau* t, const lpr_solve_opts& o, lpr_solve_result* res) {
     lpr_engine* e = t->eng;
     hipStream_t s = e->stream;
@@ -390,27 +342,15 @@ static int solve_fused(lpr_tableau* t, const lpr_solve_opts& o, lpr_solve_result
         // already, or when enough work is ahead to pay for capturing it (a few ms)
         const bool have = graph_valid(t, nb, -2);
         const bool full = (nb == batch) && (have || max_iter == 0 || max_iter - iter >= 4 * batch);
-        if (full) {
-            if (!have) {
-                drop_graph(t);
-                hipGraph_t g = nullptr;
-                LPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                for (int k = 0; k < nb; ++k)
-                    launch_pivot_fused(t, (k & 1) ? t->T2 : t->T, (k & 1) ? t->T : t->T2);
-                LPR_HIP(hipStreamEndCapture(s, &g));
-                hipError_t ierr = hipGraphInstantiate(&t->graph, g, nullptr, nullptr, 0);
-                hipGraphDestroy(g);
-                if (ierr != hipSuccess) {
-                    t->graph = nullptr;
-                    set_error("hipGraphInstantiate failed: %s", hipGetErrorString(ierr));
-                    return LPR_DEVICE_ERROR;
-                }
-                graph_stamp(t, nb, -2);
-            }
-            LPR_HIP(hipGraphLaunch(t->graph, s));
-        } else {
+        auto emit = [&] {
             for (int k = 0; k < nb; ++k)
                 launch_pivot_fused(t, (k & 1) ? t->T2 : t->T, (k & 1) ? t->T : t->T2);
+        };
+        if (full) {
+            rc = replay_or_capture(t, nb, -2, emit);
+            if (rc != LPR_OK_OPTIMAL) return rc;
+        } else {
+            emit();
         }
         LPR_HIP(hipGetLastError());
         LPR_HIP(hipMemcpyAsync(hs, t->state, sizeof(PivotState), hipMemcpyDeviceToHost, s));
@@ -429,52 +369,32 @@ static int solve_fused(lpr_tableau* t, const lpr_solve_opts& o, lpr_solve_result
         }
     }
     if (status == kRunning) {  // stopped by the pivot limit: classify the current tableau
+        int32_t ec = -1, lr = -1;
         launch_select(t, kSelEnter, -1, -1, t->scratch_i);
-        LPR_HIP(hipMemcpyAsync(t->h_scratch_i, t->scratch_i, 4 * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
-        LPR_HIP(hipStreamSynchronize(s));
-        const int ec = t->h_scratch_i[0];
-        if (ec < 0) status = LPR_OK_OPTIMAL;
-        else {
+        int rc = read_scratch(t, 0, &ec);
+        if (rc == LPR_OK_OPTIMAL && ec >= 0) {
             launch_select(t, kSelLeave, ec, -1, t->scratch_i);
-            LPR_HIP(hipMemcpyAsync(t->h_scratch_i, t->scratch_i, 4 * sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, s));
-            LPR_HIP(hipStreamSynchronize(s));
-            status = t->h_scratch_i[1] < 0 ? LPR_UNBOUNDED : LPR_PIVOT_LIMIT;
+            rc = read_scratch(t, 1, &lr);
         }
+        if (rc != LPR_OK_OPTIMAL) return rc;
+        status = ec < 0 ? LPR_OK_OPTIMAL : (lr < 0 ? LPR_UNBOUNDED : LPR_PIVOT_LIMIT);
     }
-    t->total_pivots = iter;
-    res->status = status;
-    res->block = 1;
-    res->pivots = iter - start_iter;
-    res->total_pivots = iter;
-    double z = 0.0;
-    LPR_HIP(hipMemcpyAsync(&z, t->T + (t->cols - 1), sizeof(double), hipMemcpyDeviceToHost, s));
-    LPR_HIP(hipStreamSynchronize(s));
-    res->z = z;
-    return status;
+    return finish_call(t, res, status, iter, start_iter, 1, nullptr);
 }
 
 // Cache-resident tableaux (R <= 1024, ld <= 2048: small_kernels.hip): the 16 loop heads of a block
 // in ONE workgroup, hand-offs through LDS, then one in-place sweep.  The default for every tableau
-// that fits (opts.variant == 0, opts.block == 0); opts.variant 0x20xx forces it.
+// that fits (PrimalPath::Small of primal_plan.hpp).
 // Measured on the round's final code (tools/size_sweep.sh, profiles/r03_size_sweep.jsonl; pivots/s,
 // this path vs heads-then-sweep 0x4008): m = 512 (6.3 MB) 214 k vs 154 k; 640 x 1280 (9.9 MB) 206 k
 // vs 150 k; 1020 x 400 (11.6 MB) 194 k vs 110 k; 800 x 1200 (12.8 MB) 193 k vs 145 k; m = n = 1000
 // (16 MB) 184 k vs 146 k; 1023 x 1000 (16.6 MB, the largest that fits) 183 k vs 146 k: it wins
 // wherever it fits.  (Mid round 3 the 16 MB case read 132 k vs 140 k and the default stopped at
 // 10 MB; the later work on the heads moved it.)
-static bool use_small(const lpr_tableau* t, const lpr_solve_opts& o) {
-    if (!small_fits(t)) return false;
-    if ((o.variant & 0xff00) == 0x2000) return true;
-    return o.variant == 0 && o.block == 0;
-}
-
 static int solve_small(lpr_tableau* t, const lpr_solve_opts& o, lpr_solve_result* res) {
-    hipStream_t s = t->eng->stream;
     int rc = small_ensure(t);
     if (rc != LPR_OK_OPTIMAL) return rc;
-    const int K = small_pivots_per_block();
+    const int K = kSmallK;
     const int64_t start_iter = t->total_pivots;
     const int64_t max_iter = o.max_pivots > 0 ? start_iter + o.max_pivots : 0;
     rc = small_upload_state(t, start_iter, max_iter);
@@ -504,395 +424,97 @@ static int solve_small(lpr_tableau* t, const lpr_solve_opts& o, lpr_solve_result
         if (rc != LPR_OK_OPTIMAL) return rc;
         if (nb < nb_max) nb = nb * 2 < nb_max ? nb * 2 : nb_max;
     }
-    t->total_pivots = iter;
-    res->status = status;
-    res->block = K;
-    res->pivots = iter - start_iter;
-    res->total_pivots = iter;
-    double z = 0.0;
-    LPR_HIP(hipMemcpyAsync(&z, t->T + (t->cols - 1), sizeof(double), hipMemcpyDeviceToHost, s));
-    LPR_HIP(hipStreamSynchronize(s));
-    res->z = z;
-    return status;
+    return finish_call(t, res, status, iter, start_iter, K, nullptr);
 }
 
-// Tableaux above kFusedBytes: K pivots per sweep.  opts.block: 0 = auto (16), 1 = the
-// one-pivot-per-sweep path, 2..16 = that many.
-// opts.variant: 0 = by size (heads-then-sweep up to kOverlapBytes, two-stream overlap above),
-// 0x30tr / 0x40tr force a form with tr-row sweep tiles (0x50tr / 0x60tr, retired forms, are read
-// as 0x30tr / 0x40tr), any other non-zero value (a k_update tile variant, 0x7fff) the one-pivot
-// path.
-static constexpr int kDefaultBlock = 16;
-// (round 2, tools/size_sweep.sh: with 8-10 us loop heads the two-stream overlap wins from ~80 MB:
-// 67 MB 99.6 k vs 104.2 k pivots/s for heads-then-sweep, 101 MB 98.7 k vs 92.2 k, 227 MB 93.6 k vs
-// 78.6 k; round 1's crossover was ~300 MB)
-static constexpr size_t kOverlapBytes = (size_t)80 << 20;
-// Device work queued behind a mid-call snapshot of the K-pivot driver, in microseconds.  At the
-// headline size (a step is 161 us by the driver's estimate) ONE step behind the snapshot already
-// leaves no idle stretch at a batch boundary in a kernel trace (profiles/r07_poll_gaps_lead1.json);
-// the value kept is twice that.
-static constexpr double kOvLeadUs = 320.0;
-
-static int block_size(const lpr_tableau* t, const lpr_solve_opts& o) {
-    // a specific one-pivot update-kernel variant was asked for
-    if (o.variant != 0 && (o.variant & 0xff00) != 0x4000 && (o.variant & 0xff00) != 0x3000)
-        return 1;
-    int k = o.block;
-    if (k == 0) k = kDefaultBlock;
-    if (k < 1) k = 1;
-    if (k > ov_max_pivots()) k = ov_max_pivots();
-    if (t->rows < 2) k = 1;
-    return k;
-}
-
-// Tableaux above kFusedBytes that do not fit the cache-resident path: K pivots per sweep --
-// overlap_kernels.hip.  two_streams: the next block's loop heads run on a stream of their own
-// beside the current block's out-of-place sweep (0x30tr); otherwise the heads of a block, then its
-// sweep in place, both on the engine stream (0x40tr).
-//
-// A "step" is one launch pair.  Two streams: step j sweeps block j (K pivots) while its heads decide
-// block j + 1, so a call that applies N blocks takes N + 1 steps (the first only decides, the last
-// only sweeps).  In place: step j decides block j and sweeps it.  The host learns the outcome from
-// the control block the last step wrote: `status`, or -- when the heads found the end (`pending`)
-// and left nothing staged (`kdone == 0`) -- `pending` itself, so no further launch is needed to
-// publish it.
-// opts.time_kernels: HIP events on the sweep's own stream bracket EVERY sweep launch (start =
-// both kernels of the previous step done); sweep time = stop - start, step time = start of the
-// next step - start of this one.  Only steps that swept a full block are counted.
-//
-// Polling ahead.  The host does not wait for the queue to run dry before it learns the state: in a
-// batch of nb steps a SNAPSHOT of the control block (ov2_launch_step / ov_snapshot: one copy into a
-// pinned slot and an event) is queued `lead` steps before the end, the host waits for that event
-// alone and, while the device works through the last `lead` steps, queues the next batch behind
-// them -- no join, no stream synchronisation, no idle device.  A snapshot is `lead` steps stale when
-// the next batch is sized, so the driver assumes that every step queued so far applied a full
-// block: exact unless a step met the end of the solve, and then the steps queued for nothing return
-// at once, as idle steps always have (at most `lead` of them when the snapshot itself shows the end,
-// one more batch when the end falls in the `lead` steps behind a snapshot).  With a pivot limit the
-// bound is exact, so a call queues ceil(max_pivots / K) + 1 steps whatever the batch length.  Once a
-// snapshot shows anything but a running solve -- the end found, an error -- and whenever the log has
-// to grow, the driver DRAINS (join, synchronous ov_poll) and carries on from the exact state the
-// way it always did, one step at a time while an end is pending.  What a call returns (z, the live
-// buffer, the sweep direction for the next call) comes from that final poll only.
-struct OvTimedBatch {  // a queued batch whose timing events have not been read yet
-    bool live = false;
-    bool own_close = false;  // its last window closes at its own event 2 * nb (else: at the first
-                             // start event of the batch queued behind it, in the other event set)
-    int nb = 0;
-    int64_t g0 = 0;          // index of its first step in the call
-};
-
-static int solve_overlapped(lpr_tableau* t, const lpr_solve_opts& o, int K, int tr,
-                            bool two_streams, int hflags, lpr_solve_result* res) {
-    lpr_engine* e = t->eng;
-    hipStream_t s = e->stream;
-    int rc = ov_ensure(t, two_streams);
-    if (rc != LPR_OK_OPTIMAL) return rc;
+// The one-pivot path (PrimalPath::OnePivot): a k_pivot_head + k_update pair per pivot, a batch of
+// pairs replayed as a captured graph between two polls of the status word.
+static int solve_one_pivot(lpr_tableau* t, const lpr_solve_opts& o, const PrimalPlan& plan,
+                           lpr_solve_result* res) {
+    hipStream_t s = t->eng->stream;
+    const int variant = plan.update_variant;
+    int batch = o.batch > 0 ? o.batch : default_batch(t);
     const bool timed = o.time_kernels != 0;
-    // opts.time_kernels = n > 1: events around every n-th step only (two event records per step
-    // cost the two-stream pipeline ~3 % -- they sit on the sweep's stream, on the critical cycle)
-    const int tstride = o.time_kernels > 1 ? (o.time_kernels < 16 ? o.time_kernels : 16) : 1;
-    // steps between snapshots: about 5 ms of device work (a step = one sweep at ~5 TB/s, or K loop
-    // heads at ~8 us, whichever is longer)
-    const double sweep_us = 16.0 * t->rows * (double)t->ld / 5.0e6;
-    const double step_us = sweep_us > 8.0 * K ? sweep_us : 8.0 * K;
-    int nlaunch;
-    if (o.batch > 0) {
-        nlaunch = (o.batch + K - 1) / K;
-    } else {
-        nlaunch = (int)(5000.0 / step_us);
-        if (nlaunch > 64) nlaunch = 64;
-    }
-    if (nlaunch < 2) nlaunch = 2;
-    // steps queued behind a snapshot: kOvLeadUs of device work by the same estimate (DESIGN 4b
-    // "Control": where the figure comes from), at least 1, at most half the batch
-    const int lead_steps = t->poll_lead > 0 ? t->poll_lead : (int)std::ceil(kOvLeadUs / step_us);
-    // (the opt-in forms whose kernels order themselves on the device, variant bits 21 / 22, keep
-    // the synchronous polls: ov2_launch_step's consistency argument is made for the event form)
-    const bool ahead = (hflags & (32 | 64)) == 0;
-    const bool poll_flags = (hflags & 64) != 0;
     const int64_t start_iter = t->total_pivots;
     const int64_t max_iter = o.max_pivots > 0 ? start_iter + o.max_pivots : 0;
-    rc = ov_begin(t, start_iter, max_iter);
-    if (rc != LPR_OK_OPTIMAL) return rc;
-    if (two_streams) {
-        rc = ov2_begin(t);
+
+    PivotState* hs = t->h_state;
+    hs->status = kRunning;
+    hs->iter = start_iter;
+    hs->max_iter = max_iter;
+    hs->log_cap = t->log_cap;
+    // cur_r/cur_e/sweep keep their device values: upload everything except those via two copies
+    LPR_HIP(hipMemcpyAsync(&t->state->status, &hs->status, sizeof(int32_t), hipMemcpyHostToDevice,
+                           s));
+    LPR_HIP(hipMemcpyAsync(&t->state->iter, &hs->iter, 3 * sizeof(int64_t),
+                           hipMemcpyHostToDevice, s));
+
+    // One slow pass (strided column gather) primes next_e / next_col / next_rhs; from then on every
+    // k_update leaves them ready for the following k_pivot_head.
+    launch_bootstrap(t);
+
+    int status = kRunning;
+    int64_t iter = start_iter;
+    while (status == kRunning) {
+        int nb = batch;
+        if (timed && max_iter > 0) {
+            const int64_t left = max_iter - iter;
+            if (left < nb) nb = (int)left;  // may be 0: then only the closing select runs
+        }
+        int rc = ensure_log(t, iter + nb + 1);
         if (rc != LPR_OK_OPTIMAL) return rc;
-    }
+        if (t->log_cap != hs->log_cap) {
+            hs->log_cap = t->log_cap;
+            LPR_HIP(hipMemcpyAsync(&t->state->log_cap, &hs->log_cap, sizeof(int64_t),
+                                   hipMemcpyHostToDevice, s));
+        }
 
-    OvPoll pl;
-    pl.status = kRunning;
-    pl.pending = kRunning;
-    pl.applied = start_iter;
-    int32_t status = kRunning;
-    int64_t applied = start_iter;  // pivots applied at the latest poll or snapshot
-    int64_t step = 0;              // launches (pairs) queued by this call; parity = control block
-    int idle_batches = 0;
-    bool exact = true;   // `pl` is a synchronous poll and nothing has been queued since
-    int64_t nbatch = 0;  // batches queued; parity = event set and snapshot slot
-    OvTimedBatch tb[2];  // by event set
-    int last_set = -1;   // event set of the batch queued last
-    const int first_full = two_streams ? 1 : 0;  // the first step of a two-stream call sweeps nothing
-    const int evset = 2 * nlaunch + 1;           // events per set: (start, stop) per step + closing
-
-    // Reads the events of batch `b`.  Steps sweep full blocks in order: first (two streams) the step
-    // that sweeps nothing, then full blocks, then at most one partial block and idle steps -- so the
-    // sampled steps that count are those with a call-wide index in [first_full, full_end).
-    auto read_events = [&](int b, int64_t full_end) -> int {
-        OvTimedBatch& B = tb[b];
-        hipEvent_t* ev = t->ev.data() + (size_t)b * evset;
-        hipEvent_t close = B.own_close ? ev[2 * B.nb] : t->ev[(size_t)(b ^ 1) * evset];
-        for (int k = 0; k < B.nb && B.g0 + k < full_end; k += tstride) {
-            if (B.g0 + k < first_full) continue;  // (the sampled steps are the multiples of tstride)
-            float ms = 0.f;
-            LPR_HIP(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
-            t->timed_total_ms += ms;
-            t->timed_launches += 1;
-            // start of this step to the start of the next SAMPLED one (or the closing event):
-            // that many steps, all of them full as long as they lie before full_end
-            const int kn = (k + tstride < B.nb) ? k + tstride : B.nb;
-            if (B.g0 + kn <= full_end) {
-                float st = 0.f;
-                LPR_HIP(hipEventElapsedTime(&st, ev[2 * k], kn < B.nb ? ev[2 * kn] : close));
-                t->timed_step_ms += st;
-                t->timed_steps += kn - k;
+        if (timed) {
+            while ((int)t->ev.size() < 2 * nb) {
+                hipEvent_t ev;
+                LPR_HIP(hipEventCreate(&ev));
+                t->ev.push_back(ev);
             }
-        }
-        B.live = false;
-        return LPR_OK_OPTIMAL;
-    };
-
-    // The synchronous poll: both streams joined, the control block and z read back, the events of
-    // every batch still pending read against the exact count of full blocks.
-    auto drain = [&]() -> int {
-        if (two_streams) {
-            int jr = ov2_join(t);
-            if (jr != LPR_OK_OPTIMAL) return jr;
-        }
-        if (timed && last_set >= 0 && tb[last_set].live && !tb[last_set].own_close) {
-            // closes the last step's window
-            LPR_HIP(hipEventRecord(t->ev[(size_t)last_set * evset + 2 * tb[last_set].nb], s));
-            tb[last_set].own_close = true;
+            // Bracket every kTimeStride-th rank-1 update with events: a record costs a few
+            // microseconds of stream time, which would otherwise be charged to every pivot.
+            for (int k = 0; k < nb; ++k) {
+                launch_pivot_head(t);
+                const bool sample = (k % kTimeStride) == 0;
+                if (sample) LPR_HIP(hipEventRecord(t->ev[2 * k], s));
+                launch_update(t, variant, 1, 1);
+                if (sample) LPR_HIP(hipEventRecord(t->ev[2 * k + 1], s));
+            }
+            if (nb == 0 || (max_iter > 0 && iter + nb >= max_iter))
+                launch_pivot_head(t);  // closing loop head -> final status
+        } else {
+            rc = replay_or_capture(t, nb, variant, [&] {
+                for (int k = 0; k < nb; ++k) {
+                    launch_pivot_head(t);
+                    launch_update(t, variant, 1, 1);
+                }
+            });
+            if (rc != LPR_OK_OPTIMAL) return rc;
         }
         LPR_HIP(hipGetLastError());
-        int pr = ov_poll(t, two_streams ? (int)(step & 1) : 0, poll_flags, &pl);
-        if (pr != LPR_OK_OPTIMAL) return pr;
-        if (pl.error || pl.status == LPR_DEVICE_ERROR) {
-            // the staging state is unusable (a head group never arrived): the handle is poisoned
-            t->poisoned = true;
-            set_error("overlapped pivot loop: a hand-off between the loop heads timed out; the "
-                      "tableau handle is no longer usable");
+        LPR_HIP(hipMemcpyAsync(hs, t->state, sizeof(PivotState), hipMemcpyDeviceToHost, s));
+        LPR_HIP(hipStreamSynchronize(s));
+        const int64_t done = hs->iter - iter;
+        if (timed) {
+            for (int64_t k = 0; k < done && k < nb; k += kTimeStride) {  // launches that pivoted
+                float ms = 0.f;
+                LPR_HIP(hipEventElapsedTime(&ms, t->ev[2 * k], t->ev[2 * k + 1]));
+                t->timed_total_ms += ms;
+                t->timed_launches += 1;
+            }
+        }
+        iter = hs->iter;
+        status = hs->status;
+        if (status == kRunning && done == 0 && nb > 0) {
+            set_error("pivot loop made no progress (device status still running)");
             return LPR_DEVICE_ERROR;
         }
-        status = pl.status;
-        if (status == kRunning && pl.pending != kRunning && pl.kdone == 0)
-            status = pl.pending;  // the end was found and nothing is left to sweep
-        if (timed && last_set >= 0) {
-            const int64_t full_end = first_full + (pl.applied - start_iter) / K;
-            for (int b : {last_set ^ 1, last_set})  // the older batch first
-                if (tb[b].live) {
-                    int er = read_events(b, full_end);
-                    if (er != LPR_OK_OPTIMAL) return er;
-                }
-        }
-        idle_batches = (pl.applied == applied) ? idle_batches + 1 : 0;
-        applied = pl.applied;
-        exact = true;
-        if (status == kRunning && idle_batches >= 3) {
-            set_error("overlapped pivot loop made no progress (device status still running)");
-            return LPR_DEVICE_ERROR;
-        }
-        return LPR_OK_OPTIMAL;
-    };
-
-    while (status == kRunning) {
-        // pivots applied once everything queued so far has run, if no step has met the end
-        int64_t base = applied;
-        if (!exact) {
-            base = start_iter + (step - first_full) * K;
-            if (max_iter > 0 && base > max_iter) base = max_iter;
-        }
-        int nb = nlaunch;
-        bool to_limit = false;  // this batch takes the call to its pivot limit
-        if (exact && pl.pending != kRunning) {
-            nb = 1;  // the end has been found: the staged tail is swept, the outcome published
-        } else if (max_iter > 0) {  // the blocks the limit allows (+ the step that only decides)
-            const int64_t left = max_iter - base;
-            const int64_t need = (left + K - 1) / K + (step == 0 ? 1 : 0);
-            if (need <= nb) {
-                nb = (int)need;
-                to_limit = true;
-            }
-        }
-        if (nb < 1) nb = 1;
-        if (base + (int64_t)(nb + 1) * K + 1 > t->log_cap) {
-            if (!exact) {
-                // The heads write B.log from their own stream: the old buffer must be out of use
-                // before it is replaced.  Drain, then size the batch again from the exact state.
-                rc = drain();
-                if (rc != LPR_OK_OPTIMAL) return rc;
-                continue;
-            }
-            const int64_t log_before = t->log_cap;
-            const int32_t* log_ptr = t->log;
-            rc = ensure_log(t, base + (int64_t)(nb + 1) * K + 1);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-            if (t->log_cap != log_before || t->log != log_ptr) {
-                rc = ov_set_log(t, two_streams ? (int)(step & 1) : 0);
-                if (rc != LPR_OK_OPTIMAL) return rc;
-            }
-        }
-        // A snapshot `lead` steps before the end of the batch -- unless the batch is known to be
-        // the call's last (it reaches the pivot limit, or an end is pending): the drain follows.
-        int lead = 0;
-        if (ahead && !to_limit && nb >= 2 && !(exact && pl.pending != kRunning)) {
-            lead = lead_steps < nb / 2 ? lead_steps : nb / 2;
-            if (lead < 1) lead = 1;
-        }
-        const int set = (int)(nbatch & 1);
-        // One or two launches per K pivots: plain launches keep the device busy (measured: a
-        // captured graph is no faster here, and capturing one costs milliseconds per solve call).
-        hipEvent_t* ev = nullptr;
-        if (timed) {  // (two sets, sized for full batches at once: creating an event costs ~10 us)
-            while ((int)t->ev.size() < 2 * evset) {
-                hipEvent_t x;
-                LPR_HIP(hipEventCreate(&x));
-                t->ev.push_back(x);
-            }
-            ev = t->ev.data() + (size_t)set * evset;
-            tb[set].live = true;
-            tb[set].own_close = false;
-            tb[set].nb = nb;
-            tb[set].g0 = step;
-        }
-        for (int k = 0; k < nb; ++k, ++step) {
-            const int lp = (int)(step & 1);
-            const bool tk = timed && (k % tstride == 0);
-            const bool snap = lead > 0 && k == nb - lead;
-            if (two_streams) {
-                rc = ov2_launch_step(t, K, tr, lp, hflags, tk ? ev[2 * k] : nullptr,
-                                     tk ? ev[2 * k + 1] : nullptr, snap ? set : -1);
-                if (rc != LPR_OK_OPTIMAL) return rc;
-                continue;
-            }
-            if (snap) {
-                rc = ov_snapshot(t, set);
-                if (rc != LPR_OK_OPTIMAL) return rc;
-            }
-            ov_launch_heads(t, K, hflags);
-            if (tk) LPR_HIP(hipEventRecord(ev[2 * k], s));
-            ov_launch_sweep(t, tr);
-            if (tk) LPR_HIP(hipEventRecord(ev[2 * k + 1], s));
-        }
-        last_set = set;
-        nbatch += 1;
-        exact = false;
-        if (lead > 0) {
-            LPR_HIP(hipGetLastError());
-            OvPoll sp;
-            rc = ov_snapshot_wait(t, set, &sp);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-            idle_batches = (sp.applied == applied) ? idle_batches + 1 : 0;
-            if (sp.status == kRunning && sp.pending == kRunning && !sp.error && idle_batches < 3) {
-                applied = sp.applied;
-                // The batch before this one is complete (its last step precedes the snapshot on
-                // the engine stream, and so does the start event that closes its last window) and
-                // every step of it came before a snapshot that shows no end: all its blocks were
-                // full.  hipEventQuery confirms; if it ever did not, the drain below would wait.
-                if (!timed || !tb[set ^ 1].live) continue;
-                const hipError_t q = hipEventQuery(ev[0]);
-                if (q == hipSuccess) {
-                    rc = read_events(set ^ 1, INT64_MAX);
-                    if (rc != LPR_OK_OPTIMAL) return rc;
-                    continue;
-                }
-                if (q != hipErrorNotReady) LPR_HIP(q);
-                (void)hipGetLastError();
-            }
-        }
-        rc = drain();
-        if (rc != LPR_OK_OPTIMAL) return rc;
     }
-    ov_adopt_buffer(t, pl.cur);
-    t->total_pivots = applied;
-    res->status = status;
-    res->block = K;
-    res->pivots = applied - start_iter;
-    res->total_pivots = applied;
-    res->z = pl.z[applied & 1];  // T[0, cols-1]: the RHS column the heads carry, entry 0
-    return status;
-}
-
-// The two-stream path on the condensed working layout (DESIGN 4b "Condensed layout"): for the
-// length of a call the kernels work on buffers that leave out the columns basic when it began --
-// exact unit columns that no pivot changes -- so a sweep moves (n + S + 1) / (n + m + 1) of the
-// bytes.  opts.variant bit 25: the form before (never condensed); bit 26: condensed whatever the
-// size or the length of the call (tests).
-//
-// kOvcMinPivots: a call with a pivot budget below it stays on the full layout -- condensing and
-// expanding cost one pass over the tableau each (the measured break-even).
-static constexpr int64_t kOvcMinPivots = 1024;
-
-// spare columns: an omitted variable that leaves takes one, and when none is left the driver
-// expands and condenses again.  Test hook LPR_TEST_OV_SPARES (1..4096): a small number, so that a
-// short oracle-checked solve re-condenses every few pivots (tests/test_condensed_gpu.py).
-static int ovc_spares(const lpr_tableau* t) {
-    if (const char* sp = std::getenv("LPR_TEST_OV_SPARES")) {
-        const long v = std::strtol(sp, nullptr, 10);
-        if (v >= 1 && v <= 4096) return (int)v;
-    }
-    // m / 8 - 1 (255 .. 4095 measured at m = 4096; 511 makes the buffers 17 column
-    // strips of the sweep exactly): a narrower sweep also leaves the heads beside it more of the
-    // chip, which outweighs expanding and condensing again every few hundred pivots
-    const int s = (t->rows - 1) / 8 - 1;
-    return s < 1 ? 1 : s;
-}
-
-static bool use_condensed(const lpr_tableau* t, const lpr_solve_opts& o, int cflags, int hflags) {
-    if (cflags & 1) return false;
-    // the diagnostic build of the heads and the opt-in forms that order themselves on the device
-    // exist for the full layout only
-    if (hflags & (1 | 32 | 64)) return false;
-    const int S = ovc_spares(t);
-    if (!ovc_fits(t, S)) return false;
-    if (cflags & 2) return true;
-    if (o.max_pivots > 0 && o.max_pivots < kOvcMinPivots) return false;
-    return ovc_width(t, S) < t->ld;
-}
-
-static int solve_condensed(lpr_tableau* t, const lpr_solve_opts& o, int K, int tr, int hflags,
-                           lpr_solve_result* res) {
-    const int64_t first = t->total_pivots;
-    lpr_solve_opts oc = o;
-    for (;;) {
-        const int64_t done = t->total_pivots - first;
-        if (o.max_pivots > 0) oc.max_pivots = o.max_pivots - done;
-        bool ok = false;
-        int rc = ovc_ensure(t, ovc_spares(t));
-        if (rc == LPR_OK_OPTIMAL) rc = ovc_condense(t, &ok);
-        if (rc != LPR_OK_OPTIMAL && rc != LPR_OUT_OF_MEMORY) return rc;
-        int status;
-        if (rc != LPR_OK_OPTIMAL || !ok) {
-            // a basic column is not the exact unit column (or there is no room): the full layout
-            status = solve_overlapped(t, oc, K, tr, true, hflags, res);
-        } else {
-            ovc_enter(t);
-            status = solve_overlapped(t, oc, K, tr, true, hflags, res);
-            ovc_leave(t);
-            if (status == LPR_DEVICE_ERROR || status == LPR_OUT_OF_MEMORY ||
-                status == LPR_BAD_ARGUMENT)
-                return status;
-            rc = ovc_expand(t);
-            if (rc != LPR_OK_OPTIMAL) return rc;
-            if (status == kOvLeaveSpares) continue;
-            if (status == kOvLeaveNonFinite) {
-                if (o.max_pivots > 0) oc.max_pivots = o.max_pivots - (t->total_pivots - first);
-                status = solve_overlapped(t, oc, K, tr, true, hflags, res);
-            }
-        }
-        res->pivots = t->total_pivots - first;
-        return status;
-    }
+    return finish_call(t, res, status, iter, start_iter, 1, nullptr);
 }
 
 }  // namespace lpr
@@ -1152,159 +774,18 @@ int lpr_primal_solve(lpr_tableau* t, const lpr_solve_opts* opts, lpr_solve_resul
     lpr_solve_opts o;
     std::memset(&o, 0, sizeof o);
     if (opts) o = *opts;
-    const int hflags = (o.variant >> 16) & 511;  // loop-head placement / diagnostics (K-pivot paths)
-    const int cflags = (o.variant >> 25) & 3;    // condensed layout: 1 = never, 2 = always
-    o.variant &= 0xffff;                       // path + tile
-    // retired forms, kept as aliases: 0x50tr (the overlap in one launch) runs as the two-stream
-    // overlap, 0x60tr (one launch per loop head, K <= 8) as heads-then-sweep
-    if ((o.variant & 0xff00) == 0x5000) o.variant = 0x3000 | (o.variant & 0xff);
-    if ((o.variant & 0xff00) == 0x6000) o.variant = 0x4000 | (o.variant & 0xff);
-    lpr_engine* e = t->eng;
-    hipStream_t s = e->stream;
-    LPR_HIP(hipSetDevice(e->device));
-
-    if (use_small(t, o)) return solve_small(t, o, res);
-    if (use_fused(t, o)) return solve_fused(t, o, res);
-    {
-        // 0x30tr: sweep out of place with the next block's heads beside it on a second stream;
-        // 0x40tr: all heads of a block in one persistent launch, then the sweep in place (also the
-        // fallback when the second tableau buffer or the heads' stream cannot be had)
-        const int K = block_size(t, o);
-        if (K > 1) {
-            // measured (tools/size_sweep.sh): up to ~80 MB the heads-then-sweep form is faster
-            // (9.1-9.6 us per pivot), above it hiding the sweep behind the next heads wins
-            const size_t tbytes = (size_t)t->rows * t->ld * sizeof(double);
-            // above kOverlapBytes the default is the two-stream form of the overlap (0x30tr)
-            const bool big = (o.variant & 0xff00) == 0 && tbytes > kOverlapBytes;
-            bool two_streams = (o.variant & 0xff00) == 0x3000 || big;
-            const int tr = (o.variant & 0xff00) ? (o.variant & 0xff) : 8;
-            if (two_streams && ov_ensure(t, true) != LPR_OK_OPTIMAL) two_streams = false;
-            if (two_streams && (big || (cflags & 2)) && !(cflags & 1) &&
-                ovc_fits(t, ovc_spares(t)) && ovc_width(t, ovc_spares(t)) < t->ld) {
-                // the buffers of the condensed layout come with the handle's first two-stream
-                // call, whichever layout that call itself uses
-                const int er = ovc_ensure(t, ovc_spares(t));
-                if (er != LPR_OK_OPTIMAL && er != LPR_OUT_OF_MEMORY) return er;
-            }
-            if (two_streams && use_condensed(t, o, cflags, hflags))
-                return solve_condensed(t, o, K, tr, hflags, res);
-            return solve_overlapped(t, o, K, tr, two_streams, hflags, res);
-        }
+    LPR_HIP(hipSetDevice(t->eng->device));
+    // decode (primal_plan.hpp), dispatch; every loop ends in finish_call.  What can fail at run time
+    // on a K-pivot plan is solve_kpivot's (overlap_driver.hip).
+    const PrimalPlan plan = primal_plan(o, t->rows, t->cols, t->ld, ovc_spares_hook());
+    switch (plan.path) {
+        case PrimalPath::Small: return solve_small(t, o, res);
+        case PrimalPath::Fused: return solve_fused(t, o, res);
+        case PrimalPath::TwoStream:
+        case PrimalPath::InPlace: return solve_kpivot(t, o, plan, res);
+        case PrimalPath::OnePivot: break;
     }
-    const int variant = (o.variant > 0 && o.variant < 0x7000) ? o.variant - 1 : default_variant(t);
-    int batch = o.batch > 0 ? o.batch : default_batch(t);
-    const bool timed = o.time_kernels != 0;
-    const int64_t start_iter = t->total_pivots;
-    const int64_t max_iter = o.max_pivots > 0 ? start_iter + o.max_pivots : 0;
-
-    PivotState* hs = t->h_state;
-    hs->status = kRunning;
-    hs->iter = start_iter;
-    hs->max_iter = max_iter;
-    hs->log_cap = t->log_cap;
-    // cur_r/cur_e/sweep keep their device values: upload everything except those via two copies
-    LPR_HIP(hipMemcpyAsync(&t->state->status, &hs->status, sizeof(int32_t), hipMemcpyHostToDevice,
-                           s));
-    LPR_HIP(hipMemcpyAsync(&t->state->iter, &hs->iter, 3 * sizeof(int64_t),
-                           hipMemcpyHostToDevice, s));
-
-    // One slow pass (strided column gather) primes next_e / next_col / next_rhs; from then on every
-    // k_update leaves them ready for the following k_pivot_head.
-    launch_bootstrap(t);
-
-    int status = kRunning;
-    int64_t iter = start_iter;
-    while (status == kRunning) {
-        int nb = batch;
-        if (timed && max_iter > 0) {
-            const int64_t left = max_iter - iter;
-            if (left < nb) nb = (int)left;  // may be 0: then only the closing select runs
-        }
-        int rc = ensure_log(t, iter + nb + 1);
-        if (rc != LPR_OK_OPTIMAL) return rc;
-        if (t->log_cap != hs->log_cap) {
-            hs->log_cap = t->log_cap;
-            LPR_HIP(hipMemcpyAsync(&t->state->log_cap, &hs->log_cap, sizeof(int64_t),
-                                   hipMemcpyHostToDevice, s));
-        }
-
-        if (timed) {
-            while ((int)t->ev.size() < 2 * nb) {
-                hipEvent_t ev;
-                LPR_HIP(hipEventCreate(&ev));
-                t->ev.push_back(ev);
-            }
-            // Bracket every kTimeStride-th rank-1 update with events: a record costs a few
-            // microseconds of stream time, which would otherwise be charged to every pivot.
-            for (int k = 0; k < nb; ++k) {
-                launch_pivot_head(t);
-                const bool sample = (k % kTimeStride) == 0;
-                if (sample) LPR_HIP(hipEventRecord(t->ev[2 * k], s));
-                launch_update(t, variant, 1, 1);
-                if (sample) LPR_HIP(hipEventRecord(t->ev[2 * k + 1], s));
-            }
-            if (nb == 0 || (max_iter > 0 && iter + nb >= max_iter))
-                launch_pivot_head(t);  // closing loop head -> final status
-        } else {
-            if (!graph_valid(t, nb, variant)) {
-                drop_graph(t);
-                hipGraph_t g = nullptr;
-                LPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                for (int k = 0; k < nb; ++k) {
-                    launch_pivot_head(t);
-                    launch_update(t, variant, 1, 1);
-                }
-                LPR_HIP(hipStreamEndCapture(s, &g));
-                hipError_t ierr = hipGraphInstantiate(&t->graph, g, nullptr, nullptr, 0);
-                hipGraphDestroy(g);
-                if (ierr != hipSuccess) {
-                    t->graph = nullptr;
-                    set_error("hipGraphInstantiate failed: %s", hipGetErrorString(ierr));
-                    return LPR_DEVICE_ERROR;
-                }
-                graph_stamp(t, nb, variant);
-            }
-            LPR_HIP(hipGraphLaunch(t->graph, s));
-        }
-        LPR_HIP(hipGetLastError());
-        LPR_HIP(hipMemcpyAsync(hs, t->state, sizeof(PivotState), hipMemcpyDeviceToHost, s));
-        LPR_HIP(hipStreamSynchronize(s));
-        const int64_t done = hs->iter - iter;
-        if (timed) {
-            for (int64_t k = 0; k < done && k < nb; k += kTimeStride) {  // launches that pivoted
-                float ms = 0.f;
-                LPR_HIP(hipEventElapsedTime(&ms, t->ev[2 * k], t->ev[2 * k + 1]));
-                t->timed_total_ms += ms;
-                t->timed_launches += 1;
-            }
-        }
-        iter = hs->iter;
-        status = hs->status;
-        if (status == kRunning && done == 0 && nb > 0) {
-            set_error("pivot loop made no progress (device status still running)");
-            return LPR_DEVICE_ERROR;
-        }
-    }
-    t->total_pivots = iter;
-    res->status = status;
-    res->block = 1;
-    res->pivots = iter - start_iter;
-    res->total_pivots = iter;
-    double z = 0.0;
-    LPR_HIP(hipMemcpyAsync(&z, t->T + (t->cols - 1), sizeof(double), hipMemcpyDeviceToHost, s));
-    LPR_HIP(hipStreamSynchronize(s));
-    res->z = z;
-    return status;
-}
-
-static int read_scratch(lpr_tableau* t, int idx, int32_t* out) {
-    hipStream_t s = t->eng->stream;
-    LPR_HIP(hipGetLastError());
-    LPR_HIP(hipMemcpyAsync(t->h_scratch_i, t->scratch_i, 4 * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
-    LPR_HIP(hipStreamSynchronize(s));
-    *out = t->h_scratch_i[idx];
-    return LPR_OK_OPTIMAL;
+    return solve_one_pivot(t, o, plan, res);
 }
 
 int lpr_select_entering(lpr_tableau* t, int32_t* col) {
@@ -1343,7 +824,7 @@ int lpr_pivot(lpr_tableau* t, int32_t row, int32_t col) {
     LPR_HIP(hipMemcpyAsync(&t->state->iter, &hs->iter, 3 * sizeof(int64_t),
                            hipMemcpyHostToDevice, s));
     launch_select(t, kSelCommit, col, row, nullptr);
-    launch_update(t, default_variant(t), 0, 0);
+    launch_update(t, default_update_variant(t->rows, t->ld), 0, 0);
     LPR_HIP(hipGetLastError());
     LPR_HIP(hipStreamSynchronize(s));
     t->total_pivots += 1;

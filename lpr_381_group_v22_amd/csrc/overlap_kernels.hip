@@ -26,7 +26,7 @@
 //   ov_heads                   the K loop heads of a block as ONE persistent group of G workgroups
 //                              with a hand-off between the two phases of a head.
 //   ov_tiles                   the sweep: 32-row x 256-double2 tiles.
-// and two ways of putting them on the device (lpr_engine.hip picks by tableau size):
+// and two ways of putting them on the device (primal_plan.hpp picks by tableau size):
 //   k_ov_heads + k_ov_sweep    heads, then the sweep in place (0x40tr; 1 MB .. 80 MB).
 //   k_ov2_heads || k_ov2_sweep two kernels on two streams (0x30tr; above 80 MB): the sweep is out
 //                              of place (tableau buffer `cur` -> `cur ^ 1`), so while it runs the
@@ -64,9 +64,7 @@
 
 namespace lpr {
 
-constexpr int kOvMax = 16;      // pivots per block, upper bound
-constexpr int kOvNT = 256;      // threads per workgroup (heads and tiles)
-constexpr int kOvGroups = 64;   // head workgroups, upper bound
+// (kOvMax, kOvNT, kOvGroups: primal_plan.hpp)
 constexpr unsigned kOvSpinMax = 1u << 22;
 // B.sflag also holds kOvDoneCopies copies of the heads' completion count, one per 4 352 bytes (in
 // different memory channels): the ~900 workgroups of a sweep that ask for it poll 32 different
@@ -1787,7 +1785,8 @@ __global__ __launch_bounds__(256) void k_ov_expand(const double* __restrict__ Tc
 
 #ifndef LPR_OV_KERNELS_ONLY
 // ---------------------------------------------------------------------------------------------
-// host side (the driver loop lives in lpr_engine.hip)
+// host side (the driver loop lives in overlap_driver.hip)
+#include "overlap.hpp"
 
 struct lpr_overlap_ctx {
     int rows = 0, ld = 0, Rp = 0;
@@ -1812,14 +1811,6 @@ struct lpr_overlap_ctx {
 };
 
 namespace lpr {
-
-struct OvPoll {
-    int32_t status, pending, kdone, cur, error;
-    int64_t applied;
-    double z[2];
-};
-
-int ov_max_pivots() { return kOvMax; }
 
 void ov_release(lpr_tableau* t) {
     lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
@@ -1922,18 +1913,10 @@ int ov_ensure(lpr_tableau* t, bool second_buffer) {
     return LPR_OK_OPTIMAL;
 }
 
-// sweep tile code (low byte of opts.variant): rows per chunk, + 0x20 = two chunks in flight
-static int ov_tile_code(int tr) {
-    switch (tr) {
-        case 0x04: case 0x10: case 0x24: case 0x28: return tr;
-        default: return 0x08;
-    }
-}
-
 // One XCD has 32 CUs and a head workgroup needs a CU of its own (its lanes keep their slices of the
 // block in registers: one wave per SIMD): more than 32 groups cannot be resident on one XCD
 // together, and a group that is not resident never answers a hand-off.  Wider tableaux spread.
-static int ov_spread(int G, int flags) { return ((flags & 2) || G > 32) ? 1 : 8; }
+static int ov_spread(int G, const OvForm& f) { return (f.spread || G > 32) ? 1 : 8; }
 
 // persistent sweep: enough workgroups to fill every CU at the kernel's occupancy (4 per CU)
 static int ov_sweep_grid(const lpr_tableau* t, int ntiles) {
@@ -1994,16 +1977,16 @@ int ov_set_log(lpr_tableau* t, int parity) {
     return LPR_OK_OPTIMAL;
 }
 
-// flags (opts.variant >> 16): 1 = diagnostic time stamps, 2 = do not confine the heads to one XCD
-// (one workgroup per group, memory-side hand-offs: the round-1 form), 4 = confine them but keep
-// the memory-side hand-offs.
-void ov_launch_heads(lpr_tableau* t, int K, int flags) {
+// f (primal_plan.hpp): stamps = the diagnostic build, spread = the heads not confined to one XCD
+// (one workgroup per group, memory-side hand-offs: the round-1 form), no_l2 without spread =
+// confined, but the memory-side hand-offs kept.
+void ov_launch_heads(lpr_tableau* t, int K, const OvForm& f) {
     lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
     const int G = ov_groups(t);  // 256 lanes per group; 512 measures the same, 1024 slower
-    const int spread = ov_spread(G, flags);
-    const int no_l2 = (flags & 6) ? 1 : 0;
+    const int spread = ov_spread(G, f);
+    const int no_l2 = f.no_l2 ? 1 : 0;
     hipStream_t s = t->eng->stream;
-    if (flags & 1)
+    if (f.stamps)
         hipLaunchKernelGGL((k_ov_heads<kOvNT, true>), dim3(G * spread), dim3(kOvNT), 0, s, c->b,
                            t->ld, t->rows, t->cols, c->Rp, K, G, spread, no_l2);
     else
@@ -2017,7 +2000,7 @@ void ov_launch_sweep(lpr_tableau* t, int tr) {
     const int nct = (t->ld / 2 + kOvNT - 1) / kOvNT;
     const int nrt = (t->rows + kOvTileRows - 1) / kOvTileRows;
     const int cus = t->eng->num_cus > 0 ? t->eng->num_cus : 256;
-    if (nct * nrt < 2 * cus && ov_tile_code(tr) == 0x08) {
+    if (nct * nrt < 2 * cus && ov_tile_code(tr) == kTile8) {
         // a small tableau: 32-row tiles would give fewer workgroups than CUs and the sweep is all
         // latency (m = 512: 68 tiles, 30 us for 12.6 MB); 8-row tiles spread it over the chip
         const int nrt8 = (t->rows + 7) / 8;
@@ -2030,10 +2013,10 @@ void ov_launch_sweep(lpr_tableau* t, int tr) {
     hipLaunchKernelGGL((k_ov_sweep<TR, DB>), grid, blk, 0, s, c->b, c->b.fcol, c->b.prow, t->ld,  \
                        t->rows, c->Rp)
     switch (ov_tile_code(tr)) {
-        case 0x04: LPR_OV_SWEEP(4, false); break;
-        case 0x10: LPR_OV_SWEEP(16, false); break;
-        case 0x24: LPR_OV_SWEEP(4, true); break;
-        case 0x28: LPR_OV_SWEEP(8, true); break;
+        case kTile4: LPR_OV_SWEEP(4, false); break;
+        case kTile16: LPR_OV_SWEEP(16, false); break;
+        case kTile4x2: LPR_OV_SWEEP(4, true); break;
+        case kTile8x2: LPR_OV_SWEEP(8, true); break;
         default: LPR_OV_SWEEP(8, false); break;
     }
 #undef LPR_OV_SWEEP
@@ -2069,29 +2052,29 @@ int ov2_begin(lpr_tableau* t) {
 //     wait for the completion event of sweep s, which is behind the copy on S.
 // So the host sees the state exactly as it was after s steps.  It does NOT get the RHS column's
 // entry 0 this way: the heads rewrite bvec at every pivot, beside the copy.  The driver asks for no
-// snapshot in the opt-in forms whose kernels order themselves on the device (flags 32 / 64): a
+// snapshot in the opt-in forms whose kernels order themselves on the device (plan.poll_ahead): a
 // step that carries one always orders the sweep by the event.
-int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t ev_start,
+int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, const OvForm& f, hipEvent_t ev_start,
                     hipEvent_t ev_stop, int snap_slot) {
     lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
     hipStream_t S = t->eng->stream, H = c->hstream;
     const int cur = c->ev_idx, prev = cur ^ 1;
-    // default: the heads wait for the previous sweep by a cross-stream event.  flags 32: they
+    // default: the heads wait for the previous sweep by a cross-stream event.  heads_on_device: they
     // follow their predecessor at once and wait on the device (B.sflag) -- 3 % faster, but it
     // NEEDS the two kernels of a step to run concurrently: under a tool that serialises kernels
     // (rocprofv3 --pmc does) the heads would wait for a sweep that cannot start, until the bounded
     // wait gives up with LPR_DEVICE_ERROR.  A solver must not depend on concurrency for progress,
     // so it is opt-in.
-    const bool by_event = (flags & 32) == 0;
+    const bool by_event = !f.heads_on_device;
     const int wait_sweeps = by_event ? -1 : c->steps;
-    // flags 64: the SWEEP does not wait for the heads of the step before by an event either: it
+    // sweep_on_device: the SWEEP does not wait for the heads of the step before by an event either: it
     // follows its predecessor on the engine stream at once and asks the heads' completion word as
     // it starts (ov_tiles).  Not for the first step after the streams were joined, nor for the
     // first two steps of a call (the heads it would wait for may not be resident yet: they
     // could find the chip full of polling sweep workgroups), nor while the heads' XCD is unknown.
-    const bool sweep_dev = (flags & 64) != 0 && !c->batch_first && c->steps >= 2 &&
+    const bool sweep_dev = f.sweep_on_device && !c->batch_first && c->steps >= 2 &&
                            c->head_xcc_hint >= 0 && snap_slot < 0;
-    const int heads_done = (flags & 64) ? c->steps + 1 : -1;
+    const int heads_done = f.sweep_on_device ? c->steps + 1 : -1;
     // The events that order the two streams (and the ones that time a sampled step) are the
     // completion signals of the kernels themselves (hipExtLaunchKernelGGL's stop event): a separate
     // hipEventRecord is a packet of its own on the stream, ~3 us each on the critical cycle.
@@ -2103,13 +2086,13 @@ int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t
         LPR_HIP(hipEventRecord(c->ev_snap[snap_slot], S));
     }
     const int G = ov_groups(t);
-    const int spread = ov_spread(G, flags);
-    const int no_l2 = (flags & 6) ? 1 : 0;
+    const int spread = ov_spread(G, f);
+    const int no_l2 = f.no_l2 ? 1 : 0;
     if (c->b.colid)  // the condensed layout (no diagnostic build of it)
         hipExtLaunchKernelGGL((k_ov2_heads<kOvNT, false, true>), dim3(G * spread), dim3(kOvNT), 0,
                               H, nullptr, c->ev_h[cur], 0, c->b, t->ld, t->rows, t->cols, c->Rp, K,
                               G, lp, spread, no_l2, wait_sweeps, heads_done);
-    else if (flags & 1)
+    else if (f.stamps)
         hipExtLaunchKernelGGL((k_ov2_heads<kOvNT, true>), dim3(G * spread), dim3(kOvNT), 0, H,
                               nullptr, c->ev_h[cur], 0, c->b, t->ld, t->rows, t->cols, c->Rp, K, G,
                               lp, spread, no_l2, wait_sweeps, heads_done);
@@ -2121,28 +2104,28 @@ int ov2_launch_step(lpr_tableau* t, int K, int tr, int lp, int flags, hipEvent_t
     const int nrt = (t->rows + kOvTileRows - 1) / kOvTileRows;
     const dim3 grid(ov_sweep_grid(t, nct * nrt)), blk(kOvNT);
     // leave the heads' XCD to the heads: 2 = by the previous launch's hint and this launch's
-    // word, 1 = by this launch's word only, 0 = never (flags 8 / 16; nothing to leave when the
-    // heads are not confined to one XCD)
-    const int avoid = (flags & (2 | 4 | 8)) ? 0 : ((flags & 16) ? 1 : 2);
+    // word, 1 = by this launch's word only, 0 = never (nothing to leave when the heads are not
+    // confined to one XCD)
+    const int avoid = f.avoid;
     // a sampled step: its stop event is the timing event (start = the kernel's own start)
     hipEvent_t sweep_done = ev_stop ? ev_stop : c->ev_s[cur];
-    // tiles at each end of the queue that keep the default cache policy (kOvIcMB); flags 128:
+    // tiles at each end of the queue that keep the default cache policy (kOvIcMB); ic_tiles off:
     // none, every tile non-temporal (the form before)
     const int ic_tiles =
-        (flags & 128) ? 0 : (int)(((size_t)kOvIcMB << 20) / ((size_t)kOvTileRows * kOvNT * 16));
+        !f.ic_tiles ? 0 : (int)(((size_t)kOvIcMB << 20) / ((size_t)kOvTileRows * kOvNT * 16));
     // 64-row tiles at the head of the queue: the row-tile pairs of its first half (by address
-    // on even sweeps); flags 256: none, the queue before (full tiles, then half tiles)
-    const int tall_pairs = (flags & 256) ? 0 : nrt * LPR_OV_TALL_PCT / 200;
+    // on even sweeps); tall_tiles off: none, the queue before (full tiles, then half tiles)
+    const int tall_pairs = !f.tall_tiles ? 0 : nrt * LPR_OV_TALL_PCT / 200;
 #define LPR_OV2_SWEEP(TR, DB)                                                                     \
     hipExtLaunchKernelGGL((k_ov2_sweep<TR, DB>), grid, blk, 0, S, ev_start, sweep_done, 0, c->b,   \
                           c->b.fcol, c->b.prow, t->ld, t->rows, c->Rp, lp, avoid, by_event ? 1 : 0, \
                           by_event ? -1 : c->steps, sweep_dev ? c->steps : -1, c->head_xcc_hint,    \
                           ic_tiles, tall_pairs)
     switch (ov_tile_code(tr)) {
-        case 0x04: LPR_OV2_SWEEP(4, false); break;
-        case 0x10: LPR_OV2_SWEEP(16, false); break;
-        case 0x24: LPR_OV2_SWEEP(4, true); break;
-        case 0x28: LPR_OV2_SWEEP(8, true); break;
+        case kTile4: LPR_OV2_SWEEP(4, false); break;
+        case kTile16: LPR_OV2_SWEEP(16, false); break;
+        case kTile4x2: LPR_OV2_SWEEP(4, true); break;
+        case kTile8x2: LPR_OV2_SWEEP(8, true); break;
         default: LPR_OV2_SWEEP(8, false); break;
     }
 #undef LPR_OV2_SWEEP
@@ -2180,19 +2163,13 @@ int ov_snapshot_wait(lpr_tableau* t, int slot, OvPoll* out) {
     LPR_HIP(hipEventSynchronize(c->ev_snap[slot]));
     const OvCtl& h = c->h_snap[slot];
     c->head_xcc_hint = h.head_xcc;
-    out->status = h.status;
-    out->pending = h.pending;
-    out->kdone = h.kdone;
-    out->cur = h.cur;
-    out->error = h.error;
-    out->applied = h.applied;
-    out->z[0] = out->z[1] = 0.0;
+    *out = OvPoll{h.status, h.pending, h.kdone, h.cur, h.error, h.applied, {0.0, 0.0}};
     return LPR_OK_OPTIMAL;
 }
 
 // reads control block `parity` back, and entry 0 of both RHS-column buffers (= T[0, cols-1] after
 // an even / odd number of pivots): one synchronisation per poll.  with_flags: also B.sflag, whose
-// word 3 only the device-side hand-over of the sweep (flags 64) ever sets.
+// word 3 only the device-side hand-over of the sweep (sweep_on_device) ever sets.
 int ov_poll(lpr_tableau* t, int parity, bool with_flags, OvPoll* out) {
     lpr_overlap_ctx* c = static_cast<lpr_overlap_ctx*>(t->ov);
     hipStream_t s = t->eng->stream;
@@ -2209,14 +2186,8 @@ int ov_poll(lpr_tableau* t, int parity, bool with_flags, OvPoll* out) {
     const OvCtl& h = c->h_ctl[parity];
     c->head_xcc_hint = h.head_xcc;
     c->sweep_dir = h.sweep & 1;
-    out->status = h.status;
-    out->pending = h.pending;
-    out->kdone = h.kdone;
-    out->cur = h.cur;
-    out->error = h.error | (c->h_flags[3] ? 1 : 0);  // (a sweep gave up waiting for its heads)
-    out->applied = h.applied;
-    out->z[0] = c->h_z[0];
-    out->z[1] = c->h_z[1];
+    const int32_t error = h.error | (c->h_flags[3] ? 1 : 0);  // (a sweep gave up waiting for its heads)
+    *out = OvPoll{h.status, h.pending, h.kdone, h.cur, error, h.applied, {c->h_z[0], c->h_z[1]}};
     return LPR_OK_OPTIMAL;
 }
 
@@ -2248,7 +2219,7 @@ void ov_adopt_buffer(lpr_tableau* t, int cur) {
     }
 }
 
-// ---- the condensed layout (driver: solve_condensed in lpr_engine.hip) ---------------------------
+// ---- the condensed layout (driver: solve_condensed in overlap_driver.hip) ---------------------------
 // It is a second lpr_overlap_ctx, built for a tableau of the same rows and the narrower width, with
 // the maps beside it.  Inside the regime the handle's T / ld / cols / ov name the condensed buffers,
 // so the two-stream driver and every ov_* call above run unchanged on the narrower geometry.
@@ -2282,22 +2253,6 @@ void ovc_release(lpr_tableau* t) {
     if (x->h_fail) hipHostFree(x->h_fail);
     delete x;
     t->ovc = nullptr;
-}
-
-// can this tableau use the condensed layout at all, with `spares` spare columns?
-bool ovc_fits(const lpr_tableau* t, int spares) {
-    const int nres = t->cols - t->rows;
-    if (t->rows < 2 || nres < 1 || spares < 1) return false;
-    // an entering candidate is {original column << 16 | slot} in a non-negative int
-    if (t->cols > 32767) return false;
-    const long Wp = align_up(nres + spares + 1, kLdAlign);
-    // every column pair has a lane of its own in the loop heads
-    return Wp <= 32767 && Wp / 2 <= (long)kOvGroups * kOvNT;
-}
-
-// physical width of the condensed buffers
-int ovc_width(const lpr_tableau* t, int spares) {
-    return align_up(t->cols - t->rows + spares + 1, kLdAlign);
 }
 
 void ovc_enter(lpr_tableau* t) {
@@ -2336,7 +2291,7 @@ int ovc_ensure(lpr_tableau* t, int spares) {
     x->spares = spares;
     x->nres = t->cols - t->rows;
     x->Wc = x->nres + spares + 1;
-    x->Wp = align_up(x->Wc, kLdAlign);
+    x->Wp = ovc_width(t->rows, t->cols, spares);
     t->ovc = x;
     hipError_t err = hipSuccess;
     auto chk = [&](hipError_t e) { if (err == hipSuccess) err = e; };

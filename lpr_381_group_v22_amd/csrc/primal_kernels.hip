@@ -13,14 +13,13 @@
 //             and written once (2*8*R*C algorithmic bytes), HBM-bound.
 //   k_extract ExtractSolution (:213-252), one lane per decision column.
 //   k_build*  the constructor (:27-87) and the synthetic benchmark LP.
-#include "engine_common.hpp"
+#include "primal_kernels.hpp"
 #include "select_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace lpr {
 
-enum : int { kSelEnter = 1, kSelLeave = 2, kSelCommit = 4, kSelFull = 7 };
 
 // One workgroup of 1024 threads.  In kSelFull mode this is "one C# loop head": it either ends the
 // solve (status word) or leaves (cur_r, cur_e, rowbuf, colbuf) ready for k_update.
@@ -712,7 +711,7 @@ void launch_select(lpr_tableau* t, int mode, int e_in, int r_in, int32_t* out_i)
 }
 
 // number of k_pivot_head workgroups: one per 1024 double2 of the row, capped
-int head_groups(const lpr_tableau* t) {
+static int head_groups(const lpr_tableau* t) {
     int g = (t->ld / 2 + 1023) / 1024;
     if (g < 1) g = 1;
     if (g > kMaxHeadGroups) g = kMaxHeadGroups;
@@ -743,8 +742,6 @@ static void launch_update_t(lpr_tableau* t, int check_status, int serpentine, in
 }
 
 // variant: low byte selects the tile shape, bit 8 turns the serpentine sweep on.
-int num_update_variants() { return 11; }
-
 void launch_update(lpr_tableau* t, int variant, int check_status, int dump_next) {
     const int serp = (variant >> 8) & 1;
     const int nt = (variant >> 9) & 3;  // tuning: non-temporal loads (bit 9) / stores (bit 10)

@@ -9,19 +9,6 @@
 #include <algorithm>
 #include <new>
 
-namespace lpr {
-int rev_batch_launch(int form, hipStream_t s, RevBatchDesc* desc, double* slab, int32_t* basis,
-                     int32_t* logs, double* xs, const int32_t* idx_in, int n_in,
-                     int32_t* idx_out, int32_t* n_out, int chunk, int slot_doubles);
-int rev_batch_trace_launch(int form, hipStream_t s, RevBatchDesc* desc, double* slab,
-                           int32_t* basis, int32_t* logs, double* xs, const int32_t* idx_in,
-                           int n_in, int32_t* idx_out, int32_t* n_out, int chunk,
-                           int slot_doubles, RevBatchTrace tr);
-void rev_batch_launch_build(hipStream_t s, const RevBatchDesc* desc, const RevBatchBuild* bd,
-                            int count, double* slab, int32_t* basis, double* xs,
-                            const double* obj, const double* A, const double* rhs);
-}  // namespace lpr
-
 using namespace lpr;
 
 struct lpr_rev_batch {

@@ -20,6 +20,23 @@ struct RevState {
     int32_t arrive_xu;    // k_rev_xu_ratio
 };
 
+// revised_kernels.hip
+void rev_launch_iteration(lpr_revised* s, bool snapshot);
+void rev_launch_iteration_batched(lpr_revised* s);
+void rev_launch_y(lpr_revised* s);
+void rev_launch_prices(lpr_revised* s);
+void rev_launch_zworking(lpr_revised* s);
+void rev_launch_matmul_exact(lpr_revised* s, double* Cout, int ldc);
+void rev_launch_extract(lpr_revised* s);
+void rev_launch_init(lpr_revised* s);
+void rev_launch_synthetic(lpr_revised* s, uint64_t seed);
+void rev_launch_transpose_a(lpr_revised* s);
+void rev_launch_gemm(lpr_revised* s, double* Cout, int ldc);
+// revised_fused.hip
+void rev_launch_update_y(lpr_revised* s);
+void rev_launch_rc_enter(lpr_revised* s);
+void rev_launch_xu_ratio(lpr_revised* s);
+
 }  // namespace lpr
 
 // RevisedPrimalSimplexSolver's fields (RevisedPrimalSimplexSolver.cs:15-33) in HBM.  `B` (:30) is

@@ -11,19 +11,6 @@
 
 namespace lpr {
 
-// revised_kernels.hip
-void rev_launch_iteration(lpr_revised* s, bool snapshot);
-void rev_launch_iteration_batched(lpr_revised* s);
-void rev_launch_y(lpr_revised* s);
-void rev_launch_prices(lpr_revised* s);
-void rev_launch_zworking(lpr_revised* s);
-void rev_launch_matmul_exact(lpr_revised* s, double* Cout, int ldc);
-void rev_launch_extract(lpr_revised* s);
-void rev_launch_init(lpr_revised* s);
-void rev_launch_synthetic(lpr_revised* s, uint64_t seed);
-void rev_launch_transpose_a(lpr_revised* s);
-void rev_launch_gemm(lpr_revised* s, double* Cout, int ldc);
-
 static void rev_release_device(lpr_revised* s) {
     hipSetDevice(s->eng->device);
     if (s->eng->stream) hipStreamSynchronize(s->eng->stream);

@@ -546,27 +546,10 @@ static void launch_update_y(lpr_revised* s, int do_update) {
     constexpr int RC = NSW * 8 * NQ;
     constexpr size_t lds = (size_t)3 * 16 * (RC + kRingPad) * sizeof(double);
     static unsigned long long asked = 0;  // per device bit
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !(asked & (1ull << dev))) {
-        asked |= 1ull << dev;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rev_update_y<NSW, NQ>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    (void)raise_dynamic_lds(reinterpret_cast<const void*>(&k_rev_update_y<NSW, NQ>), lds, &asked);
     hipLaunchKernelGGL((k_rev_update_y<NSW, NQ>), dim3((s->m + 15) / 16), dim3(64 * (NSW + 1)), lds,
                        s->eng->stream, s->Binv, s->ldb, s->m, s->browbuf, s->fac, s->cB, s->y,
                        s->state, do_update, s->is_basic, s->n, s->wmin + (s->n + 31) / 32);
-}
-
-template <class K>
-static void raise_dyn_lds(K kernel, size_t bytes, unsigned long long& asked) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !(asked & (1ull << dev))) {
-        asked |= 1ull << dev;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    }
 }
 
 // rc = c - y A, then the entering variable and its column
@@ -574,7 +557,7 @@ void rev_launch_rc_enter(lpr_revised* s) {
     constexpr int NSW = 6, NQ = 4;
     constexpr size_t lds = (size_t)4 * 32 * (NSW * 4 * NQ + kRingPad) * sizeof(double);
     static unsigned long long asked = 0;
-    raise_dyn_lds(&k_rev_rc_enter<NSW, NQ>, lds, asked);
+    (void)raise_dynamic_lds(reinterpret_cast<const void*>(&k_rev_rc_enter<NSW, NQ>), lds, &asked);
     hipLaunchKernelGGL((k_rev_rc_enter<NSW, NQ>), dim3((s->n + 31) / 32), dim3(64 * (NSW + 1)), lds,
                        s->eng->stream, s->A, s->lda, s->m, s->n, s->y, s->c, s->rcx, s->is_basic,
                        s->Binv, s->ldb, s->u, s->state, s->dbg_stamps, s->At, s->wmin);
@@ -585,7 +568,7 @@ void rev_launch_xu_ratio(lpr_revised* s) {
     constexpr size_t lds = (size_t)4 * 32 * (kXuRC + kRingPad) * sizeof(double);
     static_assert(lds >= kRatioLds * (2 * sizeof(double) + sizeof(int)), "the tail borrows the ring");
     static unsigned long long asked = 0;
-    raise_dyn_lds(&k_rev_xu_ratio, lds, asked);
+    (void)raise_dynamic_lds(reinterpret_cast<const void*>(&k_rev_xu_ratio), lds, &asked);
     hipLaunchKernelGGL(k_rev_xu_ratio, dim3((s->m + 15) / 16), dim3(64 * (kXuNSW + 1)), lds,
                        s->eng->stream, s->Binv, s->ldb, s->m, s->n, s->b, s->xB, s->At, s->u,
                        s->basic, s->is_basic, s->cB, s->c, s->browbuf, s->fac, s->log, s->state,

@@ -661,23 +661,12 @@ __global__ __launch_bounds__(256, 2) void k_rev_gemm(const double* __restrict__ 
 // launchers
 
 // dynamic LDS of k_rev_rowsum: two product tiles x two buffers
-// (the attribute belongs to the device the call is made on: asked once per device, not per process)
-static bool rev_first_ask(unsigned long long (&mask)[4]) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 256) return true;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (mask[dev >> 6] & bit) return false;
-    mask[dev >> 6] |= bit;
-    return true;
-}
-
+// (the attribute: raise_dynamic_lds of engine_common.hpp, once per device; these launchers return
+// nothing, so a refusal shows as the launch error that follows)
 static size_t rev_rowsum_lds() {
     constexpr size_t bytes = (size_t)4 * kRB * (kKC + kGRP + 2) * sizeof(double);
-    static unsigned long long asked[4] = {0, 0, 0, 0};
-    if (rev_first_ask(asked))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rev_rowsum),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    static unsigned long long asked = 0;
+    (void)raise_dynamic_lds(reinterpret_cast<const void*>(&k_rev_rowsum), bytes, &asked);
     return bytes;
 }
 
@@ -685,10 +674,8 @@ static size_t rev_rowsum_lds() {
 template <int RC, int CB>
 static size_t rev_colsum_lds() {
     constexpr size_t bytes = (size_t)(2 * (RC + kGRP) * CB) * sizeof(double);
-    static unsigned long long asked[4] = {0, 0, 0, 0};
-    if (rev_first_ask(asked))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rev_colsum<RC, CB>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    static unsigned long long asked = 0;
+    (void)raise_dynamic_lds(reinterpret_cast<const void*>(&k_rev_colsum<RC, CB>), bytes, &asked);
     return bytes;
 }
 
@@ -746,12 +733,6 @@ void rev_launch_iteration(lpr_revised* s, bool snapshot) {
     hipLaunchKernelGGL((k_rev_update<TR>), dim3((s->ldb / 2 + 255) / 256, (m + TR - 1) / TR),
                        dim3(256), 0, st, s->Binv, s->ldb, m, s->browbuf, s->fac, s->state);
 }
-
-// revised_fused.hip
-void rev_launch_y(lpr_revised* s);
-void rev_launch_update_y(lpr_revised* s);
-void rev_launch_rc_enter(lpr_revised* s);
-void rev_launch_xu_ratio(lpr_revised* s);
 
 // One iteration of lpr_revised_solve's batches.  Precondition: s->y = c_B B^-1 of the current state
 // (rev_launch_y at the head of a call; afterwards the update pass of every pivot leaves it).

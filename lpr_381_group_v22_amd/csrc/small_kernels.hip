@@ -21,7 +21,7 @@
 //   column e_q    gathered from T^(0) in memory, taken through pivots 1..q-1 of the block
 //   row r_q       gathered likewise, then divided by the pivot element (:195-199)
 // "taken through pivot s": x <- x - (f_s[i] * p_s[j]), or p_s[j] itself on the pivot row r_s.
-#include "engine_common.hpp"
+#include "small_kernels.hpp"
 #include "select_common.hpp"
 
 #include <cstdlib>
@@ -31,10 +31,8 @@
 
 namespace lpr {
 
-constexpr int kSmallK = 16;       // pivots per block
+// (kSmallK pivots per block, kSmallMaxR rows, kSmallMaxLd padded columns: primal_plan.hpp)
 constexpr int kSmallNT = 512;     // lanes of the heads' workgroup
-constexpr int kSmallMaxR = 1024;  // rows (one per lane)
-constexpr int kSmallMaxLd = 2048; // padded columns (one pair per lane)
 
 struct SmallState {
     int32_t status;    // kRunning or the final lpr_status
@@ -424,12 +422,6 @@ __global__ __launch_bounds__(256) void k_small_sweep(double* __restrict__ T, int
 // ------------------------------------------------------------------------------------------
 // host side (called by lpr_engine.hip)
 
-bool small_fits(const lpr_tableau* t) {
-    return t->rows >= 2 && t->rows <= kSmallMaxR && t->ld <= kSmallMaxLd &&
-           (size_t)kSmallK * (size_t)align_up(t->rows, 16) * sizeof(double) <= (size_t)(140 << 10);
-}
-int small_pivots_per_block() { return kSmallK; }
-
 void small_release(lpr_tableau* t) {
     lpr_small_ctx* c = static_cast<lpr_small_ctx*>(t->small);
     if (!c) return;
@@ -462,16 +454,17 @@ int small_ensure(lpr_tableau* t) {
         err = hipMalloc(&c->dbg, 16 * sizeof(unsigned long long));
         if (err == hipSuccess) err = hipMemset(c->dbg, 0, 16 * sizeof(unsigned long long));
     }
-    if (err == hipSuccess)
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_heads),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 140 << 10);
     t->small = c;
     if (err != hipSuccess) {
         set_error("small-tableau path: %s", hipGetErrorString(err));
         small_release(t);
         return err == hipErrorOutOfMemory ? LPR_OUT_OF_MEMORY : LPR_DEVICE_ERROR;
     }
-    return LPR_OK_OPTIMAL;
+    static unsigned long long raised = 0;  // per device: k_small_heads has its dynamic LDS
+    const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&k_small_heads), kSmallLdsBytes,
+                                     &raised);
+    if (rc != LPR_OK_OPTIMAL) small_release(t);
+    return rc;
 }
 
 int small_upload_state(lpr_tableau* t, int64_t iter, int64_t max_iter) {

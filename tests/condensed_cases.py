@@ -1,5 +1,5 @@
 """Cases for the condensed working layout of the two-stream K-pivot path (TEST ONLY;
-csrc/overlap_kernels.hip, solve_condensed in csrc/lpr_engine.hip).  For the length of a solve call
+csrc/overlap_kernels.hip, solve_condensed in csrc/overlap_driver.hip).  For the length of a solve call
 the kernels work on [columns not basic at the start | S spare columns | RHS]; a variable that was
 basic at the start ("omitted") gets a spare slot when it leaves.  What the layout can get wrong
 depends on WHEN variables leave and enter relative to the blocks of 16 pivots, so the cases are

@@ -1,4 +1,4 @@
-"""GPU tests of the K-pivot driver's polls ahead of the queue's end (csrc/lpr_engine.hip,
+"""GPU tests of the K-pivot driver's polls ahead of the queue's end (csrc/overlap_driver.hip,
 solve_overlapped; the snapshots of csrc/overlap_kernels.hip): in a batch of nb steps the host reads a
 snapshot of the control block `lead` steps before the end and queues the next batch behind the steps
 still running.  No kernel changed, so nothing a solve leaves may change: status, pivot count, pivot
