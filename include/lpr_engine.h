@@ -1277,6 +1277,46 @@ int lpr_rev_batch_trace_read(lpr_rev_batch* b, int32_t k, int64_t first, int64_t
  * orphaned handle is LPR_BAD_ARGUMENT with a message. */
 int lpr_rev_batch_trace_read_all(lpr_rev_batch* b, double* out, int64_t cap_doubles);
 
+/* Device text: the bytes of TableIterationFormater.Format
+ * (Utilities/TableIterationFormater.cs:22-48) written on the device.  A block is Format(tab,
+ * numOriginalVars, title) without its first line ("\n" + title + ":" + CRLF, which stays with the
+ * caller: one tableau is printed under several titles):
+ *   "-" x 80 CRLF
+ *   "Table\t" "x1\t" .. "x{nvars}\t" "t1\t" .. "t{cols-1-nvars}\t" "RHS" CRLF        (:27-35)
+ *   "Z\t" F3(T[0,0]) "\t" .. F3(T[0,cols-1]) "\t" CRLF                                (:36-40)
+ *   "{i}\t" F3(T[i,0]) "\t" .. "\t" CRLF  for i = 1 .. rows-1                         (:41-47)
+ * with {v:F3} of .NET Framework: the 15-significant-digit image of v (ties to even) rounded half
+ * away from zero at three decimals, no sign on an all-zero result, NaN / Infinity / -Infinity as
+ * words.  PARITY: byte for byte what table_iteration_formater.Format gives after its title line.
+ * An lpr_text holds the blocks in device memory, independent of what they were formatted from. */
+typedef struct lpr_text lpr_text;
+
+/* Format (:22-48) of a ragged list of tableaux from the host: count blocks, block k is
+ * rows[k] x cols[k] row-major in `tableaux`, one after the other, with nvars[k] original
+ * variables (the x loop of :32 runs to nvars whatever cols is; the t loop of :33 is empty when
+ * nvars >= cols - 1).  LPR_BAD_ARGUMENT with a message naming the call and the index for a NULL
+ * argument, count < 1, rows < 1, cols < 1 or nvars < 0; a failed allocation is LPR_OUT_OF_MEMORY
+ * naming the buffer and its size. */
+int lpr_text_format_tableaux(lpr_engine* e, int32_t count, const int32_t* rows, const int32_t* cols,
+                             const int32_t* nvars, const double* tableaux, lpr_text** out);
+/* Format (:22-48) of every kept record of every LP of a traced batch, read where the trace slab
+ * keeps it, in record order, followed per LP by one block of its tableau in the batch when the LP
+ * is LPR_OK_OPTIMAL or LPR_UNBOUNDED (PrimalSimplexSolver.cs:118-122, :133).  first_block[count +
+ * 1] (may be NULL): where LP k's blocks start.  Reads the batch only.  An untraced or orphaned
+ * batch is LPR_BAD_ARGUMENT; after LPR_OUT_OF_MEMORY the batch stays usable. */
+int lpr_batch_trace_text(lpr_batch* b, int64_t* first_block, lpr_text** out);
+/* Blocks, bytes of all blocks (:22-48, title lines excluded) and the milliseconds the kernels
+ * took; any may be NULL. */
+int lpr_text_info(lpr_text* t, int64_t* blocks, int64_t* bytes, double* kernel_ms);
+/* Where each block (:22-48) starts: blocks + 1 entries, the last one `bytes`. */
+int lpr_text_offsets_read(lpr_text* t, int64_t* offsets);
+/* Bytes [first_byte, first_byte + n) of the text (:22-48); a range beyond `bytes` is
+ * LPR_BAD_ARGUMENT. */
+int lpr_text_read(lpr_text* t, int64_t first_byte, int64_t n, uint8_t* out);
+/* Releases the blocks (:22-48).  After lpr_engine_close the handle is orphaned: every call but
+ * this one is LPR_BAD_ARGUMENT. */
+int lpr_text_destroy(lpr_text* t);
+
 #ifdef __cplusplus
 }
 #endif

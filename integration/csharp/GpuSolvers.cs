@@ -237,7 +237,62 @@ namespace LPR_381_Group_V22.Simplex
             return list;
         }
 
+        /// <summary>Every kept record of every LP, and the final tableau of every LP that ended, formatted on the device
+        /// (DESIGN.md section 25): block firstBlock[k] + i is the body of LP k's record i, the block after its kept records
+        /// the body of its final tableau.  Prepend "\n" + title + ":" + Environment.NewLine for the text Format gives.</summary>
+        public DeviceText FormatTrace(out long[] firstBlock)
+        {
+            firstBlock = new long[Count + 1];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_batch_trace_text(batch, firstBlock, out IntPtr text), "lpr_batch_trace_text");
+            return new DeviceText(text);
+        }
+
         public void Dispose() { if (batch != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_batch_destroy(batch), "lpr_batch_destroy"); batch = IntPtr.Zero; } }
+    }
+
+    /// <summary>Blocks of TableIterationFormater.Format (TableIterationFormater.cs:22-48) without their title lines, written on
+    /// the device (DESIGN.md section 25).  Owns the lpr_text handle; offsets and bytes are read once.</summary>
+    public class DeviceText : IDisposable
+    {
+        private IntPtr text;                            // lpr_text*
+        private long[] offsets;
+        private byte[] data;
+        public long Count { get; }
+        public long Bytes { get; }
+        public double KernelMs { get; }
+
+        internal DeviceText(IntPtr handle)
+        {
+            text = handle;
+            NativeMethods.ThrowIfError(NativeMethods.lpr_text_info(text, out long blocks, out long bytes, out double ms), "lpr_text_info");
+            Count = blocks; Bytes = bytes; KernelMs = ms;
+        }
+
+        /// <summary>One block per tableau: Format(tab, nvars[k], title) without its title line.</summary>
+        public static DeviceText FormatTableaux(IntPtr engine, List<double[,]> tableaux, int[] nvars)
+        {
+            var rows = tableaux.Select(t => t.GetLength(0)).ToArray();
+            var cols = tableaux.Select(t => t.GetLength(1)).ToArray();
+            var flat = new List<double>();
+            foreach (var t in tableaux) foreach (double v in t) flat.Add(v);   // row-major
+            NativeMethods.ThrowIfError(NativeMethods.lpr_text_format_tableaux(engine, tableaux.Count, rows, cols, nvars, flat.ToArray(), out IntPtr h),
+                                       "lpr_text_format_tableaux");
+            return new DeviceText(h);
+        }
+
+        public string Block(long i)
+        {
+            if (data == null)
+            {
+                offsets = new long[Count + 1];
+                NativeMethods.ThrowIfError(NativeMethods.lpr_text_offsets_read(text, offsets), "lpr_text_offsets_read");
+                data = new byte[Math.Max(1L, Bytes)];
+                NativeMethods.ThrowIfError(NativeMethods.lpr_text_read(text, 0, Bytes, data), "lpr_text_read");
+            }
+            return System.Text.Encoding.ASCII.GetString(data, checked((int)offsets[i]), checked((int)(offsets[i + 1] - offsets[i])));
+        }
+
+        public void Dispose() { if (text != IntPtr.Zero) { NativeMethods.ThrowIfError(NativeMethods.lpr_text_destroy(text), "lpr_text_destroy"); text = IntPtr.Zero; } }
     }
 
     /// <summary>RevisedPrimalSimplexSolver.Solve() + ExtractSolution (RevisedPrimalSimplexSolver.cs:82-251, :277-287) for many

@@ -333,6 +333,14 @@ namespace LPR_381_Group_V22.Native
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_trace_read(IntPtr revBatch, int k, long first, long n, double[] records);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_rev_batch_trace_read_all(IntPtr revBatch, double[] slab, long cap_doubles);
 
+        // ---- Device text (DESIGN.md section 25): TableIterationFormater.Format (:22-48) without its title line, written on the device ----
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_format_tableaux(IntPtr engine, int count, int[] rows, int[] cols, int[] nvars, double[] tableaux, out IntPtr text);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_trace_text(IntPtr batch, long[] first_block, out IntPtr text);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_info(IntPtr text, out long blocks, out long bytes, out double kernel_ms);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_offsets_read(IntPtr text, long[] offsets);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_read(IntPtr text, long first_byte, long n, byte[] bytes);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_destroy(IntPtr text);
+
         internal static string LastError() => Marshal.PtrToStringAnsi(lpr_last_error()) ?? "";
 
         internal static void ThrowIfError(int status, string where)

@@ -234,6 +234,9 @@ void unlist(std::vector<H*>& live, H* h) {
 // batch_engine.hip: what an engine that starts from a solved LP batch reads of it: its engine (null
 // once orphaned, or with no handle), the descriptors' host mirror and the tableau slab
 lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const double** slab);
+// batch_engine.hip: what lpr_batch_trace_text reads besides: the trace slab, every LP's offset into
+// it and the records kept per LP (0: the batch is not traced)
+int32_t batch_trace_view(lpr_batch* b, const double** trace, const std::vector<int64_t>** off);
 
 // batch_kernels.hip and, traced, batch_trace_kernels.hip: the launchers batch_engine.hip calls
 int batch_launch_simplex(int form, hipStream_t s, BatchDesc* desc, double* slab, int32_t* basis,

@@ -153,6 +153,11 @@ lpr_engine* batch_view(lpr_batch* b, const std::vector<BatchDesc>** desc, const 
     *slab = b->slab;
     return b->eng;
 }
+int32_t batch_trace_view(lpr_batch* b, const double** trace, const std::vector<int64_t>** off) {
+    *trace = b->trace;
+    *off = &b->h_trace_off;
+    return b->trace_cap;
+}
 }  // namespace lpr
 
 extern "C" {

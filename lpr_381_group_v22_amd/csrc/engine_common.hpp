@@ -132,6 +132,7 @@ struct lpr_sens_batch;
 struct lpr_cut_batch;
 struct lpr_knap_batch;
 struct lpr_rev_batch;
+struct lpr_text;
 
 struct lpr_engine {
     int device = 0;
@@ -152,6 +153,7 @@ struct lpr_engine {
     std::vector<lpr_cut_batch*> live_cut_batch;  // cutting-plane batches (cut_batch_engine.hip)
     std::vector<lpr_knap_batch*> live_knap_batch;  // knapsack batches (knapsack_batch_engine.hip)
     std::vector<lpr_rev_batch*> live_rev_batch;  // revised simplex batches (rev_batch_engine.hip)
+    std::vector<lpr_text*> live_text;  // formatted blocks (text_engine.hip)
 };
 
 struct lpr_tableau {
@@ -246,6 +248,7 @@ void sens_batch_orphan(lpr_sens_batch* b);
 void cut_batch_orphan(lpr_cut_batch* b);
 void knap_batch_orphan(lpr_knap_batch* b);
 void rev_batch_orphan(lpr_rev_batch* b);
+void text_orphan(lpr_text* t);
 // sens_engine.hip: what lpr_sens_batch_create reads of an analyzer (null: no handle); the engine is
 // null once the handle is orphaned
 lpr_engine* sens_view(lpr_sens* s, int* R, int* C, int* ld, const double** T,

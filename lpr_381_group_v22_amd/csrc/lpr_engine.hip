@@ -607,6 +607,8 @@ int lpr_engine_close(lpr_engine* e) {
     e->live_knap_batch.clear();
     for (lpr_rev_batch* b : e->live_rev_batch) rev_batch_orphan(b);
     e->live_rev_batch.clear();
+    for (lpr_text* t : e->live_text) text_orphan(t);
+    e->live_text.clear();
     if (e->stream) {
         hipStreamSynchronize(e->stream);
         hipStreamDestroy(e->stream);

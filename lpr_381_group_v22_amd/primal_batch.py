@@ -19,7 +19,9 @@ import numpy as np
 from . import _native as N
 from ._native import _ptr
 from .engine import Engine, default_engine
-from .primal_simplex_solver import format_console, format_snapshots
+from . import table_iteration_formater as fmt
+from .primal_simplex_solver import (col_label, format_console, format_snapshots,
+                                    solution_summary)
 
 
 class PackedModels(NamedTuple):
@@ -373,3 +375,97 @@ class PrimalSimplexBatch:
                              "its console text would miss pivots")
         return format_console(self._kept(k), self._shapes[k][2], self.Status[k], self.FinalZ[k],
                               self.SolutionVector[k])
+
+    # -- device text ------------------------------------------------
+    def FormatTrace(self) -> fmt.DeviceText:
+        """Every kept record of every LP, and the final tableau of every LP that ended, as text
+        blocks written on the device (lpr_batch_trace_text): one call, kept until the next
+        ``Solve``.  ``first_block[k]`` of the result is where LP k's blocks start."""
+        cached = getattr(self, "_text", None)
+        if cached is not None and cached[0] is self.LastResult:
+            return cached[1]
+        if cached is not None:
+            cached[1].destroy()
+        first = np.zeros(self.Count + 1, dtype=np.int64)
+        h = C.c_void_p()
+        N.check(N.lib.lpr_batch_trace_text(self._h, _ptr(first, C.c_int64), C.byref(h)),
+                "lpr_batch_trace_text")
+        text = fmt.DeviceText(h)
+        first.setflags(write=False)
+        text.first_block = first
+        self._text = (self.LastResult, text)
+        return text
+
+    def _bodies(self, k: int):
+        """(bodies of LP k's kept records, body of its final tableau or None), from the device."""
+        text = self.FormatTrace()
+        at, end = int(text.first_block[k]), int(text.first_block[k + 1])
+        kept = end - at - (1 if self._ended(k) else 0)
+        return ([text.block(i) for i in range(at, at + kept)],
+                text.block(at + kept) if self._ended(k) else None)
+
+    def _headers(self, k: int, n: int):
+        """(leaving_row, entering_col) of pivots 1 .. n - 1 of LP k: the pivot log when it kept
+        them all, else the records' headers."""
+        log = self.PivotLog(k)
+        if len(log) >= n - 1:
+            return [(int(r), int(e)) for r, e in log[:n - 1]]
+        return [(r, e) for r, e, _ in self._kept(k)[1:n]]
+
+    def IterationSnapshotsDevice(self, k: int) -> List[str]:
+        """``IterationSnapshots(k)``, its tableau bodies formatted on the device."""
+        bodies, final = self._bodies(k)
+        return snapshots_from_bodies(bodies, self._shapes[k][2], self.Status[k], final,
+                                     self.FinalZ[k], self.SolutionVector[k])
+
+    def ConsoleTextDevice(self, k: int) -> str:
+        """``ConsoleText(k)``, its tableau bodies formatted on the device; the same ValueError
+        for an LP with more records than TraceCap keeps."""
+        count = int(self.trace_info()[0][k])
+        if count > self.TraceCap:
+            raise ValueError(f"LP {k} made {count} records and TraceCap keeps {self.TraceCap}: "
+                             "its console text would miss pivots")
+        bodies, _ = self._bodies(k)
+        return console_from_bodies(self._headers(k, len(bodies)), bodies, self._shapes[k][2],
+                                   self.Status[k], self.FinalZ[k], self.SolutionVector[k])
+
+    def all_snapshot_texts(self) -> List[List[str]]:
+        """``IterationSnapshots`` of every LP, from one device call."""
+        return [self.IterationSnapshotsDevice(k) for k in range(self.Count)]
+
+
+def snapshots_from_bodies(bodies, numVariables: int, status: Optional[int] = None,
+                          final_body: Optional[str] = None, final_z: float = 0.0,
+                          solution=None) -> List[str]:
+    """format_snapshots of primal_simplex_solver.py from Format bodies (Format without its title
+    line) in place of tableaux: ``bodies[i]`` belongs to the tableau after i pivots."""
+    out = [fmt.title_line("Initial Tableau" if i == 0 else f"Iteration {i} - After pivot") + body
+           for i, body in enumerate(bodies)]
+    if status == N.LPR_OK_OPTIMAL:  # :118-122
+        out.append(fmt.title_line("Final Tableau (Optimal)") + final_body + fmt.NEWLINE +
+                   solution_summary(final_z, solution, numVariables) + fmt.NEWLINE)
+    elif status == N.LPR_UNBOUNDED:  # :133
+        out.append(fmt.title_line("Unbounded Tableau") + final_body)
+    return out
+
+
+def console_from_bodies(headers, bodies, numVariables: int, status: Optional[int] = None,
+                        final_z: float = 0.0, solution=None) -> str:
+    """format_console of primal_simplex_solver.py from Format bodies: ``headers[i - 1]`` is the
+    (leaving_row, entering_col) of pivot i, ``bodies[i]`` the body of the tableau after it."""
+    nl = fmt.NEWLINE
+    out = []
+    for i in range(1, len(bodies)):
+        r, e = headers[i - 1]
+        label = col_label(int(e), numVariables)
+        out.append(f"\nIteration {i}: pivot @ constraint {int(r)}, column {label}" + nl)
+        out.append(fmt.title_line("Before pivot") + bodies[i - 1] + nl)
+        out.append(f"After pivot (constraint {int(r)}, column {label}):" + nl)
+        out.append(fmt.title_line("After pivot") + bodies[i] + nl)
+    if status == N.LPR_OK_OPTIMAL:
+        out.append("Optimal Solution Found!" + nl)
+        out.append(solution_summary(final_z, solution, numVariables) + nl)
+        out.append("-" * 100 + nl)
+    elif status == N.LPR_UNBOUNDED:
+        out.append("Unbounded Solution!" + nl)
+    return "".join(out)

@@ -11,6 +11,7 @@ PARITY UNPINNED: the reference holds no formatted output to check these strings 
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from decimal import ROUND_HALF_UP, Context, Decimal
 from typing import Optional, Sequence
@@ -174,3 +175,109 @@ def Format(tab: np.ndarray, numOriginalVars: int, title: str,
             out.append(F3(float(tab[i, j])) + "\t")
         out.append(nl)
     return "".join(out)
+
+
+# -- device text: the body of Format, written on the MI355X -------------
+
+def title_line(title: str) -> str:
+    """The first line of Format (:24), the part of a block that stays on the host."""
+    return "\n" + title + ":" + NEWLINE
+
+
+class DeviceText:
+    """Blocks formatted on the device (lpr_text_*): ``block(i)`` is Format(tab, numOriginalVars,
+    title) without its title line.  Owns the handle; offsets and bytes are read once."""
+
+    def __init__(self, handle):
+        from . import _native as N
+        self._N = N
+        self._h = handle
+        blocks, nbytes, ms = C.c_int64(), C.c_int64(), C.c_double()
+        N.check(N.lib.lpr_text_info(self._h, C.byref(blocks), C.byref(nbytes), C.byref(ms)),
+                "lpr_text_info")
+        self.Count = int(blocks.value)
+        self.Bytes = int(nbytes.value)
+        self.KernelMs = float(ms.value)
+        self._offsets = None
+        self._data = None
+
+    def _read(self) -> None:
+        N = self._N
+        off = np.zeros(self.Count + 1, dtype=np.int64)
+        N.check(N.lib.lpr_text_offsets_read(self._h, N._ptr(off, C.c_int64)),
+                "lpr_text_offsets_read")
+        data = np.zeros(max(self.Bytes, 1), dtype=np.uint8)
+        N.check(N.lib.lpr_text_read(self._h, 0, self.Bytes, N._ptr(data, C.c_uint8)),
+                "lpr_text_read")
+        self._offsets = off
+        self._data = data[:self.Bytes].tobytes()
+
+    @property
+    def offsets(self) -> np.ndarray:
+        if self._offsets is None:
+            self._read()
+        return self._offsets
+
+    def block(self, i: int) -> str:
+        if self._data is None:
+            self._read()
+        if not 0 <= i < self.Count:
+            raise IndexError(f"block {i} of {self.Count}")
+        return self._data[int(self._offsets[i]):int(self._offsets[i + 1])].decode("ascii")
+
+    def blocks(self):
+        return [self.block(i) for i in range(self.Count)]
+
+    def destroy(self) -> None:
+        if self._h:
+            self._N.lib.lpr_text_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def format_device(tableaux, nvars, engine=None) -> DeviceText:
+    """lpr_text_format_tableaux: one block per tableau (2-D arrays of any shapes), ``nvars`` an
+    int for all or one per tableau."""
+    from . import _native as N
+    from .engine import default_engine
+    T = [np.ascontiguousarray(t, dtype=np.float64) for t in tableaux]
+    if not T or any(t.ndim != 2 for t in T):
+        raise ValueError("tableaux must be a non-empty list of 2-D arrays")
+    nv = [int(nvars)] * len(T) if np.isscalar(nvars) else [int(v) for v in nvars]
+    if len(nv) != len(T):
+        raise ValueError("nvars must be an int or hold one entry per tableau")
+    rows = np.asarray([t.shape[0] for t in T], dtype=np.int32)
+    cols = np.asarray([t.shape[1] for t in T], dtype=np.int32)
+    nva = np.asarray(nv, dtype=np.int32)
+    flat = np.concatenate([t.reshape(-1) for t in T])
+    eng = engine or default_engine()
+    h = C.c_void_p()
+    N.check(N.lib.lpr_text_format_tableaux(eng._h, len(T), N._ptr(rows, C.c_int32),
+                                           N._ptr(cols, C.c_int32), N._ptr(nva, C.c_int32),
+                                           N._ptr(flat, C.c_double), C.byref(h)),
+            "lpr_text_format_tableaux")
+    return DeviceText(h)
+
+
+def format_bodies(tableaux, nvars, engine=None):
+    """Format(tab, nvars, title) without its title line for every tableau, on the device."""
+    text = format_device(tableaux, nvars, engine)
+    try:
+        return text.blocks()
+    finally:
+        text.destroy()
+
+
+def FormatMany(tableaux, nvars, titles, engine=None):
+    """[Format(tab, nvars, title)] for every (tableau, title) pair: bodies from the device, the
+    title lines from the host."""
+    titles = list(titles)
+    bodies = format_bodies(tableaux, nvars, engine)
+    if len(titles) != len(bodies):
+        raise ValueError("one title per tableau")
+    return [title_line(t) + b for t, b in zip(titles, bodies)]
