@@ -180,7 +180,8 @@ struct SmallHead {
         for (int u = 0; u < kNI; ++u) {
             if (has_row[u] && row[u] >= 1 && x[u] > 1e-9) {
                 const double ratio = rq[u];
-                if (ratio >= 0 && (m.i < 0 || ratio < m.v)) {  // rows ascend with u: ties keep the lower
+                // :184, minRatio starts at MaxValue; rows ascend with u: ties keep the lower
+                if (ratio >= 0 && ratio < DBL_MAX && (m.i < 0 || ratio < m.v)) {
                     m.v = ratio;
                     m.i = row[u];
                 }

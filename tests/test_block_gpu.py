@@ -478,7 +478,9 @@ def test_ratio_that_overflows_is_not_a_candidate(engine, oracle):
                   [2.0 ** -29, 0.0, 1.0, 2.0 ** 994 * (2.0 - 2.0 ** -52)]], dtype=np.float64)
     # second row: ratio == DBL_MAX exactly ((2 - 2^-52) * 2^1023): not < MaxValue either
     assert T[2, 3] / T[2, 0] == np.finfo(np.float64).max and T[1, 3] / T[1, 0] == np.inf
-    for variant, block in ((0x7fff, 1), (0x7ffe, 1), (SEQ, 4), (OV2, 4), (OV, 4), (INPLACE, 4)):
+    # (0, 0): the default, and 0x2000 forced: the cache-resident path of small_kernels.hip
+    for variant, block in ((0x7fff, 1), (0x7ffe, 1), (SEQ, 4), (OV2, 4), (OV, 4), (INPLACE, 4),
+                           (0, 0), (0x2000, 0)):
         Tc, basis = T.copy(), np.array([1, 2], dtype=np.int32)
         st, piv, log = oracle.primal_solve(Tc, basis, 10)
         assert st == 1 and piv == 0
