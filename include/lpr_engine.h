@@ -1305,6 +1305,30 @@ int lpr_text_format_tableaux(lpr_engine* e, int32_t count, const int32_t* rows, 
  * 1] (may be NULL): where LP k's blocks start.  Reads the batch only.  An untraced or orphaned
  * batch is LPR_BAD_ARGUMENT; after LPR_OUT_OF_MEMORY the batch stays usable. */
 int lpr_batch_trace_text(lpr_batch* b, int64_t* first_block, lpr_text** out);
+/* DisplayTableau (IntegerProgramming/BranchBoundSimplexSolver.cs:623-640) of a ragged list of
+ * tableaux from the host: as lpr_text_format_tableaux, but block k is
+ * Format (:22-48) of the tableau after round4[k] applications of Math.Round(v, 4) to every cell
+ * (RoundTableau; 0 leaves the cells as they are, 2 is RoundAllTableaux followed by
+ * DisplayTableau).  An entry of round4 outside 0..2, or a NULL round4, is LPR_BAD_ARGUMENT naming
+ * the index. */
+int lpr_text_format_tableaux_rounded(lpr_engine* e, int32_t count, const int32_t* rows,
+                                     const int32_t* cols, const int32_t* nvars,
+                                     const int32_t* round4, const double* tableaux,
+                                     lpr_text** out);
+/* DisplayTableau (BranchBoundSimplexSolver.cs:623-640) of everything a narrated B&B batch keeps
+ * (DESIGN.md sections 23 and 26), read where the batch keeps it.  Per IP: one block per kept child
+ * tableau in the order of its slice -- record-id order, list order within a record; a record keeps
+ * min(ntab, (doubles_kept - tab_off) / (rows * cols)) tableaux, never below 0 -- each
+ * (R0 + depth) x (C0 + depth) with the IP's nvars, then one block of the incumbent's tableau when
+ * the IP has one.  Cells are rounded as ExecuteBranchAndBound rounds what it shows: twice for a
+ * tableau of a solved child (RoundAllTableaux :1124 / :1187, then DisplayTableau), once for one of
+ * an infeasible or failed child, once for the incumbent's (stored rounded by :1047).
+ * first_block[count + 1] (may be NULL): where IP k's blocks start.  Reads the batch only; the text
+ * owns its bytes and outlives a later run, reserve or destroy of the batch.  LPR_BAD_ARGUMENT, with
+ * a message saying which, for an un-narrated batch, no run since the last reserve, an orphaned
+ * handle, a NULL out, or nothing to format (no kept tableau and no incumbent in the whole batch);
+ * after LPR_OUT_OF_MEMORY the batch stays usable. */
+int lpr_bb_batch_narrate_text(lpr_bb_batch* b, int64_t* first_block, lpr_text** out);
 /* Blocks, bytes of all blocks (:22-48, title lines excluded) and the milliseconds the kernels
  * took; any may be NULL. */
 int lpr_text_info(lpr_text* t, int64_t* blocks, int64_t* bytes, double* kernel_ms);

@@ -280,6 +280,19 @@ namespace LPR_381_Group_V22.Simplex
             return new DeviceText(h);
         }
 
+        /// <summary>DisplayTableau (BranchBoundSimplexSolver.cs:623-640) per tableau: Format of tableau k after round4[k]
+        /// (0, 1 or 2) applications of Math.Round(v, 4), without its title line (DESIGN.md section 26).</summary>
+        public static DeviceText FormatTableauxRounded(IntPtr engine, List<double[,]> tableaux, int[] nvars, int[] round4)
+        {
+            var rows = tableaux.Select(t => t.GetLength(0)).ToArray();
+            var cols = tableaux.Select(t => t.GetLength(1)).ToArray();
+            var flat = new List<double>();
+            foreach (var t in tableaux) foreach (double v in t) flat.Add(v);   // row-major
+            NativeMethods.ThrowIfError(NativeMethods.lpr_text_format_tableaux_rounded(engine, tableaux.Count, rows, cols, nvars, round4, flat.ToArray(), out IntPtr h),
+                                       "lpr_text_format_tableaux_rounded");
+            return new DeviceText(h);
+        }
+
         public string Block(long i)
         {
             if (data == null)
@@ -578,7 +591,23 @@ namespace LPR_381_Group_V22.Simplex
         /// <summary>The console text of ExecuteBranchAndBound (:1006-1233) for IP k alone, from the records a narrated
         /// run kept.  Throws where the IP kept fewer tableaux or trace quads than it made, or hit a child pivot limit:
         /// the text of a search has no gaps.  (`failed: {e}` (:1147 / :1207) carries the exception's message, no stack trace.)</summary>
-        public string Narration(int k)
+        public string Narration(int k) => NarrationCore(k, null, null);
+
+        /// <summary>DisplayTableau (:623-640) of every kept child tableau and of every incumbent's tableau, written on the
+        /// device (DESIGN.md section 26): IP k's blocks start at firstBlock[k], one per kept tableau in record-id order,
+        /// then the incumbent's.  The text does not depend on the batch staying as it is.</summary>
+        public DeviceText FormatNarration(out long[] firstBlock)
+        {
+            firstBlock = new long[Count + 1];
+            NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_text(bb, firstBlock, out IntPtr text), "lpr_bb_batch_narrate_text");
+            return new DeviceText(text);
+        }
+
+        /// <summary>Narration(k) with every displayed tableau taken from FormatNarration's blocks: no cell is rounded or
+        /// formatted on the host.</summary>
+        public string NarrationText(int k, DeviceText text, long[] firstBlock) => NarrationCore(k, text, firstBlock);
+
+        private string NarrationCore(int k, DeviceText text, long[] firstBlock)
         {
             var made = new long[Count]; var kept = new long[Count];
             NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_info(bb, null, made, kept, null), "lpr_bb_batch_narrate_info");
@@ -595,8 +624,8 @@ namespace LPR_381_Group_V22.Simplex
             var fl = new int[nodeCap]; var zs = new double[nodeCap]; var vals = new double[Math.Max(1, nodeCap * n)];
             NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_pops_read(bb, k, fl, zs, vals, nodeCap, out long pops), "lpr_bb_batch_narrate_pops_read");
             var ids = PopOrder(k);
-            var flat = new double[Math.Max(1, kept[k])];
-            if (kept[k] > 0) NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_tableaux_read(bb, k, 0, kept[k], flat), "lpr_bb_batch_narrate_tableaux_read");
+            var flat = new double[text == null ? Math.Max(1, kept[k]) : 1];
+            if (text == null && kept[k] > 0) NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_tableaux_read(bb, k, 0, kept[k], flat), "lpr_bb_batch_narrate_tableaux_read");
             int rootRows = this.rootRows[k], rootCols = this.rootCols[k];
             var sb = new System.Text.StringBuilder();
             Action<string> wl = s => sb.Append(s).Append(Environment.NewLine);
@@ -605,6 +634,9 @@ namespace LPR_381_Group_V22.Simplex
                 if (t == null || t.Length == 0) wl($"{caption} (empty)");
                 else wl(TableIterationFormater.Format(Rounded(t), n, caption));
             };
+            var firstOf = new long[recs.Count + 1];                             // blocks before record q's (kept == made here)
+            for (int q = 0; q < recs.Count; q++) firstOf[q + 1] = firstOf[q] + nt[q];
+            Action<long, string> body = (block, caption) => wl("\n" + caption + ":" + Environment.NewLine + text.Block(block));
             wl("Initiating Branch and Bound Algorithm");
             wl(pruning ? "Pruning: Enabled" : "Pruning: Disabled");
             wl(new string('-', 50));
@@ -647,27 +679,34 @@ namespace LPR_381_Group_V22.Simplex
                         continue;
                     }
                     int rows = rootRows + recs[q].depth, cols = rootCols + recs[q].depth;
-                    var shown = Enumerable.Range(0, nt[q]).Select(j => Block(flat, off[q] + (long)j * rows * cols, rows, cols)).ToList();
+                    long at = off[q], blk0 = text != null ? firstBlock[k] + firstOf[q] : 0;
+                    var shown = text != null ? new List<double[,]>(new double[nt[q]][,])
+                                             : Enumerable.Range(0, nt[q]).Select(j => Block(flat, at + (long)j * rows * cols, rows, cols)).ToList();
+                    Action<int, string> show = (j, caption) => { if (text != null) body(blk0 + j, caption); else display(shown[j], caption); };
                     if (recs[q].status == 1)
                     {
-                        display(shown.Count > 0 ? shown[0] : null, $"branch {child}: Infeasible tableau");
+                        if (shown.Count > 0) show(0, $"branch {child}: Infeasible tableau"); else display(null, $"branch {child}: Infeasible tableau");
                         continue;
                     }
                     label[q] = child;
                     path[q] = path[id].Concat(new[] { $"x{var + 1} {(lower ? "<=" : ">=")} {G(recs[q].bound)}" }).ToList();
                     wl($"{name} branch (branch {child}) infeasible");            // (sic) :1130 / :1193
-                    for (int j = 0; j + 1 < shown.Count; j++) display(shown[j], $"branch {child} {name} branch Tableau {j + 1}");
-                    if (shown.Count > 0) display(shown[shown.Count - 1], $"branch {child} {name} branch final tableau");
+                    for (int j = 0; j + 1 < shown.Count; j++) show(j, $"branch {child} {name} branch Tableau {j + 1}");
+                    if (shown.Count > 0) show(shown.Count - 1, $"branch {child} {name} branch final tableau");
                 }
             }
             if (Status[k] == (int)LprStatus.BbNodeCap) wl("Potential infinite loop detected");
             wl("\n" + new string('-', 50)); wl("BRANCH AND BOUND COMPLETED"); wl(new string('-', 50));
             if (optimalX != null)
             {
-                NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_best_read(bb, k, null, out int br, out int bc), "lpr_bb_batch_narrate_best_read");
-                var best = new double[br * bc];
-                NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_best_read(bb, k, best, out br, out bc), "lpr_bb_batch_narrate_best_read");
-                display(Block(best, 0, br, bc), $"Optimal solution tableau at branch {optimalLabel}");
+                if (text != null) body(firstBlock[k + 1] - 1, $"Optimal solution tableau at branch {optimalLabel}");   // the IP's last block
+                else
+                {
+                    NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_best_read(bb, k, null, out int br, out int bc), "lpr_bb_batch_narrate_best_read");
+                    var best = new double[br * bc];
+                    NativeMethods.ThrowIfError(NativeMethods.lpr_bb_batch_narrate_best_read(bb, k, best, out br, out bc), "lpr_bb_batch_narrate_best_read");
+                    display(Block(best, 0, br, bc), $"Optimal solution tableau at branch {optimalLabel}");
+                }
                 wl($"Optimal branch: {optimalLabel}");
                 wl($"Optimal integer solution: [{string.Join(", ", optimalX.Select(G))}]");
                 wl($"Optimal value: {G(optimalValue)}");

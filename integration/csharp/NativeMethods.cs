@@ -336,6 +336,8 @@ namespace LPR_381_Group_V22.Native
         // ---- Device text (DESIGN.md section 25): TableIterationFormater.Format (:22-48) without its title line, written on the device ----
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_format_tableaux(IntPtr engine, int count, int[] rows, int[] cols, int[] nvars, double[] tableaux, out IntPtr text);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_batch_trace_text(IntPtr batch, long[] first_block, out IntPtr text);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_format_tableaux_rounded(IntPtr engine, int count, int[] rows, int[] cols, int[] nvars, int[] round4, double[] tableaux, out IntPtr text);
+        [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_bb_batch_narrate_text(IntPtr bbBatch, long[] first_block, out IntPtr text);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_info(IntPtr text, out long blocks, out long bytes, out double kernel_ms);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_offsets_read(IntPtr text, long[] offsets);
         [DllImport(Lib, CallingConvention = CC)] internal static extern int lpr_text_read(IntPtr text, long first_byte, long n, byte[] bytes);

@@ -496,6 +496,9 @@ SIGNATURES = {
     "lpr_rev_batch_trace_read_all": (C.c_int, [_P, _D, C.c_int64]),
     "lpr_text_format_tableaux": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32, _D, _PP]),
     "lpr_batch_trace_text": (C.c_int, [_P, _I64, _PP]),
+    "lpr_text_format_tableaux_rounded": (C.c_int, [_P, C.c_int32, _I32, _I32, _I32, _I32, _D,
+                                                   _PP]),
+    "lpr_bb_batch_narrate_text": (C.c_int, [_P, _I64, _PP]),
     "lpr_text_info": (C.c_int, [_P, _I64, _I64, _D]),
     "lpr_text_offsets_read": (C.c_int, [_P, _I64]),
     "lpr_text_read": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_uint8)]),

@@ -64,6 +64,28 @@ class PackedRoots(NamedTuple):
     nvars: np.ndarray     # int32, per IP
 
 
+def kept_tableaux(rows: int, cols: int, tab_off: int, ntab: int, doubles_kept: int) -> int:
+    """How many whole tableaux of a record's list the IP's kept prefix holds: the rule of
+    csrc/bb_narr_text_layout.hpp, min(ntab, (kept - tab_off) / (rows * cols)), never below 0."""
+    return max(0, min(int(ntab), (int(doubles_kept) - int(tab_off)) // (rows * cols)))
+
+
+def narration_block_index(root_shape, records, tab_off, ntab, doubles_kept: int) -> List[int]:
+    """Where each record's tableaux are among the blocks of its IP in ``FormatNarration``'s text:
+    entry rid is the block of the record's first kept tableau, counted from the IP's first block
+    (tableau i of the record is block ``index[rid] + i``); the last entry is the number of child
+    blocks, which is where the incumbent's block is when the IP has one.  ``records`` as
+    ``Records(k)`` gives them, ``tab_off`` / ``ntab`` as ``Children(k)``, ``doubles_kept`` the
+    IP's entry of ``narration_info()``."""
+    index, at = [], 0
+    for rid, rec in enumerate(records):
+        index.append(at)
+        at += kept_tableaux(root_shape[0] + rec["depth"], root_shape[1] + rec["depth"],
+                            tab_off[rid], ntab[rid], doubles_kept)
+    index.append(at)
+    return index
+
+
 def node_cap_of(node_cap: int) -> int:
     """The node cap a batch runs with: <= 0 is the reference's 20; above 64 is refused."""
     cap = int(node_cap) if int(node_cap) > 0 else DEFAULT_NODE_CAP
@@ -137,6 +159,7 @@ class BranchAndBoundBatch:
         self.Narrated = False
         self._pruning = False      # of the last Run
         self._narr_info = None     # read once per run
+        self._narr_text = None     # (DeviceText, first_block) of FormatNarration, per run
 
     @classmethod
     def from_tableaux(cls, tableaux: Sequence[np.ndarray], nvars: Sequence[int], node_cap: int = 0,
@@ -171,9 +194,15 @@ class BranchAndBoundBatch:
                    int(trace_cap) if trace_cap > 0 else DEFAULT_TRACE_CAP)
 
     def destroy(self) -> None:
+        self._drop_narration_text()
         if self._h:
             N.lib.lpr_bb_batch_destroy(self._h)
             self._h = None
+
+    def _drop_narration_text(self) -> None:
+        if getattr(self, "_narr_text", None) is not None:
+            self._narr_text[0].destroy()
+            self._narr_text = None
 
     def __del__(self):
         try:
@@ -191,6 +220,7 @@ class BranchAndBoundBatch:
         self.LastResult = res
         self._pruning = bool(enable_pruning)
         self._narr_info = None
+        self._drop_narration_text()
         return res
 
     # -- narration (section 23) ------------------------------------------------------------------
@@ -203,6 +233,7 @@ class BranchAndBoundBatch:
             raise ValueError(f"{caps.size} caps for {self.Count} IPs")
         self.Narrated = False
         self._narr_info = None
+        self._drop_narration_text()
         self._caps = caps
         N.check(N.lib.lpr_bb_batch_narrate_reserve(self._h, caps.ctypes.data_as(
             C.POINTER(C.c_int64))), "lpr_bb_batch_narrate_reserve")
@@ -259,7 +290,7 @@ class BranchAndBoundBatch:
     def _child_tableaux(self, k: int, rid: int, depth: int, off, nt, kept: int):
         """The kept tableaux of record rid, and how many its list holds."""
         r, c = self._shapes[k][0] + depth, self._shapes[k][1] + depth
-        have = max(0, min(int(nt[rid]), (kept - int(off[rid])) // (r * c)))
+        have = kept_tableaux(r, c, off[rid], nt[rid], kept)
         out = np.zeros((max(have, 1), r, c))
         if have:
             N.check(N.lib.lpr_bb_batch_narrate_tableaux_read(
@@ -290,10 +321,11 @@ class BranchAndBoundBatch:
                 "lpr_bb_batch_narrate_best_read")
         return out
 
-    def NarrationNumbers(self, k: int):
+    def NarrationNumbers(self, k: int, device_text: bool = False):
         """(pops, incumbent tableau, capped) of IP k for format_branch_and_bound.  The text of a
         search has no gaps: raises ValueError where IP k kept fewer tableaux or trace quads than
-        it made, or ended with LPR_PIVOT_LIMIT."""
+        it made, or ended with LPR_PIVOT_LIMIT.  With ``device_text`` every tableau is its body
+        from ``FormatNarration``'s text (a str) and no tableau is read back."""
         res = self.Result(k)
         if res["status"] == N.LPR_PIVOT_LIMIT:
             raise ValueError(f"IP {k} ended with LPR_PIVOT_LIMIT: its search is incomplete")
@@ -307,6 +339,20 @@ class BranchAndBoundBatch:
         recs = self.Records(k)
         off, nt = self.Children(k)
         kept = int(info.doubles_kept[k])
+        if device_text and (info.tableaux[k] > 0 or res["found"]):
+            text, first = self.FormatNarration()
+            index = narration_block_index(self._shapes[k], recs, off, nt, kept)
+
+            def tableaux_of(rid):
+                at = int(first[k]) + index[rid]
+                return [text.block(at + i) for i in range(index[rid + 1] - index[rid])]
+
+            incumbent = text.block(int(first[k + 1]) - 1) if res["found"] else None
+        else:
+            def tableaux_of(rid):
+                return self._child_tableaux(k, rid, recs[rid]["depth"], off, nt, kept)[0]
+
+            incumbent = None if device_text else self.IncumbentTableau(k)
         pivots = {}
         for rid, ph, r, c in self.Trace(k):
             pivots.setdefault(rid, []).append((ph, r, c))
@@ -319,12 +365,10 @@ class BranchAndBoundBatch:
         for pop in self.PopInfo(k):
             children = None
             if pop["id"] in kids:
-                children = [bnb.ChildNumbers(
-                    status[recs[rid]["status"]], pivots.get(rid, []),
-                    self._child_tableaux(k, rid, recs[rid]["depth"], off, nt, kept)[0])
-                    for rid in kids[pop["id"]]]
+                children = [bnb.ChildNumbers(status[recs[rid]["status"]], pivots.get(rid, []),
+                                             tableaux_of(rid)) for rid in kids[pop["id"]]]
             pops.append(bnb.PopNumbers(pop["z"], pop["vals"], children))
-        return pops, self.IncumbentTableau(k), res["status"] == N.LPR_BB_NODE_CAP
+        return pops, incumbent, res["status"] == N.LPR_BB_NODE_CAP
 
     def NarrationText(self, k: int, newline: str = "\n") -> str:
         """What ExecuteBranchAndBound of IP k alone writes to the console (:1006-1233), with
@@ -333,6 +377,33 @@ class BranchAndBoundBatch:
         pops, tab, capped = self.NarrationNumbers(k)
         return bnb.format_branch_and_bound(self.nvars[k], pops, tab, capped, self._pruning,
                                            newline)[0]
+
+    # -- device text (section 26) ---------------------------------------------------------------
+    def FormatNarration(self):
+        """(DeviceText, first_block) of lpr_bb_batch_narrate_text: DisplayTableau's body (:623-640)
+        of every kept child tableau of every IP, in record-id order, then the incumbent's where
+        the IP has one; IP k's blocks are first_block[k] .. first_block[k + 1] - 1
+        (``narration_block_index`` places a record's).  One call per run: kept until the next
+        ``Run`` / ``narrate_reserve``."""
+        if self._narr_text is None:
+            first = np.zeros(self.Count + 1, dtype=np.int64)
+            h = C.c_void_p()
+            N.check(N.lib.lpr_bb_batch_narrate_text(self._h, _ptr(first, C.c_int64), C.byref(h)),
+                    "lpr_bb_batch_narrate_text")
+            from .table_iteration_formater import DeviceText
+            self._narr_text = (DeviceText(h), first)
+        return self._narr_text
+
+    def NarrationTextDevice(self, k: int, newline: str = "\n") -> str:
+        """``NarrationText(k)`` with every tableau rounded and formatted on the device
+        (``FormatNarration``): the same text, the same ValueErrors."""
+        pops, body, capped = self.NarrationNumbers(k, device_text=True)
+        return bnb.format_branch_and_bound(self.nvars[k], pops, body, capped, self._pruning,
+                                           newline)[0]
+
+    def all_narration_texts(self, newline: str = "\n") -> List[str]:
+        """``NarrationTextDevice(k)`` for every IP, from one ``FormatNarration``."""
+        return [self.NarrationTextDevice(k, newline) for k in range(self.Count)]
 
     # -- bulk reads -----------------------------------------------------------------------------
     def result_arrays(self) -> dict:
@@ -428,13 +499,16 @@ def solve_integer_programs(parsers, node_cap: int = 0, enable_pruning: bool = Fa
 
 def option3_texts(parsers, node_cap: int = 0, enable_pruning: bool = False,
                   engine: Optional[Engine] = None, primal_trace_cap: int = 256,
-                  trace_cap: int = 1 << 14) -> List[Tuple[str, List[float], float]]:
+                  trace_cap: int = 1 << 14,
+                  device_text: bool = False) -> List[Tuple[str, List[float], float]]:
     """Menu option 3 (Program.cs:356-415) for many models at once, with its text: one traced
     PrimalSimplexBatch and one narrated BranchAndBoundBatch.  Per model ``(text, x, z)``: the
     console text Program.cs captures into the result file -- the banner (:358), the canonical
     form (:360-361), the primal solve's tables (``ConsoleText(k)``), everything
     ExecuteBranchAndBound writes (``NarrationText(k)``) and the result block (:401-407) -- and
-    SolveFromPrimal's ``(x, z)``.  The caller's parsers are left as they are."""
+    SolveFromPrimal's ``(x, z)``.  The caller's parsers are left as they are.  With
+    ``device_text`` the tables of both halves are formatted on the device (``ConsoleTextDevice``,
+    ``NarrationTextDevice``): the same text."""
     from . import program as prog
     from . import table_iteration_formater as fmt
     nl = fmt.NEWLINE
@@ -442,7 +516,8 @@ def option3_texts(parsers, node_cap: int = 0, enable_pruning: bool = False,
                                 trace_cap=primal_trace_cap)
     try:
         primal.Solve()
-        consoles = [primal.ConsoleText(k) for k in range(primal.Count)]
+        console = primal.ConsoleTextDevice if device_text else primal.ConsoleText
+        consoles = [console(k) for k in range(primal.Count)]
         bb = BranchAndBoundBatch.from_primal_batch(primal, node_cap=node_cap, trace_cap=trace_cap)
     finally:
         primal.destroy()
@@ -471,7 +546,8 @@ def option3_texts(parsers, node_cap: int = 0, enable_pruning: bool = False,
             tail = ["\n=== Branch & Bound Result ===" + nl,
                     f"Z* = {fmt._custom_0_hashes(z) if math.isfinite(z) else z}" + nl]
             tail += [f"x{i + 1} = {fmt._custom_0_hashes(v)}" + nl for i, v in enumerate(x)]
-            out.append((buf.getvalue() + consoles[k] + bb.NarrationText(k, newline=nl) +
+            narration = bb.NarrationTextDevice if device_text else bb.NarrationText
+            out.append((buf.getvalue() + consoles[k] + narration(k, newline=nl) +
                         "".join(tail), x, z))
     finally:
         bb.destroy()

@@ -188,7 +188,8 @@ class ChildNumbers(NamedTuple):
     """One child LP of a pop (:1083-1148 lower, :1150-1208 upper), as numbers."""
     status: int                          # BB_SOLVED / BB_INFEASIBLE / BB_FAILED
     pivots: List[Tuple[int, int, int]]   # (phase, row, col) in order; phase 2 = the drop of :392-400
-    tableaux: List[np.ndarray]           # DoDualSimplex's list (:292, :341, :388), unrounded
+    tableaux: List[np.ndarray]           # DoDualSimplex's list (:292, :341, :388), unrounded; or,
+    #                                      per tableau, a str: its pre-formatted body
 
 
 class PopNumbers(NamedTuple):
@@ -259,6 +260,11 @@ def format_branch_and_bound(n: int, pops: Sequence[PopNumbers], incumbent_tab, c
     ``write(s, end)``, if given, receives every Console.Write / WriteLine as it is made instead
     of the text being collected (the single path prints them one by one, so that a stream which
     tells print()'s terminator from a "\\n" inside a string still can).
+    PRE-FORMATTED BODIES: an entry of a child's ``tableaux``, or ``incumbent_tab``, may be a str in
+    place of an array -- what Format gives for that tableau as DisplayTableau would show it (rounded
+    twice for a solved child, once for an infeasible child and for the incumbent), without its
+    title line (bb_batch.NarrationTextDevice takes them from the device).
+    Such a tableau is shown as ``title_line(caption) + body`` and no cell is touched here.
     Returns (text, x or None, z, processed)."""
     out: List[str] = []
 
@@ -274,6 +280,9 @@ def format_branch_and_bound(n: int, pops: Sequence[PopNumbers], incumbent_tab, c
     emit("-" * 50)                                                       # :1019
 
     def display(tab, caption: str) -> None:  # DisplayTableau :623-640
+        if isinstance(tab, str):  # a body formatted elsewhere
+            emit(fmt.title_line(caption) + tab)
+            return
         if tab is None or tab.size == 0:
             emit(f"{caption} (empty)")
             return
@@ -327,7 +336,7 @@ def format_branch_and_bound(n: int, pops: Sequence[PopNumbers], incumbent_tab, c
             for ph, r, c in ch.pivots:  # PerformDualPivot :198 / PerformPrimalPivot :276
                 if ph < 2:
                     emit(f"pivot @ constraint {r}, column {c + 1}")
-            shown = [np.asarray(t) for t in ch.tableaux]
+            shown = [t if isinstance(t, str) else np.asarray(t) for t in ch.tableaux]
             if ch.status == BB_FAILED:  # an exception escaped DoDualSimplex (:396-399)
                 emit(f"{name} branch (branch {counters[label]}) failed: "
                      f"System.ArgumentOutOfRangeException: Index was out of range. Must be "
@@ -337,7 +346,8 @@ def format_branch_and_bound(n: int, pops: Sequence[PopNumbers], incumbent_tab, c
                 display(shown[0] if shown else None, f"branch {child_label}: Infeasible tableau")
                 shown = []
             else:
-                shown = [_round4_np(t) for t in shown]  # RoundAllTableaux :1124 / :1187
+                # RoundAllTableaux :1124 / :1187
+                shown = [t if isinstance(t, str) else _round4_np(t) for t in shown]
                 op = "<=" if side == 0 else ">="
                 desc = f"x{k + 1} {op} {_g(bnd[-2])}"
                 kids.append((depth + 1, child_label, path + [desc], label))
@@ -488,6 +498,8 @@ def choose_branch(vals: Sequence[float]) -> Tuple[int, float]:
     best, best_val, min_dist = -1, 0.0, math.inf
     for i, v in enumerate(vals):
         if not _is_integer(v):
+            if not math.isfinite(v):  # Math.Floor gives NaN / the infinity, the distance is NaN
+                continue              # and `NaN < minDist` is false (math.floor would raise)
             d = abs((v - math.floor(v)) - 0.5)
             if d < min_dist:
                 min_dist, best, best_val = d, i, float(v)

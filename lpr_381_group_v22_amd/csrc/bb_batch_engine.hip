@@ -3,6 +3,8 @@
 // device; the host only picks each IP's form, relaunches the bounded search kernels while IPs are
 // still running (BatchRunLists of batch_common.hpp) and copies results out.
 #include "bb_batch_common.hpp"
+#include "bb_narr_text_layout.hpp"
+#include "text_common.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -745,6 +747,93 @@ int lpr_bb_batch_narrate_best_read(lpr_bb_batch* b, int32_t k, double* out, int3
                            hipMemcpyDeviceToHost, b->eng->stream));
     LPR_HIP(hipStreamSynchronize(b->eng->stream));
     return LPR_OK_OPTIMAL;
+}
+
+// DisplayTableau (:623-640) of every kept child tableau and of the incumbent's tableau of every
+// IP, written on the device: one block per kept tableau in record-id order,
+// list order within a record (bb_narr_text_layout.hpp), then the incumbent's where there is one.
+// The descriptors come from three bulk reads -- the records' integers, tab_off, ntab -- and the
+// host mirrors of the last run; the text owns its bytes.
+int lpr_bb_batch_narrate_text(lpr_bb_batch* b, int64_t* first_block, lpr_text** out) {
+    static const char* W = "lpr_bb_batch_narrate_text";
+    if (!b || !b->eng) {
+        set_error("%s: B&B batch handle is null or orphaned: its engine has been closed", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (!bbb_narrated(W, b)) return LPR_BAD_ARGUMENT;
+    if (!b->narr_ran) {
+        set_error("%s: the batch has not run since its last lpr_bb_batch_narrate_reserve", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    if (!out) {
+        set_error("%s: null out", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    *out = nullptr;
+    LPR_HIP(hipSetDevice(b->eng->device));
+    hipStream_t s = b->eng->stream;
+    const int64_t nrec_all = b->rec_total;
+    std::vector<int32_t> ri, nt;
+    std::vector<int64_t> off;
+    std::vector<NarrTextRun> runs;
+    std::vector<TextBlock> blk;
+    try {
+        ri.resize((size_t)(nrec_all * kBBRecInts));
+        nt.resize((size_t)nrec_all);
+        off.resize((size_t)nrec_all);
+        runs.resize((size_t)(1 + 2 * b->node_cap));
+    } catch (...) {
+        return bbb_oom("record mirrors (host)", nrec_all, kBBRecInts * sizeof(int32_t) + 12);
+    }
+    if (nrec_all > 0) {
+        LPR_HIP(hipMemcpyAsync(ri.data(), b->d.rec_i, ri.size() * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+        LPR_HIP(hipMemcpyAsync(off.data(), b->narr.tab_off, off.size() * sizeof(int64_t),
+                               hipMemcpyDeviceToHost, s));
+        LPR_HIP(hipMemcpyAsync(nt.data(), b->narr.ntab, nt.size() * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+        LPR_HIP(hipStreamSynchronize(s));
+    }
+    try {
+        for (int32_t k = 0; k < b->count; ++k) {
+            const BBBatchDesc& d = b->h_desc[(size_t)k];
+            const BBNarrDesc& c = b->h_narr[(size_t)k];
+            if (first_block) first_block[k] = (int64_t)blk.size();
+            const int64_t nrec = std::min<int64_t>(d.nrec, (int64_t)runs.size());
+            const int32_t* e = ri.data() + (int64_t)kBBRecInts * d.rec_off;
+            (void)narr_text_runs(d.rows, d.cols, nrec, e + 2, e + 4, kBBRecInts,
+                                 off.data() + d.rec_off, nt.data() + d.rec_off, c.kp.cur,
+                                 runs.data());
+            TextBlock tb{};
+            tb.nvars = d.nvars;
+            for (int64_t rid = 0; rid < nrec; ++rid) {
+                const NarrTextRun& r = runs[(size_t)rid];
+                tb.rows = r.rows;
+                tb.cols = r.cols;
+                tb.round4 = (int16_t)r.round4;
+                for (int32_t i = 0; i < r.count; ++i) {
+                    tb.src = b->narr.slab + c.slab_off + r.off + (int64_t)i * r.rows * r.cols;
+                    blk.push_back(tb);
+                }
+            }
+            if (c.best_depth >= 0) {
+                tb.rows = d.rows + c.best_depth;
+                tb.cols = d.cols + c.best_depth;
+                tb.round4 = (int16_t)kNarrTextIncumbentRound4;
+                tb.src = b->narr.best + c.best_off;
+                blk.push_back(tb);
+            }
+        }
+    } catch (...) {
+        return bbb_oom("block descriptors (host)", (int64_t)blk.size(), sizeof(TextBlock));
+    }
+    if (first_block) first_block[b->count] = (int64_t)blk.size();
+    if (blk.empty()) {
+        set_error("%s: nothing to format: no IP of the batch keeps a child tableau or has an "
+                  "incumbent", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    return text_format_blocks(W, b->eng, blk, out);
 }
 
 }  // extern "C"

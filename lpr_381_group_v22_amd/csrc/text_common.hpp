@@ -482,15 +482,19 @@ LPR_TEXT_HD int64_t text_row_frame_len(int32_t i, int32_t cols) {
 
 // One block of a call, in device memory.  A row is converted by `lanes` adjacent lanes of a wave
 // (a power of two, 4 .. 64, the smallest that holds cols), so a wave takes 64 / lanes rows of one
-// block at a time: a wave task.  The host owns every field.
+// block at a time: a wave task.  round4 is how many times Math.Round(v, 4) is applied to a cell
+// before it is formatted (0, 1 or 2: DisplayTableau); only the rounded
+// kernels read it.  The host owns every field.
 struct TextBlock {
     const double* src;  // rows x cols row-major, where the source keeps it
     int64_t row0;       // the block's first row among all rows of the call
     int64_t wave0;      // its first wave task among all of the call
     int64_t hdr_end;    // bytes of the rule and "Table" lines of blocks 0 .. this one
-    int32_t rows, cols, nvars, lanes;
+    int32_t rows, cols, nvars;
+    int16_t lanes, round4;
 };
-static_assert(sizeof(TextBlock) == 48, "TextBlock is 48 bytes");
+static_assert(sizeof(TextBlock) == 48, "TextBlock is 48 bytes: round4 took half of lanes' word");
+constexpr int kTextMaxRound4 = 2;
 constexpr int text_lanes(int32_t cols) {
     int l = 4;
     while (l < 64 && l < cols) l *= 2;
@@ -510,19 +514,28 @@ constexpr int kTextScanTile = 2048;  // rows one workgroup scans: 256 lanes x 8
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+
+#include <vector>
+struct lpr_engine;
+struct lpr_text;
 namespace lpr {
+// text_engine.hip: blocks whose src (device memory that stays as it is until the call returns),
+// rows, cols, nvars and round4 are set -> an lpr_text on e; what lpr_bb_batch_narrate_text
+// (bb_batch_engine.hip) ends in.  W names the call in error messages.
+int text_format_blocks(const char* W, lpr_engine* e, std::vector<TextBlock>& blk, lpr_text** out);
 // text_kernels.hip: the launchers text_engine.hip calls, all on stream s.  rows_scan is
 // row_len[n_rows + 1] (the last entry 0): row lengths after text_launch_measure, their exclusive
 // prefix (the last entry the total) after text_launch_scan; partials holds
-// ceil((n_rows + 1) / kTextScanTile) entries.
-void text_launch_measure(hipStream_t s, const TextBlock* blk, int64_t n_blk, int64_t n_tasks,
-                         int64_t* rows_scan, uint32_t* big_count);
+// ceil((n_rows + 1) / kTextScanTile) entries.  `rounded` picks the instantiation of the two passes
+// that applies TextBlock::round4 (the same for both); false where every block has round4 == 0.
+void text_launch_measure(hipStream_t s, bool rounded, const TextBlock* blk, int64_t n_blk,
+                         int64_t n_tasks, int64_t* rows_scan, uint32_t* big_count);
 void text_launch_scan(hipStream_t s, int64_t* rows_scan, int64_t n, int64_t* partials);
 void text_launch_offsets(hipStream_t s, const TextBlock* blk, int64_t n_blk, int64_t n_rows,
                          const int64_t* rows_scan, int64_t* offsets);
-void text_launch_write(hipStream_t s, const TextBlock* blk, int64_t n_blk, int64_t n_tasks,
-                       const int64_t* rows_scan, uint8_t* text, TextBigCell* big, uint32_t big_cap,
-                       uint32_t* big_fill);
+void text_launch_write(hipStream_t s, bool rounded, const TextBlock* blk, int64_t n_blk,
+                       int64_t n_tasks, const int64_t* rows_scan, uint8_t* text, TextBigCell* big,
+                       uint32_t big_cap, uint32_t* big_fill);
 void text_launch_big(hipStream_t s, const TextBigCell* big, uint32_t n, uint8_t* text);
 }  // namespace lpr
 #endif

@@ -55,12 +55,14 @@ struct TextWork {
     }
 };
 
-// The layout fields of the descriptors (src, rows, cols, nvars are set): lanes, row0, wave0,
-// hdr_end.  Returns the rows and wave tasks of the call.
-void text_lay_out(std::vector<TextBlock>& blk, int64_t* n_rows, int64_t* n_tasks) {
+// The layout fields of the descriptors (src, rows, cols, nvars, round4 are set): lanes, row0,
+// wave0, hdr_end.  Returns the rows and wave tasks of the call, and whether any block is rounded.
+bool text_lay_out(std::vector<TextBlock>& blk, int64_t* n_rows, int64_t* n_tasks) {
     int64_t r = 0, w = 0, h = 0;
+    bool rounded = false;
     for (TextBlock& b : blk) {
-        b.lanes = text_lanes(b.cols);
+        rounded = rounded || b.round4 != 0;
+        b.lanes = (int16_t)text_lanes(b.cols);
         b.row0 = r;
         b.wave0 = w;
         h += text_header_len(b.cols, b.nvars);
@@ -71,6 +73,7 @@ void text_lay_out(std::vector<TextBlock>& blk, int64_t* n_rows, int64_t* n_tasks
     }
     *n_rows = r;
     *n_tasks = w;
+    return rounded;
 }
 
 // Blocks laid out on the host -> an lpr_text on e.  wk.upload, when set, already holds what the
@@ -79,7 +82,7 @@ int text_format(const char* W, lpr_engine* e, std::vector<TextBlock>& blk, TextW
                 lpr_text** out) {
     const int64_t n_blk = (int64_t)blk.size();
     int64_t n_rows = 0, n_tasks = 0;
-    text_lay_out(blk, &n_rows, &n_tasks);
+    const bool rounded = text_lay_out(blk, &n_rows, &n_tasks);
     const int64_t n_scan = n_rows + 1;
     const int64_t tiles = (n_scan + kTextScanTile - 1) / kTextScanTile;
     if (tiles > INT32_MAX) {
@@ -106,7 +109,7 @@ int text_format(const char* W, lpr_engine* e, std::vector<TextBlock>& blk, TextW
         LPR_HIP(hipMemsetAsync(wk.rows_scan, 0, (size_t)n_scan * sizeof(int64_t), s));
         LPR_HIP(hipMemsetAsync(wk.counters, 0, 2 * sizeof(uint32_t), s));
         LPR_HIP(hipEventRecord(wk.ev[0], s));
-        text_launch_measure(s, wk.blk, n_blk, n_tasks, wk.rows_scan, wk.counters);
+        text_launch_measure(s, rounded, wk.blk, n_blk, n_tasks, wk.rows_scan, wk.counters);
         text_launch_scan(s, wk.rows_scan, n_scan, wk.partials);
         text_launch_offsets(s, wk.blk, n_blk, n_rows, wk.rows_scan, t->offsets);
         LPR_HIP(hipGetLastError());
@@ -125,7 +128,7 @@ int text_format(const char* W, lpr_engine* e, std::vector<TextBlock>& blk, TextW
     }
     auto second = [&]() -> int {
         LPR_HIP(hipEventRecord(wk.ev[2], s));
-        text_launch_write(s, wk.blk, n_blk, n_tasks, wk.rows_scan, t->text, wk.big, sized.big,
+        text_launch_write(s, rounded, wk.blk, n_blk, n_tasks, wk.rows_scan, t->text, wk.big, sized.big,
                           wk.counters + 1);
         if (sized.big > 0) text_launch_big(s, wk.big, sized.big, t->text);
         LPR_HIP(hipGetLastError());
@@ -158,14 +161,18 @@ void text_orphan(lpr_text* t) {  // lpr_engine_close
     text_release_device(t);
     t->eng = nullptr;
 }
+int text_format_blocks(const char* W, lpr_engine* e, std::vector<TextBlock>& blk, lpr_text** out) {
+    TextWork wk;
+    return text_format(W, e, blk, wk, out);
+}
 }  // namespace lpr
 
-extern "C" {
+namespace {
 
-// TableIterationFormater.Format (:22-48) without its title line, per tableau of a ragged list
-int lpr_text_format_tableaux(lpr_engine* e, int32_t count, const int32_t* rows, const int32_t* cols,
-                             const int32_t* nvars, const double* tableaux, lpr_text** out) {
-    static const char* W = "lpr_text_format_tableaux";
+// lpr_text_format_tableaux (round4 null: no block is rounded) and lpr_text_format_tableaux_rounded
+int text_format_tableaux(const char* W, lpr_engine* e, int32_t count, const int32_t* rows,
+                         const int32_t* cols, const int32_t* nvars, const int32_t* round4,
+                         const double* tableaux, lpr_text** out) {
     if (!e || !out || count < 1 || !rows || !cols || !nvars || !tableaux) {
         set_error("%s: bad arguments (count=%d, or a null engine / out / rows / cols / nvars / "
                   "tableaux)", W, count);
@@ -177,6 +184,10 @@ int lpr_text_format_tableaux(lpr_engine* e, int32_t count, const int32_t* rows, 
         if (rows[k] < 1 || cols[k] < 1 || nvars[k] < 0) {
             set_error("%s: block %d is %d x %d with nvars %d; it needs rows >= 1, cols >= 1 and "
                       "nvars >= 0", W, k, rows[k], cols[k], nvars[k]);
+            return LPR_BAD_ARGUMENT;
+        }
+        if (round4 && (round4[k] < 0 || round4[k] > kTextMaxRound4)) {
+            set_error("%s: round4[%d] = %d; a block is rounded 0, 1 or 2 times", W, k, round4[k]);
             return LPR_BAD_ARGUMENT;
         }
         total += (int64_t)rows[k] * cols[k];  // a term is below 2^62 and total was at most 2^59
@@ -206,11 +217,37 @@ int lpr_text_format_tableaux(lpr_engine* e, int32_t count, const int32_t* rows, 
         b.rows = rows[k];
         b.cols = cols[k];
         b.nvars = nvars[k];
+        b.round4 = (int16_t)(round4 ? round4[k] : 0);
         at += (int64_t)rows[k] * cols[k];
     }
     rc = text_format(W, e, blk, wk, out);
     if (rc != LPR_OK_OPTIMAL) hipStreamSynchronize(e->stream);
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+// TableIterationFormater.Format (:22-48) without its title line, per tableau of a ragged list
+int lpr_text_format_tableaux(lpr_engine* e, int32_t count, const int32_t* rows, const int32_t* cols,
+                             const int32_t* nvars, const double* tableaux, lpr_text** out) {
+    return text_format_tableaux("lpr_text_format_tableaux", e, count, rows, cols, nvars, nullptr,
+                                tableaux, out);
+}
+
+// DisplayTableau (BranchBoundSimplexSolver.cs:623-640) per tableau of a ragged list: Format of the
+// tableau after round4[k] applications of Math.Round(v, 4)
+int lpr_text_format_tableaux_rounded(lpr_engine* e, int32_t count, const int32_t* rows,
+                                     const int32_t* cols, const int32_t* nvars,
+                                     const int32_t* round4, const double* tableaux,
+                                     lpr_text** out) {
+    static const char* W = "lpr_text_format_tableaux_rounded";
+    if (!round4) {
+        set_error("%s: null round4", W);
+        return LPR_BAD_ARGUMENT;
+    }
+    return text_format_tableaux(W, e, count, rows, cols, nvars, round4, tableaux, out);
 }
 
 // Format (:22-48) of every kept record of a traced batch and of the final tableau of every LP

@@ -5,6 +5,7 @@
 // exclusive scan of the row lengths; cells of 1e15 or more are listed by the write pass and
 // finished by a kernel of their own, so the two passes carry none of its arrays.  No kernel waits
 // for another workgroup: the order is the stream's.
+#include "bb_device_round.hpp"
 #include "engine_common.hpp"
 #include "text_common.hpp"
 
@@ -31,8 +32,25 @@ __device__ __forceinline__ int64_t text_block_of(const TextBlock* blk, int64_t n
     return lo;
 }
 
+// The bits of a cell as it is formatted.  kRound: after B.round4 applications of Math.Round(v, 4)
+// (DisplayTableau, BranchBoundSimplexSolver.cs:623-640) -- dn_round4, the
+// second one evaluated as dn_round4_twice evaluates it, only where the first result is 1e11 or
+// more.  Both passes load their cells through this, so they see the same value.
+template <bool kRound>
+__device__ __forceinline__ uint64_t text_cell_bits(const double* p, int n) {
+    double v = *p;
+    if constexpr (kRound) {
+        if (n >= 1) {
+            v = dn_round4(v);
+            if (n >= 2 && !(fabs(v) < 1e11)) v = dn_round4(v);
+        }
+    }
+    return (uint64_t)__double_as_longlong(v);
+}
+
 // Measure: row_len[r] = the bytes of row r, label and line end included; *big_count += the cells
 // of 1e15 or more.
+template <bool kRound>
 __global__ __launch_bounds__(kTextWg) void k_text_measure(const TextBlock* __restrict__ blk,
                                                           int64_t n_blk, int64_t n_tasks,
                                                           int64_t* __restrict__ row_len,
@@ -50,7 +68,7 @@ __global__ __launch_bounds__(kTextWg) void k_text_measure(const TextBlock* __res
         if (valid) {
             const double* src = B.src + row * B.cols;
             for (int32_t j = g; j < B.cols; j += L) {
-                const TextCell c = text_cell_measure((uint64_t)__double_as_longlong(src[j]));
+                const TextCell c = text_cell_measure(text_cell_bits<kRound>(src + j, B.round4));
                 sum += c.len;
                 big += c.cls == kTextBig;
             }
@@ -150,6 +168,7 @@ __device__ __forceinline__ void text_put_labels(uint8_t* dst, char letter, int64
 }
 
 // Write: every byte of every block but the bytes of the big cells, which are listed.
+template <bool kRound>
 __global__ __launch_bounds__(kTextWg) void k_text_write(const TextBlock* __restrict__ blk,
                                                         int64_t n_blk, int64_t n_tasks,
                                                         const int64_t* __restrict__ row_at,
@@ -199,7 +218,7 @@ __global__ __launch_bounds__(kTextWg) void k_text_write(const TextBlock* __restr
             c.len = 0;
             uint64_t bits = 0;
             if (has) {
-                bits = (uint64_t)__double_as_longlong(src[j0 + g]);
+                bits = text_cell_bits<kRound>(src + j0 + g, B.round4);
                 c = text_cell_measure(bits);
             }
             const int32_t len1 = has ? c.len + 1 : 0;  // the cell and its tab
@@ -241,10 +260,11 @@ int text_grid(int64_t n_tasks) {
 
 }  // namespace
 
-void text_launch_measure(hipStream_t s, const TextBlock* blk, int64_t n_blk, int64_t n_tasks,
-                         int64_t* rows_scan, uint32_t* big_count) {
-    hipLaunchKernelGGL(k_text_measure, dim3(text_grid(n_tasks)), dim3(kTextWg), 0, s, blk, n_blk,
-                       n_tasks, rows_scan, big_count);
+void text_launch_measure(hipStream_t s, bool rounded, const TextBlock* blk, int64_t n_blk,
+                         int64_t n_tasks, int64_t* rows_scan, uint32_t* big_count) {
+    auto* k = rounded ? k_text_measure<true> : k_text_measure<false>;
+    hipLaunchKernelGGL(k, dim3(text_grid(n_tasks)), dim3(kTextWg), 0, s, blk, n_blk, n_tasks,
+                       rows_scan, big_count);
 }
 
 void text_launch_scan(hipStream_t s, int64_t* rows_scan, int64_t n, int64_t* partials) {
@@ -262,11 +282,12 @@ void text_launch_offsets(hipStream_t s, const TextBlock* blk, int64_t n_blk, int
                        dim3(kTextWg), 0, s, blk, n_blk, n_rows, rows_scan, offsets);
 }
 
-void text_launch_write(hipStream_t s, const TextBlock* blk, int64_t n_blk, int64_t n_tasks,
-                       const int64_t* rows_scan, uint8_t* text, TextBigCell* big, uint32_t big_cap,
-                       uint32_t* big_fill) {
-    hipLaunchKernelGGL(k_text_write, dim3(text_grid(n_tasks)), dim3(kTextWg), 0, s, blk, n_blk,
-                       n_tasks, rows_scan, text, big, big_cap, big_fill);
+void text_launch_write(hipStream_t s, bool rounded, const TextBlock* blk, int64_t n_blk,
+                       int64_t n_tasks, const int64_t* rows_scan, uint8_t* text, TextBigCell* big,
+                       uint32_t big_cap, uint32_t* big_fill) {
+    auto* k = rounded ? k_text_write<true> : k_text_write<false>;
+    hipLaunchKernelGGL(k, dim3(text_grid(n_tasks)), dim3(kTextWg), 0, s, blk, n_blk, n_tasks,
+                       rows_scan, text, big, big_cap, big_fill);
 }
 
 void text_launch_big(hipStream_t s, const TextBigCell* big, uint32_t n, uint8_t* text) {

@@ -240,9 +240,13 @@ class DeviceText:
             pass
 
 
-def format_device(tableaux, nvars, engine=None) -> DeviceText:
+def format_device(tableaux, nvars, engine=None, round4=0) -> DeviceText:
     """lpr_text_format_tableaux: one block per tableau (2-D arrays of any shapes), ``nvars`` an
-    int for all or one per tableau."""
+    int for all or one per tableau.  ``round4`` (an int for all, or one per tableau; 0, 1 or 2)
+    is how many times Math.Round(v, 4) is applied to every cell on the device before it is
+    formatted -- DisplayTableau (BranchBoundSimplexSolver.cs:623-640) is 1, a tableau that went
+    through RoundAllTableaux first is 2; with any entry non-zero the call is
+    lpr_text_format_tableaux_rounded."""
     from . import _native as N
     from .engine import default_engine
     T = [np.ascontiguousarray(t, dtype=np.float64) for t in tableaux]
@@ -257,6 +261,16 @@ def format_device(tableaux, nvars, engine=None) -> DeviceText:
     flat = np.concatenate([t.reshape(-1) for t in T])
     eng = engine or default_engine()
     h = C.c_void_p()
+    r4 = [int(round4)] * len(T) if np.isscalar(round4) else [int(v) for v in round4]
+    if len(r4) != len(T):
+        raise ValueError("round4 must be an int or hold one entry per tableau")
+    if any(r4):
+        r4a = np.asarray(r4, dtype=np.int32)
+        N.check(N.lib.lpr_text_format_tableaux_rounded(
+            eng._h, len(T), N._ptr(rows, C.c_int32), N._ptr(cols, C.c_int32),
+            N._ptr(nva, C.c_int32), N._ptr(r4a, C.c_int32), N._ptr(flat, C.c_double),
+            C.byref(h)), "lpr_text_format_tableaux_rounded")
+        return DeviceText(h)
     N.check(N.lib.lpr_text_format_tableaux(eng._h, len(T), N._ptr(rows, C.c_int32),
                                            N._ptr(cols, C.c_int32), N._ptr(nva, C.c_int32),
                                            N._ptr(flat, C.c_double), C.byref(h)),
@@ -264,20 +278,21 @@ def format_device(tableaux, nvars, engine=None) -> DeviceText:
     return DeviceText(h)
 
 
-def format_bodies(tableaux, nvars, engine=None):
-    """Format(tab, nvars, title) without its title line for every tableau, on the device."""
-    text = format_device(tableaux, nvars, engine)
+def format_bodies(tableaux, nvars, engine=None, round4=0):
+    """Format(tab, nvars, title) without its title line for every tableau, on the device;
+    ``round4`` as format_device takes it."""
+    text = format_device(tableaux, nvars, engine, round4)
     try:
         return text.blocks()
     finally:
         text.destroy()
 
 
-def FormatMany(tableaux, nvars, titles, engine=None):
+def FormatMany(tableaux, nvars, titles, engine=None, round4=0):
     """[Format(tab, nvars, title)] for every (tableau, title) pair: bodies from the device, the
-    title lines from the host."""
+    title lines from the host; ``round4`` as format_device takes it."""
     titles = list(titles)
-    bodies = format_bodies(tableaux, nvars, engine)
+    bodies = format_bodies(tableaux, nvars, engine, round4)
     if len(titles) != len(bodies):
         raise ValueError("one title per tableau")
     return [title_line(t) + b for t, b in zip(titles, bodies)]

@@ -26,6 +26,20 @@ marked "extrapolated" where scaled to the whole workload.  The only speed-up sta
 status, pivots and every child tableau, the incumbent's tableau); mismatches make the exit status
 non-zero.
 
+--narrate --device-text measures the device text of the narrated batch on
+the same three workloads, cut by --text-ips (default W=2048,G=512,H=32: the slab of child tableaux
+and its text, about 6.5 bytes per cell, are both on the device and the text is read back whole, so
+the 20 GB slabs of G and H are cut to about 2.5 GB) and writes one JSON line per workload and a
+summary line to profiles/bb_batch_narr_text_bench.json: (a) the kernels of one
+lpr_bb_batch_narrate_text (kernel_ms of lpr_text_info) and the call's wall-clock, one warm-up and
+--repeat recorded passes; (b) end to end, FormatNarration() and NarrationTextDevice(k) for every
+IP, --repeat passes; (c) the host path on the same handle, NarrationText(k) over evenly spaced IPs
+in a fixed shuffled order, each pass cut at --host-seconds (an IP that has begun is finished), per
+IP.  clears_bar: on every workload the slowest device pass per IP is below the fastest host pass
+per IP.  NarrationTextDevice(k) == NarrationText(k) is checked on up to 256 of those IPs, as many
+as --check-seconds of host formatting allow; the mismatch count is recorded and makes the exit
+status non-zero.
+
 Run it under a time limit:  timeout -k 10 1200 python tools/bb_batch_bench.py [--out FILE]
 Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python
 tools/bb_batch_bench.py --no-check --repeat 1
@@ -51,13 +65,14 @@ TRACE_CAP = 256
 W_MAX, G_MAX = (64 * 1024 - 1024) // 4, 160 * 1024 - 1024  # kBatchMaxLdsW / kBatchMaxLdsG
 
 
-def gen_models(name: str, seed: int):
-    """Option-3 models (objective, constraints with the unit rows, True) of one workload."""
+def gen_models(name: str, seed: int, limit: int = 0):
+    """Option-3 models (objective, constraints with the unit rows, True) of one workload; with
+    ``limit`` its first ``limit`` models (the generator draws model by model)."""
     from lpr_381_group_v22_amd import Constraint
     rng = np.random.RandomState(seed)
     count, fixed = {"W": (65536, None), "G": (4096, (24, 8)), "H": (256, (96, 32))}[name]
     models = []
-    for _ in range(count):
+    for _ in range(min(count, limit) if limit > 0 else count):
         n, m = fixed if fixed else (int(rng.randint(6, 11)), int(rng.randint(1, 4)))
         c = rng.randint(1, 20, size=n).astype(float)
         A = rng.randint(1, 15, size=(m, n)).astype(float)
@@ -255,6 +270,90 @@ def narrate_workload(pkg, N, eng, name, roots, nvars, packed, args):
     return rec
 
 
+def device_text_workload(pkg, N, eng, name, packed, args):
+    """--narrate --device-text: one narrated batch, then (a), (b), (c) and the comparison of the
+    module docstring on that handle."""
+    from lpr_381_group_v22_amd.bb_batch import BranchAndBoundBatch, node_cap_of
+    count = len(packed.rows)
+    _, run_s, res, info, slab, h = run_narrated(N, eng, packed)
+    del slab
+    bb = BranchAndBoundBatch(h, eng, zip(packed.rows.tolist(), packed.cols.tolist()), packed.nvars,
+                             node_cap_of(NODE_CAP), TRACE_CAP)
+    bb.Narrated, bb._caps = True, info["need"]
+    progress(f"{name}: narrated run {run_s:.4f}s, slab {8e-9 * float(info['need'].sum()):.3f} GB")
+
+    def call_pass():
+        bb._drop_narration_text()
+        eng.sync()
+        t0 = time.perf_counter()
+        text, _ = bb.FormatNarration()
+        return text.KernelMs, time.perf_counter() - t0, text.Count, text.Bytes
+
+    def e2e_pass():
+        bb._drop_narration_text()
+        eng.sync()
+        t0 = time.perf_counter()
+        done = refused = chars = 0
+        for k in range(count):
+            try:
+                chars += len(bb.NarrationTextDevice(k))
+                done += 1
+            except ValueError:  # a short trace or LPR_PIVOT_LIMIT: the host path refuses it too
+                refused += 1
+        return done, refused, chars, time.perf_counter() - t0
+
+    call_pass()  # warm-up
+    calls = [call_pass() for _ in range(max(1, args.repeat))]
+    progress(f"{name}: (a) kernel_ms {[round(c[0], 3) for c in calls]}")
+    e2e = [e2e_pass() for _ in range(max(1, args.repeat))]
+    progress(f"{name}: (b) e2e seconds {[round(e[3], 3) for e in e2e]} for {e2e[0][0]} IPs")
+    picks = np.linspace(0, count - 1, min(CHECK, count)).astype(np.int64)
+    np.random.RandomState(args.seed).shuffle(picks)
+    host, texts = [], {}
+    for _ in range(max(1, args.repeat)):
+        done = 0
+        t0 = time.perf_counter()
+        for k in picks:
+            try:
+                texts[int(k)] = bb.NarrationText(int(k))
+                done += 1
+            except ValueError:
+                pass
+            if time.perf_counter() - t0 > args.host_seconds:
+                break
+        host.append((done, time.perf_counter() - t0))
+        progress(f"{name}: (c) host pass: {done} IPs in {host[-1][1]:.2f}s")
+    t0 = time.perf_counter()
+    for k in picks:  # more IPs for the comparison, while the budget lasts
+        if time.perf_counter() - t0 > args.check_seconds:
+            break
+        if int(k) not in texts:
+            try:
+                texts[int(k)] = bb.NarrationText(int(k))
+            except ValueError:
+                pass
+    bad = sum(bb.NarrationTextDevice(k) != t for k, t in texts.items())
+    progress(f"{name}: compared {len(texts)} IPs, {bad} mismatches")
+    dev_per_ip = max(e[3] / max(e[0], 1) for e in e2e)
+    host_per_ip = min(t / max(d, 1) for d, t in host)
+    rec = dict(workload=name, mode="narrate-device-text", ips=count, node_cap=NODE_CAP,
+               rows=[int(packed.rows.min()), int(packed.rows.max())],
+               cols=[int(packed.cols.min()), int(packed.cols.max())],
+               slab_doubles=int(info["need"].sum()), slab_gb=8e-9 * float(info["need"].sum()),
+               kept_all=bool((info["kept"] == info["need"]).all()),
+               blocks=int(calls[0][2]), text_bytes=int(calls[0][3]),
+               a_kernel_ms_all=[c[0] for c in calls], a_call_seconds_all=[c[1] for c in calls],
+               a_cells_per_s_kernel=float(info["need"].sum()) / (min(c[0] for c in calls) / 1e3),
+               b_e2e_ips_refused_chars_seconds_all=e2e,
+               b_device_seconds_per_ip_slowest=dev_per_ip,
+               c_host_ips_seconds_all=host, c_host_seconds_per_ip_fastest=host_per_ip,
+               c_host_seconds_whole_workload_extrapolated=host_per_ip * count,
+               speedup_per_ip=host_per_ip / dev_per_ip, clears_bar=bool(dev_per_ip < host_per_ip),
+               ips_compared=len(texts), mismatches=int(bad))
+    bb.destroy()
+    return rec
+
+
 def _whole(bb, k) -> bool:
     """IP k keeps its whole trace (TRACE_CAP quads): its numbers can be rebuilt."""
     return bb.Result(k)["pivots"] <= bb.trace_cap
@@ -351,6 +450,13 @@ def main() -> int:
     ap.add_argument("--no-check", action="store_true", help="skip the bit check and the loops")
     ap.add_argument("--narrate", action="store_true", help="measure the narrated batch")
     ap.add_argument("--ips", type=int, default=0, help="keep the first N IPs of each workload")
+    ap.add_argument("--device-text", action="store_true",
+                    help="with --narrate: measure the device text of the narrated batch")
+    ap.add_argument("--text-ips", default="W=2048,G=512,H=32",
+                    help="--device-text: IPs kept per workload")
+    ap.add_argument("--host-seconds", type=float, default=4.0, help="budget of one host pass")
+    ap.add_argument("--check-seconds", type=float, default=45.0,
+                    help="--device-text: host formatting spent on further IPs to compare")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
 
@@ -363,15 +469,27 @@ def main() -> int:
         orc = Oracle()
     failures = 0
     lines = []
+    text_ips = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in args.text_ips.split(","))
+    if args.device_text:
+        if not args.narrate:
+            ap.error("--device-text goes with --narrate")
+        args.out = args.out or os.path.join(ROOT, "profiles", "bb_batch_narr_text_bench.json")
     with pkg.Engine(0) as eng:
         for i, name in enumerate(args.workloads.split(",")):
             progress(f"{name}: generating")
-            models = gen_models(name, args.seed + i)
+            limit = args.ips if args.ips > 0 else (text_ips.get(name, 0) if args.device_text
+                                                   else 0)
+            models = gen_models(name, args.seed + i, limit)
             progress(f"{name}: primal batch")
-            if args.ips > 0:
-                models = models[:args.ips]
             roots, nvars = roots_of(pkg, N, eng, models)
             packed = pack_roots(roots, nvars, NODE_CAP)
+            if args.device_text:
+                rec = device_text_workload(pkg, N, eng, name, packed, args)
+                failures += rec["mismatches"]
+                line = json.dumps(rec)
+                print(line, flush=True)
+                lines.append(line)
+                continue
             if args.narrate:
                 rec = narrate_workload(pkg, N, eng, name, roots, nvars, packed, args)
                 failures += rec.get("record_mismatches", 0)
@@ -428,6 +546,13 @@ def main() -> int:
             line = json.dumps(rec)
             print(line, flush=True)
             lines.append(line)
+    if args.device_text:
+        recs = [json.loads(x) for x in lines]
+        lines.append(json.dumps(dict(mode="summary", text_ips=args.text_ips,
+                                     clears_bar=all(r["clears_bar"] for r in recs),
+                                     mismatches=sum(r["mismatches"] for r in recs),
+                                     ips_compared=sum(r["ips_compared"] for r in recs))))
+        print(lines[-1], flush=True)
     if args.out:
         with open(args.out, "a") as f:
             f.write("\n".join(lines) + "\n")

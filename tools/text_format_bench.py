@@ -10,7 +10,10 @@ extrapolation when scaled to the batch.  --check LPs per workload, evenly spaced
 string for string (IterationSnapshotsDevice(k) == IterationSnapshots(k)); the mismatch count is
 recorded.  clears_bar: the slowest device pass per block is below the fastest host pass per block
 on every workload.  With --parent-lib the untraced lpr_batch_solve of W is also timed against the
-parent commit's library in alternating fresh processes (batch_bench.against_parent).  Appends one
+parent commit's library in alternating fresh processes (batch_bench.against_parent), and so is (a)
+-- the kernel_ms of lpr_batch_trace_text on every workload, --parent-rounds fresh processes per
+library, alternated; within_margin: this library's best is within the parent's best plus the
+parent's own spread (its largest max - min over the passes of one process).  Appends one
 JSON line per workload and a summary line to profiles/text_format_bench.json.
 
     python tools/text_format_bench.py [--workloads W,G,H] [--check 256] [--check-h 256]
@@ -87,6 +90,63 @@ def host_passes(b, picks, passes, budget_s):
     return out
 
 
+def trace_text_child(lib_path: str, names, seed: int, passes: int) -> int:
+    """--trace-text-child: (a) alone with the engine library at lib_path (it may predate calls this
+    package declares: what it lacks is not bound), one JSON line {workload: [kernel_ms, ...]}."""
+    import lpr_381_group_v22_amd as pkg
+    from lpr_381_group_v22_amd import _native as N
+    if os.path.abspath(lib_path) != os.path.abspath(N.LIB_PATH):
+        lib = C.CDLL(lib_path)
+        for name, (res, argtypes) in N.SIGNATURES.items():
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = res, argtypes
+        N.lib = lib  # every call of the package goes through N.lib
+    out = {}
+    with pkg.Engine(0) as eng:
+        for i, name in enumerate(names):
+            b, _ = traced_batch(pkg, N, eng, bb.gen_workload(name, seed + i), name)
+            ms = []
+            for p in range(passes + 1):  # the first one warms up
+                b._text = None
+                eng.sync()
+                text = b.FormatTrace()
+                if p:
+                    ms.append(text.KernelMs)
+                text.destroy()
+            b._text = None
+            out[name] = ms
+            b.destroy()
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+def trace_text_against_parent(args, names):
+    import subprocess
+    from lpr_381_group_v22_amd import _native as N
+    runs = {"this": [], "parent": []}
+    for _ in range(max(1, args.parent_rounds)):
+        for tag, path in (("this", N.LIB_PATH), ("parent", args.parent_lib)):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--trace-text-child",
+                                path, "--workloads", ",".join(names), "--seed", str(args.seed),
+                                "--passes", str(args.passes)], capture_output=True, text=True,
+                               timeout=900)
+            if p.returncode != 0:
+                raise RuntimeError(f"trace-text child on {path} failed: {p.stderr[-600:]}")
+            runs[tag].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    out = {}
+    for name in names:
+        this = [t for r in runs["this"] for t in r[name]]
+        parent = [t for r in runs["parent"] for t in r[name]]
+        margin = max(max(r[name]) - min(r[name]) for r in runs["parent"])
+        out[name] = dict(this_kernel_ms_by_process=[r[name] for r in runs["this"]],
+                         parent_kernel_ms_by_process=[r[name] for r in runs["parent"]],
+                         this_best=min(this), parent_best=min(parent),
+                         parent_margin_max_minus_min=margin,
+                         within_margin=min(this) <= min(parent) + margin)
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="W,G,H")
@@ -96,10 +156,14 @@ def main() -> int:
     ap.add_argument("--check-h", type=int, default=256, help="LPs compared of workload H")
     ap.add_argument("--host-seconds", type=float, default=4.0, help="budget of one host pass")
     ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--trace-text-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--parent-rounds", type=int, default=3)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "text_format_bench.json"))
     args = ap.parse_args()
+    if args.trace_text_child:
+        return trace_text_child(args.trace_text_child, args.workloads.split(","), args.seed,
+                                args.passes)
     import lpr_381_group_v22_amd as pkg
     from lpr_381_group_v22_amd import _native as N
     lines, clears, mismatches = [], True, 0
@@ -144,6 +208,8 @@ def main() -> int:
                    lps_compared=int(sum(r["lps_compared"] for r in lines)))
     if args.parent_lib:
         summary["untraced_solve_vs_parent"] = bb.against_parent(args, ["W"])["W"]
+        summary["trace_text_kernel_ms_vs_parent"] = trace_text_against_parent(
+            args, args.workloads.split(","))
     lines.append(summary)
     print(json.dumps(summary), flush=True)
     with open(args.out, "a") as f:
